@@ -12,8 +12,8 @@ in HBM, plus -- for N > 1 -- the reassembly exchange.  The foci of a rank are wh
 
 For N > 1 (launched by torch.distributed.run, one rank per GPU; weak scaling: 8 foci per GPU, 64 at N = 8) the timed
 step uses `--reassemble aggregate` by default -- the reduce-scatter of max |p| / mean intensity (plan/protocol.py:382-387), the
-one cross-rank dependency of calc_solution's result, on a side stream, overlapped with the next step's compute; the same run
-then reports north_star's `allgather` (every per-focus |p| volume to every rank over RCCL/xGMI: 3.8 GB inbound per rank and
+one cross-rank dependency of calc_solution's result, on a side stream, overlapped with the next step's compute; with `--full` the same
+run then reports north_star's `allgather` (every per-focus |p| volume to every rank over RCCL/xGMI: 3.8 GB inbound per rank and
 step at N = 8, link-bound by construction) and the compute without any exchange beside it.  A line whose
 exchange did not run as asked carries "degraded": true and the process exits non-zero.
 torch is used only for the rendezvous / barrier (gloo); the product path is ctypes -> HIP.
@@ -21,12 +21,19 @@ torch is used only for the rendezvous / barrier (gloo); the product path is ctyp
 Arithmetic: fp32 accumulate of fp16 hi/lo operands on the matrix cores.  `value` is measured in the LIBRARY DEFAULT mode
 (`--corrections auto`): what Protocol.calc_solution runs unless told otherwise -- on this shard the two hi x lo correction products
 go through e4m3 (<= 7.5e-6 of the volume maximum, include/olx.h; north_star's gate is 1e-5).  `--corrections fp16` times the opted-out mode (plan flag
-OLX_FIELD_FP16_CORRECTION / SimSetup.options["fp8_correction"] = "0": three fp16 products, <= 2e-6) as the headline instead.  At
-N = 1 the line carries the other mode beside it (`precision_safe` / `library_default`), a `parity` block measured in this run against the fp64 C oracle, and the other
-shapes of the path (`legs`: single focus on / off axis, off-axis shard, 64-focus sweep), each planned, clock-ramped and timed
-over its own >= 200 steps; `scans` = GB/s of the HBM-bound streaming kernels; `kernel1` with its CPU baselines.
+OLX_FIELD_FP16_CORRECTION / SimSetup.options["fp8_correction"] = "0": three fp16 products, <= 2e-6) as the headline instead.
 
-Prints ONE JSON line (rank 0).  `value` = V * N_el * F_total / time [Mvoxel-elements/s].
+A plain run does only what the headline needs: plan, clock ramp, W warm-up steps, K timed steps, the outputs (`--dump-outputs`), the line.
+`--full` adds everything else, after the headline: at N = 1 the other correction mode (`precision_safe` / `library_default`), a `parity`
+block measured in this run against the fp64 C oracle, the other shapes of the path (`legs`: single focus on / off axis, off-axis shard,
+64-focus sweep, the other BASELINE configurations), each planned, clock-ramped and timed over its own >= 200 steps; `scans` = GB/s of the
+HBM-bound streaming kernels; `kernel1` with its CPU baselines; `end_to_end`; `cpu_baseline(_c)`; roofline traffic and `achievable` from
+rocprofv3 counter passes in child runs.  At N > 1 it adds the other exchanges beside the headline (`config.with_*`, `without_exchange`).
+
+`--dump-outputs DIR` writes what the last timed step left on each rank, the |p| and intensity volumes of its foci (what
+Protocol.calc_solution hands its caller), as DIR/<name>.npy: see dump_outputs.  The inputs are synthetic and fixed by the arguments.
+
+Prints ONE JSON line (rank 0).  `value` = V * N_el * F_total / time [Mvoxel-elements/s], `ms_per_step` = wall time of one timed step.
 """
 from __future__ import annotations
 
@@ -212,6 +219,29 @@ def _library_stamp(nat):
         return "unknown"
 
 
+DUMP_BYTES = 32 << 20      # --dump-outputs: the voxel sample of every rank is 32 MiB of float32, whatever the shard
+
+
+def dump_outputs(ctx, out_dir: str, F: int, suffix: str = ""):
+    """--dump-outputs: the |p| and intensity volumes the last timed step left on this rank, fetched one focus at a time (whole, they are
+    2 x F x 64 MB at 256^3).  `pmag<suffix>.npy` / `intensity<suffix>.npy` = float32 [F, S]: the same S voxels of every focus, drawn once from
+    a fixed seed (sorted flat C-order indices into the rank's volume, S = min(V, DUMP_BYTES / 8 F)); `pmag_max<suffix>.npy` /
+    `intensity_max<suffix>.npy` = float32 [F]: each volume's maximum over all of its voxels."""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = None
+    got = {k: [] for k in ("pmag", "intensity", "pmag_max", "intensity_max")}
+    for f in range(F):
+        vol = ctx.field_fetch(f, want=("pmag", "intensity"))
+        for k in ("pmag", "intensity"):
+            v = vol[k].ravel()
+            if idx is None:
+                idx = np.sort(np.random.default_rng(2026).choice(v.size, min(v.size, DUMP_BYTES // (8 * F)), replace=False))
+            got[k].append(v[idx])
+            got[k + "_max"].append(v.max())
+    for k, vals in got.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), np.asarray(vals, dtype=np.float32))
+
+
 def static_traffic(kernel_name: str, grid_n: int):
     """HBM bytes per launch from the committed PMC summaries (profiles/traffic.json), matched on the kernel variant
     string: a STATIC figure from tools/profile_round.sh's counter passes, not measured in this run; None when the
@@ -389,11 +419,11 @@ def main():
     ap.add_argument("--reassemble", choices=["allgather", "aggregate", "none"], default=None,
                     help="what the timed step exchanges.  Default for N > 1: aggregate -- the reduce-scatter of max |p| / mean intensity, the one cross-rank "
                          "dependency of calc_solution's result (plan/protocol.py:382-387) and the exchange that can scale on point-to-point xGMI "
-                         "(DESIGN.md 6); north_star's all-gather of every per-focus volume and the compute without exchange are timed beside it.  N = 1: none")
+                         "(DESIGN.md 6); north_star's all-gather of every per-focus volume and the compute without exchange are timed beside it with --full.  N = 1: none")
     ap.add_argument("--corrections", choices=["auto", "fp8", "fp16"], default="auto",
                     help="hi x lo correction products of the fp16 operand split: auto (= fp8) = the library default, e4m3 products where their "
                          "bound (<= 7.5e-6 of the volume maximum, include/olx.h) is a bound on the planned volume; fp16 = opted out (plan flag "
-                         "OLX_FIELD_FP16_CORRECTION, <= 2e-6); the other one is timed beside it at N = 1")
+                         "OLX_FIELD_FP16_CORRECTION, <= 2e-6); the other one is timed beside it at N = 1 with --full")
     ap.add_argument("--grid", type=int, default=256)
     ap.add_argument("--spacing-mm", type=float, default=0.25)
     ap.add_argument("--elements", type=str, default="16x16")
@@ -403,7 +433,7 @@ def main():
     ap.add_argument("--force-comm", action="store_true", help="exercise the RCCL path even with 1 rank")
     ap.add_argument("--gather", choices=["rccl", "p2p"], default="rccl",
                     help="transport of the reassembly (include/olx.h OLX_GATHER): rccl = ncclAllGather (north_star), p2p = direct pulls over "
-                         "HIP IPC, one stream per peer; the other one is timed beside it (and takes over if this one cannot be initialised)")
+                         "HIP IPC, one stream per peer; the other one is timed beside it with --full (and takes over if this one cannot be initialised)")
     ap.add_argument("--medium", choices=["water", "skull"], default="water",
                     help="skull: BASELINE configs[4] synthetic skull-slab mask, heterogeneous layered-ray kernel, x-slabs per GPU")
     ap.add_argument("--hetero-planes-per-layer", type=int, default=1,
@@ -413,9 +443,14 @@ def main():
                     help="--medium skull: ray-integral model (olx_field_medium_model): marched = running ray sums, one look-up per ray "
                          "(kernel 2m, what auto picks for this phantom); sampled = one sample per non-trivial plane (kernel 2h)")
     ap.add_argument("--device", type=int, default=None, help="HIP device for every rank (debug: oversubscribe one GPU)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="0 disables the cpu_baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip the post-timing legs (other correction mode, parity, calc_solution)")
-    ap.add_argument("--static-traffic", action="store_true", help="report roofline.traffic from profiles/traffic.json instead of measuring it in child rocprofv3 passes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other measurement and check (other correction mode, parity, legs, scans, kernel 1, "
+                         "calc_solution, CPU baselines, counter passes; N > 1: the other exchanges); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32; a fixed, seeded sample of voxels)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: 0 disables the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the post-timing legs (other correction mode, parity, calc_solution)")
+    ap.add_argument("--static-traffic", action="store_true", help="--full: report roofline.traffic from profiles/traffic.json instead of measuring it in child rocprofv3 passes")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -525,7 +560,7 @@ def main():
     stuck = []       # set when a communicator init never returned (see init_transport)
     if gather:
         # north_star's reassembly is RCCL; the direct peer-to-peer all-gather (HIP IPC, all 7 xGMI links at once) is timed beside
-        # it, and takes over as the primary transport when RCCL cannot be brought up
+        # it (--full), and takes over as the primary transport when RCCL cannot be brought up
         order = [args.gather] + [k for k in ("rccl", "p2p") if k != args.gather]
         notes = []
         for kind in order:
@@ -639,6 +674,8 @@ def main():
     if res is None:
         sys.exit(f"bench: the accumulate itself failed: {timed.last_error}")
     elapsed, kern_ms = res
+    if args.dump_outputs:      # before anything else plans over the resident result
+        dump_outputs(ctx, args.dump_outputs, F, "" if world == 1 else f"_rank{rank}")
     try:
         ranks_seen = ctx.comm_ranks_seen() if gather else 0     # what RCCL / the p2p control block counted (0: no exchange ran)
     except Exception:  # noqa: BLE001
@@ -650,7 +687,7 @@ def main():
     pairs_per_step = V_step * N * F_total
     value = pairs_per_step * args.steps / elapsed / 1e6
     beside = {}
-    if dist is not None and gather:  # reported beside the headline (never instead of it): other exchange, no exchange
+    if dist is not None and gather and args.full:  # reported beside the headline (never instead of it): other exchange, no exchange
         k2 = min(args.steps, 200)
         other = "aggregate" if mode == "allgather" else "allgather"
         def beside_leg(key, m):
@@ -728,7 +765,7 @@ def main():
             "issue_ceiling": {"achieved_Mpairs_s": float(vox_launch) * N * F / (k_ms * 1e-3) / 1e6, "peak_Mpairs_s": ceil_pairs / 1e6,
                               "frac": float(vox_launch) * N * F / (k_ms * 1e-3) / ceil_pairs, "model": model},
         }
-        if world == 1 and not args.no_extras and not args.static_traffic:
+        if world == 1 and args.full and not args.no_extras and not args.static_traffic:
             wl = ["--grid", str(args.grid), "--spacing-mm", str(args.spacing_mm), "--elements", args.elements, "--pitch-mm", str(args.pitch_mm),
                   "--offset-mm", args.offset_mm, "--foci-per-gpu", str(args.foci_per_gpu), "--corrections", args.corrections, "--medium", args.medium]
             nbytes, src = live_traffic(kernel_name, wl)
@@ -737,7 +774,7 @@ def main():
             else:
                 out["roofline"]["traffic_source"] = (traffic_src or "none") + f" [live measurement unavailable: {src}]"
             out["achievable"] = achievable(kernel_name, wl, alg_bytes, k_ms)
-        if world == 1 and not args.no_extras and skull is None:
+        if world == 1 and args.full and not args.no_extras and skull is None:
             pos_m, _, area, _, _ = arr.element_table()
             out["parity"] = {("e4m3" if fp8_on else "fp16"): sampled_parity(ctx, coords_m, pos_m, area, run_foci[:F])}
             k2 = max(200, min(args.steps, 500))     # secondary legs: their own floor, whatever --steps says
@@ -794,7 +831,7 @@ def main():
             us = ctx.bf_time(50)
             out["kernel1"] = {"us_per_solve": float(np.median(us)), "foci": F, "elements": N, "dtype": "f64", **kernel1_cpu(arr, run_foci[:F])}
             out["end_to_end"] = end_to_end(ol, arr, setup, target, sweep, run_idx[:F], args)
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             pos_m, _, area, _, _ = arr.element_table()
             out["cpu_baseline"] = cpu_baseline(pos_m, area, coords_m, run_foci[0], args.cpu_seconds)
             out["cpu_baseline_c"] = cpu_baseline_c(pos_m, area, coords_m, run_foci[0], min(args.cpu_seconds, 10.0))

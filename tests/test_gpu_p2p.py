@@ -142,14 +142,14 @@ def test_bench_self_launches_its_ranks():
         env.pop(k, None)
     env["OLX_P2P_TIMEOUT_S"] = "60"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "0", "--gather", "p2p", "--steps", "5", "--warmup", "2",
-                        "--grid", "128", "--spacing-mm", "0.5", "--no-extras", "--cpu-seconds", "0"], env=env, cwd=ROOT, stdout=subprocess.PIPE,
+                        "--grid", "128", "--spacing-mm", "0.5", "--no-extras", "--cpu-seconds", "0", "--full"], env=env, cwd=ROOT, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout[-2000:]
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["steps"] == 5 and out["value"] > 0
-    # default exchange of an N > 1 run: the aggregate (reduce-scatter of max |p| / mean intensity); north_star's all-gather is timed beside it
+    # default exchange of an N > 1 run: the aggregate (reduce-scatter of max |p| / mean intensity); north_star's all-gather is timed beside it (--full)
     assert out["scaling_claim"] == "aggregate" and out["n_ranks_seen"] == 2 and "p2p" in out["n_ranks_seen_by"] and out["degraded"] is False
     assert out["config"]["reassembly"].startswith("p2p-aggregate")
     assert out["config"]["with_allgather"]["value"] > 0 and out["config"]["without_exchange"]["value"] > 0
