@@ -47,6 +47,7 @@ extern "C" {
 #define OLX_OUT_PMAG 1u      /* |p| [Pa]  -> p_max and p_min of kwave_if.py:131-139 */
 #define OLX_OUT_INTENSITY 2u /* 1e-4 |p|^2 / (2 rho c) [W/cm^2]  (kwave_if.py:140-144) */
 #define OLX_OUT_COMPLEX 4u   /* (re, im) interleaved, float32 */
+#define OLX_OUT_PMAX 64u     /* pulsed plans (olx_field_pulse) only: also keep the peak positive pressure p_max [Pa] (olx_field_fetch_pmax) */
 /* accuracy / speed options of olx_field_plan (OR-ed into flags; see the accuracy note there) */
 #define OLX_FIELD_FP8_CORRECTION 8u   /* accepted for source compatibility: asks for what is the default since ABI v2 */
 #define OLX_FIELD_FP16_CORRECTION 32u /* opt out of the e4m3 correction products: three fp16 products everywhere (<= 2e-6) */
@@ -215,6 +216,22 @@ int olx_field_medium_model(olx_ctx *ctx, int model);
  * layered-ray kernels of olx_field_set_medium -- which it excludes.  Example: the reference's example_protocol.json (water with
  * 0.0022 dB/cm/MHz). */
 int olx_field_absorption(olx_ctx *ctx, double np_per_m);
+
+/* Pulsed (tone-burst) field model for the plans that follow, the reference's time-domain run (sim/kwave_if.py:100-139 drives every
+ * element with `cycles` cycles sampled at `dt` and records the peak pressures up to t_end); n_t = 0 (the default) = the continuous-wave
+ * model of every kernel above.  With n_t > 0 the field of focus f is the time-domain Rayleigh sum (kernel 2p)
+ *   p(v, t) = sum_e w_e exp(-a d_e) / d_e cos(2 pi f0 (t - t_e)) 1[0 <= t - t_e < cycles / f0],  t_e = floor(tau_e / dt) dt + d_e / c
+ * sampled at t_k = k dt, k = 0 .. n_t - 1 (w_e, d_e and a as in the CW model).  The plan's OLX_OUT_PMAG slot then holds the peak negative
+ * pressure p_min = max(0, -min_k p) -- what the analysis, the scaling and the intensity 1e-4 p_min^2 / (2 rho c) read -- and
+ * OLX_OUT_PMAX asks for p_max = max(0, max_k p) as one more resident volume: olx_field_scale, olx_field_scale_aggregate and the scaling
+ * of olx_solution_analyze scale it too, the device aggregate also forms max_f p_max_f (olx_aggregate_fetch_pmax).  Homogeneous media
+ * (with olx_field_absorption) and any element geometry; a pulsed plan refuses a slab, a communicator, OLX_FIELD_DIRECTIVITY,
+ * OLX_OUT_COMPLEX and olx_field_set_medium.  cycles > 0 and dt > 0 [s] are used as given (the caller applies its defaults). */
+int olx_field_pulse(olx_ctx *ctx, double cycles, double dt, int n_t);
+/* p_max of every planned focus of the last pulsed launch ([F * voxels] floats), as scaled since. */
+int olx_field_fetch_pmax(olx_ctx *ctx, float *pmax_out);
+/* max_f p_max_f of the last device aggregate of a pulsed plan's volumes ([voxels] floats). */
+int olx_aggregate_fetch_pmax(olx_ctx *ctx, float *pmax_out);
 
 /* Bind host volumes (e.g. a Solution loaded from disk) as the context's resident result so
  * that the aggregate / scale / masked-peak entry points can run on them: [n_foci * slab voxels]

@@ -1,0 +1,186 @@
+// kernel 2p (field_pulse_k): pulsed (tone-burst) field -- peak positive / peak negative pressure over a sampled time axis.
+// gfx950 (CDNA4, wave64) only.  Definition: DESIGN.md section 2 ("pulsed model"), fp64 oracle tests/pulsed_oracle.py.
+//
+// For focus f, voxel v and element e, with d_e = max(|r_v - r_e|, min(spacing) / 2), w_e = a_e P0 S_e / lambda and absorption a [Np/m]:
+//     drive     s_e(t) = a_e P0 sin(2 pi f0 (t - tau~_e)) for 0 <= t - tau~_e < T,  T = cycles / f0,  tau~_e = floor(tau_e / dt) dt
+//     field     p(v, t) = sum_e w_e exp(-a d_e) / d_e cos(2 pi f0 (t - t_e)) 1[0 <= t - t_e < T],   t_e = tau~_e + d_e / c
+//     samples   t_k = k dt, k = 0 .. n_t - 1
+//     outputs   p_max = max(0, max_k p(v, t_k)),  p_min = max(0, -min_k p(v, t_k)),  intensity = 1e-4 p_min^2 / (2 rho c)
+// Element e is active at samples k0_e <= k < k1_e, k0_e = m_e + ceil(q_e), k1_e = m_e + ceil(q_e + T / dt), m_e = floor(tau_e / dt),
+// q_e = d_e / (c dt).  Those two integers are formed in fp64 (distance, q, ceil): a 1-ulp fp32 error in t_e / dt moves a whole element
+// term in or out of a sample, ~1/N of the focal peak.  Everything else is fp32.
+//
+// Between consecutive arrivals / burst ends the complex envelope is constant:
+//     p(v, t_k) = Re(e^{j theta_k} C_k),  C_k = sum_{e active at k} c_e,  c_e = w_e exp(-a d_e) / d_e e^{-j phi_e}
+// with the phases relative to a per-voxel time origin K (the first sample of the voxel's window): theta_k = 2 pi f0 dt (k - K),
+// phi_e = 2 pi frac(f0 dt (m_e - K + q_e)) -- fp64 up to the fractional part, so the fp32 phase error does not grow with t_e.
+// One wave per voxel: every lane walks elements lane, lane + 64, ...:
+//   1. window [K, K_end): min / max of the arrival and burst-end samples from fp32 distances (2 samples of slack), clipped to [0, n_t);
+//   2. per LDS pass of PULSE_L samples: scatter +c_e at sample k0_e and -c_e at k1_e into a difference array (ds_add_f32; samples
+//      before the pass go to its slot 0, samples after it are dropped), prefix-scan it across the wave (21 contiguous samples per lane,
+//      then a wave scan of the lane totals), evaluate p at every sample of the pass and keep the lane's max / min;
+//   3. wave max / min, one lane stores.
+// Single-pass capacity: PULSE_L = 64 x 21 = 1344 samples per voxel window (20 cycles at 400 kHz on a 0.25 mm grid with the default
+// dt = 0.5 x 0.25 mm / 1500 m/s: T / dt = 600 samples + the arrival spread of a 256-element array, ~1100 in all).  Longer windows take
+// ceil(window / 1344) passes, each re-walking the elements (the time axis is split, nothing else changes).
+#include "k_types.hip.h"
+#include "olx_ctx.h"
+#include "olx_launch.h"
+
+namespace olx {
+
+constexpr int PULSE_SEG = 21;                    // contiguous samples per lane and pass (odd: the 64 lanes' segments start on distinct LDS banks)
+constexpr int PULSE_L = 64 * PULSE_SEG;          // samples per LDS pass
+constexpr int PULSE_WAVES = 4;                   // waves per block, one voxel each (2 x 1344 floats = 10.5 KiB of LDS per wave)
+
+// wave-level ordering of LDS traffic between the scatter, scan and clear phases (the lanes of one wave read each other's samples)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+}
+
+// per (focus, element): { x, y, z [m], m_e = floor(tau_e / dt) } fp64 and w_e = a_e P0 S_e / lambda fp32
+__global__ __launch_bounds__(256) void pulse_table_k(const double* __restrict__ pos, const double* __restrict__ area, const double* __restrict__ delays,
+                                                     const double* __restrict__ apod, int n, int n_foci, double dt, double wscale,
+                                                     double4* __restrict__ tab, float* __restrict__ w) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * n_foci) return;
+    const int e = t % n;
+    tab[t] = make_double4(pos[e], pos[n + e], pos[2 * n + e], floor(delays[t] / dt));
+    w[t] = (float)(apod[t] * area[e] * wscale);
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+    return v;
+}
+
+__global__ __launch_bounds__(64 * PULSE_WAVES) void field_pulse_k(const double4* __restrict__ tab, const float* __restrict__ wtab, const PulseParams P,
+                                                                  float* __restrict__ pmin_out, float* __restrict__ pmax_out, float* __restrict__ inten_out) {
+    __shared__ float lds[PULSE_WAVES][2][PULSE_L];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long v = (long long)blockIdx.x * PULSE_WAVES + wave;
+    if (v >= P.vox) return;                      // (whole waves: nothing below synchronises across waves)
+    const int f = blockIdx.y;
+    float* re = lds[wave][0];
+    float* im = lds[wave][1];
+    const int plane = P.ny * P.nz;
+    const int i = (int)(v / plane), j = (int)((v % plane) / P.nz), k = (int)(v % P.nz);
+    const double px = P.ox + i * P.hx, py = P.oy + j * P.hy, pz = P.oz + k * P.hz;
+    const double4* T = tab + (size_t)f * P.n_el;
+    const float* W = wtab + (size_t)f * P.n_el;
+
+    // 1. the voxel's window of samples (fp32 distances: only its ends move, by the slack)
+    float umin = 3.0e38f, umax = -3.0e38f;
+    for (int e = lane; e < P.n_el; e += 64) {
+        if (W[e] == 0.f) continue;
+        const double4 el = T[e];
+        const float dx = (float)(px - el.x), dy = (float)(py - el.y), dz = (float)(pz - el.z);
+        const float d = fmaxf(sqrtf(fmaf(dx, dx, fmaf(dy, dy, dz * dz))), P.dmin_f);
+        const float u = (float)el.w + d * P.inv_cdt_f;
+        umin = fminf(umin, u); umax = fmaxf(umax, u);
+    }
+    umin = wave_min(umin); umax = wave_max(umax);
+    const long long vf = (long long)f * P.vox + v;
+    if (umin > umax) {                            // no driven element
+        if (lane == 0) { pmin_out[vf] = 0.f; if (pmax_out) pmax_out[vf] = 0.f; if (inten_out) inten_out[vf] = 0.f; }
+        return;
+    }
+    const double lo = fmax(floor((double)umin) - 2.0, 0.0);
+    const double hi = fmin(ceil((double)umax + P.tdt) + 2.0, (double)P.n_t);          // exclusive
+
+    float pmax = 0.f, pmin = 0.f;                 // (samples outside the window are 0: they bound both from the zero side)
+    const int s0 = lane * PULSE_SEG;
+#pragma unroll
+    for (int s = 0; s < PULSE_SEG; ++s) { re[s0 + s] = 0.f; im[s0 + s] = 0.f; }
+    for (double base = lo; base < hi; base += PULSE_L) {
+        wave_lds_sync();
+        // 2a. scatter the element terms into the difference array of this pass
+        for (int e = lane; e < P.n_el; e += 64) {
+            const float we = W[e];
+            if (we == 0.f) continue;
+            const double4 el = T[e];
+            const double dx = px - el.x, dy = py - el.y, dz = pz - el.z;
+            const double d = fmax(sqrt(fma(dx, dx, fma(dy, dy, dz * dz))), P.dmin);
+            const double q = d * P.inv_cdt;
+            const double k0 = el.w + ceil(q), k1 = el.w + ceil(q + P.tdt);
+            if (k0 >= base + PULSE_L || k1 <= base || k1 <= k0) continue;      // after this pass, or over before it: nothing here
+            double cyc = P.f0dt * ((el.w - lo) + q);
+            cyc -= floor(cyc);
+            const float ph = (float)cyc;
+            const float df = (float)d;
+            float a = we * __builtin_amdgcn_rcpf(df);
+            if (P.absorb > 0.f) a *= __expf(-P.absorb * df);
+            const float cr = a * __builtin_amdgcn_cosf(ph), ci = -a * __builtin_amdgcn_sinf(ph);
+            const int i0 = k0 <= base ? 0 : (int)(k0 - base);
+            if (OLX_IN(i0, PULSE_L, 0)) { atomicAdd(&re[i0], cr); atomicAdd(&im[i0], ci); }
+            if (k1 < base + PULSE_L) {
+                const int i1 = (int)(k1 - base);
+                if (OLX_IN(i1, PULSE_L, 1)) { atomicAdd(&re[i1], -cr); atomicAdd(&im[i1], -ci); }
+            }
+        }
+        wave_lds_sync();
+        // 2b. prefix scan: the lane's own segment, then the exclusive scan of the segment totals across the wave
+        float sr[PULSE_SEG], si[PULSE_SEG];
+        float tr = 0.f, ti = 0.f;
+#pragma unroll
+        for (int s = 0; s < PULSE_SEG; ++s) {
+            sr[s] = re[s0 + s]; si[s] = im[s0 + s];
+            tr += sr[s]; ti += si[s];
+            sr[s] = tr; si[s] = ti;
+        }
+        float cr = tr, ci = ti;                  // inclusive scan of the totals
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float ur = __shfl_up(cr, o), ui = __shfl_up(ci, o);
+            if (lane >= o) { cr += ur; ci += ui; }
+        }
+        cr -= tr; ci -= ti;                      // ... exclusive: the carry into this lane's segment
+        wave_lds_sync();
+#pragma unroll
+        for (int s = 0; s < PULSE_SEG; ++s) { re[s0 + s] = 0.f; im[s0 + s] = 0.f; }     // (cleared for the next pass)
+        // 2c. p at the pass's samples: theta_k = 2 pi f0 dt (k - lo), exact at the segment's first sample, rotated by 2 pi f0 dt after it
+        const double kfirst = base + s0;
+        double cyc = P.f0dt * (kfirst - lo);
+        cyc -= floor(cyc);
+        float er = __builtin_amdgcn_cosf((float)cyc), ei = __builtin_amdgcn_sinf((float)cyc);
+        const int nvalid = (int)fmin(fmax(hi - kfirst, 0.0), (double)PULSE_SEG);
+#pragma unroll
+        for (int s = 0; s < PULSE_SEG; ++s) {
+            const float p = er * (cr + sr[s]) - ei * (ci + si[s]);
+            if (s < nvalid) { pmax = fmaxf(pmax, p); pmin = fminf(pmin, p); }
+            const float nr = er * P.rot_c - ei * P.rot_s;
+            ei = fmaf(er, P.rot_s, ei * P.rot_c);
+            er = nr;
+        }
+    }
+    pmax = wave_max(pmax); pmin = wave_min(pmin);
+    if (lane == 0 && OLX_IN(vf, P.vox * P.n_foci, 2)) {
+        const float pn = 0.f - pmin;          // (+0 where nothing arrived)
+        pmin_out[vf] = pn;
+        if (pmax_out) pmax_out[vf] = pmax;
+        if (inten_out) inten_out[vf] = P.inten_scale * pn * pn;
+    }
+}
+
+OLX_BOUNDS_READER(pulse)
+
+}  // namespace olx
+
+using namespace olx;
+
+void olx_launch_pulse(olx_ctx* c, float* pm) {
+    const PulseParams& P = c->pulse;
+    const int fn = c->n_el * c->plan_foci;
+    hipLaunchKernelGGL(pulse_table_k, dim3((fn + 255) / 256), dim3(256), 0, c->stream, c->d_pos, c->d_area, c->d_delays, c->d_apod, c->n_el,
+                       c->plan_foci, c->pulse_dt, c->p0_pa * c->freq / c->c, c->d_ptab, c->d_pw);
+    hipLaunchKernelGGL(field_pulse_k, dim3((unsigned)((P.vox + PULSE_WAVES - 1) / PULSE_WAVES), c->plan_foci), dim3(64 * PULSE_WAVES), 0, c->stream,
+                       c->d_ptab, c->d_pw, P, pm, (c->flags & OLX_OUT_PMAX) ? c->d_pmax : nullptr, (c->flags & OLX_OUT_INTENSITY) ? c->d_inten : nullptr);
+}

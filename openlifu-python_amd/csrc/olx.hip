@@ -63,7 +63,7 @@ int olx_ctx_destroy(olx_ctx* c) {
     void* ptrs[] = {c->d_pos, c->d_nrm, c->d_area, c->d_delays, c->d_apod, c->d_foci, c->d_M, c->d_tab,
                     c->d_pmag[0], c->d_pmag[1], c->d_inten, c->d_cplx, c->d_agg_p, c->d_agg_i,
                     c->d_scale, c->d_gather, c->d_peakA, c->d_peak, c->d_perm, c->d_coords, c->d_bfrag, c->d_colinfo, c->d_wint, c->d_med, c->d_plane_k, c->d_plane_of_k,
-                    c->d_an, c->d_inv2z, c->d_kfirst, c->d_klast, c->d_slot, c->d_jobs, c->d_med_layer, c->d_layer_lo, c->d_layer_hi, c->d_U[0], c->d_U[1], c->d_Utex, c->d_sig, c->d_cell, c->d_afrag, c->d_tab2, c->d_cpblocks};
+                    c->d_an, c->d_inv2z, c->d_kfirst, c->d_klast, c->d_slot, c->d_jobs, c->d_med_layer, c->d_layer_lo, c->d_layer_hi, c->d_U[0], c->d_U[1], c->d_Utex, c->d_sig, c->d_cell, c->d_afrag, c->d_tab2, c->d_cpblocks, c->d_pmax, c->d_agg_pmax, c->d_ptab, c->d_pw};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -73,10 +73,11 @@ int olx_ctx_destroy(olx_ctx* c) {
 const char* olx_last_error(const olx_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 #ifdef OLX_DEBUG_BOUNDS   // debug build (k_types.hip.h): the kernels' index checks report here
-extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); }
+extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); }
 static int report_bounds(olx_ctx* c) {
     struct { const char* name; int (*read)(unsigned*); } units[] = {{"2g (k_coset2.hip)", olx_dbg_bounds_cosetp}, {"2e (k_coset.hip)", olx_dbg_bounds_coset},
-                                                                     {"2f (k_toep.hip)", olx_dbg_bounds_toep}, {"2m (k_hmarch.hip)", olx_dbg_bounds_hmarch}};
+                                                                     {"2f (k_toep.hip)", olx_dbg_bounds_toep}, {"2m (k_hmarch.hip)", olx_dbg_bounds_hmarch},
+                                                                     {"2p (k_pulse.hip)", olx_dbg_bounds_pulse}};
     int rc = OLX_OK;
     for (auto& u : units) {
         unsigned w[4] = {0, 0, 0, 0};
@@ -938,6 +939,75 @@ static int pack_if_needed(olx_ctx* c) {
     return OLX_OK;
 }
 
+}  // extern "C"
+
+// olx_field_plan of a pulsed model (olx_field_pulse, kernel 2p): whole grid, homogeneous medium, one launch of field_pulse_k
+static int plan_pulse(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_foci, double freq, double cs, double rho, double p0_pa,
+                      unsigned flags) {
+    if (flags & ~(OLX_OUT_PMAG | OLX_OUT_INTENSITY | OLX_OUT_PMAX | OLX_FIELD_FP8_CORRECTION | OLX_FIELD_FP16_CORRECTION))
+        return fail(c, OLX_EINVAL, "olx_field_plan: a pulsed plan (olx_field_pulse) takes OLX_OUT_PMAG / OLX_OUT_INTENSITY / OLX_OUT_PMAX only "
+                    "(no complex output, no OLX_FIELD_DIRECTIVITY), flags 0x%x", flags);
+    if (slab && !(slab->x_begin == 0 && slab->x_count == g->n[0]))
+        return fail(c, OLX_EINVAL, "olx_field_plan: a pulsed plan (olx_field_pulse) covers the whole grid: no slab");
+    if (c->comm_active()) return fail(c, OLX_ESTATE, "olx_field_plan: a pulsed plan (olx_field_pulse) has no multi-GPU path: destroy the communicator first");
+    const long long vox = (long long)g->n[0] * g->n[1] * g->n[2];
+    if (vox > (1ll << 31) * 4) return fail(c, OLX_EINVAL, "olx_field_plan: grid too large for a pulsed plan");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t total = (size_t)vox * n_foci;
+    c->grid = *g; c->slab = olx_slab{0, g->n[0]}; c->plan_foci = n_foci; c->hetero = false; c->marched = false;
+    c->agg_local = -1; c->agg_total = 0;
+    c->freq = freq; c->c = cs; c->rho = rho; c->p0_pa = p0_pa; c->flags = flags; c->plan_absorb = c->absorb_np_m;
+    c->directivity = false; c->nbuf = 1; c->cur = 0;
+    if (c->out_cap < total) {
+        for (float** p : {&c->d_pmag[0], &c->d_pmag[1], &c->d_inten, &c->d_cplx, &c->d_agg_p, &c->d_agg_i}) { if (*p) hipFree(*p); *p = nullptr; }
+        c->out_cap = 0;
+    }
+    if (!c->d_pmag[0]) { HIPCHK(c, hipMalloc((void**)&c->d_pmag[0], sizeof(float) * total)); c->out_cap = total; }
+    if ((flags & OLX_OUT_INTENSITY) && !c->d_inten) HIPCHK(c, hipMalloc((void**)&c->d_inten, sizeof(float) * c->out_cap));
+    if ((flags & OLX_OUT_PMAX) && c->pmax_cap < total) {
+        if (c->d_pmax) hipFree(c->d_pmax);
+        c->d_pmax = nullptr; c->pmax_cap = 0;
+        HIPCHK(c, hipMalloc((void**)&c->d_pmax, sizeof(float) * total));
+        c->pmax_cap = total;
+    }
+    const size_t fn = (size_t)n_foci * c->n_el;
+    if (c->ptab_cap < fn) {
+        for (void* p : {(void*)c->d_ptab, (void*)c->d_pw}) if (p) hipFree(p);
+        c->d_ptab = nullptr; c->d_pw = nullptr; c->ptab_cap = 0;
+        HIPCHK(c, hipMalloc((void**)&c->d_ptab, sizeof(double4) * fn));
+        HIPCHK(c, hipMalloc((void**)&c->d_pw, sizeof(float) * fn));
+        c->ptab_cap = fn;
+    }
+    // (the scans -- aggregate, scale, analysis -- read the volume shape from fp)
+    FieldParams& F = c->fp;
+    F.nx = g->n[0]; F.ny = g->n[1]; F.nz = g->n[2]; F.n_el = c->n_el; F.x_begin = 0; F.vox = vox;
+    F.flags = (flags & 3u) | OLX_OUT_PMAG; F.inten_scale = (float)(1e-4 / (2.0 * rho * cs));
+    PulseParams& P = c->pulse;
+    const double dt = c->pulse_dt;
+    P.n_el = c->n_el; P.n_foci = n_foci; P.n_t = c->pulse_nt; P.ny = g->n[1]; P.nz = g->n[2];
+    P.ox = g->origin[0]; P.oy = g->origin[1]; P.oz = g->origin[2];
+    P.hx = g->spacing[0]; P.hy = g->spacing[1]; P.hz = g->spacing[2];
+    P.dmin = 0.5 * std::min({g->spacing[0], g->spacing[1], g->spacing[2]});
+    P.inv_cdt = 1.0 / (cs * dt);
+    P.tdt = c->pulse_cycles / (freq * dt);
+    P.f0dt = freq * dt;
+    P.dmin_f = (float)P.dmin; P.inv_cdt_f = (float)P.inv_cdt;
+    P.absorb = (float)c->absorb_np_m;
+    P.rot_c = (float)std::cos(2.0 * M_PI * P.f0dt); P.rot_s = (float)std::sin(2.0 * M_PI * P.f0dt);
+    P.inten_scale = F.inten_scale;
+    P.vox = vox;
+    c->pulsed = true; c->pmax_live = false; c->agg_pmax_valid = false;
+    char nm[128];
+    snprintf(nm, sizeof nm, "field_pulse_k (pulsed: %d samples, %.4g samples per burst)", c->pulse_nt, P.tdt);
+    c->variant = nm;
+    c->packed_version = ~0ull;
+    c->planned = true; c->uploaded = false;
+    return OLX_OK;
+}
+
+extern "C" {
+
 int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_foci, double freq, double cs,
                    double rho, double p0_pa, unsigned flags) {
     if (!c) return OLX_EINVAL;
@@ -949,6 +1019,8 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
         if (g->n[a] < 1 || !(g->spacing[a] > 0)) return fail(c, OLX_EINVAL, "olx_field_plan: bad grid axis %d", a);
     if (!(freq > 0) || !(cs > 0) || !(rho > 0)) return fail(c, OLX_EINVAL, "olx_field_plan: freq, c, rho must be > 0");
     if (!(flags & (OLX_OUT_PMAG | OLX_OUT_INTENSITY | OLX_OUT_COMPLEX))) return fail(c, OLX_EINVAL, "olx_field_plan: no outputs selected");
+    if (c->pulse_nt > 0) return plan_pulse(c, g, slab, n_foci, freq, cs, rho, p0_pa, flags);
+    if (flags & OLX_OUT_PMAX) return fail(c, OLX_EINVAL, "olx_field_plan: OLX_OUT_PMAX needs a pulsed plan (olx_field_pulse)");
     if (flags & ~(OLX_OUT_PMAG | OLX_OUT_INTENSITY | OLX_OUT_COMPLEX | OLX_FIELD_FP8_CORRECTION | OLX_FIELD_FP16_CORRECTION | OLX_FIELD_DIRECTIVITY)) return fail(c, OLX_EINVAL, "olx_field_plan: unknown flag bits 0x%x", flags);
     if ((flags & OLX_FIELD_DIRECTIVITY) && c->h_xaxis.size() != 3 * (size_t)c->n_el)
         return fail(c, OLX_ESTATE, "olx_field_plan: OLX_FIELD_DIRECTIVITY needs olx_set_element_apertures");
@@ -961,7 +1033,7 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
         // dependent part (configure_variant + packing) is redone at the next launch anyway when the table changed.
         std::string env;   // the developer switches the plan below reads
         for (const char* name : {"OLX_FIELD_VARIANT", "OLX_FP8_CORRECTION", "OLX_EXP_TOEP_SAW", "OLX_EXP_TOEP_NM", "OLX_EXP_KGRP"}) { const char* e = getenv(name); env += e ? e : ""; env += '|'; }
-        const bool same = c->planned && !c->uploaded && !c->hetero && memcmp(&c->grid, g, sizeof *g) == 0 && c->slab.x_begin == s.x_begin &&
+        const bool same = c->planned && !c->uploaded && !c->hetero && !c->pulsed && memcmp(&c->grid, g, sizeof *g) == 0 && c->slab.x_begin == s.x_begin &&
                           c->slab.x_count == s.x_count && c->plan_foci == n_foci && c->freq == freq && c->c == cs && c->rho == rho &&
                           c->p0_pa == p0_pa && c->flags == flags && c->plan_absorb == c->absorb_np_m && c->nbuf == (c->comm_active() ? olx_ctx::NBUF : 1) && c->plan_env == env;
         c->plan_env = env;
@@ -973,6 +1045,7 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->grid = *g; c->slab = s; c->plan_foci = n_foci; c->hetero = false;
+    c->pulsed = false; c->pmax_live = false; c->agg_pmax_valid = false;
     c->agg_local = -1; c->agg_total = 0;   // aggregate over all planned foci unless olx_field_aggregate_counts says otherwise
     c->freq = freq; c->c = cs; c->rho = rho; c->p0_pa = p0_pa; c->flags = flags; c->plan_absorb = c->absorb_np_m;
     const long long vox = (long long)s.x_count * g->n[1] * g->n[2];
@@ -1123,6 +1196,18 @@ int olx_field_launch(olx_ctx* c) {
     if (c->uploaded) return fail(c, OLX_ESTATE, "olx_field_launch: resident volumes were uploaded, not planned");
     if (c->n_foci != c->plan_foci) return fail(c, OLX_ESTATE, "olx_field_launch: steering table changed shape since plan");
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->pulsed) {     // kernel 2p: its own table from the steering, no variant packing
+        if (c->flags & OLX_OUT_PMAX) c->pmax_live = false;
+        c->agg_pmax_valid = false;
+        const bool prof = c->prof_on && (size_t)(2 * c->prof_n + 1) < c->prof_ev.size();
+        if (prof) HIPCHK(c, hipEventRecord(c->prof_ev[2 * c->prof_n], c->stream));
+        olx_launch_pulse(c, c->d_pmag[0]);
+        HIPCHK(c, hipGetLastError());
+        if (prof) { HIPCHK(c, hipEventRecord(c->prof_ev[2 * c->prof_n + 1], c->stream)); c->prof_n++; }
+        c->pmax_live = (c->flags & OLX_OUT_PMAX) != 0;
+        c->cur = 0;
+        return OLX_OK;
+    }
     int rc = pack_if_needed(c);
     if (rc) return rc;
     const int b = (c->nbuf == 2) ? (c->cur ^ 1) : 0;
@@ -1335,6 +1420,15 @@ int olx_field_fetch_all(olx_ctx* c, float* pmag, float* intensity) {
     return rc;
 }
 
+int olx_field_fetch_pmax(olx_ctx* c, float* pmax_out) {
+    if (!c) return OLX_EINVAL;
+    if (!pmax_out) return fail(c, OLX_EINVAL, "olx_field_fetch_pmax: null output");
+    if (!c->pmax_live) return fail(c, OLX_ESTATE, "olx_field_fetch_pmax: no p_max volumes (a launched pulsed plan with OLX_OUT_PMAX)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return fetch_to_host(c, pmax_out, c->d_pmax, sizeof(float) * (size_t)c->fp.vox * c->plan_foci);
+}
+
 int olx_field(olx_ctx* c, const olx_grid* g, int n_foci, double freq, double cs, double rho, double p0_pa,
               float* pmag_out, float* intensity_out) {
     if (!c) return OLX_EINVAL;
@@ -1357,6 +1451,7 @@ int olx_field_set_medium(olx_ctx* c, const float* sound_speed, const float* atte
     if (!c) return OLX_EINVAL;
     if (!c->planned || c->uploaded) return fail(c, OLX_ESTATE, "olx_field_set_medium: call olx_field_plan first");
     if (c->directivity) return fail(c, OLX_EINVAL, "olx_field_set_medium: OLX_FIELD_DIRECTIVITY is not available with a heterogeneous medium");
+    if (c->pulsed) return fail(c, OLX_EINVAL, "olx_field_set_medium: the pulsed model (olx_field_pulse) has no heterogeneous-medium kernel");
     if (c->absorb_np_m > 0) return fail(c, OLX_EINVAL, "olx_field_set_medium: a uniform absorption (olx_field_absorption) and a heterogeneous medium exclude each other: put the absorption into the medium volumes");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1536,6 +1631,17 @@ int olx_field_absorption(olx_ctx* c, double np_per_m) {
     return OLX_OK;
 }
 
+int olx_field_pulse(olx_ctx* c, double cycles, double dt, int n_t) {
+    if (!c) return OLX_EINVAL;
+    if (n_t < 0) return fail(c, OLX_EINVAL, "olx_field_pulse: n_t must be >= 0 (0 = continuous wave)");
+    if (n_t > 0 && (!(cycles > 0) || !std::isfinite(cycles) || !(dt > 0) || !std::isfinite(dt)))
+        return fail(c, OLX_EINVAL, "olx_field_pulse: cycles and dt must be finite and > 0");
+    c->pulse_nt = n_t;
+    c->pulse_cycles = n_t > 0 ? cycles : 0.0;
+    c->pulse_dt = n_t > 0 ? dt : 0.0;
+    return OLX_OK;
+}
+
 int olx_field_medium_layering(olx_ctx* c, int planes_per_layer) {
     if (!c) return OLX_EINVAL;
     if (planes_per_layer < 1 || planes_per_layer > 4096) return fail(c, OLX_EINVAL, "olx_field_medium_layering: planes_per_layer must be in [1, 4096]");
@@ -1576,6 +1682,7 @@ int olx_field_upload(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_
     c->grid = *g; c->slab = s; c->plan_foci = n_foci;
     c->agg_local = -1; c->agg_total = 0;   // like olx_field_plan: the counts of a former padded sweep do not describe these volumes
     c->hetero = false; c->marched = false;
+    c->pulsed = false; c->pmax_live = false; c->agg_pmax_valid = false;    // (an upload holds no p_max)
     c->fp.nx = s.x_count; c->fp.ny = g->n[1]; c->fp.nz = g->n[2]; c->fp.vox = vox;
     c->flags = OLX_OUT_PMAG | (intensity ? OLX_OUT_INTENSITY : 0u);
     c->cur = 0; c->nbuf = 1;
@@ -1596,7 +1703,7 @@ int olx_field_time(olx_ctx* c, int iters, float* ms_each) {
     T.ev.assign(iters + 1, nullptr);
     std::vector<hipEvent_t>& ev = T.ev;
     for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
-    int rc = pack_if_needed(c);
+    int rc = c->pulsed ? OLX_OK : pack_if_needed(c);     // (kernel 2p builds its own table at every launch)
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(ev[0], c->stream));
     for (int i = 0; i < iters; ++i) {
@@ -1611,6 +1718,25 @@ int olx_field_time(olx_ctx* c, int iters, float* ms_each) {
 }
 
 static int aggregate_local(olx_ctx* c, bool with_p, bool with_i);
+// Pulsed plans: what the scans do to |p| (the p_min slot) they do to the resident p_max volumes as well -- scale them by the per-focus
+// factors already on the device (`scale`: F floats, NULL = no scaling) and, with `aggregate`, form max_f p_max_f.  Nothing without them.
+static int pmax_post(olx_ctx* c, const float* scale, bool aggregate) {
+    if (!c->pmax_live) return OLX_OK;
+    if (scale) hipLaunchKernelGGL(field_scale_k, dim3(1024, c->plan_foci), dim3(256), 0, c->stream, c->d_pmax, (float*)nullptr, (float*)nullptr, scale, c->fp.vox);
+    if (aggregate) {
+        if (c->agg_pmax_cap < (size_t)c->fp.vox) {
+            if (c->d_agg_pmax) hipFree(c->d_agg_pmax);
+            c->d_agg_pmax = nullptr; c->agg_pmax_cap = 0;
+            HIPCHK(c, hipMalloc((void**)&c->d_agg_pmax, sizeof(float) * c->fp.vox));
+            c->agg_pmax_cap = (size_t)c->fp.vox;
+        }
+        hipLaunchKernelGGL(field_aggregate_k, dim3(2048), dim3(256), 0, c->stream, c->d_pmax, (const float*)nullptr, c->plan_foci, (long long)c->fp.vox,
+                           1.0f / (float)c->plan_foci, c->d_agg_pmax, (float*)nullptr);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (aggregate) c->agg_pmax_valid = true;
+    return OLX_OK;
+}
 }
 static void fill_scan_params(const olx_ctx* c, PeakParams& P, const double* aspect);
 // Blocks per focus of the masked scans: ~2048 blocks in flight over all foci (8 per CU, all resident), each living long enough
@@ -1733,6 +1859,7 @@ const char* olx_field_variant(const olx_ctx* c) { return (c && c->planned) ? c->
 static int aggregate_local(olx_ctx* c, bool with_p, bool with_i) {
     const size_t vox = (size_t)c->fp.vox;
     { int rc_ = aggregate_buffers_free(c); if (rc_) return rc_; }
+    if (with_p) { int rc_ = pmax_post(c, nullptr, true); if (rc_) return rc_; }
     if (with_p && !c->d_agg_p) HIPCHK(c, hipMalloc((void**)&c->d_agg_p, sizeof(float) * c->out_cap));
     if (with_i && !c->d_agg_i) HIPCHK(c, hipMalloc((void**)&c->d_agg_i, sizeof(float) * c->out_cap));
     hipLaunchKernelGGL(field_aggregate_k, dim3(2048), dim3(256), 0, c->stream, with_p ? c->d_pmag[c->cur] : nullptr,
@@ -1781,6 +1908,8 @@ int olx_field_scale(olx_ctx* c, const double* scale, int n_foci) {
                        (c->flags & OLX_OUT_INTENSITY) ? c->d_inten : nullptr,
                        (c->flags & OLX_OUT_COMPLEX) ? c->d_cplx : nullptr, c->d_scale, c->fp.vox);
     HIPCHK(c, hipGetLastError());
+    { int rc_ = pmax_post(c, c->d_scale, false); if (rc_) return rc_; }
+    c->agg_pmax_valid = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return OLX_OK;
 }
@@ -1810,6 +1939,7 @@ int olx_field_scale_aggregate(olx_ctx* c, const double* scale, int n_foci) {
     hipLaunchKernelGGL(field_scale_aggregate_k, dim3(4096), dim3(256), 0, c->stream, c->d_pmag[c->cur], c->d_inten, c->d_scale, n_foci,
                        (long long)c->fp.vox, 1.0f / (float)n_foci, c->d_agg_p, c->d_agg_i);
     HIPCHK(c, hipGetLastError());
+    { int rc_ = pmax_post(c, c->d_scale, true); if (rc_) return rc_; }
     HIPCHK(c, hipStreamSynchronize(c->stream));      // (s lives on this frame)
     return OLX_OK;
 }
@@ -2163,6 +2293,7 @@ int olx_solution_analyze_begin(olx_ctx* c, const double* A, const double* ita_we
     if (fused)      // scale + aggregate + peaks + time-average volume (with its global peak) in one pass
         hipLaunchKernelGGL((c->fp.nz & 3) ? field_scale_agg_analyze_k<true> : field_scale_agg_analyze_k<false>, dim3(2048), dim3(256), 0, c->stream, c->d_pmag[c->cur], c->d_inten, reinterpret_cast<const float*>(d + in_sc),
                            reinterpret_cast<const float*>(d + in_w), d_A, F, P, o->r_side_m, 1.0f / (float)F, c->d_agg_p, c->d_agg_i, c->d_wint, d_pk, d_ita + F);
+    if (fused) { int rc_ = pmax_post(c, reinterpret_cast<const float*>(d + in_sc), true); if (rc_) return rc_; }
     else if (quad) hipLaunchKernelGGL(field_analysis_peaks4_k, dim3(scan_blocks(want, F), F), dim3(256), 0, c->stream, pm, c->d_inten, d_A, P, o->r_side_m, d_pk);
     else hipLaunchKernelGGL(field_analysis_peaks_k, dim3((unsigned)std::min<long long>(want, 2048), F), dim3(256), 0, c->stream, pm, c->d_inten, d_A, P, o->r_side_m, d_pk);
     // (2) -3 dB centroid of the mainlobe: cut-off from the peak just found
@@ -2442,6 +2573,15 @@ int olx_aggregate_fetch(olx_ctx* c, float* pmax_out, float* imean_out) {
     if (pmax_out) rc = fetch_to_host(c, pmax_out, c->d_agg_p, sizeof(float) * vox);      // (pipelined staged copy, as the per-focus fetches)
     if (!rc && imean_out) rc = fetch_to_host(c, imean_out, c->d_agg_i, sizeof(float) * vox);
     return rc;
+}
+
+int olx_aggregate_fetch_pmax(olx_ctx* c, float* pmax_out) {
+    if (!c) return OLX_EINVAL;
+    if (!pmax_out) return fail(c, OLX_EINVAL, "olx_aggregate_fetch_pmax: null output");
+    if (!c->agg_pmax_valid) return fail(c, OLX_ESTATE, "olx_aggregate_fetch_pmax: no aggregate of p_max volumes (aggregate a launched pulsed plan with OLX_OUT_PMAX first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return fetch_to_host(c, pmax_out, c->d_agg_pmax, sizeof(float) * (size_t)c->fp.vox);
 }
 
 int olx_allgather_fetch(olx_ctx* c, int rank, float* out) {

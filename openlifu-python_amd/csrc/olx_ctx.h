@@ -116,6 +116,14 @@ struct olx_ctx {
     size_t out_cap = 0; int nbuf = 1; int cur = 0;
     std::string variant;
     std::vector<hipEvent_t> prof_ev; int prof_n = 0; bool prof_on = false;
+    // pulsed model (kernel 2p): the setting of olx_field_pulse for the plans that follow, and what the current plan holds
+    double pulse_cycles = 0, pulse_dt = 0; int pulse_nt = 0;   // n_t = 0: continuous wave
+    bool pulsed = false;                       // the current plan is pulsed: d_pmag holds p_min
+    bool pmax_live = false;                    // d_pmax holds the launched (and possibly scaled) p_max volumes
+    bool agg_pmax_valid = false;               // d_agg_pmax holds max_f p_max_f of them
+    PulseParams pulse{};
+    float* d_pmax = nullptr; size_t pmax_cap = 0; float* d_agg_pmax = nullptr; size_t agg_pmax_cap = 0;
+    double4* d_ptab = nullptr; float* d_pw = nullptr; size_t ptab_cap = 0;
     // comm: RCCL communicator, or the direct peer-to-peer transport (exactly one of comm / p2p is set once initialised)
     P2PState* p2p = nullptr;
     bool comm_active() const { return comm != nullptr || p2p != nullptr; }

@@ -15,3 +15,4 @@ void olx_pack_toep(olx_ctx* c);                      //     its Toeplitz weight 
 void olx_launch_hetero(olx_ctx* c, float* pm);       // 2h  field_hetero_k
 void olx_launch_hmarch(olx_ctx* c, float* pm);       // 2m  field_hmarch_k (marched ray sums: one launch per plane segment)
 void olx_pack_hetero(olx_ctx* c);                    //     its steering table (c->nf foci per launch tile)
+void olx_launch_pulse(olx_ctx* c, float* pm);       // 2p  field_pulse_k (pulsed model, olx_field_pulse; writes p_min to pm)

@@ -140,6 +140,22 @@ struct HeteroParams {
     float kappa;           // kernel 2m's one-sum form: a' = kappa sig in every voxel (0 otherwise)
 };
 
+// kernel 2p (field_pulse_k, k_pulse.hip): pulsed field over a sampled time axis (olx_field_pulse)
+struct PulseParams {
+    int n_el, n_foci, n_t;          // elements, planned foci, samples of the time axis
+    int ny, nz;
+    double ox, oy, oz, hx, hy, hz;  // voxel (0,0,0) position and spacing [m]
+    double dmin;                    // distance clamp min(spacing) / 2 [m]
+    double inv_cdt;                 // 1 / (c dt) [samples per m]
+    double tdt;                     // T / dt = cycles / (f0 dt) [samples]
+    double f0dt;                    // f0 dt [periods per sample]
+    float dmin_f, inv_cdt_f;        // the same in fp32 (window bounds)
+    float absorb;                   // uniform absorption [Np/m]; 0 = lossless
+    float rot_c, rot_s;             // cos, sin (2 pi f0 dt)
+    float inten_scale;              // 1e-4 / (2 rho c)
+    long long vox;
+};
+
 struct PeakParams {
     int nx, ny, nz;
     double ox, oy, oz, hx, hy, hz;  // slab voxel (0,0,0) position and spacing [m]

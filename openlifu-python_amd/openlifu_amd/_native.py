@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("OLX_LIB_PATH") or os.path.join(os.path.dirname(_PKG_D
 OLX_OK, OLX_EINVAL, OLX_ESTATE, OLX_EHIP, OLX_ENOMEM, OLX_ECOMM = 0, -1, -2, -3, -4, -5
 APOD_UNIFORM, APOD_MAXANGLE, APOD_PIECEWISE = 0, 1, 2
 OUT_PMAG, OUT_INTENSITY, OUT_COMPLEX = 1, 2, 4
+OUT_PMAX = 64             # pulsed plans only (olx_field_pulse): also keep p_max; the OUT_PMAG slot then holds p_min
 MEDIUM_MODELS = {"auto": 0, "sampled": 1, "marched": 2}   # OLX_MEDIUM_*
 FIELD_DIRECTIVITY = 16     # opt-in plan flag: far-field piston directivity (needs set_element_apertures; exact per-pair kernel)
 FIELD_FP8_CORRECTION = 8   # (source compatibility: asks for what is the default since ABI v2)
@@ -37,6 +38,7 @@ SYMBOLS = [
     "olx_aggregate_fetch", "olx_field_aggregate_device", "olx_field_analysis_peaks", "olx_field_aggregate_counts", "olx_rccl_path", "olx_bf_time", "olx_field_fetch_all", "olx_field_medium_layering", "olx_field_medium_model", "olx_set_element_apertures",
     "olx_solution_analyze", "olx_scan_time", "olx_comm_export", "olx_comm_import", "olx_comm_transport",
     "olx_field_scale_aggregate", "olx_field_absorption", "olx_comm_ranks_seen",
+    "olx_field_pulse", "olx_field_fetch_pmax", "olx_aggregate_fetch_pmax",
 ]
 
 
@@ -124,6 +126,9 @@ def load(require_gpu: bool = True):
         lib.olx_field_medium_layering.argtypes = [vp, c_int]
         lib.olx_field_medium_model.argtypes = [vp, c_int]
         lib.olx_field_absorption.argtypes = [vp, c_double]
+        lib.olx_field_pulse.argtypes = [vp, c_double, c_double, c_int]
+        lib.olx_field_fetch_pmax.argtypes = [vp, fp]
+        lib.olx_aggregate_fetch_pmax.argtypes = [vp, fp]
         lib.olx_set_element_apertures.argtypes = [vp, dp, dp]
         lib.olx_comm_export.argtypes = [vp, vp]
         lib.olx_comm_import.argtypes = [vp, vp]
@@ -292,7 +297,7 @@ class Context:
         self._shape = (nx, int(n[1]), int(n[2]))
         self._grid_shape = (int(n[0]), int(n[1]), int(n[2]))
         self._vox = nx * int(n[1]) * int(n[2])
-        self._flags = (int(flags) | OUT_PMAG) & 7
+        self._flags = (int(flags) | OUT_PMAG) & (7 | OUT_PMAX)
         self._plan_foci = F
 
     def field_set_medium(self, sound_speed=None, attenuation=None, density=None, alpha_power=0.9, planes_per_layer=1, model="auto"):
@@ -330,10 +335,14 @@ class Context:
         shape = (self._plan_foci,) + self._shape
         pm = np.empty(shape, dtype=np.float32) if "pmag" in want else None
         it = np.empty(shape, dtype=np.float32) if "intensity" in want else None
-        self._chk(self._lib.olx_field_fetch_all(self._h, _fptr(pm), _fptr(it)))
+        if pm is not None or it is not None:
+            self._chk(self._lib.olx_field_fetch_all(self._h, _fptr(pm), _fptr(it)))
         out = {}
         if pm is not None: out["pmag"] = pm
         if it is not None: out["intensity"] = it
+        if "pmax" in want:      # pulsed plans with OUT_PMAX: the peak positive pressure
+            out["pmax"] = np.empty(shape, dtype=np.float32)
+            self._chk(self._lib.olx_field_fetch_pmax(self._h, _fptr(out["pmax"])))
         return out
 
     def bf_time(self, iters: int = 20) -> np.ndarray:
@@ -422,6 +431,11 @@ class Context:
     def field_absorption(self, np_per_m: float):
         """Uniform absorbing medium for the plans that follow (0 = lossless): every term carries exp(-a d)."""
         self._chk(self._lib.olx_field_absorption(self._h, float(np_per_m)))
+
+    def field_pulse(self, cycles: float = 0.0, dt: float = 0.0, n_t: int = 0):
+        """Pulsed (tone-burst) model for the plans that follow: ``cycles`` cycles sampled at ``dt`` [s] over ``n_t`` samples;
+        ``n_t = 0`` = continuous wave (the default).  A pulsed plan's OUT_PMAG slot holds p_min, OUT_PMAX adds p_max."""
+        self._chk(self._lib.olx_field_pulse(self._h, float(cycles), float(dt), int(n_t)))
 
     def field_scale_aggregate(self, scale_per_focus):
         """``field_scale`` + ``field_aggregate_device`` in one pass (identical values)."""
@@ -624,6 +638,12 @@ class Context:
         it = np.empty(self._shape, dtype=np.float32) if want_intensity else None
         self._chk(self._lib.olx_aggregate_fetch(self._h, _fptr(pm), _fptr(it)))
         return pm, it
+
+    def aggregate_fetch_pmax(self) -> np.ndarray:
+        """max_f p_max_f of the last device aggregate of a pulsed plan with OUT_PMAX."""
+        pm = np.empty(self._shape, dtype=np.float32)
+        self._chk(self._lib.olx_aggregate_fetch_pmax(self._h, _fptr(pm)))
+        return pm
 
     def allgather_fetch(self, rank: int) -> np.ndarray:
         out = np.empty((self._plan_foci,) + self._shape, dtype=np.float32)

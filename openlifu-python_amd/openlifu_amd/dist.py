@@ -109,6 +109,16 @@ def assemble_foci_sharded(gathered: np.ndarray, shards, n_foci: int) -> np.ndarr
     return out
 
 
+def _continuous_wave_only(engine, pulse):
+    """The sharded sweeps run the continuous-wave model only: a pulsed request is refused, and a pulsed setting the engine's context
+    still holds from an earlier Engine.field call is cleared (olx_field_pulse is sticky)."""
+    if pulse is not None:
+        raise NotImplementedError("pulsed field model: the multi-GPU slab / shard paths are not implemented (whole grid on one GPU only)")
+    if getattr(engine, "_pulsed", False):
+        engine.ctx.field_pulse(0.0, 0.0, 0)
+        engine._pulsed = False
+
+
 def plan_slabs(nx: int, world: int):
     """x-slabs (x is the slowest axis of the C-order [nx,ny,nz] volume, so a slab is one contiguous
     block).  Every rank computes exactly ``per = ceil(nx / world)`` planes; a slab that would overrun
@@ -180,9 +190,10 @@ class ShardedField:
 
     # ---- planning ---------------------------------------------------------------------------------
     def plan_foci_sweep(self, arr, foci_m, c, apod_args, origin_m, spacing_m, n, freq, rho, p0_pa, flags=None,
-                        fp8_correction=None, absorption=0.0):
+                        fp8_correction=None, absorption=0.0, pulse=None):
         """mode "foci": this rank solves (kernel 1) and plans its orbit-aware block of foci over the whole grid."""
         from . import _native as nat
+        _continuous_wave_only(self.engine, pulse)
         foci_m = np.atleast_2d(np.asarray(foci_m, dtype=np.float64))
         self.F, self.mode = foci_m.shape[0], "foci"
         centre = tuple(origin_m[a] + 0.5 * (int(n[a]) - 1) * spacing_m[a] for a in (0, 1))
@@ -202,11 +213,13 @@ class ShardedField:
         self._publish_blocks()
         return self.shards[self.rank]
 
-    def plan_slab_sweep(self, arr, delays, apod, origin_m, spacing_m, n, freq, c, rho, p0_pa, flags=None, medium=None, absorption=0.0):
+    def plan_slab_sweep(self, arr, delays, apod, origin_m, spacing_m, n, freq, c, rho, p0_pa, flags=None, medium=None, absorption=0.0,
+                        pulse=None):
         """mode "slabs": every rank accumulates ALL foci over its x-slab (better balance when F < world; what the
         heterogeneous configuration uses -- ``medium`` = dict of WHOLE-grid volumes, replicated on every rank because
         the rays to a slab cross the full lateral extent)."""
         from . import _native as nat
+        _continuous_wave_only(self.engine, pulse)
         eng, ctx = self.engine, self.engine.ctx
         eng.retire_results()
         eng.bind(arr)

@@ -42,6 +42,30 @@ def gpu_available() -> bool:
         return False
 
 
+PULSE_C_GRID = 1500.0     # the sound speed of the time-axis defaults (get_kgrid's makeTime(1500, cfl))
+
+
+def pulse_time_axis(spacing_m, n, dt: float = 0.0, t_end: float = 0.0, cfl: float = 0.5):
+    """(dt [s], n_t) of the pulsed model's time axis t_k = k dt, k < n_t.  ``dt > 0`` is used as given, ``dt == 0``
+    gives cfl min(spacing) / 1500; ``t_end > 0`` gives n_t = floor(t_end / dt) + 1, ``t_end == 0`` uses t_end = |(nx, ny, nz) spacing| / 1500.
+    The two defaults are this project's contract, written after get_kgrid's makeTime(1500, cfl) as SURVEY.md records it."""
+    spacing = np.broadcast_to(np.asarray(spacing_m, dtype=np.float64), (3,))
+    n = np.asarray(n, dtype=np.float64)
+    dt, t_end, cfl = float(dt), float(t_end), float(cfl)
+    if not (np.isfinite(dt) and dt >= 0 and np.isfinite(t_end) and t_end >= 0):
+        raise ValueError(f"dt and t_end must be finite and >= 0 (0 = default), got dt={dt}, t_end={t_end}")
+    if dt == 0:
+        if not (np.isfinite(cfl) and cfl > 0):
+            raise ValueError(f"the default dt needs cfl > 0, got {cfl}")
+        dt = cfl * float(spacing.min()) / PULSE_C_GRID
+    if t_end == 0:
+        t_end = float(np.sqrt(np.sum((n * spacing) ** 2))) / PULSE_C_GRID
+    n_t = int(np.floor(t_end / dt)) + 1
+    if n_t >= 2 ** 31:
+        raise ValueError(f"time axis of {n_t} samples is too long")
+    return dt, n_t
+
+
 def focus_positions_m(targets) -> np.ndarray:
     """[F,3] metres from a Point, a list of Points, or an array already in metres."""
     if isinstance(targets, Point):
@@ -93,12 +117,15 @@ class AggregateResult:
 
     def __init__(self, engine, shape):
         self.engine, self.shape = engine, tuple(int(v) for v in shape)
+        self.pulsed = bool(getattr(engine, "_pmax_resident", False))   # pulsed volumes: p_max is aggregated apart ("pmax")
         self._lazies = []
         self.retired = False
 
     def fetch(self, key):
         if self.retired:
             raise RuntimeError("the device aggregate this array belongs to has been overwritten")
+        if key == "pmax":       # pulsed plans: max_f p_max_f
+            return self.engine.ctx.aggregate_fetch_pmax()
         pm, it = self.engine.ctx.aggregate_fetch(want_intensity=(key == "intensity"), want_pmag=(key == "pmag"))
         return pm if key == "pmag" else it
 
@@ -241,7 +268,7 @@ class Engine:
     # ---- kernel 2 -----------------------------------------------------------------------------
     def field(self, arr, delays, apod, origin_m, spacing_m, n, freq, c, rho, p0_pa,
               want=("pmag", "intensity"), slab=None, steering_resident=False, medium=None, fp8_correction=None,
-              lazy=False, directivity=False, absorption=0.0):
+              lazy=False, directivity=False, absorption=0.0, pulse=None):
         """Pressure field for F foci -> dict of float32 arrays [F, nx, ny, nz] (fresh, writable,
         caller-owned).  ``steering_resident`` reuses the table the last ``beamform`` left on the
         device instead of uploading ``delays`` / ``apod``.  ``fp8_correction=False`` opts OUT of the e4m3
@@ -250,7 +277,20 @@ class Engine:
         (OLX_FIELD_DIRECTIVITY; folded into the lattice kernels' tables for flat arrays of equal axis-aligned elements, else the exact
         per-pair kernel; homogeneous media).  ``absorption`` [Np/m] > 0: uniform absorbing medium, every term carries exp(-a d)
         (olx_field_absorption).  ``lazy=True`` returns a ``DeviceResult`` instead: the volumes
-        stay in HBM until somebody reads them."""
+        stay in HBM until somebody reads them.  ``pulse = (cycles, dt, t_end, cfl)`` selects the pulsed model (olx_field_pulse, time axis by
+        ``pulse_time_axis``): "pmag" then holds p_min and the result carries p_max under "pmax"."""
+        if pulse is not None:
+            if medium is not None:
+                raise NotImplementedError("pulsed field model: heterogeneous media are not implemented (homogeneous media, with or without uniform absorption, only)")
+            if directivity:
+                raise NotImplementedError("pulsed field model: element directivity is not implemented")
+            if slab is not None:
+                raise NotImplementedError("pulsed field model: the multi-GPU slab / shard paths are not implemented (whole grid on one GPU only)")
+            if "complex" in want:
+                raise ValueError("pulsed field model: there is no complex output (the field is a peak over time)")
+            cycles, dt, t_end, cfl = pulse
+            dt, n_t = pulse_time_axis(spacing_m, n, dt, t_end, cfl)
+            want = tuple(want) + ("pmax",)
         self.retire_results()
         if steering_resident:
             # the resident steering table belongs to the resident element table: another transducer (or the same one with edited
@@ -268,6 +308,13 @@ class Engine:
             flags |= nat.OUT_COMPLEX
         if fp8_correction is False:
             flags |= nat.FIELD_FP16_CORRECTION
+        if pulse is not None:
+            self.ctx.field_pulse(cycles, dt, n_t)
+            self._pulsed = True
+            flags |= nat.OUT_PMAX
+        elif getattr(self, "_pulsed", False):
+            self.ctx.field_pulse(0.0, 0.0, 0)       # back to continuous wave
+            self._pulsed = False
         if directivity:
             self.ctx.set_element_apertures(*arr.element_apertures())
             flags |= nat.FIELD_DIRECTIVITY
@@ -278,6 +325,7 @@ class Engine:
                                       planes_per_layer=int(medium.get("planes_per_layer", 1)), model=medium.get("model", "auto"))
         self.ctx.field_launch()
         self.result_token += 1
+        self._pmax_resident = pulse is not None
         if lazy and "complex" not in want:
             nx = int(n[0]) if slab is None else int(slab[1])
             self._live_result = DeviceResult(self, self.ctx.n_foci, (nx, int(n[1]), int(n[2])), want)
@@ -292,6 +340,7 @@ class Engine:
         self.retire_results()
         self.ctx.field_upload(origin_m, spacing_m, n, pmag, intensity)
         self.result_token += 1
+        self._pmax_resident = False
         self.__dict__.pop("_plan_sig", None)
 
 

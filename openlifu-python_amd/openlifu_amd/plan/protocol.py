@@ -26,7 +26,7 @@ from ..bf.apod_methods import ApodizationMethod
 from ..bf.delay_methods import Direct
 from ..engine import get_engine, gpu_available
 from ..geo import Point
-from ..sim.field import dataset_from_fields, lazy_stack, simulate_foci, _ATTRS
+from ..sim.field import dataset_from_fields, lazy_stack, parse_field_model, simulate_foci, _ATTRS
 from ..util import dataset as ds
 from .param_constraint import ParameterConstraint
 from .solution import Solution
@@ -48,9 +48,23 @@ def aggregate_dataset_eager(agg, coords, dims):
     """Dataset{p_min, p_max, intensity} of an ``AggregateResult`` read to the host NOW (three fresh arrays), built through
     ``ds.make_dataarray`` -- the form that also works when ``ds`` hands out real xarray objects."""
     pm, it = agg.fetch("pmag"), agg.fetch("intensity")
+    px = agg.fetch("pmax") if getattr(agg, "pulsed", False) else pm.copy()      # (pulsed volumes: max_f p_max_f of its own)
     return ds.make_dataset({"p_min": ds.make_dataarray(pm, coords=coords, dims=dims, name="p_min", attrs=_ATTRS["p_min"]),
-                            "p_max": ds.make_dataarray(pm.copy(), coords=coords, dims=dims, name="p_max", attrs=_ATTRS["p_max"]),
+                            "p_max": ds.make_dataarray(px, coords=coords, dims=dims, name="p_max", attrs=_ATTRS["p_max"]),
                             "intensity": ds.make_dataarray(it, coords=coords, dims=dims, name="intensity", attrs=_ATTRS["intensity"])})
+
+
+def pulse_cycles(pulse) -> float:
+    """Tone-burst cycles of a Pulse as the reference hands them to run_simulation (plan/protocol.py:223): min(round(duration f0), 20)."""
+    return float(np.min([np.round(pulse.duration * pulse.frequency), 20]))
+
+
+def pulse_from_options(sim_setup, pulse):
+    """``SimSetup.options["field_model"]`` (sim_setup.py:51 "Additional simulation options"; default "cw"): None for the continuous-wave
+    model, else the pulsed model's (cycles, dt, t_end, cfl) -- cycles as the reference computes them, dt / t_end / cfl of the SimSetup."""
+    if parse_field_model(getattr(sim_setup, "options", {}).get("field_model", "cw")) != "pulsed":
+        return None
+    return (pulse_cycles(pulse), float(sim_setup.dt), float(sim_setup.t_end), float(sim_setup.cfl))
 
 
 # module-level seam, as in the reference (plan/protocol.py:24; its tests patch this name)
@@ -210,13 +224,16 @@ class Protocol:
             # precision option, SimSetup.options["fp8_correction"] = "0" (sim_setup.py:51 "Additional simulation options"): keeps three fp16
             # products where the lattice kernels would use their e4m3 correction products (the default; <= 7.5e-6 of the volume maximum, include/olx.h)
             fp8 = False if str(getattr(sim_options, "options", {}).get("fp8_correction", "auto")).lower() in ("0", "false", "no") else None
+            # field model option, SimSetup.options["field_model"] = "pulsed": tone bursts of the reference's cycles / dt / t_end (sim/field.py)
+            pulse = pulse_from_options(sim_options, self.pulse)
             # the per-focus volumes stay in HBM (scale / aggregate / analyze below run there); the Dataset hands them to the host on first
             # access.  Real xarray objects cannot defer: with xarray installed the call works on the SAME lazy stand-ins and converts at
             # the end (`eager_out` below) -- one fetch of the final, scaled volumes instead of fetch, host-side scaling and re-upload
             fields = simulate_foci(transducer, params, delays, apod, self.pulse.frequency,
                                    self.pulse.amplitude * voltage, steering_resident=resident, fp8_correction=fp8, lazy=True,
                                    hetero_planes_per_layer=int(getattr(sim_options, "options", {}).get("hetero_planes_per_layer", 1)),
-                                   directivity=str(getattr(sim_options, "options", {}).get("directivity", "0")).lower() in ("1", "true", "yes"))
+                                   directivity=str(getattr(sim_options, "options", {}).get("directivity", "0")).lower() in ("1", "true", "yes"),
+                                   pulse=pulse)
             coords = params.coords
             stacked = lazy_stack(fields, _standin_coords(coords) if ds.HAVE_XARRAY else coords, internal=ds.HAVE_XARRAY)
         elif simulate:
@@ -271,7 +288,8 @@ class Protocol:
             def lazy(name, key):
                 return agg.lazy_array(key, lambda fetch: ds.LazyDataArray(shape, np.float32, fetch, coords=coords, dims=dims, name=name,
                                                                           attrs=_ATTRS[name]))
-            aggregated = ds.make_dataset({"p_min": lazy("p_min", "pmag"), "p_max": lazy("p_max", "pmag"), "intensity": lazy("intensity", "intensity")})
+            aggregated = ds.make_dataset({"p_min": lazy("p_min", "pmag"), "p_max": lazy("p_max", "pmax" if agg.pulsed else "pmag"),
+                                          "intensity": lazy("intensity", "intensity")})
         if analysis is None:
             analysis = solution.analyze(options=analysis_options, param_constraints=self.param_constraints, _host_unchanged=True)
         if eager_out:

@@ -3,10 +3,17 @@
 plan/protocol.py:324-336).
 
 Same signature, same output schema (Dataset{p_max [Pa], p_min [Pa], intensity [W/cm^2]} on
-``params.coords``), but the field is the steady-state monochromatic point-source superposition
-accumulated by HIP kernel 2 (definition: DESIGN.md section 3, oracle/field_oracle.py), not a
-time-domain k-space solve.  ``cycles/dt/t_end/cfl/bli_tolerance/upsampling_rate`` are accepted
-and ignored; ``gpu`` is accepted and ignored -- there is no CPU path and a missing MI355X raises.
+``params.coords``), but not a time-domain k-space solve.  Two field models (``field_model``, an extension
+like ``directivity``):
+  * ``"cw"`` (default): the steady-state monochromatic point-source superposition accumulated by HIP
+    kernel 2 (definition: DESIGN.md section 3, oracle/field_oracle.py); ``p_max == p_min == |p|`` and
+    ``cycles/dt/t_end/cfl`` are ignored.
+  * ``"pulsed"``: the time-domain Rayleigh sum of ``cycles``-cycle tone bursts with the delays truncated
+    to whole steps of ``dt``, sampled at k dt up to ``t_end``: peak positive / peak negative pressure
+    (HIP kernel 2p; definition DESIGN.md section 2, time axis ``pulse_time_axis``).  Homogeneous media
+    only; directivity, impulse responses and the multi-GPU paths raise NotImplementedError.
+``bli_tolerance/upsampling_rate`` are accepted and ignored; ``gpu`` is accepted and ignored -- there is
+no CPU path and a missing MI355X raises.
 ``ref_values_only=True`` simulates the homogeneous reference medium whatever ``params`` holds, as sim/kwave_if.py:49-56 does.
 """
 from __future__ import annotations
@@ -15,7 +22,7 @@ import logging
 
 import numpy as np
 
-from ..engine import get_engine, grid_from_coords
+from ..engine import get_engine, grid_from_coords, pulse_time_axis  # noqa: F401 - pulse_time_axis: part of this module's interface
 from ..util import dataset as ds
 
 _ATTRS = {"p_max": {"units": "Pa", "long_name": "PPP"}, "p_min": {"units": "Pa", "long_name": "PNP"},
@@ -23,6 +30,30 @@ _ATTRS = {"p_max": {"units": "Pa", "long_name": "PPP"}, "p_min": {"units": "Pa",
 
 
 ALPHA_POWER = 0.9      # the reference's kWaveMedium(alpha_power=0.9), sim/kwave_if.py:57
+FIELD_MODELS = ("cw", "pulsed")
+
+
+def parse_field_model(value) -> str:
+    """``field_model`` of run_simulation / ``SimSetup.options["field_model"]``: "cw" (default, also for None / "") or "pulsed"."""
+    model = "cw" if value is None or str(value).strip() == "" else str(value).strip().lower()
+    if model not in FIELD_MODELS:
+        raise ValueError(f"field_model must be one of {FIELD_MODELS}, got {value!r}")
+    return model
+
+
+def truncate_delays(delays, dt):
+    """The reference's whole-step delays (sim/kwave_if.py: zeros(int(delay / dt)) in front of the drive): floor(tau / dt) dt."""
+    return np.floor(np.asarray(delays, dtype=np.float64) / float(dt)) * float(dt)
+
+
+def check_pulsed_supported(arr, directivity=False):
+    """NotImplementedError, naming the reason, for what the pulsed model does not cover on the transducer side."""
+    if directivity:
+        raise NotImplementedError("pulsed field model: element directivity is not implemented")
+    if getattr(arr, "impulse_response", None) is not None:
+        raise NotImplementedError("pulsed field model: the transducer's impulse_response is not implemented (the drive is the bare tone burst)")
+    if any(getattr(el, "impulse_response", None) is not None for el in arr.elements):
+        raise NotImplementedError("pulsed field model: element impulse_response is not implemented (the drive is the bare tone burst)")
 
 
 def _np_per_m(alpha_db_cm_mhz, freq):
@@ -65,12 +96,17 @@ def _medium(params, freq, ref_values_only=False):
 
 def simulate_foci(arr, params, delays, apod, freq, amplitude, want=("pmag", "intensity"),
                   steering_resident=False, slab=None, fp8_correction=None, lazy=False, hetero_planes_per_layer=1,
-                  hetero_model="auto", directivity=False, ref_values_only=False):
+                  hetero_model="auto", directivity=False, ref_values_only=False, pulse=None):
     """Batched core: F foci in one launch -> dict of float32 arrays [F, nx, ny, nz], or with ``lazy`` a
-    ``DeviceResult`` whose volumes stay in HBM until read (``lazy_stack`` wraps it in the reference's schema)."""
+    ``DeviceResult`` whose volumes stay in HBM until read (``lazy_stack`` wraps it in the reference's schema).
+    ``pulse = (cycles, dt, t_end, cfl)``: the pulsed model -- "pmag" holds p_min, "pmax" p_max."""
+    if pulse is not None:
+        check_pulsed_supported(arr, directivity)
     coords = params.coords
     origin, spacing, n = grid_from_coords(coords)
     c, rho, medium, absorption = _medium(params, freq, ref_values_only)
+    if pulse is not None and medium is not None:
+        raise NotImplementedError("pulsed field model: heterogeneous media are not implemented (homogeneous media, with or without uniform absorption, only)")
     if medium is not None and int(hetero_planes_per_layer) > 1:   # opt-in layered-screen quadrature (DESIGN.md section 7)
         medium["planes_per_layer"] = int(hetero_planes_per_layer)
     if medium is not None:   # "auto": marched ray sums (kernel 2m) when the elements lie below the medium, else sampled (2h)
@@ -78,19 +114,19 @@ def simulate_foci(arr, params, delays, apod, freq, amplitude, want=("pmag", "int
     p0 = float(amplitude) * (1.0 if arr.sensitivity is None else float(arr.sensitivity))
     return get_engine().field(arr, delays, apod, origin, spacing, n, float(freq), c, rho, p0, want=want,
                               slab=slab, steering_resident=steering_resident, medium=medium,
-                              fp8_correction=fp8_correction, lazy=lazy, directivity=directivity, absorption=absorption)
+                              fp8_correction=fp8_correction, lazy=lazy, directivity=directivity, absorption=absorption, pulse=pulse)
 
 
 def lazy_stack(result, coords, dim="focal_point_index", internal=False):
     """Dataset{p_max, p_min, intensity}[focal_point_index, x, y, z] (plan/protocol.py:341-347) over a DeviceResult:
     three independent LazyDataArrays (p_max and p_min are separate host arrays once read, as callers scale them
-    independently, plan/solution.py:333-334)."""
+    independently, plan/solution.py:333-334).  A pulsed result's p_max is its own volume ("pmax")."""
     from collections import OrderedDict
     dims = (dim,) + tuple(coords.dims if hasattr(coords, "dims") else coords.keys())
     c = OrderedDict([(dim, np.arange(result.shape[0]))])
     c.update(coords)
     out = {}
-    for name, key in (("p_max", "pmag"), ("p_min", "pmag"), ("intensity", "intensity")):
+    for name, key in (("p_max", "pmax" if "pmax" in result.keys else "pmag"), ("p_min", "pmag"), ("intensity", "intensity")):
         out[name] = result.lazy_array(key, lambda fetch, name=name: ds.LazyDataArray(
             result.shape, np.float32, fetch, coords=c, dims=dims, name=name, attrs=_ATTRS[name]))
     # (internal: the stand-in Dataset whatever the factories hand out -- calc_solution's working copy when xarray is installed)
@@ -103,7 +139,8 @@ def dataset_from_fields(fields, coords, focus=None):
     dims = list(coords.dims) if hasattr(coords, "dims") else list(coords.keys())
     sel = (lambda a: a) if focus is None else (lambda a: a[focus])
     pm = sel(fields["pmag"])
-    out = {"p_max": ds.make_dataarray(pm, coords=coords, dims=dims, name="p_max", attrs=_ATTRS["p_max"]),
+    px = sel(fields["pmax"]) if "pmax" in fields else pm      # pulsed model: the peak positive pressure is a volume of its own
+    out = {"p_max": ds.make_dataarray(px, coords=coords, dims=dims, name="p_max", attrs=_ATTRS["p_max"]),
            "p_min": ds.make_dataarray(pm.copy(), coords=coords, dims=dims, name="p_min", attrs=_ATTRS["p_min"]),
            "intensity": ds.make_dataarray(sel(fields["intensity"]), coords=coords, dims=dims, name="I",
                                           attrs=_ATTRS["intensity"])}
@@ -113,8 +150,9 @@ def dataset_from_fields(fields, coords, focus=None):
 def run_simulation(arr, params, delays=None, apod=None, freq: float = 1e6, cycles: float = 20,
                    amplitude: float = 1, dt: float = 0, t_end: float = 0, cfl: float = 0.5,
                    bli_tolerance: float = 0.05, upsampling_rate: int = 5, gpu: bool = True,
-                   ref_values_only: bool = False, directivity: bool = False):
+                   ref_values_only: bool = False, directivity: bool = False, field_model: str = "cw"):
     n = arr.numelements()
+    pulse = (float(cycles), float(dt), float(t_end), float(cfl)) if parse_field_model(field_model) == "pulsed" else None
     delays = np.zeros(n) if delays is None else np.asarray(delays, dtype=np.float64)
     apod = np.ones(n) if apod is None else np.asarray(apod, dtype=np.float64)
     if delays.shape != (n,) or apod.shape != (n,):
@@ -122,7 +160,7 @@ def run_simulation(arr, params, delays=None, apod=None, freq: float = 1e6, cycle
     logging.info("Running simulation")
     # (directivity: this path's extension -- the far-field pattern of the rectangular elements k-Wave models as finite sources)
     fields = simulate_foci(arr, params, delays[None, :], apod[None, :], freq, amplitude, directivity=directivity,
-                           ref_values_only=ref_values_only)
+                           ref_values_only=ref_values_only, pulse=pulse)
     logging.info("Simulation Complete")
     if ref_values_only:
         # The reference then SIMULATES the reference medium (get_medium, sim/kwave_if.py:49-56) but still forms the intensity with
@@ -135,5 +173,5 @@ def run_simulation(arr, params, delays=None, apod=None, freq: float = 1e6, cycle
             fields = dict(fields)
             fields["intensity"] = (1e-4 * fields["pmag"].astype(np.float64) ** 2 / (2.0 * Z)[None]).astype(np.float32)
     dataset = dataset_from_fields(fields, params.coords, focus=0)
-    raw = {"p_max": fields["pmag"][0], "p_min": -fields["pmag"][0], "backend": "openlifu_amd/hip-gfx950"}
+    raw = {"p_max": fields["pmax"][0] if "pmax" in fields else fields["pmag"][0], "p_min": -fields["pmag"][0], "backend": "openlifu_amd/hip-gfx950"}
     return dataset, raw
