@@ -233,6 +233,31 @@ int olx_field_fetch_pmax(olx_ctx *ctx, float *pmax_out);
 /* max_f p_max_f of the last device aggregate of a pulsed plan's volumes ([voxels] floats). */
 int olx_aggregate_fetch_pmax(olx_ctx *ctx, float *pmax_out);
 
+/* Thermal model (DESIGN.md section 2 "thermal model", kernel 3): Pennes bioheat rise dT above a baseline over a pulse sequence,
+ *   rho Cp d(dT)/dt = div(kappa grad dT) - W dT + Q,   Q = 2 alpha 1e4 I_f(v) while a pulse aimed at focus f is on [W/m^3],
+ * explicit FTCS on a grid of its own (7-point stencil, face conductance = harmonic mean of kappa / h^2, dT = 0 one spacing outside the grid).
+ * Its buffers are apart from the field / aggregate volumes: a thermal run reads the resident intensity at most and changes nothing of it.
+ * Plan the grid and the medium: per-voxel density [kg/m^3], specific heat [J/kg/K], thermal conductivity [W/m/K] and absorption [Np/m]
+ * ([nx * ny * nz] floats each, C order), each may be NULL for the uniform value that follows it; perfusion W [W/m^3/K] is uniform.
+ * With all four volumes NULL no coefficient volume is formed or streamed.  dt_max_out (may be NULL) receives the FTCS bound
+ * 1 / max_v (sum_faces K_face / h^2 + W) / (rho Cp)_v [s] (fp32 coefficients). */
+int olx_thermal_plan(olx_ctx *ctx, const olx_grid *grid, const float *density, const float *specific_heat, const float *conductivity,
+                     const float *absorption, double density0, double specific_heat0, double conductivity0, double absorption0,
+                     double perfusion, double *dt_max_out);
+/* The source schedule of the plan, CSR over n_steps steps: step n heats with sum_e tau[e] s(v) I_{focus[e]}(v), e in
+ * [row_ptr[n], row_ptr[n + 1]) (tau = the on-time [s] of the focus' pulses inside the step).  n_points voxels (linear C-order indices)
+ * are traced: olx_thermal_fetch returns dT there after every step. */
+int olx_thermal_schedule(olx_ctx *ctx, int n_steps, const int *row_ptr, const int *focus, const double *tau, int n_points, const long long *points);
+/* The intensity volumes I_f [W/cm^2] the schedule's focus indices refer to: [n_foci * voxels] floats uploaded once, or NULL = the
+ * context's resident intensity (a whole-grid result of n_foci foci on the thermal grid, read in place at every olx_thermal_run). */
+int olx_thermal_source(olx_ctx *ctx, int n_foci, const float *intensity);
+/* Steps [first_step, first_step + n_steps) of the schedule with time step dt [s] (<= the FTCS bound) and baseline temperature [deg C];
+ * first_step = 0 starts from dT = 0, any other first_step continues the last run.  Per voxel it keeps the maximum rise [K] and
+ * CEM43 = sum_n dt / 60 R^(43 - T) [min] (T = baseline + dT after the step, R = 0.5 at T >= 43, 0.25 below).  Asynchronous. */
+int olx_thermal_run(olx_ctx *ctx, double dt, double baseline, int first_step, int n_steps);
+/* The maximum rise and CEM43 volumes ([voxels] floats) and the traces ([steps run * n_points] floats, step-major); any may be NULL. */
+int olx_thermal_fetch(olx_ctx *ctx, float *rise_max, float *cem43, float *traces);
+
 /* Bind host volumes (e.g. a Solution loaded from disk) as the context's resident result so
  * that the aggregate / scale / masked-peak entry points can run on them: [n_foci * slab voxels]
  * floats each; intensity may be NULL.  Needs no element or steering table; olx_field_launch is

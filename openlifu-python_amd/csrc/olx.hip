@@ -63,7 +63,8 @@ int olx_ctx_destroy(olx_ctx* c) {
     void* ptrs[] = {c->d_pos, c->d_nrm, c->d_area, c->d_delays, c->d_apod, c->d_foci, c->d_M, c->d_tab,
                     c->d_pmag[0], c->d_pmag[1], c->d_inten, c->d_cplx, c->d_agg_p, c->d_agg_i,
                     c->d_scale, c->d_gather, c->d_peakA, c->d_peak, c->d_perm, c->d_coords, c->d_bfrag, c->d_colinfo, c->d_wint, c->d_med, c->d_plane_k, c->d_plane_of_k,
-                    c->d_an, c->d_inv2z, c->d_kfirst, c->d_klast, c->d_slot, c->d_jobs, c->d_med_layer, c->d_layer_lo, c->d_layer_hi, c->d_U[0], c->d_U[1], c->d_Utex, c->d_sig, c->d_cell, c->d_afrag, c->d_tab2, c->d_cpblocks, c->d_pmax, c->d_agg_pmax, c->d_ptab, c->d_pw};
+                    c->d_an, c->d_inv2z, c->d_kfirst, c->d_klast, c->d_slot, c->d_jobs, c->d_med_layer, c->d_layer_lo, c->d_layer_hi, c->d_U[0], c->d_U[1], c->d_Utex, c->d_sig, c->d_cell, c->d_afrag, c->d_tab2, c->d_cpblocks, c->d_pmax, c->d_agg_pmax, c->d_ptab, c->d_pw,
+                    c->d_th_T[0], c->d_th_T[1], c->d_th_max, c->d_th_cem, c->d_th_coef, c->d_th_irc, c->d_th_sfac, c->d_th_rate, c->d_th_sf, c->d_th_tau, c->d_th_pts, c->d_th_trace, c->d_th_I};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -73,11 +74,11 @@ int olx_ctx_destroy(olx_ctx* c) {
 const char* olx_last_error(const olx_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 #ifdef OLX_DEBUG_BOUNDS   // debug build (k_types.hip.h): the kernels' index checks report here
-extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); }
+extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); }
 static int report_bounds(olx_ctx* c) {
     struct { const char* name; int (*read)(unsigned*); } units[] = {{"2g (k_coset2.hip)", olx_dbg_bounds_cosetp}, {"2e (k_coset.hip)", olx_dbg_bounds_coset},
                                                                      {"2f (k_toep.hip)", olx_dbg_bounds_toep}, {"2m (k_hmarch.hip)", olx_dbg_bounds_hmarch},
-                                                                     {"2p (k_pulse.hip)", olx_dbg_bounds_pulse}};
+                                                                     {"2p (k_pulse.hip)", olx_dbg_bounds_pulse}, {"3 (k_thermal.hip)", olx_dbg_bounds_thermal}};
     int rc = OLX_OK;
     for (auto& u : units) {
         unsigned w[4] = {0, 0, 0, 0};
@@ -2593,6 +2594,204 @@ int olx_allgather_fetch(olx_ctx* c, int rank, float* out) {
     if (c->p2p) { int rc = olx_p2p_drain(c); if (rc) return rc; }
     const size_t count = (size_t)c->fp.vox * c->plan_foci;
     return fetch_to_host(c, out, c->d_gather + count * rank, sizeof(float) * count);
+}
+
+}  // extern "C"
+
+// ---- thermal model (kernel 3, k_thermal.hip) ---------------------------------------------------------------------------------------
+// grow a device buffer to hold n elements (contents not kept)
+template <class T> static int th_grow(olx_ctx* c, T** p, size_t* cap, size_t n) {
+    if (*cap >= n && *p) return OLX_OK;
+    if (*p) hipFree(*p);
+    *p = nullptr; *cap = 0;
+    HIPCHK(c, hipMalloc((void**)p, sizeof(T) * std::max(n, (size_t)1)));
+    *cap = n;
+    return OLX_OK;
+}
+
+extern "C" {
+
+int olx_thermal_plan(olx_ctx* c, const olx_grid* g, const float* density, const float* specific_heat, const float* conductivity,
+                     const float* absorption, double density0, double specific_heat0, double conductivity0, double absorption0,
+                     double perfusion, double* dt_max_out) {
+    if (!c) return OLX_EINVAL;
+    if (!g) return fail(c, OLX_EINVAL, "olx_thermal_plan: null grid");
+    for (int a = 0; a < 3; ++a)
+        if (g->n[a] < 1 || !(g->spacing[a] > 0) || !std::isfinite(g->spacing[a])) return fail(c, OLX_EINVAL, "olx_thermal_plan: bad grid axis %d", a);
+    if ((!density && !(density0 > 0)) || (!specific_heat && !(specific_heat0 > 0)) || (!conductivity && !(conductivity0 > 0)) ||
+        (!absorption && !(absorption0 >= 0)) || !(perfusion >= 0) || !std::isfinite(perfusion))
+        return fail(c, OLX_EINVAL, "olx_thermal_plan: the scalars of NULL volumes must be > 0 (absorption >= 0) and perfusion finite and >= 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ThermalParams& P = c->th;
+    P = ThermalParams{};
+    P.nx = g->n[0]; P.ny = g->n[1]; P.nz = g->n[2];
+    P.vox = (long long)P.nx * P.ny * P.nz;
+    P.ihx2 = (float)(1.0 / (g->spacing[0] * g->spacing[0]));
+    P.ihy2 = (float)(1.0 / (g->spacing[1] * g->spacing[1]));
+    P.ihz2 = (float)(1.0 / (g->spacing[2] * g->spacing[2]));
+    P.rho0 = (float)density0; P.cp0 = (float)specific_heat0; P.kappa0 = (float)conductivity0; P.alpha0 = (float)absorption0;
+    P.perf = (float)perfusion;
+    c->th_uniform = !density && !specific_heat && !conductivity && !absorption;
+    const size_t vox = (size_t)P.vox;
+    for (float** p : {&c->d_th_T[0], &c->d_th_T[1], &c->d_th_max, &c->d_th_cem})
+        if (c->th_cap < vox && *p) { hipFree(*p); *p = nullptr; }
+    if (c->th_cap < vox) c->th_cap = 0;
+    for (float** p : {&c->d_th_T[0], &c->d_th_T[1], &c->d_th_max, &c->d_th_cem})
+        if (!*p) HIPCHK(c, hipMalloc((void**)p, sizeof(float) * vox));
+    c->th_cap = vox;
+    if (!c->d_th_rate) HIPCHK(c, hipMalloc((void**)&c->d_th_rate, sizeof(unsigned)));
+    if (c->th_uniform) {
+        const double rc = density0 * specific_heat0;
+        P.gx = (float)(conductivity0 * P.ihx2); P.gy = (float)(conductivity0 * P.ihy2); P.gz = (float)(conductivity0 * P.ihz2);
+        P.irc0 = (float)(1.0 / rc); P.sfac0 = (float)(2.0 * absorption0 * 1e4 / rc);
+        const double ih2 = 1.0 / (g->spacing[0] * g->spacing[0]) + 1.0 / (g->spacing[1] * g->spacing[1]) + 1.0 / (g->spacing[2] * g->spacing[2]);
+        c->th_rate = (2.0 * conductivity0 * ih2 + perfusion) / rc;
+    } else {
+        // the four volumes (or their scalars) go up once, the pack kernel forms the coefficients, the volumes are freed again
+        DevScratch scr;
+        const float* src[4] = {density, specific_heat, conductivity, absorption};
+        size_t nvol = 0;
+        for (const float* p : src) nvol += p ? 1 : 0;
+        HIPCHK(c, hipMalloc(&scr.p, sizeof(float) * vox * std::max(nvol, (size_t)1)));
+        const float* dv[4] = {nullptr, nullptr, nullptr, nullptr};
+        size_t at = 0;
+        for (int q = 0; q < 4; ++q) {
+            if (!src[q]) continue;
+            float* d = scr.at<float>(sizeof(float) * vox * at++);
+            HIPCHK(c, hipMemcpy(d, src[q], sizeof(float) * vox, hipMemcpyHostToDevice));
+            dv[q] = d;
+        }
+        if (c->th_coef_cap < vox) {
+            for (void* p : {(void*)c->d_th_coef, (void*)c->d_th_irc, (void*)c->d_th_sfac}) if (p) hipFree(p);
+            c->d_th_coef = nullptr; c->d_th_irc = c->d_th_sfac = nullptr; c->th_coef_cap = 0;
+            HIPCHK(c, hipMalloc((void**)&c->d_th_coef, sizeof(float4) * vox));
+            HIPCHK(c, hipMalloc((void**)&c->d_th_irc, sizeof(float) * vox));
+            HIPCHK(c, hipMalloc((void**)&c->d_th_sfac, sizeof(float) * vox));
+            c->th_coef_cap = vox;
+        }
+        HIPCHK(c, hipMemsetAsync(c->d_th_rate, 0, sizeof(unsigned), c->stream));
+        olx_thermal_pack(c, dv[0], dv[1], dv[2], dv[3]);
+        HIPCHK(c, hipGetLastError());
+        unsigned bits = 0;
+        HIPCHK(c, hipMemcpyAsync(&bits, c->d_th_rate, sizeof bits, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        float rate;
+        memcpy(&rate, &bits, sizeof rate);
+        c->th_rate = rate;
+    }
+    if (!(c->th_rate > 0) || !std::isfinite(c->th_rate)) return fail(c, OLX_EINVAL, "olx_thermal_plan: the medium gives no finite FTCS bound");
+    if (dt_max_out) *dt_max_out = 1.0 / c->th_rate;
+    c->th_planned = true;
+    c->th_steps = 0; c->th_npts = 0; c->th_next = -1;
+    c->th_src_foci = 0; c->th_src_resident = false;
+    return OLX_OK;
+}
+
+int olx_thermal_schedule(olx_ctx* c, int n_steps, const int* row_ptr, const int* focus, const double* tau_s, int n_points, const long long* points) {
+    if (!c) return OLX_EINVAL;
+    if (!c->th_planned) return fail(c, OLX_ESTATE, "olx_thermal_schedule: no thermal plan");
+    if (n_steps < 1 || !row_ptr || n_points < 0 || (n_points > 0 && !points)) return fail(c, OLX_EINVAL, "olx_thermal_schedule: n_steps < 1, null row_ptr or bad points");
+    if (row_ptr[0] != 0) return fail(c, OLX_EINVAL, "olx_thermal_schedule: row_ptr[0] must be 0");
+    for (int n = 0; n < n_steps; ++n)
+        if (row_ptr[n + 1] < row_ptr[n]) return fail(c, OLX_EINVAL, "olx_thermal_schedule: row_ptr must not decrease");
+    const int ne = row_ptr[n_steps];
+    if (ne > 0 && (!focus || !tau_s)) return fail(c, OLX_EINVAL, "olx_thermal_schedule: null focus / tau");
+    std::vector<float> tau(ne);
+    int fmax = -1;
+    for (int e = 0; e < ne; ++e) {
+        fmax = std::max(fmax, focus[e]);
+        if (focus[e] < 0) return fail(c, OLX_EINVAL, "olx_thermal_schedule: negative focus index");
+        if (!(tau_s[e] >= 0) || !std::isfinite(tau_s[e])) return fail(c, OLX_EINVAL, "olx_thermal_schedule: on-times must be finite and >= 0");
+        tau[e] = (float)tau_s[e];
+    }
+    for (int p = 0; p < n_points; ++p)
+        if (points[p] < 0 || points[p] >= c->th.vox) return fail(c, OLX_EINVAL, "olx_thermal_schedule: trace point %d outside the grid", p);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->th_sched_cap < (size_t)ne || !c->d_th_sf) {
+        if (c->d_th_sf) hipFree(c->d_th_sf);
+        if (c->d_th_tau) hipFree(c->d_th_tau);
+        c->d_th_sf = nullptr; c->d_th_tau = nullptr; c->th_sched_cap = 0;
+        HIPCHK(c, hipMalloc((void**)&c->d_th_sf, sizeof(int) * std::max(ne, 1)));
+        HIPCHK(c, hipMalloc((void**)&c->d_th_tau, sizeof(float) * std::max(ne, 1)));
+        c->th_sched_cap = (size_t)std::max(ne, 1);
+    }
+    if (ne > 0) {
+        HIPCHK(c, hipMemcpy(c->d_th_sf, focus, sizeof(int) * ne, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_th_tau, tau.data(), sizeof(float) * ne, hipMemcpyHostToDevice));
+    }
+    { int rc_ = th_grow(c, &c->d_th_pts, &c->th_pts_cap, (size_t)n_points); if (rc_) return rc_; }
+    if (n_points > 0) HIPCHK(c, hipMemcpy(c->d_th_pts, points, sizeof(long long) * n_points, hipMemcpyHostToDevice));
+    { int rc_ = th_grow(c, &c->d_th_trace, &c->th_trace_cap, (size_t)n_steps * n_points); if (rc_) return rc_; }
+    c->th_row.assign(row_ptr, row_ptr + n_steps + 1);
+    c->th_steps = n_steps; c->th_npts = n_points; c->th_next = -1; c->th_max_focus = fmax;
+    return OLX_OK;
+}
+
+int olx_thermal_source(olx_ctx* c, int n_foci, const float* intensity) {
+    if (!c) return OLX_EINVAL;
+    if (!c->th_planned) return fail(c, OLX_ESTATE, "olx_thermal_source: no thermal plan");
+    if (n_foci < 1) return fail(c, OLX_EINVAL, "olx_thermal_source: n_foci < 1");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (intensity) {
+        const size_t total = (size_t)c->th.vox * n_foci;
+        { int rc_ = th_grow(c, &c->d_th_I, &c->th_I_cap, total); if (rc_) return rc_; }
+        HIPCHK(c, hipMemcpy(c->d_th_I, intensity, sizeof(float) * total, hipMemcpyHostToDevice));
+        c->th_src_resident = false;
+    } else {
+        c->th_src_resident = true;     // checked against the resident result at every olx_thermal_run
+    }
+    c->th_src_foci = n_foci;
+    return OLX_OK;
+}
+
+int olx_thermal_run(olx_ctx* c, double dt, double baseline, int first_step, int n_steps) {
+    if (!c) return OLX_EINVAL;
+    if (!c->th_planned || c->th_steps < 1 || c->th_src_foci < 1) return fail(c, OLX_ESTATE, "olx_thermal_run: needs olx_thermal_plan, _schedule and _source first");
+    if (!(dt > 0) || !std::isfinite(dt) || !std::isfinite(baseline)) return fail(c, OLX_EINVAL, "olx_thermal_run: dt must be finite and > 0, baseline finite");
+    if (dt * c->th_rate > 1.0 + 1e-5) return fail(c, OLX_EINVAL, "olx_thermal_run: dt = %g s is above the FTCS bound %g s", dt, 1.0 / c->th_rate);
+    if (n_steps < 0 || first_step < 0 || first_step + n_steps > c->th_steps) return fail(c, OLX_EINVAL, "olx_thermal_run: steps [%d, %d) outside the schedule's %d", first_step, first_step + n_steps, c->th_steps);
+    if (first_step > 0 && first_step != c->th_next) return fail(c, OLX_ESTATE, "olx_thermal_run: step %d does not continue the last run (next step %d)", first_step, c->th_next);
+    const float* inten = c->d_th_I;
+    if (c->th_src_resident) {
+        const bool whole = c->planned && c->d_inten && (c->flags & OLX_OUT_INTENSITY) && c->slab.x_begin == 0 && c->slab.x_count == c->grid.n[0] &&
+                           c->grid.n[0] == c->th.nx && c->grid.n[1] == c->th.ny && c->grid.n[2] == c->th.nz && c->plan_foci == c->th_src_foci;
+        if (!whole) return fail(c, OLX_ESTATE, "olx_thermal_run: the resident result holds no whole-grid intensity of %d foci on the thermal grid", c->th_src_foci);
+        inten = c->d_inten;
+    }
+    if (c->th_max_focus >= c->th_src_foci) return fail(c, OLX_EINVAL, "olx_thermal_run: the schedule names focus %d, the source has %d", c->th_max_focus, c->th_src_foci);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t vox = (size_t)c->th.vox;
+    if (first_step == 0) {
+        for (float* p : {c->d_th_T[0], c->d_th_max, c->d_th_cem}) HIPCHK(c, hipMemsetAsync(p, 0, sizeof(float) * vox, c->stream));
+        c->th_cur = 0;
+    }
+    ThermalStep S{};
+    S.dt = (float)dt; S.dt_min = (float)(dt / 60.0); S.tb43 = (float)(baseline - 43.0);
+    S.npts = c->th_npts; S.n_foci = c->th_src_foci;
+    for (int n = first_step; n < first_step + n_steps; ++n) olx_thermal_step(c, inten, n, S);
+    if (n_steps > 0) olx_thermal_trace_last(c, first_step + n_steps - 1);
+    HIPCHK(c, hipGetLastError());
+    c->th_next = first_step + n_steps;
+    return OLX_OK;
+}
+
+int olx_thermal_fetch(olx_ctx* c, float* rise_max, float* cem43, float* traces) {
+    if (!c) return OLX_EINVAL;
+    if (!c->th_planned || c->th_next < 0) return fail(c, OLX_ESTATE, "olx_thermal_fetch: nothing run");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+#ifdef OLX_DEBUG_BOUNDS
+    { int rc_ = report_bounds(c); if (rc_) return rc_; }
+#endif
+    const size_t vox = (size_t)c->th.vox;
+    int rc = OLX_OK;
+    if (rise_max) rc = fetch_to_host(c, rise_max, c->d_th_max, sizeof(float) * vox);
+    if (!rc && cem43) rc = fetch_to_host(c, cem43, c->d_th_cem, sizeof(float) * vox);
+    if (!rc && traces && c->th_npts > 0) rc = fetch_to_host(c, traces, c->d_th_trace, sizeof(float) * (size_t)c->th_next * c->th_npts);
+    return rc;
 }
 
 }  // extern "C"

@@ -124,6 +124,15 @@ struct olx_ctx {
     PulseParams pulse{};
     float* d_pmax = nullptr; size_t pmax_cap = 0; float* d_agg_pmax = nullptr; size_t agg_pmax_cap = 0;
     double4* d_ptab = nullptr; float* d_pw = nullptr; size_t ptab_cap = 0;
+    // thermal model (kernel 3, olx_thermal_*): buffers of their own, apart from the field / aggregate volumes
+    bool th_planned = false, th_uniform = false; ThermalParams th{};
+    double th_rate = 0;                        // max_v (sum_faces K + W) / (rho Cp)_v [1/s]: the FTCS bound is dt <= 1 / th_rate
+    float* d_th_T[2] = {nullptr, nullptr}; int th_cur = 0; float *d_th_max = nullptr, *d_th_cem = nullptr; size_t th_cap = 0;
+    float4* d_th_coef = nullptr; float *d_th_irc = nullptr, *d_th_sfac = nullptr; size_t th_coef_cap = 0; unsigned* d_th_rate = nullptr;
+    int th_steps = 0, th_max_focus = -1; std::vector<int> th_row; int* d_th_sf = nullptr; float* d_th_tau = nullptr; size_t th_sched_cap = 0;
+    int th_npts = 0; long long* d_th_pts = nullptr; size_t th_pts_cap = 0; float* d_th_trace = nullptr; size_t th_trace_cap = 0;
+    int th_src_foci = 0; bool th_src_resident = false; float* d_th_I = nullptr; size_t th_I_cap = 0;
+    int th_next = -1;                          // the step the next olx_thermal_run continues with (-1: nothing run since the last plan / schedule)
     // comm: RCCL communicator, or the direct peer-to-peer transport (exactly one of comm / p2p is set once initialised)
     P2PState* p2p = nullptr;
     bool comm_active() const { return comm != nullptr || p2p != nullptr; }

@@ -156,6 +156,23 @@ struct PulseParams {
     long long vox;
 };
 
+// kernel 3 (thermal_pack_k / thermal_step_k, k_thermal.hip): Pennes bioheat rise, explicit FTCS (olx_thermal_*)
+struct ThermalParams {
+    int nx, ny, nz;
+    long long vox;
+    float ihx2, ihy2, ihz2;          // 1 / h^2 per axis [1/m^2]
+    float rho0, cp0, kappa0, alpha0; // the scalars of the volumes passed as NULL
+    float perf;                      // uniform perfusion W [W/m^3/K]
+    float gx, gy, gz;                // uniform medium: kappa / h^2 per axis
+    float irc0, sfac0;               // uniform medium: 1 / (rho Cp), 2 alpha 1e4 / (rho Cp)
+};
+struct ThermalStep {
+    float dt;                        // [s]
+    float dt_min;                    // dt / 60 [min]: the CEM43 increment at T = 43
+    float tb43;                      // T_b - 43 [K]
+    int npts, n_foci;                // trace points; foci of the source volumes
+};
+
 struct PeakParams {
     int nx, ny, nz;
     double ox, oy, oz, hx, hy, hz;  // slab voxel (0,0,0) position and spacing [m]

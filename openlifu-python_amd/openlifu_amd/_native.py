@@ -39,6 +39,7 @@ SYMBOLS = [
     "olx_solution_analyze", "olx_scan_time", "olx_comm_export", "olx_comm_import", "olx_comm_transport",
     "olx_field_scale_aggregate", "olx_field_absorption", "olx_comm_ranks_seen",
     "olx_field_pulse", "olx_field_fetch_pmax", "olx_aggregate_fetch_pmax",
+    "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
 ]
 
 
@@ -129,6 +130,11 @@ def load(require_gpu: bool = True):
         lib.olx_field_pulse.argtypes = [vp, c_double, c_double, c_int]
         lib.olx_field_fetch_pmax.argtypes = [vp, fp]
         lib.olx_aggregate_fetch_pmax.argtypes = [vp, fp]
+        lib.olx_thermal_plan.argtypes = [vp, POINTER(OlxGrid), fp, fp, fp, fp, c_double, c_double, c_double, c_double, c_double, dp]
+        lib.olx_thermal_schedule.argtypes = [vp, c_int, POINTER(c_int), POINTER(c_int), dp, c_int, POINTER(ctypes.c_longlong)]
+        lib.olx_thermal_source.argtypes = [vp, c_int, fp]
+        lib.olx_thermal_run.argtypes = [vp, c_double, c_double, c_int, c_int]
+        lib.olx_thermal_fetch.argtypes = [vp, fp, fp, fp]
         lib.olx_set_element_apertures.argtypes = [vp, dp, dp]
         lib.olx_comm_export.argtypes = [vp, vp]
         lib.olx_comm_import.argtypes = [vp, vp]
@@ -436,6 +442,59 @@ class Context:
         """Pulsed (tone-burst) model for the plans that follow: ``cycles`` cycles sampled at ``dt`` [s] over ``n_t`` samples;
         ``n_t = 0`` = continuous wave (the default).  A pulsed plan's OUT_PMAG slot holds p_min, OUT_PMAX adds p_max."""
         self._chk(self._lib.olx_field_pulse(self._h, float(cycles), float(dt), int(n_t)))
+
+    # ---- thermal model (kernel 3) ------------------------------------------------------------------------------------------
+    def thermal_plan(self, origin_m, spacing_m, n, density, specific_heat, conductivity, absorption, perfusion=0.0) -> float:
+        """Grid and medium of the thermal model; each medium argument is a float (uniform) or a [nx, ny, nz] volume
+        (absorption in Np/m).  Returns the device's FTCS bound dt_max [s]."""
+        shape = tuple(int(v) for v in n)
+        g = OlxGrid()
+        for a in range(3):
+            g.origin[a] = float(origin_m[a]); g.spacing[a] = float(spacing_m[a]); g.n[a] = shape[a]
+        vols, scal = [], []
+        for v in (density, specific_heat, conductivity, absorption):
+            if np.ndim(v) == 0:
+                vols.append(None); scal.append(float(v))
+            else:
+                a = np.ascontiguousarray(v, dtype=np.float32)
+                if a.shape != shape:
+                    raise ValueError(f"thermal medium volume must be {shape}, got {a.shape}")
+                vols.append(a); scal.append(0.0)
+        dt_max = c_double(0.0)
+        self._chk(self._lib.olx_thermal_plan(self._h, ctypes.byref(g), *[_fptr(a) for a in vols], *scal, float(perfusion), ctypes.byref(dt_max)))
+        self._th_shape = shape
+        return float(dt_max.value)
+
+    def thermal_schedule(self, row_ptr, focus, tau, points=None):
+        """CSR schedule (row_ptr [n_steps + 1], focus / tau [entries]) and trace points (linear voxel indices)."""
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        fo = np.ascontiguousarray(focus, dtype=np.int32)
+        ta = np.ascontiguousarray(tau, dtype=np.float64)
+        pts = np.ascontiguousarray([] if points is None else points, dtype=np.int64)
+        ip, lp = POINTER(c_int), POINTER(ctypes.c_longlong)
+        self._chk(self._lib.olx_thermal_schedule(self._h, int(rp.size - 1), rp.ctypes.data_as(ip), fo.ctypes.data_as(ip), _dptr(ta),
+                                                 int(pts.size), pts.ctypes.data_as(lp)))
+        self._th_steps, self._th_npts = int(rp.size - 1), int(pts.size)
+
+    def thermal_source(self, n_foci: int, intensity=None):
+        """Source volumes [F, nx, ny, nz] W/cm^2 uploaded once, or None = the resident intensity, read in place."""
+        it = None if intensity is None else np.ascontiguousarray(intensity, dtype=np.float32)
+        if it is not None and it.shape != (int(n_foci),) + self._th_shape:
+            raise ValueError(f"intensity must be {(int(n_foci),) + self._th_shape}, got {it.shape}")
+        self._chk(self._lib.olx_thermal_source(self._h, int(n_foci), _fptr(it)))
+
+    def thermal_run(self, dt: float, baseline: float, first_step: int = 0, n_steps=None):
+        n_steps = self._th_steps - int(first_step) if n_steps is None else int(n_steps)
+        self._chk(self._lib.olx_thermal_run(self._h, float(dt), float(baseline), int(first_step), n_steps))
+        self._th_ran = int(first_step) + n_steps
+
+    def thermal_fetch(self):
+        """(rise_max [K], CEM43 [min], traces [steps run, points])."""
+        rise = np.empty(self._th_shape, dtype=np.float32)
+        cem = np.empty(self._th_shape, dtype=np.float32)
+        tr = np.empty((self._th_ran, self._th_npts), dtype=np.float32)
+        self._chk(self._lib.olx_thermal_fetch(self._h, _fptr(rise), _fptr(cem), _fptr(tr) if tr.size else None))
+        return rise, cem, tr
 
     def field_scale_aggregate(self, scale_per_focus):
         """``field_scale`` + ``field_aggregate_device`` in one pass (identical values)."""

@@ -335,6 +335,18 @@ class Engine:
             return {k: np.stack([o[k] for o in outs], axis=0) for k in outs[0]}
         return self.ctx.field_fetch_all(want=want)
 
+    # ---- kernel 3 -----------------------------------------------------------------------------
+    def thermal(self, origin_m, spacing_m, n, medium, perfusion, schedule, n_foci, dt, baseline, intensity=None, points=None):
+        """Thermal model (sim/thermal.py, kernel 3) -> (rise_max [K], CEM43 [min], traces [n_steps, P] rise [K]), float32.
+        ``medium = (density, specific_heat, conductivity, absorption [Np/m])``, each a float or a [nx, ny, nz] volume;
+        ``schedule = (row_ptr, focus, tau)``; ``intensity`` [F, nx, ny, nz] W/cm^2 is uploaded once, None reads the resident
+        intensity in place.  The field / aggregate volumes and every lazy array over them are left as they are."""
+        self.ctx.thermal_plan(origin_m, spacing_m, n, *medium, perfusion=perfusion)
+        self.ctx.thermal_schedule(*schedule, points=points)
+        self.ctx.thermal_source(n_foci, intensity)
+        self.ctx.thermal_run(dt, baseline)
+        return self.ctx.thermal_fetch()
+
     def upload_result(self, origin_m, spacing_m, n, pmag, intensity=None):
         """Bind host volumes [F,nx,ny,nz] as the resident result (analysis of a detached Solution)."""
         self.retire_results()

@@ -1,10 +1,12 @@
-"""Simulation grid + the ``run_simulation`` seam (HIP kernel 2 instead of k-Wave)."""
+"""Simulation grid + the ``run_simulation`` seam (HIP kernel 2 instead of k-Wave) + the thermal model (HIP kernel 3)."""
 from __future__ import annotations
 
 from . import field
 from . import sim_setup as _sim_setup
+from . import thermal
 
 run_simulation = field.run_simulation
 SimSetup = _sim_setup.SimSetup
+run_thermal_simulation = thermal.run_thermal_simulation
 
-__all__ = ("SimSetup", "run_simulation", "field")
+__all__ = ("SimSetup", "run_simulation", "run_thermal_simulation", "field", "thermal")
