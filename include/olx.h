@@ -117,6 +117,22 @@ int olx_bf_solve(olx_ctx *ctx, const double *foci_m, int n_foci, const double *M
  * equal values) with HIP events on the context's stream; us_each[iters] = microseconds per F x N solve (bench.py). */
 int olx_bf_time(olx_ctx *ctx, int iters, float *us_each);
 
+/* ---- kernel 1m: StraightRay delays through a medium (DESIGN.md section 2 "StraightRay") --------------
+ * The DelayMethod.calc_delays seam again (its `params` argument carries the medium): the delays that make
+ * the straight-ray field model of olx_field_set_medium (section 7) add up in phase at each focus,
+ *   tau_e = tof_e + E_e / c_ref,   delays = max_e tau_e - tau_e,
+ * tof_e = kernel 1's |focus - g_e| / c_ref, E_e = the straight-ray extra path through sigma = c_ref / c - 1.
+ * Set the medium: sound_speed [nx*ny*nz] floats on `grid` (C order; NULL = c_ref everywhere), in the frame
+ * of the foci.  Only the planes with some sound speed != c_ref are held, in buffers of their own: a field
+ * plan, its medium and its volumes are left as they are.  Refused (nothing on the device touched): c_ref
+ * non-finite or <= 0, a sound speed non-finite or <= 0, a bad grid. */
+int olx_bf_set_medium(olx_ctx *ctx, const float *sound_speed, const olx_grid *grid, double c_ref);
+/* olx_bf_solve's arguments and outputs with the delays corrected through the medium of olx_bf_set_medium
+ * (c must equal its c_ref); the apodization is kernel 1's.  All foci in one launch; the results stay
+ * device-resident as the context's steering table, like olx_bf_solve's.  OLX_ESTATE before a medium is set. */
+int olx_bf_solve_medium(olx_ctx *ctx, const double *foci_m, int n_foci, const double *M, double c,
+                        int apod_kind, double p0, double p1, double *delays_out, double *apod_out);
+
 /* Upload externally computed delays / apodizations [F*N] as the steering table
  * (run_simulation's `delays`, `apod` arguments, sim/kwave_if.py:81-83, 98-99). */
 int olx_set_steering(olx_ctx *ctx, const double *delays_s, const double *apod, int n_foci);

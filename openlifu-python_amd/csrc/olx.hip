@@ -64,7 +64,8 @@ int olx_ctx_destroy(olx_ctx* c) {
                     c->d_pmag[0], c->d_pmag[1], c->d_inten, c->d_cplx, c->d_agg_p, c->d_agg_i,
                     c->d_scale, c->d_gather, c->d_peakA, c->d_peak, c->d_perm, c->d_coords, c->d_bfrag, c->d_colinfo, c->d_wint, c->d_med, c->d_plane_k, c->d_plane_of_k,
                     c->d_an, c->d_inv2z, c->d_kfirst, c->d_klast, c->d_slot, c->d_jobs, c->d_med_layer, c->d_layer_lo, c->d_layer_hi, c->d_U[0], c->d_U[1], c->d_Utex, c->d_sig, c->d_cell, c->d_afrag, c->d_tab2, c->d_cpblocks, c->d_pmax, c->d_agg_pmax, c->d_ptab, c->d_pw,
-                    c->d_th_T[0], c->d_th_T[1], c->d_th_max, c->d_th_cem, c->d_th_coef, c->d_th_irc, c->d_th_sfac, c->d_th_rate, c->d_th_sf, c->d_th_tau, c->d_th_pts, c->d_th_trace, c->d_th_I};
+                    c->d_th_T[0], c->d_th_T[1], c->d_th_max, c->d_th_cem, c->d_th_coef, c->d_th_irc, c->d_th_sfac, c->d_th_rate, c->d_th_sf, c->d_th_tau, c->d_th_pts, c->d_th_trace, c->d_th_I,
+                    c->d_bm_sig, c->d_bm_zp, c->d_bm_pk};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -74,11 +75,12 @@ int olx_ctx_destroy(olx_ctx* c) {
 const char* olx_last_error(const olx_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 #ifdef OLX_DEBUG_BOUNDS   // debug build (k_types.hip.h): the kernels' index checks report here
-extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); }
+extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); int olx_dbg_bounds_bfmed(unsigned*); }
 static int report_bounds(olx_ctx* c) {
     struct { const char* name; int (*read)(unsigned*); } units[] = {{"2g (k_coset2.hip)", olx_dbg_bounds_cosetp}, {"2e (k_coset.hip)", olx_dbg_bounds_coset},
                                                                      {"2f (k_toep.hip)", olx_dbg_bounds_toep}, {"2m (k_hmarch.hip)", olx_dbg_bounds_hmarch},
-                                                                     {"2p (k_pulse.hip)", olx_dbg_bounds_pulse}, {"3 (k_thermal.hip)", olx_dbg_bounds_thermal}};
+                                                                     {"2p (k_pulse.hip)", olx_dbg_bounds_pulse}, {"3 (k_thermal.hip)", olx_dbg_bounds_thermal},
+                                                                     {"1m (k_bfmed.hip)", olx_dbg_bounds_bfmed}};
     int rc = OLX_OK;
     for (auto& u : units) {
         unsigned w[4] = {0, 0, 0, 0};
@@ -248,6 +250,87 @@ int olx_bf_time(olx_ctx* c, int iters, float* us_each) {
     for (int i = 0; i < iters && e == hipSuccess; ++i) { float ms = 0; e = hipEventElapsedTime(&ms, ev[i], ev[i + 1]); us_each[i] = ms * 1e3f; }
     for (auto& v : ev) hipEventDestroy(v);
     if (e != hipSuccess) return fail(c, OLX_EHIP, "olx_bf_time: %s", hipGetErrorString(e));
+    return OLX_OK;
+}
+
+// ---- kernel 1m: StraightRay delays through a medium ------------------------------------------------------------------
+int olx_bf_set_medium(olx_ctx* c, const float* sound_speed, const olx_grid* grid, double c_ref) {
+    if (!c) return OLX_EINVAL;
+    if (!grid) return fail(c, OLX_EINVAL, "olx_bf_set_medium: null grid");
+    if (!(c_ref > 0) || !std::isfinite(c_ref)) return fail(c, OLX_EINVAL, "olx_bf_set_medium: c_ref must be finite and > 0");
+    for (int a = 0; a < 3; ++a) {
+        if (grid->n[a] < 1) return fail(c, OLX_EINVAL, "olx_bf_set_medium: grid sizes must be >= 1");
+        if (!(grid->spacing[a] > 0) || !std::isfinite(grid->spacing[a]) || !std::isfinite(grid->origin[a]))
+            return fail(c, OLX_EINVAL, "olx_bf_set_medium: grid spacing must be finite and > 0, origin finite");
+    }
+    const int nx = grid->n[0], ny = grid->n[1], nz = grid->n[2];
+    const size_t nxy = (size_t)nx * ny;
+    if (sound_speed)
+        for (size_t o = 0; o < nxy * nz; ++o)
+            if (!(sound_speed[o] > 0.f) || !std::isfinite(sound_speed[o])) return fail(c, OLX_EINVAL, "olx_bf_set_medium: sound speed must be finite and > 0");
+    // the held planes: olx_field_set_medium's rule for the sound speed (a plane with any voxel != c_ref), sigma = c_ref / c - 1 in fp64
+    std::vector<int> pk(nz, -1);
+    std::vector<double> zp, sig;
+    for (int k = 0; k < nz && sound_speed; ++k) {
+        bool any = false;
+        for (size_t ij = 0; ij < nxy && !any; ++ij) any = (double)sound_speed[ij * nz + k] != c_ref;
+        if (!any) continue;
+        pk[k] = (int)zp.size();
+        zp.push_back(grid->origin[2] + k * grid->spacing[2]);
+        for (size_t ij = 0; ij < nxy; ++ij) sig.push_back(c_ref / (double)sound_speed[ij * nz + k] - 1.0);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a solve of the previous medium may still read the buffers)
+    c->bm_set = false;
+    auto grow = [&](void** p, size_t& cap, size_t bytes) -> int {
+        if (cap >= bytes) return OLX_OK;
+        if (*p) hipFree(*p);
+        *p = nullptr; cap = 0;
+        HIPCHK(c, hipMalloc(p, bytes));
+        cap = bytes;
+        return OLX_OK;
+    };
+    int rc = grow((void**)&c->d_bm_sig, c->bm_sig_cap, sizeof(double) * std::max<size_t>(sig.size(), 1));
+    if (!rc) rc = grow((void**)&c->d_bm_zp, c->bm_zp_cap, sizeof(double) * std::max<size_t>(zp.size(), 1));
+    if (!rc) rc = grow((void**)&c->d_bm_pk, c->bm_pk_cap, sizeof(int) * nz);
+    if (rc) return rc;
+    if (!sig.empty()) HIPCHK(c, hipMemcpy(c->d_bm_sig, sig.data(), sizeof(double) * sig.size(), hipMemcpyHostToDevice));
+    if (!zp.empty()) HIPCHK(c, hipMemcpy(c->d_bm_zp, zp.data(), sizeof(double) * zp.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_bm_pk, pk.data(), sizeof(int) * nz, hipMemcpyHostToDevice));
+    BfMedParams& P = c->bm;
+    P.ox = grid->origin[0]; P.oy = grid->origin[1]; P.oz = grid->origin[2];
+    P.hx = grid->spacing[0]; P.hy = grid->spacing[1]; P.hz = grid->spacing[2];
+    P.dmin = 0.5 * std::min(P.hx, std::min(P.hy, P.hz));
+    P.ztol = 1e-6 * P.hz;
+    P.c = c_ref;
+    P.nx = nx; P.ny = ny; P.nz = nz; P.n_planes = (int)zp.size();
+    c->bm_set = true;
+    return OLX_OK;
+}
+
+int olx_bf_solve_medium(olx_ctx* c, const double* foci_m, int n_foci, const double* M, double cs, int apod_kind,
+                        double p0, double p1, double* delays_out, double* apod_out) {
+    if (!c) return OLX_EINVAL;
+    if (!c->bm_set) return fail(c, OLX_ESTATE, "olx_bf_solve_medium: call olx_bf_set_medium first");
+    if (c->n_el <= 0) return fail(c, OLX_ESTATE, "olx_bf_solve_medium: call olx_set_elements first");
+    if (!foci_m || n_foci <= 0) return fail(c, OLX_EINVAL, "olx_bf_solve_medium: no foci");
+    if (cs != c->bm.c) return fail(c, OLX_EINVAL, "olx_bf_solve_medium: c (%.17g) must be the c_ref of olx_bf_set_medium (%.17g)", cs, c->bm.c);
+    for (size_t q = 0; q < 3 * (size_t)n_foci; ++q)
+        if (!std::isfinite(foci_m[q])) return fail(c, OLX_EINVAL, "olx_bf_solve_medium: focus positions must be finite");
+    for (int q = 0; M && q < 16; ++q)
+        if (!std::isfinite(M[q])) return fail(c, OLX_EINVAL, "olx_bf_solve_medium: transform must be finite");
+    // kernel 1 (the apodization, the foci and the transform on the device), then kernel 1m over its delays
+    int rc = olx_bf_solve(c, foci_m, n_foci, M, cs, apod_kind, p0, p1, nullptr, apod_out);
+    if (rc) return rc;
+    olx_launch_bfmed(c, n_foci);
+    HIPCHK(c, hipGetLastError());
+    const size_t fn = (size_t)n_foci * c->n_el;
+    HIPCHK(c, hipMemcpyAsync(c->h_delays.data(), c->d_delays, sizeof(double) * fn, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (delays_out) memcpy(delays_out, c->h_delays.data(), sizeof(double) * fn);
+    c->steer_version++;
+    c->h_foci.clear();      // not geometric delays: the planner must not take the foci as known (infer_foci decides)
+    c->bf_valid = false;    // (olx_bf_time would rewrite the table with kernel 1's delays)
     return OLX_OK;
 }
 

@@ -133,6 +133,12 @@ struct olx_ctx {
     int th_npts = 0; long long* d_th_pts = nullptr; size_t th_pts_cap = 0; float* d_th_trace = nullptr; size_t th_trace_cap = 0;
     int th_src_foci = 0; bool th_src_resident = false; float* d_th_I = nullptr; size_t th_I_cap = 0;
     int th_next = -1;                          // the step the next olx_thermal_run continues with (-1: nothing run since the last plan / schedule)
+    // StraightRay delays (kernel 1m, olx_bf_set_medium / olx_bf_solve_medium): the non-trivial sigma planes in buffers of their own, apart from
+    // the field plan's medium and volumes
+    bool bm_set = false; BfMedParams bm{};
+    double* d_bm_sig = nullptr; size_t bm_sig_cap = 0;        // [n_planes][nx][ny] sigma = c_ref / c - 1 (fp64)
+    double* d_bm_zp = nullptr; size_t bm_zp_cap = 0;          // [n_planes] z of the held planes [m]
+    int* d_bm_pk = nullptr; size_t bm_pk_cap = 0;             // [nz] held plane of grid plane k, -1 = sigma == 0 there
     // comm: RCCL communicator, or the direct peer-to-peer transport (exactly one of comm / p2p is set once initialised)
     P2PState* p2p = nullptr;
     bool comm_active() const { return comm != nullptr || p2p != nullptr; }

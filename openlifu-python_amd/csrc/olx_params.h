@@ -173,6 +173,15 @@ struct ThermalStep {
     int npts, n_foci;                // trace points; foci of the source volumes
 };
 
+// kernel 1m (bf_med_k, k_bfmed.hip): straight-ray delays through the medium of olx_bf_set_medium (DESIGN.md section 2 "StraightRay")
+struct BfMedParams {
+    double ox, oy, oz, hx, hy, hz;  // grid origin and spacing [m]
+    double dmin;                    // min(spacing) / 2: the clamp of the path length l
+    double ztol;                    // 1e-6 hz: a plane this close to the focus is the focus' own plane, not a crossing
+    double c;                       // c_ref [m/s]
+    int nx, ny, nz, n_planes;       // grid; non-trivial sigma planes held
+};
+
 struct PeakParams {
     int nx, ny, nz;
     double ox, oy, oz, hx, hy, hz;  // slab voxel (0,0,0) position and spacing [m]

@@ -40,6 +40,7 @@ SYMBOLS = [
     "olx_field_scale_aggregate", "olx_field_absorption", "olx_comm_ranks_seen",
     "olx_field_pulse", "olx_field_fetch_pmax", "olx_aggregate_fetch_pmax",
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
+    "olx_bf_set_medium", "olx_bf_solve_medium",
 ]
 
 
@@ -87,6 +88,8 @@ def load(require_gpu: bool = True):
         lib.olx_sync.argtypes = [vp]
         lib.olx_set_elements.argtypes = [vp, dp, dp, dp, c_int]
         lib.olx_bf_solve.argtypes = [vp, dp, c_int, dp, c_double, c_int, c_double, c_double, dp, dp]
+        lib.olx_bf_set_medium.argtypes = [vp, fp, POINTER(OlxGrid), c_double]
+        lib.olx_bf_solve_medium.argtypes = [vp, dp, c_int, dp, c_double, c_int, c_double, c_double, dp, dp]
         lib.olx_set_steering.argtypes = [vp, dp, dp, c_int]
         lib.olx_bf_quantize.argtypes = [vp, c_double, c_int, c_void_p, c_void_p, dp, c_void_p]
         lib.olx_field_plan.argtypes = [vp, POINTER(OlxGrid), POINTER(OlxSlab), c_int, c_double, c_double,
@@ -245,6 +248,32 @@ class Context:
         apod = np.empty((F, self.n_el)) if want_outputs else None
         self._chk(self._lib.olx_bf_solve(self._h, _dptr(foci_m), F, _dptr(M), float(c), int(apod_kind),
                                          float(p0), float(p1), _dptr(delays), _dptr(apod)))
+        self.n_foci = F
+        return delays, apod
+
+    # -- kernel 1m (StraightRay delays)
+    def bf_set_medium(self, sound_speed, origin_m, spacing_m, n, c_ref):
+        """The medium of ``bf_solve_medium``: sound speed [nx,ny,nz] (None = c_ref everywhere) on the grid (origin, spacing [m], n),
+        in the frame of the foci.  Leaves any field plan, its medium and its volumes as they are."""
+        shape = tuple(int(v) for v in n)
+        g = OlxGrid()
+        for a in range(3):
+            g.origin[a] = float(origin_m[a]); g.spacing[a] = float(spacing_m[a]); g.n[a] = shape[a]
+        ss = None if sound_speed is None else np.ascontiguousarray(sound_speed, dtype=np.float32)
+        if ss is not None and ss.shape != shape:
+            raise ValueError(f"sound speed volume must have the grid shape {shape}, got {ss.shape}")
+        self._chk(self._lib.olx_bf_set_medium(self._h, _fptr(ss), ctypes.byref(g), float(c_ref)))
+
+    def bf_solve_medium(self, foci_m, c, matrix=None, apod_kind=APOD_UNIFORM, p0=1.0, p1=0.0):
+        """``bf_solve`` with the delays corrected through the medium of ``bf_set_medium`` (c = its c_ref) -> (delays, apod) [F,N]."""
+        foci_m = _f64(np.atleast_2d(foci_m))
+        if foci_m.shape[1] != 3:
+            raise ValueError("foci_m must be [F,3]")
+        F = foci_m.shape[0]
+        M = None if matrix is None else _f64(matrix, (4, 4))
+        delays, apod = np.empty((F, self.n_el)), np.empty((F, self.n_el))
+        self._chk(self._lib.olx_bf_solve_medium(self._h, _dptr(foci_m), F, _dptr(M), float(c), int(apod_kind),
+                                                float(p0), float(p1), _dptr(delays), _dptr(apod)))
         self.n_foci = F
         return delays, apod
 

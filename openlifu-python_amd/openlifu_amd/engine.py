@@ -265,6 +265,17 @@ class Engine:
         kind, p0, p1 = apod
         return self.ctx.bf_solve(focus_positions_m(targets), c, matrix=transform, apod_kind=kind, p0=p0, p1=p1)
 
+    # ---- kernel 1m ----------------------------------------------------------------------------
+    def beamform_medium(self, arr, targets, c_ref: float, sound_speed, origin_m, spacing_m, n, transform=None,
+                        apod=(nat.APOD_UNIFORM, 1.0, 0.0)):
+        """StraightRay delays[F,N] (s) through the sound-speed volume (None = c_ref everywhere) and kernel 1's apod[F,N]: the medium is
+        uploaded once, all foci are solved in one launch and the corrected table stays resident as the steering table.  The field
+        plan, its medium and its volumes are left as they are."""
+        self.bind(arr)
+        kind, p0, p1 = apod
+        self.ctx.bf_set_medium(sound_speed, origin_m, spacing_m, n, c_ref)
+        return self.ctx.bf_solve_medium(focus_positions_m(targets), c_ref, matrix=transform, apod_kind=kind, p0=p0, p1=p1)
+
     # ---- kernel 2 -----------------------------------------------------------------------------
     def field(self, arr, delays, apod, origin_m, spacing_m, n, freq, c, rho, p0_pa,
               want=("pmag", "intensity"), slab=None, steering_resident=False, medium=None, fp8_correction=None,

@@ -23,7 +23,7 @@ import numpy as np
 
 from .. import bf, seg, sim
 from ..bf.apod_methods import ApodizationMethod
-from ..bf.delay_methods import Direct
+from ..bf.delay_methods import Direct, StraightRay
 from ..engine import get_engine, gpu_available
 from ..geo import Point
 from ..sim.field import dataset_from_fields, lazy_stack, parse_field_model, simulate_foci, _ATTRS
@@ -146,14 +146,21 @@ class Protocol:
 
     # ---- beamforming ------------------------------------------------------------------------------
     def _fused(self) -> bool:
-        return (type(self.delay_method) is Direct and isinstance(self.apod_method, ApodizationMethod)
+        return (type(self.delay_method) in (Direct, StraightRay) and isinstance(self.apod_method, ApodizationMethod)
                 and hasattr(self.apod_method, "kernel_args"))
+
+    def _solve_fused(self, arr, targets, params):
+        """(delays[F,N], apod[F,N]) of the built-in methods: kernel 1 (Direct), or kernels 1 + 1m (StraightRay: the corrected delays
+        are what the resident steering table holds)."""
+        if type(self.delay_method) is StraightRay:
+            return self.delay_method.solve(arr, targets, params, apod=self.apod_method.kernel_args())
+        return get_engine().beamform(arr, targets, self.delay_method.speed(params), apod=self.apod_method.kernel_args())
 
     def beamform(self, arr, target, params):
         """(delays[N], apod[N]) for one focus (plan/protocol.py:129-132).  With the built-in methods
         both come from a single kernel-1 launch; custom plug-ins fall back to their own calc_* calls."""
         if self._fused():
-            d, a = get_engine().beamform(arr, target, self.delay_method.speed(params), apod=self.apod_method.kernel_args())
+            d, a = self._solve_fused(arr, target, params)
             return d[0], a[0]
         return (self.delay_method.calc_delays(arr, target, params),
                 self.apod_method.calc_apodization(arr, target, params))
@@ -161,7 +168,7 @@ class Protocol:
     def beamform_foci(self, arr, foci: List[Point], params):
         """(delays[F,N], apod[F,N]) for all foci in one launch; leaves the steering table on the device."""
         if self._fused():
-            return get_engine().beamform(arr, foci, self.delay_method.speed(params), apod=self.apod_method.kernel_args()) + (True,)
+            return self._solve_fused(arr, foci, params) + (True,)
         pairs = [self.beamform(arr, f, params) for f in foci]
         return np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs]), False
 
