@@ -411,34 +411,34 @@ using namespace olx;
 OLX_BOUNDS_READER(coset)
 
 template <int NT, int MX, int MY>
-static void launch_coset(olx_ctx* c, float* pm, bool clamp) {
+static void launch_coset(olx_ctx* c, const LatticePart& q, float* pm, bool clamp) {
     const CosetParams& Q = c->cp;
-    dim3 grid(c->cp_nblocks, c->mp.n_tiles), blk(COS_NW * 64);      // (the block records of this launch: all of them, or one side of a launch split at fp8_kcut)
-#define OLX_COS(CL, F8) hipLaunchKernelGGL((field_coset_k<NT, MX, MY, CL, F8, false>), grid, blk, 0, c->stream, c->d_bfrag, pm, c->d_inten, c->d_cplx, c->d_jobs, c->d_cpblocks, Q)
+    dim3 grid(q.n_blocks, c->mp.n_tiles), blk(COS_NW * 64);
+#define OLX_COS(CL, F8) hipLaunchKernelGGL((field_coset_k<NT, MX, MY, CL, F8, false>), grid, blk, 0, c->stream, q.bfrag, pm, c->d_inten, c->d_cplx, c->d_jobs, q.blocks, Q)
     if (c->dir_lattice) {   // piston directivity folded into the geometry tables (fp16 corrections only)
-        if (clamp) hipLaunchKernelGGL((field_coset_k<NT, MX, MY, true, false, true>), grid, blk, 0, c->stream, c->d_bfrag, pm, c->d_inten, c->d_cplx, c->d_jobs, c->d_cpblocks, Q);
-        else hipLaunchKernelGGL((field_coset_k<NT, MX, MY, false, false, true>), grid, blk, 0, c->stream, c->d_bfrag, pm, c->d_inten, c->d_cplx, c->d_jobs, c->d_cpblocks, Q);
+        if (clamp) hipLaunchKernelGGL((field_coset_k<NT, MX, MY, true, false, true>), grid, blk, 0, c->stream, q.bfrag, pm, c->d_inten, c->d_cplx, c->d_jobs, q.blocks, Q);
+        else hipLaunchKernelGGL((field_coset_k<NT, MX, MY, false, false, true>), grid, blk, 0, c->stream, q.bfrag, pm, c->d_inten, c->d_cplx, c->d_jobs, q.blocks, Q);
         return;
     }
     if constexpr (cos_fp8(NT)) {
-        if (c->fp8corr) { if (clamp) OLX_COS(true, true); else OLX_COS(false, true); return; }
+        if (q.fp8) { if (clamp) OLX_COS(true, true); else OLX_COS(false, true); return; }
     }
     if (clamp) OLX_COS(true, false); else OLX_COS(false, false);
 #undef OLX_COS
 }
 
 template <int MX, int MY>
-static void dispatch_coset_nt(olx_ctx* c, float* pm) {
+static void dispatch_coset_nt(olx_ctx* c, const LatticePart& q, float* pm) {
     const bool clamp = c->clamp || c->lat.clamp;
-    if (c->nt == 1) launch_coset<1, MX, MY>(c, pm, clamp); else if (c->nt == 2) launch_coset<2, MX, MY>(c, pm, clamp);
-    else launch_coset<4, MX, MY>(c, pm, clamp);
+    if (c->nt == 1) launch_coset<1, MX, MY>(c, q, pm, clamp); else if (c->nt == 2) launch_coset<2, MX, MY>(c, q, pm, clamp);
+    else launch_coset<4, MX, MY>(c, q, pm, clamp);
 }
 
-void olx_launch_coset(olx_ctx* c, float* pm) {
-    if (c->mx == 2 && c->my == 2) dispatch_coset_nt<2, 2>(c, pm);
-    else if (c->mx == 2) dispatch_coset_nt<2, 1>(c, pm);
-    else if (c->my == 2) dispatch_coset_nt<1, 2>(c, pm);
-    else dispatch_coset_nt<1, 1>(c, pm);
+void olx_launch_coset(olx_ctx* c, const LatticePart& q, float* pm) {
+    if (c->mx == 2 && c->my == 2) dispatch_coset_nt<2, 2>(c, q, pm);
+    else if (c->mx == 2) dispatch_coset_nt<2, 1>(c, q, pm);
+    else if (c->my == 2) dispatch_coset_nt<1, 2>(c, q, pm);
+    else dispatch_coset_nt<1, 1>(c, q, pm);
 }
 
 #ifdef OLX_EXP_STAMPS

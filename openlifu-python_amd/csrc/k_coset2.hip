@@ -412,20 +412,20 @@ extern "C" int olx_exp_read_stamps_cosetp(unsigned long long* out) {
 #endif
 
 template <int MX, int MY>
-static void launch_cosetp(olx_ctx* c, float* pm) {
+static void launch_cosetp(olx_ctx* c, const LatticePart& q, float* pm) {
     CosetParams Q = c->cp;
 #ifdef OLX_DEBUG_BOUNDS   // self-test of the debug build: pretend the output arrays hold one focus less -- the last focus' stores must be reported (and skipped)
     if (getenv("OLX_DEBUG_BOUNDS_SELFTEST")) Q.n_foci -= 1;
 #endif
     float* inten_exp = c->d_inten;
     const bool clamp = c->clamp || c->lat.clamp;
-    dim3 grid((unsigned)c->cp_nblocks, c->mp.n_tiles), blk(COS_NW * 64);
+    dim3 grid(q.n_blocks, c->mp.n_tiles), blk(COS_NW * 64);
     const bool both = (Q.flags & 3u) == 3u;
-#define OLX_CP(CL, F8, DR) do { if (both) hipLaunchKernelGGL((field_cosetp_k<MX, MY, CL, F8, DR, true>), grid, blk, 0, c->stream, c->d_bfrag, pm, inten_exp, c->d_targets, c->d_cpblocks, Q); \
-                                else hipLaunchKernelGGL((field_cosetp_k<MX, MY, CL, F8, DR, false>), grid, blk, 0, c->stream, c->d_bfrag, pm, inten_exp, c->d_targets, c->d_cpblocks, Q); } while (0)
+#define OLX_CP(CL, F8, DR) do { if (both) hipLaunchKernelGGL((field_cosetp_k<MX, MY, CL, F8, DR, true>), grid, blk, 0, c->stream, q.bfrag, pm, inten_exp, c->d_targets, q.blocks, Q); \
+                                else hipLaunchKernelGGL((field_cosetp_k<MX, MY, CL, F8, DR, false>), grid, blk, 0, c->stream, q.bfrag, pm, inten_exp, c->d_targets, q.blocks, Q); } while (0)
     if (c->dir_lattice) {   // piston directivity / uniform absorption folded into the geometry tables (fp16 corrections only)
         if (clamp) OLX_CP(true, false, true); else OLX_CP(false, false, true);
-    } else if (c->fp8corr) {
+    } else if (q.fp8) {
         if (clamp) OLX_CP(true, true, false); else OLX_CP(false, true, false);
     } else {
         if (clamp) OLX_CP(true, false, false); else OLX_CP(false, false, false);
@@ -433,9 +433,9 @@ static void launch_cosetp(olx_ctx* c, float* pm) {
 #undef OLX_CP
 }
 
-void olx_launch_cosetp(olx_ctx* c, float* pm) {
-    if (c->mx == 2 && c->my == 2) launch_cosetp<2, 2>(c, pm);
-    else if (c->mx == 2) launch_cosetp<2, 1>(c, pm);
-    else if (c->my == 2) launch_cosetp<1, 2>(c, pm);
-    else launch_cosetp<1, 1>(c, pm);
+void olx_launch_cosetp(olx_ctx* c, const LatticePart& q, float* pm) {
+    if (c->mx == 2 && c->my == 2) launch_cosetp<2, 2>(c, q, pm);
+    else if (c->mx == 2) launch_cosetp<2, 1>(c, q, pm);
+    else if (c->my == 2) launch_cosetp<1, 2>(c, q, pm);
+    else launch_cosetp<1, 1>(c, q, pm);
 }

@@ -647,7 +647,7 @@ static void launch_hmarch_nf(olx_ctx* c, float* pm) {
         S.k_lo = k_lo; S.k_hi = k_hi; S.k_src = p_src >= 0 ? c->h_plane_k[p_src] : -1; S.write = write ? 1 : 0;
         S.i0 = write ? 0 : c->slab.x_begin; S.ni = write ? c->hp.nxg : P.nx;
         S.reverse = write && (n_written & 1);
-        const float2* src = tex ? reinterpret_cast<const float2*>(c->d_Utex) : (p_src >= 0 ? c->d_U[ub] : nullptr);
+        const float2* src = tex ? static_cast<const float2*>(c->d_Utex) : (p_src >= 0 ? c->d_U[ub] : nullptr);
         float2* dst = write ? c->d_U[p_src >= 0 ? ub ^ 1 : ub] : nullptr;       // (the first non-trivial plane has no source: it fills d_U[ub] itself)
         const long long tiles = (long long)((S.ni + HM_TI - 1) / HM_TI) * ((P.ny + HM_TJ - 1) / HM_TJ);
 #define OLX_HM___(ES_, CL, SR, ON, IN) S.nblocks = (unsigned)(tiles * ((ES_ == 1) ? (k_hi - k_lo + 4) / 4 : 1)); \
@@ -698,8 +698,8 @@ static void launch_hmarch_nf(olx_ctx* c, float* pm) {
         if (lds > 78 * 1024) return false;             // two blocks per CU
         S.nblocks = (unsigned)(((c->hp.nxg + fti - 1) / fti) * ((c->hp.nyg + HF_T - 1) / HF_T));
         S.reverse = n_written & 1;
-        const float* src = reinterpret_cast<const float*>(c->d_U[ub]);
-        float* dst = reinterpret_cast<float*>(c->d_U[ub ^ 1]);
+        const float* src = reinterpret_cast<const float*>(static_cast<float2*>(c->d_U[ub]));
+        float* dst = reinterpret_cast<float*>(static_cast<float2*>(c->d_U[ub ^ 1]));
         const dim3 grid((S.nblocks + 7u) / 8u * 8u, ftiles), blk(64 * HF_WAVES);
 #define OLX_HF___(G_, TI_, CL, IN) do { auto kern = field_hmarch_fused_k<G_, TI_, CL, IN>; \
             static size_t attr_set = 0; if (lds > attr_set) { hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = lds; } \
@@ -732,8 +732,8 @@ static void launch_hmarch_nf(olx_ctx* c, float* pm) {
     const bool tex = c->march_one && c->d_Utex && nz - top_lo >= 16 && !getenv("OLX_MARCH_NO_TEXELS");
     if (tex) {
         const long long cells = (long long)c->hp.nxg * c->n_el * c->hp.nyg;
-        hipLaunchKernelGGL(u_texel_k, dim3((unsigned)((cells + 1 + 255) / 256)), dim3(256), 0, c->stream, reinterpret_cast<const float*>(c->d_U[ub]),
-                           reinterpret_cast<float2*>(c->d_Utex), c->hp.nxg, c->n_el, c->hp.nyg);
+        hipLaunchKernelGGL(u_texel_k, dim3((unsigned)((cells + 1 + 255) / 256)), dim3(256), 0, c->stream, reinterpret_cast<const float*>(static_cast<float2*>(c->d_U[ub])),
+                           static_cast<float2*>(c->d_Utex), c->hp.nxg, c->n_el, c->hp.nyg);
     }
     go(top_lo, nz - 1, np - 1, false, tex);
     {   // olx_field_variant names what ran: "...; fused writers: 28 planes in 7 launches"

@@ -588,41 +588,41 @@ extern "C" int olx_exp_read_stamps_toep(unsigned long long* out) {
 }
 #endif
 
-void olx_pack_toep(olx_ctx* c) {
+void olx_pack_toep(olx_ctx* c, const LatticePart& q) {
     const olx_ctx::Lattice& A = c->lat;
     dim3 g(c->toep_nsa * 8 * A.nsb, c->mp.n_tiles);
     hipLaunchKernelGGL(toep_pack_k, g, dim3(64), 0, c->stream, c->d_area, c->n_el, c->d_delays, c->d_apod, c->d_perm, c->freq,
-                       c->mfma_wscale, c->plan_foci, c->d_colinfo, c->d_cell, A.ax, A.ay, 8 * A.nsb, c->fp8corr ? 1 : 0, c->toep_saw, c->cp.xs,
-                       (c->fp8corr && c->toep_nm == 2) ? 1 : 0, c->d_afrag);
+                       c->mfma_wscale, c->plan_foci, c->d_colinfo, c->d_cell, A.ax, A.ay, 8 * A.nsb, q.fp8 ? 1 : 0, c->toep_saw, c->cp.xs,
+                       (q.fp8 && c->toep_nm == 2) ? 1 : 0, q.afrag);
 }
 
 template <int MX, int MY>
-static void launch_toep(olx_ctx* c, float* pm) {
+static void launch_toep(olx_ctx* c, const LatticePart& q, float* pm) {
     ToepParams T;
     T.q = c->cp; T.nsa = c->toep_nsa; T.sa_w = c->toep_saw; T.ax = c->lat.ax; T.ks_mask = c->toep_ksmask; T.ay_pad = 8 * c->lat.nsb;
     for (int q = 0; q < 4; ++q) T.targets[q] = c->toep_targets[q];
     const int nm = c->toep_nm;                          // row tiles per block (the planner's choice: olx.hip)
-    T.n_rec = c->cp_nblocks;
+    T.n_rec = q.n_blocks;
     // (three row tiles: one block per CU walks the records; a multiple of 8 blocks so that a block's records stay on its XCD)
     const unsigned walkers = (unsigned)std::max(8, c->n_cu / 8 * 8);
-    dim3 grid(nm == 3 ? std::min(c->cp_nblocks, walkers) : c->cp_nblocks, c->mp.n_tiles), blk((nm == 3 ? ToepShape<3>::WAVES : ToepShape<1>::WAVES) * 64);      // (the block records of this launch: all of them, or one side of a launch split at fp8_kcut)
+    dim3 grid(nm == 3 ? std::min(q.n_blocks, walkers) : q.n_blocks, c->mp.n_tiles), blk((nm == 3 ? ToepShape<3>::WAVES : ToepShape<1>::WAVES) * 64);
     if (c->dir_lattice) {   // piston directivity folded into the geometry tables (one row tile: the planner keeps nm = 1 here)
-        if (c->clamp || c->lat.clamp) hipLaunchKernelGGL((field_toep_k<MX, MY, true, true>), grid, blk, 0, c->stream, c->d_afrag, pm, c->d_inten, c->d_cpblocks, T);
-        else hipLaunchKernelGGL((field_toep_k<MX, MY, false, true>), grid, blk, 0, c->stream, c->d_afrag, pm, c->d_inten, c->d_cpblocks, T);
+        if (c->clamp || c->lat.clamp) hipLaunchKernelGGL((field_toep_k<MX, MY, true, true>), grid, blk, 0, c->stream, q.afrag, pm, c->d_inten, q.blocks, T);
+        else hipLaunchKernelGGL((field_toep_k<MX, MY, false, true>), grid, blk, 0, c->stream, q.afrag, pm, c->d_inten, q.blocks, T);
         return;
     }
-#define OLX_TP(CL, F8, NM_) hipLaunchKernelGGL((field_toep_k<MX, MY, CL, false, F8, NM_>), grid, blk, 0, c->stream, c->d_afrag, pm, c->d_inten, c->d_cpblocks, T)
+#define OLX_TP(CL, F8, NM_) hipLaunchKernelGGL((field_toep_k<MX, MY, CL, false, F8, NM_>), grid, blk, 0, c->stream, q.afrag, pm, c->d_inten, q.blocks, T)
 #define OLX_TPN(CL, F8) do { if (nm == 3) OLX_TP(CL, F8, 3); else if (nm == 2) OLX_TP(CL, F8, 2); else OLX_TP(CL, F8, 1); } while (0)
     const bool cl = c->clamp || c->lat.clamp;
-    if (c->fp8corr) { if (cl) OLX_TPN(true, true); else OLX_TPN(false, true); }      // e4m3 correction products (the planner's gated default)
+    if (q.fp8) { if (cl) OLX_TPN(true, true); else OLX_TPN(false, true); }      // e4m3 correction products (the planner's gated default)
     else            { if (cl) OLX_TPN(true, false); else OLX_TPN(false, false); }
 #undef OLX_TPN
 #undef OLX_TP
 }
 
-void olx_launch_toep(olx_ctx* c, float* pm) {
-    if (c->mx == 2 && c->my == 2) launch_toep<2, 2>(c, pm);
-    else if (c->mx == 2) launch_toep<2, 1>(c, pm);
-    else if (c->my == 2) launch_toep<1, 2>(c, pm);
-    else launch_toep<1, 1>(c, pm);
+void olx_launch_toep(olx_ctx* c, const LatticePart& q, float* pm) {
+    if (c->mx == 2 && c->my == 2) launch_toep<2, 2>(c, q, pm);
+    else if (c->mx == 2) launch_toep<2, 1>(c, q, pm);
+    else if (c->my == 2) launch_toep<1, 2>(c, q, pm);
+    else launch_toep<1, 1>(c, q, pm);
 }

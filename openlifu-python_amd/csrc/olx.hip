@@ -17,6 +17,18 @@
 #include "olx_plan.h"
 #include "k_toep.hip.h"
 
+// A device table kept with a host copy of what it holds (`held`): uploaded only when `v` differs from that copy.  The copy runs on the
+// context's stream, behind whatever is queued there, and is waited for (`v` may live on the caller's frame).
+template <class T> static int upload_if_changed(olx_ctx* c, DevBuf<T>& d, std::vector<T>& held, const std::vector<T>& v) {
+    if (d.capacity() < v.size() || !d) held.clear();      // (reserve takes a new block: it holds nothing yet)
+    { int rc = d.reserve(c, v.size()); if (rc) return rc; }
+    if (held.size() == v.size() && (v.empty() || !memcmp(held.data(), v.data(), sizeof(T) * v.size()))) return OLX_OK;
+    HIPCHK(c, hipMemcpyAsync(d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    held = v;
+    return OLX_OK;
+}
+
 extern "C" {
 
 int olx_abi_version(void) { return OLX_ABI_VERSION; }
@@ -60,15 +72,8 @@ int olx_ctx_destroy(olx_ctx* c) {
     olx_comm_destroy(c);
     free_fetch_lanes(c);
     if (c->h_an) hipHostFree(c->h_an);
-    void* ptrs[] = {c->d_pos, c->d_nrm, c->d_area, c->d_delays, c->d_apod, c->d_foci, c->d_M, c->d_tab,
-                    c->d_pmag[0], c->d_pmag[1], c->d_inten, c->d_cplx, c->d_agg_p, c->d_agg_i,
-                    c->d_scale, c->d_gather, c->d_peakA, c->d_peak, c->d_perm, c->d_coords, c->d_bfrag, c->d_colinfo, c->d_wint, c->d_med, c->d_plane_k, c->d_plane_of_k,
-                    c->d_an, c->d_inv2z, c->d_kfirst, c->d_klast, c->d_slot, c->d_jobs, c->d_med_layer, c->d_layer_lo, c->d_layer_hi, c->d_U[0], c->d_U[1], c->d_Utex, c->d_sig, c->d_cell, c->d_afrag, c->d_tab2, c->d_cpblocks, c->d_pmax, c->d_agg_pmax, c->d_ptab, c->d_pw,
-                    c->d_th_T[0], c->d_th_T[1], c->d_th_max, c->d_th_cem, c->d_th_coef, c->d_th_irc, c->d_th_sfac, c->d_th_rate, c->d_th_sf, c->d_th_tau, c->d_th_pts, c->d_th_trace, c->d_th_I,
-                    c->d_bm_sig, c->d_bm_zp, c->d_bm_pk};
-    for (void* p : ptrs) if (p) hipFree(p);
     if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;     // (the device buffers free themselves)
     return OLX_OK;
 }
 
@@ -132,6 +137,22 @@ static int exported_buffers_quiesce(olx_ctx* c, int buf) {
     return rc;
 }
 
+// The output volumes: d_pmag[0, nbuf) of `total` floats, d_inten / d_cplx when wanted, at the capacity of d_pmag[0] like the aggregate
+// volumes (reserve_aggregate).  The group is freed together when it is too small or a second buffer is missing -- after the peers'
+// pulls from it are over when `quiesce` (p2p: the blocks are IPC-exported).
+static int reserve_outputs(olx_ctx* c, size_t total, int nbuf, bool want_inten, bool want_cplx, bool quiesce) {
+    if (c->d_pmag[0].capacity() < total || (nbuf == 2 && !c->d_pmag[1])) {
+        if (quiesce) { int rc = exported_buffers_quiesce(c, -1); if (rc) return rc; }
+        for (DevBuf<float>* b : {&c->d_pmag[0], &c->d_pmag[1], &c->d_inten, &c->d_cplx, &c->d_agg_p, &c->d_agg_i}) b->release();
+    }
+    int rc = OLX_OK;
+    for (int b = 0; b < nbuf && !rc; ++b) rc = c->d_pmag[b].reserve(c, total);
+    const size_t cap = c->d_pmag[0].capacity();
+    if (!rc && want_inten) rc = c->d_inten.reserve(c, cap);
+    if (!rc && want_cplx) rc = c->d_cplx.reserve(c, 2 * cap);
+    return rc;
+}
+
 // ---- element table ---------------------------------------------------------------------
 int olx_set_elements(olx_ctx* c, const double* pos_m, const double* normal, const double* area_m2, int n) {
     if (!c) return OLX_EINVAL;
@@ -139,10 +160,11 @@ int olx_set_elements(olx_ctx* c, const double* pos_m, const double* normal, cons
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (n != c->n_el) {
-        for (double** p : {&c->d_pos, &c->d_nrm, &c->d_area}) { if (*p) hipFree(*p); *p = nullptr; }
-        HIPCHK(c, hipMalloc((void**)&c->d_pos, sizeof(double) * 3 * n));
-        HIPCHK(c, hipMalloc((void**)&c->d_nrm, sizeof(double) * 3 * n));
-        HIPCHK(c, hipMalloc((void**)&c->d_area, sizeof(double) * n));
+        for (DevBuf<double>* b : {&c->d_pos, &c->d_nrm, &c->d_area}) b->release();
+        int rc = c->d_pos.reserve(c, 3 * (size_t)n);
+        if (!rc) rc = c->d_nrm.reserve(c, 3 * (size_t)n);
+        if (!rc) rc = c->d_area.reserve(c, n);
+        if (rc) return rc;
     }
     // AoS [N][3] (the caller's natural layout) -> SoA [3][N] (coalesced on device)
     std::vector<double> soa(3 * (size_t)n), nso(3 * (size_t)n);
@@ -196,20 +218,11 @@ int olx_bf_solve(olx_ctx* c, const double* foci_m, int n_foci, const double* M, 
     if (apod_kind == OLX_APOD_PIECEWISE && !(p1 < p0)) return fail(c, OLX_EINVAL, "olx_bf_solve: rolloff must be < zero angle");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t fn = (size_t)n_foci * c->n_el;
-    if (c->steer_cap < fn) {
-        for (double** p : {&c->d_delays, &c->d_apod}) { if (*p) hipFree(*p); *p = nullptr; }
-        c->steer_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_delays, sizeof(double) * fn));
-        HIPCHK(c, hipMalloc((void**)&c->d_apod, sizeof(double) * fn));
-        c->steer_cap = fn;
-    }
-    if (c->foci_cap < (size_t)n_foci) {
-        if (c->d_foci) hipFree(c->d_foci);
-        c->d_foci = nullptr; c->foci_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_foci, sizeof(double) * 3 * n_foci));
-        c->foci_cap = n_foci;
-    }
-    if (!c->d_M) HIPCHK(c, hipMalloc((void**)&c->d_M, sizeof(double) * 16));
+    int rc = c->d_delays.reserve(c, fn);
+    if (!rc) rc = c->d_apod.reserve(c, fn);
+    if (!rc) rc = c->d_foci.reserve(c, 3 * (size_t)n_foci);
+    if (!rc) rc = c->d_M.reserve(c, 16);
+    if (rc) return rc;
     static const double I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     HIPCHK(c, hipMemcpyAsync(c->d_foci, foci_m, sizeof(double) * 3 * n_foci, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_M, M ? M : I4, sizeof(double) * 16, hipMemcpyHostToDevice, c->stream));
@@ -282,17 +295,9 @@ int olx_bf_set_medium(olx_ctx* c, const float* sound_speed, const olx_grid* grid
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));      // (a solve of the previous medium may still read the buffers)
     c->bm_set = false;
-    auto grow = [&](void** p, size_t& cap, size_t bytes) -> int {
-        if (cap >= bytes) return OLX_OK;
-        if (*p) hipFree(*p);
-        *p = nullptr; cap = 0;
-        HIPCHK(c, hipMalloc(p, bytes));
-        cap = bytes;
-        return OLX_OK;
-    };
-    int rc = grow((void**)&c->d_bm_sig, c->bm_sig_cap, sizeof(double) * std::max<size_t>(sig.size(), 1));
-    if (!rc) rc = grow((void**)&c->d_bm_zp, c->bm_zp_cap, sizeof(double) * std::max<size_t>(zp.size(), 1));
-    if (!rc) rc = grow((void**)&c->d_bm_pk, c->bm_pk_cap, sizeof(int) * nz);
+    int rc = c->d_bm_sig.reserve(c, sig.size());
+    if (!rc) rc = c->d_bm_zp.reserve(c, zp.size());
+    if (!rc) rc = c->d_bm_pk.reserve(c, nz);
     if (rc) return rc;
     if (!sig.empty()) HIPCHK(c, hipMemcpy(c->d_bm_sig, sig.data(), sizeof(double) * sig.size(), hipMemcpyHostToDevice));
     if (!zp.empty()) HIPCHK(c, hipMemcpy(c->d_bm_zp, zp.data(), sizeof(double) * zp.size(), hipMemcpyHostToDevice));
@@ -340,13 +345,9 @@ int olx_set_steering(olx_ctx* c, const double* delays_s, const double* apod, int
     if (!delays_s || !apod || n_foci <= 0) return fail(c, OLX_EINVAL, "olx_set_steering: null pointer or n_foci <= 0");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t fn = (size_t)n_foci * c->n_el;
-    if (c->steer_cap < fn) {
-        for (double** p : {&c->d_delays, &c->d_apod}) { if (*p) hipFree(*p); *p = nullptr; }
-        c->steer_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_delays, sizeof(double) * fn));
-        HIPCHK(c, hipMalloc((void**)&c->d_apod, sizeof(double) * fn));
-        c->steer_cap = fn;
-    }
+    int rc = c->d_delays.reserve(c, fn);
+    if (!rc) rc = c->d_apod.reserve(c, fn);
+    if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_delays, delays_s, sizeof(double) * fn, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_apod, apod, sizeof(double) * fn, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -367,13 +368,13 @@ int olx_bf_quantize(olx_ctx* c, double bf_clk_hz, int width_bits, uint16_t* tick
     const int F = c->n_foci, n = c->n_el;
     const size_t fn = (size_t)F * n;
     // one scratch allocation: [F] max apod (fp64) | [F] overflow counts | [F N] ticks | [F N] apod-off bytes
-    unsigned char* scratch = nullptr;
+    DevScratch scratch;
     const size_t off_o = sizeof(double) * F, off_t = off_o + sizeof(int) * (size_t)((F + 1) & ~1), off_a = off_t + sizeof(unsigned short) * fn;
-    HIPCHK(c, hipMalloc((void**)&scratch, off_a + fn));
-    double* d_m = reinterpret_cast<double*>(scratch);
-    int* d_o = reinterpret_cast<int*>(scratch + off_o);
-    unsigned short* d_t = reinterpret_cast<unsigned short*>(scratch + off_t);
-    unsigned char* d_a = scratch + off_a;
+    HIPCHK(c, hipMalloc(&scratch.p, off_a + fn));
+    double* d_m = scratch.at<double>(0);
+    int* d_o = scratch.at<int>(off_o);
+    unsigned short* d_t = scratch.at<unsigned short>(off_t);
+    unsigned char* d_a = scratch.at<unsigned char>(off_a);
     hipLaunchKernelGGL(bf_quantize_k, dim3(F), dim3(BF_THREADS), 0, c->stream, c->d_delays, c->d_apod, n, bf_clk_hz,
                        (1u << width_bits) - 1u, d_t, d_a, d_m, d_o);
     int rc = OLX_OK;
@@ -383,7 +384,6 @@ int olx_bf_quantize(olx_ctx* c, double bf_clk_hz, int width_bits, uint16_t* tick
     if (!rc && max_apod_out && hipMemcpyAsync(max_apod_out, d_m, sizeof(double) * F, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = OLX_EHIP;
     if (!rc && n_overflow_out && hipMemcpyAsync(n_overflow_out, d_o, sizeof(int) * F, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = OLX_EHIP;
     if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = OLX_EHIP;
-    hipFree(scratch);
     if (rc == OLX_EHIP) return fail(c, OLX_EHIP, "olx_bf_quantize: HIP error");
     return rc;
 }
@@ -432,13 +432,7 @@ static int configure_variant_impl(olx_ctx* c) {
         c->mx = c->my = c->dx = c->dy = c->nt = 1; c->use_mfma = false; c->use_lattice = false;
         c->nf = 1;
         while (c->nf * 2 <= F && c->nf < 8) c->nf *= 2;
-        const size_t need = (size_t)((F + c->nf - 1) / c->nf) * n * (HET_TAB_HEAD + 2 * c->nf);
-        if (c->tab_cap < need) {
-            if (c->d_tab) hipFree(c->d_tab);
-            c->d_tab = nullptr; c->tab_cap = 0;
-            HIPCHK(c, hipMalloc((void**)&c->d_tab, sizeof(float) * need));
-            c->tab_cap = need;
-        }
+        { int rc = c->d_tab.reserve(c, (size_t)((F + c->nf - 1) / c->nf) * n * (HET_TAB_HEAD + 2 * c->nf)); if (rc) return rc; }
         c->hp.n_foci = F;
         char hb[160];
         if (c->marched)
@@ -622,62 +616,32 @@ static int configure_variant_impl(olx_ctx* c) {
         }
         const int n_pad = c->use_lattice ? c->lat.n_pad : (n + 15) / 16 * 16;
         const int ntiles = (int)tiles.size();
-        std::vector<int> colinfo((size_t)ntiles * MAXC * 2, -1), targets((size_t)ntiles * MAXC * 4, -1);
+        // [column][f, m] then [column][4 store targets]: one table, d_targets points at its second part
+        const size_t n_col = (size_t)ntiles * MAXC;
+        std::vector<int> colinfo(n_col * 6, -1);
         for (int t = 0; t < ntiles; ++t)
             for (size_t o = 0; o < tiles[t].size(); ++o) {
                 colinfo[((size_t)t * MAXC + o) * 2] = tiles[t][o].f;
                 colinfo[((size_t)t * MAXC + o) * 2 + 1] = tiles[t][o].m;
-                for (int q = 0; q < 4; ++q) targets[((size_t)t * MAXC + o) * 4 + q] = tiles[t][o].tgt[q];
+                for (int q = 0; q < 4; ++q) colinfo[n_col * 2 + ((size_t)t * MAXC + o) * 4 + q] = tiles[t][o].tgt[q];
             }
         // (uploaded tables are remembered: an interactive caller re-plans per target, and a new target of the same focal pattern leaves the mirror
         // permutations, the columns' representatives and their store targets as they were -- no copies, no wait for the stream)
-        bool sent = false;
-        if (c->up_perm != perm) {
-            HIPCHK(c, hipMemcpyAsync(c->d_perm, perm.data(), sizeof(int) * perm.size(), hipMemcpyHostToDevice, c->stream));
-            c->up_perm = perm; sent = true;
-        }
-        if (c->colinfo_cap < colinfo.size() + targets.size()) {
-            if (c->d_colinfo) hipFree(c->d_colinfo);
-            c->d_colinfo = nullptr; c->colinfo_cap = 0; c->up_colinfo.clear(); c->up_targets.clear();
-            HIPCHK(c, hipMalloc((void**)&c->d_colinfo, sizeof(int) * (colinfo.size() + targets.size())));
-            c->colinfo_cap = colinfo.size() + targets.size();
-        }
-        int* const d_targets_new = c->d_colinfo + colinfo.size();
-        if (c->up_colinfo != colinfo || c->up_targets != targets || c->d_targets != d_targets_new) {
-            c->d_targets = d_targets_new;
-            HIPCHK(c, hipMemcpyAsync(c->d_colinfo, colinfo.data(), sizeof(int) * colinfo.size(), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->d_targets, targets.data(), sizeof(int) * targets.size(), hipMemcpyHostToDevice, c->stream));
-            c->up_colinfo = colinfo; c->up_targets = targets; sent = true;
-        }
-        if (sent) HIPCHK(c, hipStreamSynchronize(c->stream));  // perm / colinfo / targets live on this stack frame
-        if (c->coords_cap < (size_t)n_pad) {
-            if (c->d_coords) hipFree(c->d_coords);
-            c->d_coords = nullptr; c->coords_cap = 0;
-            HIPCHK(c, hipMalloc((void**)&c->d_coords, sizeof(float4) * 2 * n_pad));      // (index, residual) per element: kernel 2c
-            c->coords_cap = n_pad;
-        }
+        { int rc = upload_if_changed(c, c->d_perm, c->up_perm, perm); if (rc) return rc; }
+        { int rc = upload_if_changed(c, c->d_colinfo, c->up_colinfo, colinfo); if (rc) return rc; }
+        c->d_targets = c->d_colinfo + n_col * 2;
         c->bfrag_half = (size_t)ntiles * (n_pad / 16) * 128 * c->nt;      // uint4 per K-step and column tile: hi, lo of the 64 lanes
-        const size_t need = 2 * c->bfrag_half;                            // (a second set in the other arithmetic for a launch split at fp8_kcut)
-        if (c->bfrag_cap < need) {
-            if (c->d_bfrag) hipFree(c->d_bfrag);
-            c->d_bfrag = nullptr; c->bfrag_cap = 0;
-            HIPCHK(c, hipMalloc((void**)&c->d_bfrag, sizeof(uint4) * need));
-            c->bfrag_cap = need;
+        {   // (index, residual) per element: kernel 2c; a second operand set in the other arithmetic for a launch split at fp8_kcut
+            int rc = c->d_coords.reserve(c, 2 * (size_t)n_pad);
+            if (!rc) rc = c->d_bfrag.reserve(c, 2 * c->bfrag_half);
+            if (rc) return rc;
         }
         const double dmin_m = 0.5 * std::min({c->grid.spacing[0], c->grid.spacing[1], c->grid.spacing[2]});
         const bool lat_clamp = c->use_lattice && (c->clamp || c->lat.clamp);
         const double min_dist = !c->use_lattice ? c->min_dist : (lat_clamp ? dmin_m : std::sqrt(c->lat.min_d2));
-        if (c->use_lattice) {
-            if (c->slot_cap < (size_t)n_pad) {
-                if (c->d_slot) hipFree(c->d_slot);
-                c->d_slot = nullptr; c->slot_cap = 0; c->up_slot.clear();
-                HIPCHK(c, hipMalloc((void**)&c->d_slot, sizeof(int) * n_pad));
-                c->slot_cap = n_pad;
-            }
-            if (c->up_slot != c->lat.slot_elem) {     // (uploaded tables are remembered: a new steering table alone changes none of them)
-                HIPCHK(c, hipMemcpy(c->d_slot, c->lat.slot_elem.data(), sizeof(int) * n_pad, hipMemcpyHostToDevice));
-                c->up_slot = c->lat.slot_elem;
-            }
+        if (c->use_lattice) {     // (a new steering table alone changes no slot map)
+            int rc = upload_if_changed(c, c->d_slot, c->up_slot, c->lat.slot_elem);
+            if (rc) return rc;
         }
         // power-of-two operand scales: |G| <= 1/d'_min, |W| <= wmax  ->  hi parts <= 2^14, lo parts normal
         const double dmin_w = std::max(min_dist * rev, 1e-6);
@@ -768,16 +732,8 @@ static int configure_variant_impl(olx_ctx* c) {
                 Q.absorb_l2 = c->dir_lattice ? (float)(c->absorb_np_m * lambda * 1.4426950408889634) : 0.f;   // exp(-a d) = exp2(-a lambda log2(e) d'), d' [wavelengths]
                 {   // dense store-job lists per (launch tile, column tile): job = c16 | image << 4 | focus << 6
                     const std::vector<int> jobs = olxplan::build_store_jobs(tiles, MFMA_MAX_NT, MFMA_COLS, COS_JOBS, (P.flags & OLX_OUT_PMAG) != 0, (P.flags & OLX_OUT_INTENSITY) != 0);
-                    if (c->jobs_cap < jobs.size()) {
-                        if (c->d_jobs) hipFree(c->d_jobs);
-                        c->d_jobs = nullptr; c->jobs_cap = 0; c->up_jobs.clear();
-                        HIPCHK(c, hipMalloc((void**)&c->d_jobs, sizeof(int) * jobs.size()));
-                        c->jobs_cap = jobs.size();
-                    }
-                    if (c->up_jobs != jobs) {
-                        HIPCHK(c, hipMemcpy(c->d_jobs, jobs.data(), sizeof(int) * jobs.size(), hipMemcpyHostToDevice));
-                        c->up_jobs = jobs;
-                    }
+                    int rc = upload_if_changed(c, c->d_jobs, c->up_jobs, jobs);
+                    if (rc) return rc;
                 }
                 {   // kernel 2e / 2g / 2f / 2q block records: blockIdx.x -> (coset, part, plane block), in the kernels' former decode order
                     // (the records depend on the partition only, not on the steering table: a call that changes nothing but the foci finds the
@@ -819,16 +775,7 @@ static int configure_variant_impl(olx_ctx* c) {
                     }
                     const unsigned nblk = (unsigned)blk.size();
                     c->cp_nfar = nblk - (unsigned)((unsigned long long)Q.xs * Q.mx * Q.my * Q.nsx * Q.nsy * kb_near);
-                    if (c->cpblocks_cap < nblk) {
-                        if (c->d_cpblocks) hipFree(c->d_cpblocks);
-                        c->d_cpblocks = nullptr; c->cpblocks_cap = 0; c->up_blocks.clear();
-                        HIPCHK(c, hipMalloc((void**)&c->d_cpblocks, sizeof(CosetBlock) * nblk));
-                        c->cpblocks_cap = nblk;
-                    }
-                    if (c->up_blocks.size() != blk.size() || memcmp(c->up_blocks.data(), blk.data(), sizeof(CosetBlock) * nblk) != 0) {
-                        HIPCHK(c, hipMemcpy(c->d_cpblocks, blk.data(), sizeof(CosetBlock) * nblk, hipMemcpyHostToDevice));
-                        c->up_blocks = blk;
-                    }
+                    { int rc = upload_if_changed(c, c->d_cpblocks, c->up_blocks, blk); if (rc) return rc; }
                     memcpy(c->up_blocks_key, rec_key, sizeof rec_key);
                     c->cp_nblocks = nblk;
                 }
@@ -861,21 +808,10 @@ static int configure_variant_impl(olx_ctx* c) {
                         e4_units += (c->toep_nm == 3 && m == 2u) ? 1 : 2;      // (three row tiles: a column with K-step 1 only takes its element rows in pairs, k_toep.hip)
                     }
                     for (int q = 0; q < 4; ++q) c->toep_targets[q] = tiles[0][0].tgt[q];
-                    if (c->cell_cap < A.cell.size()) {
-                        if (c->d_cell) hipFree(c->d_cell);
-                        c->d_cell = nullptr; c->cell_cap = 0;
-                        HIPCHK(c, hipMalloc((void**)&c->d_cell, sizeof(int) * A.cell.size()));
-                        c->cell_cap = A.cell.size();
-                    }
+                    { int rc = c->d_cell.reserve(c, A.cell.size()); if (rc) return rc; }
                     HIPCHK(c, hipMemcpy(c->d_cell, A.cell.data(), sizeof(int) * A.cell.size(), hipMemcpyHostToDevice));
                     c->afrag_half = (size_t)ntiles * c->toep_nsa * 8 * A.nsb * 4 * 64;
-                    const size_t need = 2 * c->afrag_half;      // (a second set in the other arithmetic for a launch split at fp8_kcut)
-                    if (c->afrag_cap < need) {
-                        if (c->d_afrag) hipFree(c->d_afrag);
-                        c->d_afrag = nullptr; c->afrag_cap = 0;
-                        HIPCHK(c, hipMalloc((void**)&c->d_afrag, sizeof(uint4) * need));
-                        c->afrag_cap = need;
-                    }
+                    { int rc = c->d_afrag.reserve(c, 2 * c->afrag_half); if (rc) return rc; }      // (a second set in the other arithmetic for a launch split at fp8_kcut)
                     // matrix-pipe units (one v_mfma_f32_16x16x32_f16 = 16 cycles): per block and element row, for each of its KY y positions 2 K-steps x 3 fp16
                     // products -- or, with e4m3 corrections, 2 fp16 products + one K = 128 e4m3 instruction (2 units)
                     long long n_mfma = 0;
@@ -937,16 +873,9 @@ static int configure_variant_impl(olx_ctx* c) {
                 if (fy) o = c->h_py[o];
                 perm[(size_t)m * n + e] = o;
             }
-        HIPCHK(c, hipMemcpyAsync(c->d_perm, perm.data(), sizeof(int) * perm.size(), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));  // perm is a stack vector
-        c->up_perm.clear();                          // (the lattice / matrix path's remembered copy no longer describes d_perm)
-        const size_t need = (size_t)((F + c->nf - 1) / c->nf) * n * (SH_HEAD + 2 * nm * c->nf);  // never trust the plan-time bound
-        if (c->tab_cap < need) {
-            if (c->d_tab) hipFree(c->d_tab);
-            c->d_tab = nullptr; c->tab_cap = 0;
-            HIPCHK(c, hipMalloc((void**)&c->d_tab, sizeof(float) * need));
-            c->tab_cap = need;
-        }
+        int rc = upload_if_changed(c, c->d_perm, c->up_perm, perm);
+        if (!rc) rc = c->d_tab.reserve(c, (size_t)((F + c->nf - 1) / c->nf) * n * (SH_HEAD + 2 * nm * c->nf));  // never trust the plan-time bound
+        if (rc) return rc;
         snprintf(nmbuf, sizeof nmbuf, "field_shared_k<4,mx%d,my%d,dx%d,dy%d,nf%d,%s,%s>", c->mx, c->my, c->dx, c->dy, c->nf,
                  c->flat ? "flat" : "general", c->clamp ? "clamp" : (c->near ? "near" : "noclamp"));
     }
@@ -958,6 +887,14 @@ static int configure_variant_impl(olx_ctx* c) {
     if (c->absorb_np_m > 0 && c->use_mfma) strncat(nmbuf, " +uniform absorption in the tables", sizeof nmbuf - strlen(nmbuf) - 1);
     c->variant = nmbuf;
     return OLX_OK;
+}
+
+// Operands and block records of a kernel 2e / 2f / 2g launch: all of them -- or, for a launch split at fp8_kcut, the plane blocks from the
+// cut on (e4m3 corrections: records [0, cp_nfar)) and with `below` the blocks under it (fp16 x 3: the rest, their operands a half further on)
+static LatticePart lattice_part(const olx_ctx* c, bool below) {
+    if (below) return {c->d_bfrag + c->bfrag_half, c->d_afrag + c->afrag_half, c->d_cpblocks + c->cp_nfar, c->cp_nblocks - c->cp_nfar, false};
+    const bool split = c->fp8corr && c->cp_nfar < c->cp_nblocks;
+    return {c->d_bfrag, c->d_afrag, c->d_cpblocks, split ? c->cp_nfar : c->cp_nblocks, c->fp8corr};
 }
 
 static int pack_if_needed(olx_ctx* c) {
@@ -975,12 +912,12 @@ static int pack_if_needed(olx_ctx* c) {
                            c->plan_foci, c->d_colinfo, c->use_lattice ? c->d_slot : nullptr,
                            (c->use_lattice && c->use_coset && c->fp8corr) ? 1 : 0, (c->use_lattice && c->use_cosetp) ? 1 : 0,
                            c->near ? (c->mx == 2 ? 0.5 : 1.0) * c->grid.spacing[0] : 0.0, (c->my == 2 ? 0.5 : 1.0) * c->grid.spacing[1], c->grid.spacing[2], c->d_coords, c->d_bfrag);
-        if (c->use_lattice && c->use_toep) olx_pack_toep(c);
+        if (c->use_lattice && c->use_toep) olx_pack_toep(c, lattice_part(c, false));
         if (c->use_lattice && c->use_coset && c->fp8corr && c->cp_nfar < c->cp_nblocks) {   // a launch split at fp8_kcut: the fp16 operands of the plane blocks below the cut
             hipLaunchKernelGGL(mfma_pack_k, g, dim3(64), 0, c->stream, c->d_pos, c->d_area, c->n_el, c->mp.n_el_pad, c->d_delays,
                                c->d_apod, c->d_perm, ox, oy, c->grid.origin[2], c->freq, c->mfma_wscale, c->freq / c->c,
                                c->plan_foci, c->d_colinfo, c->d_slot, 0, c->use_cosetp ? 1 : 0, 1.0, 1.0, 1.0, c->d_coords, c->d_bfrag + c->bfrag_half);
-            if (c->use_toep) { c->fp8corr = false; c->d_afrag += c->afrag_half; olx_pack_toep(c); c->d_afrag -= c->afrag_half; c->fp8corr = true; }
+            if (c->use_toep) olx_pack_toep(c, lattice_part(c, true));
         }
     } else if (c->mx * c->my * c->nf == 1) {
         dim3 g((c->n_el + 127) / 128, c->plan_foci);
@@ -999,12 +936,7 @@ static int pack_if_needed(olx_ctx* c) {
                 t[0] = (float)x[0]; t[1] = (float)x[1]; t[2] = (float)x[2]; t[3] = (float)(0.5 * c->h_size[2 * (size_t)e] / lambda);
                 t[4] = (float)y[0]; t[5] = (float)y[1]; t[6] = (float)y[2]; t[7] = (float)(0.5 * c->h_size[2 * (size_t)e + 1] / lambda);
             }
-            if (c->tab2_cap < t2.size()) {
-                if (c->d_tab2) hipFree(c->d_tab2);
-                c->d_tab2 = nullptr; c->tab2_cap = 0;
-                HIPCHK(c, hipMalloc((void**)&c->d_tab2, sizeof(float) * t2.size()));
-                c->tab2_cap = t2.size();
-            }
+            { int rc = c->d_tab2.reserve(c, t2.size()); if (rc) return rc; }
             HIPCHK(c, hipMemcpyAsync(c->d_tab2, t2.data(), sizeof(float) * t2.size(), hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));   // t2 lives on this stack frame
         }
@@ -1043,26 +975,12 @@ static int plan_pulse(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n
     c->agg_local = -1; c->agg_total = 0;
     c->freq = freq; c->c = cs; c->rho = rho; c->p0_pa = p0_pa; c->flags = flags; c->plan_absorb = c->absorb_np_m;
     c->directivity = false; c->nbuf = 1; c->cur = 0;
-    if (c->out_cap < total) {
-        for (float** p : {&c->d_pmag[0], &c->d_pmag[1], &c->d_inten, &c->d_cplx, &c->d_agg_p, &c->d_agg_i}) { if (*p) hipFree(*p); *p = nullptr; }
-        c->out_cap = 0;
-    }
-    if (!c->d_pmag[0]) { HIPCHK(c, hipMalloc((void**)&c->d_pmag[0], sizeof(float) * total)); c->out_cap = total; }
-    if ((flags & OLX_OUT_INTENSITY) && !c->d_inten) HIPCHK(c, hipMalloc((void**)&c->d_inten, sizeof(float) * c->out_cap));
-    if ((flags & OLX_OUT_PMAX) && c->pmax_cap < total) {
-        if (c->d_pmax) hipFree(c->d_pmax);
-        c->d_pmax = nullptr; c->pmax_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_pmax, sizeof(float) * total));
-        c->pmax_cap = total;
-    }
     const size_t fn = (size_t)n_foci * c->n_el;
-    if (c->ptab_cap < fn) {
-        for (void* p : {(void*)c->d_ptab, (void*)c->d_pw}) if (p) hipFree(p);
-        c->d_ptab = nullptr; c->d_pw = nullptr; c->ptab_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_ptab, sizeof(double4) * fn));
-        HIPCHK(c, hipMalloc((void**)&c->d_pw, sizeof(float) * fn));
-        c->ptab_cap = fn;
-    }
+    int rc = reserve_outputs(c, total, 1, (flags & OLX_OUT_INTENSITY) != 0, false, false);
+    if (!rc && (flags & OLX_OUT_PMAX)) rc = c->d_pmax.reserve(c, total);
+    if (!rc) rc = c->d_ptab.reserve(c, fn);
+    if (!rc) rc = c->d_pw.reserve(c, fn);
+    if (rc) return rc;
     // (the scans -- aggregate, scale, analysis -- read the volume shape from fp)
     FieldParams& F = c->fp;
     F.nx = g->n[0]; F.ny = g->n[1]; F.nz = g->n[2]; F.n_el = c->n_el; F.x_begin = 0; F.vox = vox;
@@ -1135,26 +1053,9 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
     const long long vox = (long long)s.x_count * g->n[1] * g->n[2];
     const size_t total = (size_t)vox * n_foci;
     c->nbuf = c->comm_active() ? olx_ctx::NBUF : 1;
-    // outputs
-    if (c->out_cap < total || (c->nbuf == 2 && !c->d_pmag[1])) {
-        { int rc_ = exported_buffers_quiesce(c, -1); if (rc_) return rc_; }   // (p2p: peers may still be pulling from the blocks freed here)
-        for (float** p : {&c->d_pmag[0], &c->d_pmag[1], &c->d_inten, &c->d_cplx, &c->d_agg_p, &c->d_agg_i}) { if (*p) hipFree(*p); *p = nullptr; }
-        c->out_cap = 0;
-    }
-    if (!c->d_pmag[0]) {
-        // |p| is always materialised (aggregate / allgather consume it)
-        for (int b = 0; b < c->nbuf; ++b) HIPCHK(c, hipMalloc((void**)&c->d_pmag[b], sizeof(float) * total));
-        c->out_cap = total;
-    }
-    if ((flags & OLX_OUT_INTENSITY) && !c->d_inten) HIPCHK(c, hipMalloc((void**)&c->d_inten, sizeof(float) * c->out_cap));
-    if ((flags & OLX_OUT_COMPLEX) && !c->d_cplx) HIPCHK(c, hipMalloc((void**)&c->d_cplx, sizeof(float) * 2 * c->out_cap));
-    const size_t tabn = (size_t)n_foci * c->n_el * TAB_STRIDE;
-    if (c->tab_cap < tabn) {
-        if (c->d_tab) hipFree(c->d_tab);
-        c->d_tab = nullptr; c->tab_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_tab, sizeof(float) * tabn));
-        c->tab_cap = tabn;
-    }
+    // outputs (|p| is always materialised: aggregate / allgather consume it)
+    { int rc = reserve_outputs(c, total, c->nbuf, (flags & OLX_OUT_INTENSITY) != 0, (flags & OLX_OUT_COMPLEX) != 0, true); if (rc) return rc; }
+    { int rc = c->d_tab.reserve(c, (size_t)n_foci * c->n_el * TAB_STRIDE); if (rc) return rc; }
     // kernel parameters.  Table origin = grid origin; slab start expressed relative to it.
     FieldParams& P = c->fp;
     P.nx = s.x_count; P.ny = g->n[1]; P.nz = g->n[2]; P.n_el = c->n_el;
@@ -1243,19 +1144,10 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
     c->my = (c->allow_shared && g->n[1] >= 2 && n <= 8192 && mirror_perm(1, c->h_py)) ? 2 : 1;
     {   // worst-case kernel-2a/2b table over every (dx, dy, nf) the steering may select later: tiles = ceil(F / nf)
         // entries of 4 + 2 dx dy nf <= 20 floats, i.e. at most 12 F + 20 floats per element (the last tile is padded)
-        const size_t need = ((size_t)n_foci * 12 + 24) * n;
-        if (c->tab_cap < need) {
-            if (c->d_tab) hipFree(c->d_tab);
-            c->d_tab = nullptr; c->tab_cap = 0;
-            HIPCHK(c, hipMalloc((void**)&c->d_tab, sizeof(float) * need));
-            c->tab_cap = need;
-        }
-        if (c->perm_cap < (size_t)4 * n) {
-            if (c->d_perm) hipFree(c->d_perm);
-            c->d_perm = nullptr; c->perm_cap = 0; c->up_perm.clear();
-            HIPCHK(c, hipMalloc((void**)&c->d_perm, sizeof(int) * 4 * n));
-            c->perm_cap = (size_t)4 * n;
-        }
+        int rc = c->d_tab.reserve(c, ((size_t)n_foci * 12 + 24) * n);
+        if (c->d_perm.capacity() < (size_t)4 * n) c->up_perm.clear();     // (a new block holds no uploaded permutation)
+        if (!rc) rc = c->d_perm.reserve(c, (size_t)4 * n);
+        if (rc) return rc;
     }
     SharedParams& S = c->sp;
     S.nx = P.nx; S.ny = P.ny; S.nz = P.nz; S.n_el = n; S.x_begin = s.x_begin; S.n_foci = n_foci;
@@ -1307,15 +1199,11 @@ int olx_field_launch(olx_ctx* c) {
     else if (c->use_mfma) {
         if (!c->use_lattice) olx_launch_mfma(c, pm);
         else if (c->use_coset) {
-            auto go = [&]() { if (c->use_toep) olx_launch_toep(c, pm); else if (c->use_cosetp) olx_launch_cosetp(c, pm); else olx_launch_coset(c, pm); };
+            auto go = [&](const LatticePart& q) { if (c->use_toep) olx_launch_toep(c, q, pm); else if (c->use_cosetp) olx_launch_cosetp(c, q, pm); else olx_launch_coset(c, q, pm); };
             if (c->fp8corr && c->cp_nfar < c->cp_nblocks) {   // split at fp8_kcut: e4m3 corrections for the plane blocks from the cut on, three fp16 products below it
-                const unsigned nall = c->cp_nblocks;
-                c->cp_nblocks = c->cp_nfar;
-                if (c->cp_nblocks) go();
-                c->fp8corr = false; c->d_cpblocks += c->cp_nfar; c->cp_nblocks = nall - c->cp_nfar; c->d_bfrag += c->bfrag_half; c->d_afrag += c->afrag_half;
-                go();
-                c->fp8corr = true; c->d_cpblocks -= c->cp_nfar; c->cp_nblocks = nall; c->d_bfrag -= c->bfrag_half; c->d_afrag -= c->afrag_half;
-            } else go();
+                if (c->cp_nfar) go(lattice_part(c, false));
+                go(lattice_part(c, true));
+            } else go(lattice_part(c, false));
         }
         else olx_launch_lattice(c, pm);
     }
@@ -1610,33 +1498,21 @@ int olx_field_set_medium(olx_ctx* c, const float* sound_speed, const float* atte
         if (one && s_ref != 0.0 && !(pin && !strcmp(pin, "2"))) { c->march_one = true; c->hp.kappa = (float)(a_ref / s_ref); }
     }
     if (c->march_one) {     // row-pair form of the last running sums (k_hmarch.hip TEX): 8 bytes per cell + one cell of padding, 32-bit byte offsets like U
-        const size_t need = (size_t)n * nx * ny + 1;
-        if (c->Utex_cap < need) {
-            if (c->d_Utex) hipFree(c->d_Utex);
-            c->d_Utex = nullptr; c->Utex_cap = 0;
-            HIPCHK(c, hipMalloc((void**)&c->d_Utex, sizeof(float2) * need));
-            c->Utex_cap = need;
-        }
+        { int rc = c->d_Utex.reserve(c, (size_t)n * nx * ny + 1); if (rc) return rc; }
     }
     c->h_plane_k = plane_k;
-    for (void** q : {(void**)&c->d_med, (void**)&c->d_plane_k, (void**)&c->d_plane_of_k, (void**)&c->d_inv2z, (void**)&c->d_kfirst, (void**)&c->d_klast,
-                     (void**)&c->d_med_layer, (void**)&c->d_layer_lo, (void**)&c->d_layer_hi, (void**)&c->d_sig})
-        if (*q) { hipFree(*q); *q = nullptr; }
+    // the medium buffers belong to this medium: freed here, allocated again below only where this medium needs them (a null d_inv2z,
+    // d_med_layer or d_sig means something to the kernels)
+    c->d_med.release(); c->d_plane_k.release(); c->d_plane_of_k.release(); c->d_inv2z.release(); c->d_kfirst.release(); c->d_klast.release();
+    c->d_med_layer.release(); c->d_layer_lo.release(); c->d_layer_hi.release(); c->d_sig.release();
     if (c->march_one && np > 0) {   // compact copy of the planes' own slowness terms for the fused writers (k_hmarch.hip, field_hmarch_fused_k)
         std::vector<float> sig((size_t)np * nx * ny);
         for (size_t q = 0; q < sig.size(); ++q) sig[q] = med[q * 8];
-        HIPCHK(c, hipMalloc((void**)&c->d_sig, sizeof(float) * sig.size()));
+        { int rc = c->d_sig.reserve(c, sig.size()); if (rc) return rc; }
         HIPCHK(c, hipMemcpy(c->d_sig, sig.data(), sizeof(float) * sig.size(), hipMemcpyHostToDevice));
     }
-    if (c->marched) {
-        const size_t need = (size_t)n * nx * ny;
-        if (c->U_cap < need) {
-            for (float2*& u : c->d_U) { if (u) hipFree(u); u = nullptr; }
-            c->U_cap = 0;
-            for (float2*& u : c->d_U) HIPCHK(c, hipMalloc((void**)&u, sizeof(float2) * need));
-            c->U_cap = need;
-        }
-    }
+    if (c->marched)
+        for (DevBuf<float2>& u : c->d_U) { int rc = u.reserve(c, (size_t)n * nx * ny); if (rc) return rc; }
     // two-level quadrature (opt-in, olx_field_medium_layering): every maximal run of consecutive non-trivial planes is cut
     // into layers of <= G planes; a layer's stencil holds the column sums of its planes (fp64 sums, rounded once)
     std::vector<int> layer_lo, layer_hi;
@@ -1670,20 +1546,24 @@ int olx_field_set_medium(olx_ctx* c, const float* sound_speed, const float* atte
                     }
                 }
         }
-        HIPCHK(c, hipMalloc((void**)&c->d_med_layer, sizeof(float) * lay.size()));
-        HIPCHK(c, hipMalloc((void**)&c->d_layer_lo, sizeof(int) * std::max(nl, 1)));
-        HIPCHK(c, hipMalloc((void**)&c->d_layer_hi, sizeof(int) * std::max(nl, 1)));
+        int rc = c->d_med_layer.reserve(c, lay.size() / 4);
+        if (!rc) rc = c->d_layer_lo.reserve(c, nl);
+        if (!rc) rc = c->d_layer_hi.reserve(c, nl);
+        if (rc) return rc;
         HIPCHK(c, hipMemcpy(c->d_med_layer, lay.data(), sizeof(float) * lay.size(), hipMemcpyHostToDevice));
         if (nl) {
             HIPCHK(c, hipMemcpy(c->d_layer_lo, layer_lo.data(), sizeof(int) * nl, hipMemcpyHostToDevice));
             HIPCHK(c, hipMemcpy(c->d_layer_hi, layer_hi.data(), sizeof(int) * nl, hipMemcpyHostToDevice));
         }
     }
-    HIPCHK(c, hipMalloc((void**)&c->d_med, sizeof(float) * med.size()));
-    HIPCHK(c, hipMalloc((void**)&c->d_plane_k, sizeof(int) * std::max(np, 1)));
-    HIPCHK(c, hipMalloc((void**)&c->d_plane_of_k, sizeof(int) * nz));
-    HIPCHK(c, hipMalloc((void**)&c->d_kfirst, sizeof(int) * n));
-    HIPCHK(c, hipMalloc((void**)&c->d_klast, sizeof(int) * n));
+    {
+        int rc = c->d_med.reserve(c, med.size() / 4);
+        if (!rc) rc = c->d_plane_k.reserve(c, np);
+        if (!rc) rc = c->d_plane_of_k.reserve(c, nz);
+        if (!rc) rc = c->d_kfirst.reserve(c, n);
+        if (!rc) rc = c->d_klast.reserve(c, n);
+        if (rc) return rc;
+    }
     HIPCHK(c, hipMemcpy(c->d_med, med.data(), sizeof(float) * med.size(), hipMemcpyHostToDevice));
     if (np) HIPCHK(c, hipMemcpy(c->d_plane_k, plane_k.data(), sizeof(int) * np, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_plane_of_k, plane_of_k.data(), sizeof(int) * nz, hipMemcpyHostToDevice));
@@ -1696,7 +1576,7 @@ int olx_field_set_medium(olx_ctx* c, const float* sound_speed, const float* atte
             const double rho = density ? (double)density[off + o] : c->rho, cs = sound_speed ? (double)sound_speed[off + o] : c0;
             iz[o] = (float)(1e-4 / (2.0 * rho * cs));
         }
-        HIPCHK(c, hipMalloc((void**)&c->d_inv2z, sizeof(float) * sv));
+        { int rc = c->d_inv2z.reserve(c, sv); if (rc) return rc; }
         HIPCHK(c, hipMemcpy(c->d_inv2z, iz.data(), sizeof(float) * sv, hipMemcpyHostToDevice));
     }
     HeteroParams& H = c->hp;
@@ -1755,12 +1635,7 @@ int olx_field_upload(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_
     const long long vox = (long long)s.x_count * g->n[1] * g->n[2];
     const size_t total = (size_t)vox * n_foci;
     { int rc_ = exported_buffers_quiesce(c, -1); if (rc_) return rc_; }   // (p2p: buffer 0 is rewritten, all of them may be freed)
-    if (c->out_cap < total) {
-        for (float** p : {&c->d_pmag[0], &c->d_pmag[1], &c->d_inten, &c->d_cplx, &c->d_agg_p, &c->d_agg_i}) { if (*p) hipFree(*p); *p = nullptr; }
-        c->out_cap = 0;
-    }
-    if (!c->d_pmag[0]) { HIPCHK(c, hipMalloc((void**)&c->d_pmag[0], sizeof(float) * total)); c->out_cap = total; }
-    if (intensity && !c->d_inten) HIPCHK(c, hipMalloc((void**)&c->d_inten, sizeof(float) * c->out_cap));
+    { int rc_ = reserve_outputs(c, total, 1, intensity != nullptr, false, false); if (rc_) return rc_; }
     HIPCHK(c, hipMemcpy(c->d_pmag[0], pmag, sizeof(float) * total, hipMemcpyHostToDevice));
     if (intensity) HIPCHK(c, hipMemcpy(c->d_inten, intensity, sizeof(float) * total, hipMemcpyHostToDevice));
     c->grid = *g; c->slab = s; c->plan_foci = n_foci;
@@ -1808,12 +1683,7 @@ static int pmax_post(olx_ctx* c, const float* scale, bool aggregate) {
     if (!c->pmax_live) return OLX_OK;
     if (scale) hipLaunchKernelGGL(field_scale_k, dim3(1024, c->plan_foci), dim3(256), 0, c->stream, c->d_pmax, (float*)nullptr, (float*)nullptr, scale, c->fp.vox);
     if (aggregate) {
-        if (c->agg_pmax_cap < (size_t)c->fp.vox) {
-            if (c->d_agg_pmax) hipFree(c->d_agg_pmax);
-            c->d_agg_pmax = nullptr; c->agg_pmax_cap = 0;
-            HIPCHK(c, hipMalloc((void**)&c->d_agg_pmax, sizeof(float) * c->fp.vox));
-            c->agg_pmax_cap = (size_t)c->fp.vox;
-        }
+        { int rc = c->d_agg_pmax.reserve(c, (size_t)c->fp.vox); if (rc) return rc; }
         hipLaunchKernelGGL(field_aggregate_k, dim3(2048), dim3(256), 0, c->stream, c->d_pmax, (const float*)nullptr, c->plan_foci, (long long)c->fp.vox,
                            1.0f / (float)c->plan_foci, c->d_agg_pmax, (float*)nullptr);
     }
@@ -1878,19 +1748,13 @@ int olx_scan_time(olx_ctx* c, int kernel, int iters, float* ms_each, double* byt
         HIPCHK(c, hipMemcpy(d_w, hw.data(), sizeof(float) * F, hipMemcpyHostToDevice));
         HIPCHK(c, hipMemset(d_pk, 0, sizeof(unsigned) * 6 * F));
     }
-    if ((kernel == OLX_SCAN_WEIGHTED_SUM || kernel == OLX_SCAN_FUSED_POST) && (!c->d_wint || c->wint_cap < (size_t)c->fp.vox)) {
-        if (c->d_wint) hipFree(c->d_wint);
-        c->d_wint = nullptr; c->wint_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_wint, sizeof(float) * c->fp.vox));
-        c->wint_cap = (size_t)c->fp.vox;
-    }
+    if (kernel == OLX_SCAN_WEIGHTED_SUM || kernel == OLX_SCAN_FUSED_POST) { int rc_ = c->d_wint.reserve(c, (size_t)c->fp.vox); if (rc_) return rc_; }
     if (kernel == OLX_SCAN_FUSED_POST) {
         { int rc_ = aggregate_buffers_free(c); if (rc_) return rc_; }
-        if (!c->d_agg_p) HIPCHK(c, hipMalloc((void**)&c->d_agg_p, sizeof(float) * c->out_cap));
-        if (!c->d_agg_i) HIPCHK(c, hipMalloc((void**)&c->d_agg_i, sizeof(float) * c->out_cap));
+        { int rc_ = reserve_aggregate(c, true, true); if (rc_) return rc_; }
     }
     if (kernel == OLX_SCAN_SCALE || kernel == OLX_SCAN_FUSED_POST) {
-        if (!c->d_scale) HIPCHK(c, hipMalloc((void**)&c->d_scale, sizeof(float) * 4096));
+        { int rc_ = c->d_scale.reserve(c, 4096); if (rc_) return rc_; }
         if (F > 4096) return fail(c, OLX_EINVAL, "olx_scan_time: too many foci");
         std::vector<float> one(F, 1.0f);        // x 1.0f is exact: the resident result is unchanged
         HIPCHK(c, hipMemcpy(c->d_scale, one.data(), sizeof(float) * F, hipMemcpyHostToDevice));
@@ -1944,8 +1808,7 @@ static int aggregate_local(olx_ctx* c, bool with_p, bool with_i) {
     const size_t vox = (size_t)c->fp.vox;
     { int rc_ = aggregate_buffers_free(c); if (rc_) return rc_; }
     if (with_p) { int rc_ = pmax_post(c, nullptr, true); if (rc_) return rc_; }
-    if (with_p && !c->d_agg_p) HIPCHK(c, hipMalloc((void**)&c->d_agg_p, sizeof(float) * c->out_cap));
-    if (with_i && !c->d_agg_i) HIPCHK(c, hipMalloc((void**)&c->d_agg_i, sizeof(float) * c->out_cap));
+    { int rc_ = reserve_aggregate(c, with_p, with_i); if (rc_) return rc_; }
     hipLaunchKernelGGL(field_aggregate_k, dim3(2048), dim3(256), 0, c->stream, with_p ? c->d_pmag[c->cur] : nullptr,
                        with_i ? c->d_inten : nullptr, c->plan_foci, (long long)vox, 1.0f / (float)c->plan_foci,
                        with_p ? c->d_agg_p : nullptr, with_i ? c->d_agg_i : nullptr);
@@ -1982,7 +1845,7 @@ int olx_field_scale(olx_ctx* c, const double* scale, int n_foci) {
     if (!c->planned) return fail(c, OLX_ESTATE, "olx_field_scale: nothing planned");
     if (!scale || n_foci != c->plan_foci) return fail(c, OLX_EINVAL, "olx_field_scale: need %d scale factors", c->plan_foci);
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_scale) HIPCHK(c, hipMalloc((void**)&c->d_scale, sizeof(float) * 4096));
+    { int rc_ = c->d_scale.reserve(c, 4096); if (rc_) return rc_; }
     if (n_foci > 4096) return fail(c, OLX_EINVAL, "olx_field_scale: too many foci");
     { int rc_ = exported_buffers_quiesce(c, c->cur); if (rc_) return rc_; }   // (p2p: no peer may pull a half-scaled block)
     std::vector<float> s(n_foci);
@@ -2012,11 +1875,10 @@ int olx_field_scale_aggregate(olx_ctx* c, const double* scale, int n_foci) {
         return rc ? rc : olx_field_aggregate_device(c, 1);
     }
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_scale) HIPCHK(c, hipMalloc((void**)&c->d_scale, sizeof(float) * 4096));
+    { int rc_ = c->d_scale.reserve(c, 4096); if (rc_) return rc_; }
     { int rc_ = exported_buffers_quiesce(c, c->cur); if (rc_) return rc_; }   // (p2p: the volumes are scaled in place)
     { int rc_ = aggregate_buffers_free(c); if (rc_) return rc_; }
-    if (!c->d_agg_p) HIPCHK(c, hipMalloc((void**)&c->d_agg_p, sizeof(float) * c->out_cap));
-    if (!c->d_agg_i) HIPCHK(c, hipMalloc((void**)&c->d_agg_i, sizeof(float) * c->out_cap));
+    { int rc_ = reserve_aggregate(c, true, true); if (rc_) return rc_; }
     std::vector<float> s(n_foci);
     for (int i = 0; i < n_foci; ++i) s[i] = (float)scale[i];
     HIPCHK(c, hipMemcpyAsync(c->d_scale, s.data(), sizeof(float) * n_foci, hipMemcpyHostToDevice, c->stream));
@@ -2064,17 +1926,12 @@ static void focus_boxes(const olx_ctx* c, const double* A, const double* aspect,
 }
 
 static int analysis_scratch(olx_ctx* c, size_t dev_bytes, size_t host_bytes) {
-    if (c->an_dev_cap < dev_bytes) {
-        if (c->d_an) hipFree(c->d_an);
-        c->d_an = nullptr; c->an_dev_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_an, dev_bytes));
-        c->an_dev_cap = dev_bytes;
-    }
-    if (c->an_host_cap < host_bytes) {
+    { int rc = c->d_an.reserve(c, dev_bytes); if (rc) return rc; }
+    if (c->h_an_bytes < host_bytes) {
         if (c->h_an) hipHostFree(c->h_an);
-        c->h_an = nullptr; c->an_host_cap = 0;
+        c->h_an = nullptr; c->h_an_bytes = 0;
         HIPCHK(c, hipHostMalloc(&c->h_an, host_bytes, hipHostMallocDefault));
-        c->an_host_cap = host_bytes;
+        c->h_an_bytes = host_bytes;
     }
     return OLX_OK;
 }
@@ -2089,13 +1946,10 @@ int olx_field_masked_peak(olx_ctx* c, int which, const double* A, const double* 
     if (which == 2 && !c->d_wint) return fail(c, OLX_ESTATE, "olx_field_masked_peak: call olx_field_weighted_intensity first");
     HIPCHK(c, hipSetDevice(c->device));
     const int F = c->plan_foci;
-    if (!c->d_peakA || c->peak_cap < (size_t)F) {
-        if (c->d_peakA) hipFree(c->d_peakA);
-        if (c->d_peak) hipFree(c->d_peak);
-        c->d_peakA = nullptr; c->d_peak = nullptr; c->peak_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_peakA, sizeof(double) * 12 * F));
-        HIPCHK(c, hipMalloc((void**)&c->d_peak, sizeof(unsigned) * F));
-        c->peak_cap = F;
+    {
+        int rc = c->d_peakA.reserve(c, 12 * (size_t)F);
+        if (!rc) rc = c->d_peak.reserve(c, F);
+        if (rc) return rc;
     }
     if (A) HIPCHK(c, hipMemcpyAsync(c->d_peakA, A, sizeof(double) * 12 * F, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_peak, 0, sizeof(unsigned) * F, c->stream));
@@ -2114,7 +1968,7 @@ int olx_field_masked_peak(olx_ctx* c, int which, const double* A, const double* 
         focus_boxes(c, A, aspect, radius_m, F, boxes.data());
         { int rc = analysis_scratch(c, sizeof(int) * 6 * F, 0); if (rc) return rc; }
         HIPCHK(c, hipMemcpyAsync(c->d_an, boxes.data(), sizeof(int) * 6 * F, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(field_masked_peak_box_k, dim3(32, F), dim3(256), 0, c->stream, vol, c->d_peakA, P, static_cast<const int*>(c->d_an), c->d_peak);
+        hipLaunchKernelGGL(field_masked_peak_box_k, dim3(32, F), dim3(256), 0, c->stream, vol, c->d_peakA, P, reinterpret_cast<const int*>(static_cast<unsigned char*>(c->d_an)), c->d_peak);
         HIPCHK(c, hipStreamSynchronize(c->stream));   // (boxes lives on this frame)
     } else
     hipLaunchKernelGGL(field_masked_peak_k, grid, dim3(256), 0, c->stream, vol, c->d_peakA, P, c->d_peak);
@@ -2215,10 +2069,11 @@ int olx_offset_grid(olx_ctx* c, const double* xs, int nx, const double* ys, int 
     if (dist_out && aspect) for (int a = 0; a < 3; ++a) if (!(aspect[a] != 0.0)) return fail(c, OLX_EINVAL, "olx_offset_grid: zero aspect ratio");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t vox = (size_t)nx * ny * nz;
-    double *d_ax = nullptr, *d_c = nullptr, *d_d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d_ax, sizeof(double) * ((size_t)nx + ny + nz + 12)));
-    if (coords_out && hipMalloc((void**)&d_c, sizeof(double) * 3 * vox) != hipSuccess) { hipFree(d_ax); return fail(c, OLX_ENOMEM, "olx_offset_grid: out of device memory"); }
-    if (dist_out && hipMalloc((void**)&d_d, sizeof(double) * vox) != hipSuccess) { hipFree(d_ax); if (d_c) hipFree(d_c); return fail(c, OLX_ENOMEM, "olx_offset_grid: out of device memory"); }
+    DevScratch ax, co, di;
+    HIPCHK(c, hipMalloc(&ax.p, sizeof(double) * ((size_t)nx + ny + nz + 12)));
+    if (coords_out && hipMalloc(&co.p, sizeof(double) * 3 * vox) != hipSuccess) return fail(c, OLX_ENOMEM, "olx_offset_grid: out of device memory");
+    if (dist_out && hipMalloc(&di.p, sizeof(double) * vox) != hipSuccess) return fail(c, OLX_ENOMEM, "olx_offset_grid: out of device memory");
+    double *d_ax = ax.at<double>(0), *d_c = co.at<double>(0), *d_d = di.at<double>(0);
     hipMemcpyAsync(d_ax, xs, sizeof(double) * nx, hipMemcpyHostToDevice, c->stream);
     hipMemcpyAsync(d_ax + nx, ys, sizeof(double) * ny, hipMemcpyHostToDevice, c->stream);
     hipMemcpyAsync(d_ax + nx + ny, zs, sizeof(double) * nz, hipMemcpyHostToDevice, c->stream);
@@ -2231,7 +2086,6 @@ int olx_offset_grid(olx_ctx* c, const double* xs, int nx, const double* ys, int 
     if (!rc && coords_out && hipMemcpyAsync(coords_out, d_c, sizeof(double) * 3 * vox, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = OLX_EHIP;
     if (!rc && dist_out && hipMemcpyAsync(dist_out, d_d, sizeof(double) * vox, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = OLX_EHIP;
     if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = OLX_EHIP;
-    hipFree(d_ax); if (d_c) hipFree(d_c); if (d_d) hipFree(d_d);
     if (rc) return fail(c, OLX_EHIP, "olx_offset_grid: HIP error");
     return OLX_OK;
 }
@@ -2243,8 +2097,9 @@ int olx_tof_spread(olx_ctx* c, const double* xs, int nx, const double* ys, int n
     if (!xs || !ys || !zs || !max_dtof_s || nx < 1 || ny < 1 || nz < 1 || !(c0 > 0)) return fail(c, OLX_EINVAL, "olx_tof_spread: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     const int n = c->n_el;
-    double* d_buf = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d_buf, sizeof(double) * ((size_t)nx + ny + nz + n + 1)));
+    DevScratch scratch;
+    HIPCHK(c, hipMalloc(&scratch.p, sizeof(double) * ((size_t)nx + ny + nz + n + 1)));
+    double* d_buf = scratch.at<double>(0);
     double* d_del = d_buf + nx + ny + nz;
     unsigned long long* d_out = reinterpret_cast<unsigned long long*>(d_del + n);
     hipMemcpyAsync(d_buf, xs, sizeof(double) * nx, hipMemcpyHostToDevice, c->stream);
@@ -2260,7 +2115,6 @@ int olx_tof_spread(olx_ctx* c, const double* xs, int nx, const double* ys, int n
     unsigned long long bits = 0;
     if (!rc && hipMemcpyAsync(&bits, d_out, sizeof bits, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = OLX_EHIP;
     if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = OLX_EHIP;
-    hipFree(d_buf);
     if (rc) return fail(c, OLX_EHIP, "olx_tof_spread: HIP error");
     memcpy(max_dtof_s, &bits, sizeof bits);
     return OLX_OK;
@@ -2272,12 +2126,10 @@ int olx_field_weighted_intensity(olx_ctx* c, const double* weights, int n_foci) 
     if (!(c->flags & OLX_OUT_INTENSITY)) return fail(c, OLX_ESTATE, "olx_field_weighted_intensity: intensity not planned");
     if (!weights || n_foci != c->plan_foci || n_foci > 4096) return fail(c, OLX_EINVAL, "olx_field_weighted_intensity: need %d weights", c->plan_foci);
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_scale) HIPCHK(c, hipMalloc((void**)&c->d_scale, sizeof(float) * 4096));
-    if (!c->d_wint || c->wint_cap < (size_t)c->fp.vox) {
-        if (c->d_wint) hipFree(c->d_wint);
-        c->d_wint = nullptr; c->wint_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_wint, sizeof(float) * c->fp.vox));
-        c->wint_cap = (size_t)c->fp.vox;
+    {
+        int rc = c->d_scale.reserve(c, 4096);
+        if (!rc) rc = c->d_wint.reserve(c, (size_t)c->fp.vox);
+        if (rc) return rc;
     }
     std::vector<float> w(n_foci);
     for (int i = 0; i < n_foci; ++i) w[i] = (float)weights[i];
@@ -2290,7 +2142,7 @@ int olx_field_weighted_intensity(olx_ctx* c, const double* weights, int n_foci) 
 
 int olx_field_weighted_fetch(olx_ctx* c, float* out) {
     if (!c || !out) return OLX_EINVAL;
-    if (!c->planned || !c->d_wint || c->wint_cap < (size_t)c->fp.vox) return fail(c, OLX_ESTATE, "olx_field_weighted_fetch: no time-average volume on the device");
+    if (!c->planned || c->d_wint.capacity() < (size_t)c->fp.vox) return fail(c, OLX_ESTATE, "olx_field_weighted_fetch: no time-average volume on the device");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return fetch_to_host(c, out, c->d_wint, sizeof(float) * (size_t)c->fp.vox);
@@ -2335,14 +2187,9 @@ int olx_solution_analyze_begin(olx_ctx* c, const double* A, const double* ita_we
     const size_t out_mom = up8(out_bd + sizeof(int) * 12 * F), out_end = out_mom + sizeof(double) * 4 * F;
     const size_t wk_cut = out_end, wk_smp = up8(wk_cut + sizeof(float) * F), dev_bytes = wk_smp + sizeof(float) * (size_t)npts * F + 8;
     { int rc = analysis_scratch(c, dev_bytes, out_end); if (rc) return rc; }
-    if (!c->d_wint || c->wint_cap < (size_t)c->fp.vox) {
-        if (c->d_wint) hipFree(c->d_wint);
-        c->d_wint = nullptr; c->wint_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_wint, sizeof(float) * c->fp.vox));
-        c->wint_cap = (size_t)c->fp.vox;
-    }
+    { int rc = c->d_wint.reserve(c, (size_t)c->fp.vox); if (rc) return rc; }
     unsigned char* h = static_cast<unsigned char*>(c->h_an);
-    unsigned char* d = static_cast<unsigned char*>(c->d_an);
+    unsigned char* d = c->d_an;
     memcpy(h + in_A, A, sizeof(double) * 12 * F);
     if (npts) memcpy(h + in_pts, line_pts, sizeof(double) * 3 * (size_t)npts * F);
     for (int f = 0; f < F; ++f) reinterpret_cast<float*>(h + in_w)[f] = (float)ita_weights[f];
@@ -2358,8 +2205,7 @@ int olx_solution_analyze_begin(olx_ctx* c, const double* A, const double* ita_we
     if (fused) {
         { int rc_ = exported_buffers_quiesce(c, c->cur); if (rc_) return rc_; }   // (p2p: the fused pass scales the volumes in place)
         { int rc_ = aggregate_buffers_free(c); if (rc_) return rc_; }
-        if (!c->d_agg_p) HIPCHK(c, hipMalloc((void**)&c->d_agg_p, sizeof(float) * c->out_cap));
-        if (!c->d_agg_i) HIPCHK(c, hipMalloc((void**)&c->d_agg_i, sizeof(float) * c->out_cap));
+        { int rc_ = reserve_aggregate(c, true, true); if (rc_) return rc_; }
         for (int f = 0; f < F; ++f) reinterpret_cast<float*>(h + in_sc)[f] = (float)scale_per_focus[f];
     }
     HIPCHK(c, hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, c->stream));
@@ -2571,12 +2417,10 @@ int olx_field_allgather(olx_ctx* c) {
     if (c->p2p) return olx_p2p_allgather(c);
     const size_t count = (size_t)c->fp.vox * c->plan_foci;
     const size_t need = count * c->nranks;
-    if (c->gather_cap < need) {
-        HIPCHK(c, hipStreamSynchronize(c->comm_stream));
-        if (c->d_gather) hipFree(c->d_gather);
-        c->d_gather = nullptr; c->gather_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_gather, sizeof(float) * need));
-        c->gather_cap = need;
+    if (c->d_gather.capacity() < need) {
+        HIPCHK(c, hipStreamSynchronize(c->comm_stream));     // (an earlier gather may still write the block)
+        int rc = c->d_gather.reserve(c, need);
+        if (rc) return rc;
     }
     const int b = c->cur;
     HIPCHK(c, hipEventRecord(c->ev_field[b], c->stream));
@@ -2597,8 +2441,7 @@ static int aggregate_exchange(olx_ctx* c, bool want_scatter) {
     HIPCHK(c, hipSetDevice(c->device));
     const size_t vox = (size_t)c->fp.vox;
     const bool with_i = (c->flags & OLX_OUT_INTENSITY) != 0;
-    if (!c->d_agg_p) HIPCHK(c, hipMalloc((void**)&c->d_agg_p, sizeof(float) * c->out_cap));
-    if (with_i && !c->d_agg_i) HIPCHK(c, hipMalloc((void**)&c->d_agg_i, sizeof(float) * c->out_cap));
+    { int rc = reserve_aggregate(c, true, with_i); if (rc) return rc; }
     if (!c->ev_agg) { HIPCHK(c, hipEventCreateWithFlags(&c->ev_agg, hipEventDisableTiming)); HIPCHK(c, hipEventCreateWithFlags(&c->ev_red, hipEventDisableTiming)); }
     { int rc = aggregate_buffers_free(c); if (rc) return rc; }   // the previous exchange still owns the aggregate buffers
     // genuine foci of this rank come first in its shard (padding repeats the last one, dist.plan_foci_orbits): only they enter
@@ -2682,16 +2525,6 @@ int olx_allgather_fetch(olx_ctx* c, int rank, float* out) {
 }  // extern "C"
 
 // ---- thermal model (kernel 3, k_thermal.hip) ---------------------------------------------------------------------------------------
-// grow a device buffer to hold n elements (contents not kept)
-template <class T> static int th_grow(olx_ctx* c, T** p, size_t* cap, size_t n) {
-    if (*cap >= n && *p) return OLX_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr; *cap = 0;
-    HIPCHK(c, hipMalloc((void**)p, sizeof(T) * std::max(n, (size_t)1)));
-    *cap = n;
-    return OLX_OK;
-}
-
 extern "C" {
 
 int olx_thermal_plan(olx_ctx* c, const olx_grid* g, const float* density, const float* specific_heat, const float* conductivity,
@@ -2717,13 +2550,8 @@ int olx_thermal_plan(olx_ctx* c, const olx_grid* g, const float* density, const 
     P.perf = (float)perfusion;
     c->th_uniform = !density && !specific_heat && !conductivity && !absorption;
     const size_t vox = (size_t)P.vox;
-    for (float** p : {&c->d_th_T[0], &c->d_th_T[1], &c->d_th_max, &c->d_th_cem})
-        if (c->th_cap < vox && *p) { hipFree(*p); *p = nullptr; }
-    if (c->th_cap < vox) c->th_cap = 0;
-    for (float** p : {&c->d_th_T[0], &c->d_th_T[1], &c->d_th_max, &c->d_th_cem})
-        if (!*p) HIPCHK(c, hipMalloc((void**)p, sizeof(float) * vox));
-    c->th_cap = vox;
-    if (!c->d_th_rate) HIPCHK(c, hipMalloc((void**)&c->d_th_rate, sizeof(unsigned)));
+    for (DevBuf<float>* b : {&c->d_th_T[0], &c->d_th_T[1], &c->d_th_max, &c->d_th_cem}) { int rc = b->reserve(c, vox); if (rc) return rc; }
+    { int rc = c->d_th_rate.reserve(c, 1); if (rc) return rc; }
     if (c->th_uniform) {
         const double rc = density0 * specific_heat0;
         P.gx = (float)(conductivity0 * P.ihx2); P.gy = (float)(conductivity0 * P.ihy2); P.gz = (float)(conductivity0 * P.ihz2);
@@ -2745,14 +2573,10 @@ int olx_thermal_plan(olx_ctx* c, const olx_grid* g, const float* density, const 
             HIPCHK(c, hipMemcpy(d, src[q], sizeof(float) * vox, hipMemcpyHostToDevice));
             dv[q] = d;
         }
-        if (c->th_coef_cap < vox) {
-            for (void* p : {(void*)c->d_th_coef, (void*)c->d_th_irc, (void*)c->d_th_sfac}) if (p) hipFree(p);
-            c->d_th_coef = nullptr; c->d_th_irc = c->d_th_sfac = nullptr; c->th_coef_cap = 0;
-            HIPCHK(c, hipMalloc((void**)&c->d_th_coef, sizeof(float4) * vox));
-            HIPCHK(c, hipMalloc((void**)&c->d_th_irc, sizeof(float) * vox));
-            HIPCHK(c, hipMalloc((void**)&c->d_th_sfac, sizeof(float) * vox));
-            c->th_coef_cap = vox;
-        }
+        int rc = c->d_th_coef.reserve(c, vox);
+        if (!rc) rc = c->d_th_irc.reserve(c, vox);
+        if (!rc) rc = c->d_th_sfac.reserve(c, vox);
+        if (rc) return rc;
         HIPCHK(c, hipMemsetAsync(c->d_th_rate, 0, sizeof(unsigned), c->stream));
         olx_thermal_pack(c, dv[0], dv[1], dv[2], dv[3]);
         HIPCHK(c, hipGetLastError());
@@ -2792,21 +2616,16 @@ int olx_thermal_schedule(olx_ctx* c, int n_steps, const int* row_ptr, const int*
         if (points[p] < 0 || points[p] >= c->th.vox) return fail(c, OLX_EINVAL, "olx_thermal_schedule: trace point %d outside the grid", p);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->th_sched_cap < (size_t)ne || !c->d_th_sf) {
-        if (c->d_th_sf) hipFree(c->d_th_sf);
-        if (c->d_th_tau) hipFree(c->d_th_tau);
-        c->d_th_sf = nullptr; c->d_th_tau = nullptr; c->th_sched_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_th_sf, sizeof(int) * std::max(ne, 1)));
-        HIPCHK(c, hipMalloc((void**)&c->d_th_tau, sizeof(float) * std::max(ne, 1)));
-        c->th_sched_cap = (size_t)std::max(ne, 1);
-    }
+    int rc = c->d_th_sf.reserve(c, ne);
+    if (!rc) rc = c->d_th_tau.reserve(c, ne);
+    if (!rc) rc = c->d_th_pts.reserve(c, n_points);
+    if (!rc) rc = c->d_th_trace.reserve(c, (size_t)n_steps * n_points);
+    if (rc) return rc;
     if (ne > 0) {
         HIPCHK(c, hipMemcpy(c->d_th_sf, focus, sizeof(int) * ne, hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->d_th_tau, tau.data(), sizeof(float) * ne, hipMemcpyHostToDevice));
     }
-    { int rc_ = th_grow(c, &c->d_th_pts, &c->th_pts_cap, (size_t)n_points); if (rc_) return rc_; }
     if (n_points > 0) HIPCHK(c, hipMemcpy(c->d_th_pts, points, sizeof(long long) * n_points, hipMemcpyHostToDevice));
-    { int rc_ = th_grow(c, &c->d_th_trace, &c->th_trace_cap, (size_t)n_steps * n_points); if (rc_) return rc_; }
     c->th_row.assign(row_ptr, row_ptr + n_steps + 1);
     c->th_steps = n_steps; c->th_npts = n_points; c->th_next = -1; c->th_max_focus = fmax;
     return OLX_OK;
@@ -2820,7 +2639,7 @@ int olx_thermal_source(olx_ctx* c, int n_foci, const float* intensity) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (intensity) {
         const size_t total = (size_t)c->th.vox * n_foci;
-        { int rc_ = th_grow(c, &c->d_th_I, &c->th_I_cap, total); if (rc_) return rc_; }
+        { int rc_ = c->d_th_I.reserve(c, total); if (rc_) return rc_; }
         HIPCHK(c, hipMemcpy(c->d_th_I, intensity, sizeof(float) * total, hipMemcpyHostToDevice));
         c->th_src_resident = false;
     } else {
@@ -2848,7 +2667,7 @@ int olx_thermal_run(olx_ctx* c, double dt, double baseline, int first_step, int 
     HIPCHK(c, hipSetDevice(c->device));
     const size_t vox = (size_t)c->th.vox;
     if (first_step == 0) {
-        for (float* p : {c->d_th_T[0], c->d_th_max, c->d_th_cem}) HIPCHK(c, hipMemsetAsync(p, 0, sizeof(float) * vox, c->stream));
+        for (float* p : {(float*)c->d_th_T[0], (float*)c->d_th_max, (float*)c->d_th_cem}) HIPCHK(c, hipMemsetAsync(p, 0, sizeof(float) * vox, c->stream));
         c->th_cur = 0;
     }
     ThermalStep S{};

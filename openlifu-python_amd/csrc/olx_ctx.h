@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
@@ -32,6 +33,24 @@ struct RcclApi {
 static constexpr int kNcclFloat32 = 7;  // ncclFloat32 in rccl.h's ncclDataType_t
 static constexpr int kNcclSum = 0, kNcclMax = 2;  // ncclRedOp_t
 
+struct olx_ctx;
+
+// A device buffer of n elements of T: owned (freed with its owner), never copied -- passing one by value, through a templated launch
+// wrapper say, fails to compile instead of freeing the block twice.  Reads as a T* (kernel arguments, offsets, null tests).
+template <class T> class DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;     // elements
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    int reserve(olx_ctx* c, size_t n);     // room for n elements (at least one); grows only, and a block that grows does not keep its contents
+    void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
+    size_t capacity() const { return cap; }
+    operator T*() const { return p; }
+};
+
 struct FetchLane;   // olx.hip: pinned staging of the device -> host fetches
 struct P2PState;    // olx_p2p.hip: direct peer-to-peer reassembly (OLX_GATHER=p2p)
 
@@ -45,20 +64,17 @@ struct olx_ctx {
     std::string err;
     // element table (device fp64 SoA + host copy for variant decisions)
     int n_el = 0;
-    double *d_pos = nullptr, *d_nrm = nullptr, *d_area = nullptr;
+    DevBuf<double> d_pos, d_nrm, d_area;
     std::vector<double> h_pos;  // [3][N]
     std::vector<double> h_area, h_delays, h_apod;  // host mirrors for variant decisions
     std::vector<double> h_foci; unsigned long long foci_version = ~0ull;  // foci of the last olx_bf_solve in the element frame (M == identity)
     // optional piston directivity: local x axes [N][3] and sizes [N][2] on the host, packed frame table on the device
-    std::vector<double> h_xaxis, h_size, h_nrm; float* d_tab2 = nullptr; size_t tab2_cap = 0; bool directivity = false; double absorb_np_m = 0; bool modifier() const { return directivity || absorb_np_m > 0; }   // per-term factors beyond w / d: piston directivity, uniform absorption
+    std::vector<double> h_xaxis, h_size, h_nrm; DevBuf<float> d_tab2; bool directivity = false; double absorb_np_m = 0; bool modifier() const { return directivity || absorb_np_m > 0; }   // per-term factors beyond w / d: piston directivity, uniform absorption
     bool dir_lattice = false;   // dir_lattice: flat, axis-aligned, equal-size elements -> D_e folds into the lattice kernels' tables
     bool allow_shared = true;
     // steering
     int n_foci = 0;
-    double *d_delays = nullptr, *d_apod = nullptr;
-    size_t steer_cap = 0;
-    double *d_foci = nullptr, *d_M = nullptr;
-    size_t foci_cap = 0;
+    DevBuf<double> d_delays, d_apod, d_foci, d_M;
     unsigned long long steer_version = 0, packed_version = ~0ull, configured_version = ~0ull;   // steering table / what the operands were packed from / what configure_variant decided for
     // field plan
     bool planned = false;
@@ -73,47 +89,48 @@ struct olx_ctx {
     FieldParams fp{};
     bool flat = false, clamp = false;
     // shared-geometry variant (kernel 2b): mirror folds and foci per tile; 1,1,1 = kernel 2a
-    bool use_mfma = false; int nt = 1; MfmaParams mp{}; float4* d_coords = nullptr; uint4* d_bfrag = nullptr; int* d_colinfo = nullptr; int* d_targets = nullptr; size_t colinfo_cap = 0;
-    size_t coords_cap = 0, bfrag_cap = 0; double min_dist = 0, mfma_wscale = 0; int force_kind = 0;  // 0 auto, 1 general, 2 shared, 3 mfma
-    int mx = 1, my = 1, dx = 1, dy = 1, nf = 1; std::vector<int> h_px, h_py; int* d_perm = nullptr; size_t perm_cap = 0; SharedParams sp{};
-    float* d_tab = nullptr; size_t tab_cap = 0;
+    bool use_mfma = false; int nt = 1; MfmaParams mp{}; DevBuf<float4> d_coords; DevBuf<uint4> d_bfrag; DevBuf<int> d_colinfo;
+    int* d_targets = nullptr;                  // (not owned) the store targets: the tail of d_colinfo
+    double min_dist = 0, mfma_wscale = 0; int force_kind = 0;  // 0 auto, 1 general, 2 shared, 3 mfma
+    int mx = 1, my = 1, dx = 1, dy = 1, nf = 1; std::vector<int> h_px, h_py; DevBuf<int> d_perm; SharedParams sp{};
+    DevBuf<float> d_tab;
     // lattice variant (kernel 2d): matrix array whose pitch is a whole number of voxels
     typedef olxplan::Lattice Lattice;          // olx_plan.h: regular (a, b) lattice in one z plane, pitch = whole voxels
     Lattice lat;
-    bool use_lattice = false; int lat_mt = 8; LatParams lp{}; int* d_slot = nullptr; size_t slot_cap = 0;
+    bool use_lattice = false; int lat_mt = 8; LatParams lp{}; DevBuf<int> d_slot;
     std::vector<double> nf_s2;   // [plane block q]: max_v sum_e 1 / d'(v, e)^2 over the planes >= 16 q of the planned slab [1/m^2] (olxplan::nearfield_s2; < 0 = not derived yet): the e4m3 error bound's near-field term
     int fp8_kcut = 0;            // e4m3 correction products for the plane blocks from this plane on, fp16 x 3 below (0: everywhere); meaningful while fp8corr
     unsigned cp_nfar = 0;        // block records [0, cp_nfar): planes >= fp8_kcut; [cp_nfar, cp_nblocks): the planes below (their operands sit bfrag_half / afrag_half further on)
     size_t bfrag_half = 0, afrag_half = 0;
-    bool use_coset = false; bool fp8corr = false; CosetParams cp{}; int* d_jobs = nullptr; size_t jobs_cap = 0;   // kernel 2e (whole cosets per wave) instead of 2d's row tiles
+    bool use_coset = false; bool fp8corr = false; CosetParams cp{}; DevBuf<int> d_jobs;   // kernel 2e (whole cosets per wave) instead of 2d's row tiles
     // kernel 2f (one steering column: Toeplitz weights stationary, 16 planes per MFMA tile)
-    CosetBlock* d_cpblocks = nullptr; size_t cpblocks_cap = 0; unsigned cp_nblocks = 0;   // kernel 2g block records
+    DevBuf<CosetBlock> d_cpblocks; unsigned cp_nblocks = 0;   // kernel 2g block records
     int up_blocks_key[16] = {0};               // the partition up_blocks was derived from
     std::vector<CosetBlock> up_blocks; std::vector<int> up_jobs, up_slot;   // host copies of what d_cpblocks / d_jobs / d_slot hold (re-uploaded only when they change)
-    std::vector<int> up_perm, up_colinfo, up_targets;                      // ... and of d_perm / d_colinfo / d_targets (a new target of the same pattern changes none of them)
+    std::vector<int> up_perm, up_colinfo;                                  // ... and of d_perm / d_colinfo (a new target of the same pattern changes none of them)
     bool use_cosetp = false;   // kernel 2g: 2e's NT = 2 shape with the planes in the MFMA rows (no output staging)
     bool use_toep = false; int toep_nsa = 0, toep_saw = 16; unsigned toep_ksmask = 0; int toep_nm = 1;   /* row tiles per block (ToepShape) */   /* super-block columns, their width, non-zero K-steps */ int toep_targets[4] = {-1, -1, -1, -1};
-    int* d_cell = nullptr; size_t cell_cap = 0; uint4* d_afrag = nullptr; size_t afrag_cap = 0;
+    DevBuf<int> d_cell; DevBuf<uint4> d_afrag;
     static constexpr int NBUF = 2;
-    float* d_pmag[NBUF] = {nullptr, nullptr};
-    float* d_inten = nullptr; float* d_cplx = nullptr;
-    float* d_agg_p = nullptr; float* d_agg_i = nullptr; float* d_scale = nullptr;
-    double* d_peakA = nullptr; unsigned* d_peak = nullptr; size_t peak_cap = 0;
-    float* d_wint = nullptr; size_t wint_cap = 0;  // weighted-intensity (time-average) volume
-    void* d_an = nullptr; void* h_an = nullptr; size_t an_dev_cap = 0, an_host_cap = 0;   // olx_solution_analyze: device scratch, pinned staging
+    DevBuf<float> d_pmag[NBUF];               // the output volumes (reserve_outputs): |p| ...
+    DevBuf<float> d_inten, d_cplx, d_agg_p, d_agg_i;   // ... and the members created lazily at its capacity
+    DevBuf<float> d_scale;
+    DevBuf<double> d_peakA; DevBuf<unsigned> d_peak;
+    DevBuf<float> d_wint;  // weighted-intensity (time-average) volume
+    DevBuf<unsigned char> d_an; void* h_an = nullptr; size_t h_an_bytes = 0;   // olx_solution_analyze: device scratch, pinned staging
     bool an_pending = false; int an_F = 0, an_npts = 0; size_t an_out_pk = 0, an_out_ita = 0, an_out_bd = 0, an_out_mom = 0;   // an analysis enqueued by olx_solution_analyze_begin
     // heterogeneous medium (kernel 2h)
-    bool hetero = false; HeteroParams hp{}; float4* d_med = nullptr; int *d_plane_k = nullptr, *d_plane_of_k = nullptr;
-    float* d_inv2z = nullptr; int *d_kfirst = nullptr, *d_klast = nullptr;
+    bool hetero = false; HeteroParams hp{}; DevBuf<float4> d_med; DevBuf<int> d_plane_k, d_plane_of_k;
+    DevBuf<float> d_inv2z; DevBuf<int> d_kfirst, d_klast;
     int planes_per_layer = 1;                  // olx_field_medium_layering: 1 = one sample per plane (default)
-    float4* d_med_layer = nullptr; int *d_layer_lo = nullptr, *d_layer_hi = nullptr;
+    DevBuf<float4> d_med_layer; DevBuf<int> d_layer_lo, d_layer_hi;
     // marched ray sums (kernel 2m): model requested for the next olx_field_set_medium, decision, double-buffered U[element][i][j]
     int medium_model = 0;                      // OLX_MEDIUM_AUTO / _SAMPLED / _MARCHED
     bool march_one = false;                    // kernel 2m: a' = kappa sig everywhere -> ONE running sum per ray (hp.kappa)
-    float2* d_Utex = nullptr; size_t Utex_cap = 0;   // kernel 2m, one-sum form: the last running sums as row pairs {U(i,j), U(i+1,j)} (one 16-byte load per look-up above the medium)
-    bool marched = false; float2* d_U[2] = {nullptr, nullptr}; size_t U_cap = 0; std::vector<int> h_plane_k;
-    float* d_sig = nullptr;                   // kernel 2m, one-sum form: the planes' own terms as ONE float per cell, sig[plane][i][j] (the fused writers read them coalesced)
-    size_t out_cap = 0; int nbuf = 1; int cur = 0;
+    DevBuf<float2> d_Utex;   // kernel 2m, one-sum form: the last running sums as row pairs {U(i,j), U(i+1,j)} (one 16-byte load per look-up above the medium)
+    bool marched = false; DevBuf<float2> d_U[2]; std::vector<int> h_plane_k;
+    DevBuf<float> d_sig;                      // kernel 2m, one-sum form: the planes' own terms as ONE float per cell, sig[plane][i][j] (the fused writers read them coalesced)
+    int nbuf = 1; int cur = 0;
     std::string variant;
     std::vector<hipEvent_t> prof_ev; int prof_n = 0; bool prof_on = false;
     // pulsed model (kernel 2p): the setting of olx_field_pulse for the plans that follow, and what the current plan holds
@@ -122,30 +139,30 @@ struct olx_ctx {
     bool pmax_live = false;                    // d_pmax holds the launched (and possibly scaled) p_max volumes
     bool agg_pmax_valid = false;               // d_agg_pmax holds max_f p_max_f of them
     PulseParams pulse{};
-    float* d_pmax = nullptr; size_t pmax_cap = 0; float* d_agg_pmax = nullptr; size_t agg_pmax_cap = 0;
-    double4* d_ptab = nullptr; float* d_pw = nullptr; size_t ptab_cap = 0;
+    DevBuf<float> d_pmax, d_agg_pmax;
+    DevBuf<double4> d_ptab; DevBuf<float> d_pw;
     // thermal model (kernel 3, olx_thermal_*): buffers of their own, apart from the field / aggregate volumes
     bool th_planned = false, th_uniform = false; ThermalParams th{};
     double th_rate = 0;                        // max_v (sum_faces K + W) / (rho Cp)_v [1/s]: the FTCS bound is dt <= 1 / th_rate
-    float* d_th_T[2] = {nullptr, nullptr}; int th_cur = 0; float *d_th_max = nullptr, *d_th_cem = nullptr; size_t th_cap = 0;
-    float4* d_th_coef = nullptr; float *d_th_irc = nullptr, *d_th_sfac = nullptr; size_t th_coef_cap = 0; unsigned* d_th_rate = nullptr;
-    int th_steps = 0, th_max_focus = -1; std::vector<int> th_row; int* d_th_sf = nullptr; float* d_th_tau = nullptr; size_t th_sched_cap = 0;
-    int th_npts = 0; long long* d_th_pts = nullptr; size_t th_pts_cap = 0; float* d_th_trace = nullptr; size_t th_trace_cap = 0;
-    int th_src_foci = 0; bool th_src_resident = false; float* d_th_I = nullptr; size_t th_I_cap = 0;
+    DevBuf<float> d_th_T[2]; int th_cur = 0; DevBuf<float> d_th_max, d_th_cem;
+    DevBuf<float4> d_th_coef; DevBuf<float> d_th_irc, d_th_sfac; DevBuf<unsigned> d_th_rate;
+    int th_steps = 0, th_max_focus = -1; std::vector<int> th_row; DevBuf<int> d_th_sf; DevBuf<float> d_th_tau;
+    int th_npts = 0; DevBuf<long long> d_th_pts; DevBuf<float> d_th_trace;
+    int th_src_foci = 0; bool th_src_resident = false; DevBuf<float> d_th_I;
     int th_next = -1;                          // the step the next olx_thermal_run continues with (-1: nothing run since the last plan / schedule)
     // StraightRay delays (kernel 1m, olx_bf_set_medium / olx_bf_solve_medium): the non-trivial sigma planes in buffers of their own, apart from
     // the field plan's medium and volumes
     bool bm_set = false; BfMedParams bm{};
-    double* d_bm_sig = nullptr; size_t bm_sig_cap = 0;        // [n_planes][nx][ny] sigma = c_ref / c - 1 (fp64)
-    double* d_bm_zp = nullptr; size_t bm_zp_cap = 0;          // [n_planes] z of the held planes [m]
-    int* d_bm_pk = nullptr; size_t bm_pk_cap = 0;             // [nz] held plane of grid plane k, -1 = sigma == 0 there
+    DevBuf<double> d_bm_sig;        // [n_planes][nx][ny] sigma = c_ref / c - 1 (fp64)
+    DevBuf<double> d_bm_zp;         // [n_planes] z of the held planes [m]
+    DevBuf<int> d_bm_pk;            // [nz] held plane of grid plane k, -1 = sigma == 0 there
     // comm: RCCL communicator, or the direct peer-to-peer transport (exactly one of comm / p2p is set once initialised)
     P2PState* p2p = nullptr;
     bool comm_active() const { return comm != nullptr || p2p != nullptr; }
     RcclApi rccl; olx_nccl_comm comm = nullptr; int nranks = 1, rank = 0;
     hipStream_t comm_stream = nullptr; hipEvent_t ev_field[NBUF] = {nullptr, nullptr};
     hipEvent_t ev_gather[NBUF] = {nullptr, nullptr}; bool gather_pending[NBUF] = {false, false};
-    float* d_gather = nullptr; size_t gather_cap = 0;
+    DevBuf<float> d_gather;
     hipEvent_t ev_agg = nullptr, ev_red = nullptr; bool reduce_pending = false;
     int agg_local = -1, agg_total = 0;        // olx_field_aggregate_counts: genuine local foci / global focus count (padding excluded)
     std::string rccl_path;                     // file the RCCL symbols were bound from
@@ -181,6 +198,23 @@ static inline int fail(olx_ctx* c, int code, const char* fmt, ...) {
             return fail((c), e_ == hipErrorOutOfMemory ? OLX_ENOMEM : OLX_EHIP, "%s: %s", #call, \
                         hipGetErrorString(e_));                                          \
     } while (0)
+
+template <class T> int DevBuf<T>::reserve(olx_ctx* c, size_t n) {
+    if (cap >= n && p) return OLX_OK;
+    release();
+    n = std::max(n, (size_t)1);
+    HIPCHK(c, hipMalloc((void**)&p, sizeof(T) * n));
+    cap = n;
+    return OLX_OK;
+}
+
+// The aggregate volumes, created lazily at the output volumes' capacity (the group is freed together: reserve_outputs in olx.hip)
+static inline int reserve_aggregate(olx_ctx* c, bool with_p, bool with_i) {
+    const size_t n = c->d_pmag[0].capacity();
+    int rc = with_p ? c->d_agg_p.reserve(c, n) : OLX_OK;
+    if (!rc && with_i) rc = c->d_agg_i.reserve(c, n);
+    return rc;
+}
 
 // call-scoped device scratch: freed on every return path
 struct DevScratch {

@@ -85,8 +85,7 @@ struct P2PState {
     const float* peer_agg[P2P_MAX_RANKS][2] = {};    // IPC mappings of the peers' aggregate buffers
     uint64_t agg_vox = 0;
     bool agg_with_i = false;
-    float* agg_scratch = nullptr;                    // [rank][2][slice]: the peers' partials of this rank's slice
-    size_t agg_scratch_cap = 0;
+    DevBuf<float> agg_scratch;                       // [rank][2][slice]: the peers' partials of this rank's slice
     uint64_t agg_gen = 0, agg_done_gen = 0;          // aggregate generations issued / finished by this rank's worker
     uint64_t gen = 0;                                // generations issued by this rank
     uint64_t buf_gen[2] = {0, 0};                    // generation that last used output buffer b as its source
@@ -138,7 +137,7 @@ static std::string p2p_aggregate_job(olx_ctx* c, P2PState* s, const Job& j) {
     const size_t vox = j.count;
     size_t lo, hi;
     p2p_slice(vox, s->nranks, s->rank, lo, hi);
-    const size_t n = hi - lo, stride = s->agg_scratch_cap / (2 * (size_t)s->nranks);
+    const size_t n = hi - lo, stride = s->agg_scratch.capacity() / (2 * (size_t)s->nranks);
     float* own[2] = {c->d_agg_p, j.with_i ? c->d_agg_i : nullptr};
     if (hipEventSynchronize(c->ev_agg) != hipSuccess) return "p2p: waiting for the local aggregate failed";
     s->ctl->agg_ready[s->rank].store(j.gen, std::memory_order_release);
@@ -321,10 +320,9 @@ int olx_p2p_destroy(olx_ctx* c) {
     }
     p2p_close_peers(s);
     for (int r = 0; r < P2P_MAX_RANKS; ++r) if (s->copy_stream[r]) hipStreamDestroy(s->copy_stream[r]);
-    if (s->agg_scratch) hipFree(s->agg_scratch);
     if (s->ctl) munmap(s->ctl, sizeof(P2PControl));
     if (s->owner) shm_unlink(s->shm_name.c_str());      // (already gone when every rank attached: ENOENT is fine)
-    delete s;
+    delete s;     // (frees agg_scratch)
     c->p2p = nullptr;
     return OLX_OK;
 }
@@ -342,8 +340,7 @@ int olx_p2p_export(olx_ctx* c, void* blob_out) {
     b.device = c->device; b.pid = (int)getpid();
     // the aggregate buffers travel with the blocks (allocated here if no aggregate has been formed yet)
     const bool with_i = (c->flags & OLX_OUT_INTENSITY) != 0;
-    if (!c->d_agg_p) HIPCHK(c, hipMalloc((void**)&c->d_agg_p, sizeof(float) * c->out_cap));
-    if (with_i && !c->d_agg_i) HIPCHK(c, hipMalloc((void**)&c->d_agg_i, sizeof(float) * c->out_cap));
+    { int rc = reserve_aggregate(c, true, with_i); if (rc) return rc; }
     HIPCHK(c, hipIpcGetMemHandle(&b.agg[0], c->d_agg_p));
     if (with_i) HIPCHK(c, hipIpcGetMemHandle(&b.agg[1], c->d_agg_i));
     b.agg_vox = (uint64_t)c->fp.vox; b.agg_i = with_i ? 1 : 0;
@@ -395,12 +392,10 @@ int olx_p2p_allgather(olx_ctx* c) {
     if (!s->imported || s->peer_count != count)
         return fail(c, OLX_ESTATE, "olx_field_allgather (p2p): exchange olx_comm_export / olx_comm_import after the plan first");
     const size_t need = count * s->nranks;
-    if (c->gather_cap < need) {
-        { int rc = olx_p2p_drain(c); if (rc) return rc; }
-        if (c->d_gather) hipFree(c->d_gather);
-        c->d_gather = nullptr; c->gather_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_gather, sizeof(float) * need));
-        c->gather_cap = need;
+    if (c->d_gather.capacity() < need) {
+        int rc = olx_p2p_drain(c);
+        if (!rc) rc = c->d_gather.reserve(c, need);
+        if (rc) return rc;
     }
     const int b = c->cur;
     HIPCHK(c, hipEventRecord(c->ev_field[b], c->stream));
@@ -456,12 +451,10 @@ int olx_p2p_aggregate(olx_ctx* c, bool scatter, bool with_i) {
     size_t lo, hi;
     p2p_slice((size_t)c->fp.vox, s->nranks, 0, lo, hi);
     const size_t need = 2 * (size_t)s->nranks * (hi - lo);
-    if (s->agg_scratch_cap < need) {
-        { int rc = olx_p2p_drain(c); if (rc) return rc; }
-        if (s->agg_scratch) hipFree(s->agg_scratch);
-        s->agg_scratch = nullptr; s->agg_scratch_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&s->agg_scratch, sizeof(float) * need));
-        s->agg_scratch_cap = need;
+    if (s->agg_scratch.capacity() < need) {
+        int rc = olx_p2p_drain(c);
+        if (!rc) rc = s->agg_scratch.reserve(c, need);
+        if (rc) return rc;
     }
     {
         std::lock_guard<std::mutex> lk(s->mu);
