@@ -133,6 +133,30 @@ int olx_bf_set_medium(olx_ctx *ctx, const float *sound_speed, const olx_grid *gr
 int olx_bf_solve_medium(olx_ctx *ctx, const double *foci_m, int n_foci, const double *M, double c,
                         int apod_kind, double p0, double p1, double *delays_out, double *apod_out);
 
+/* ---- kernel 1a: MediumCompensated apodization through a medium (DESIGN.md section 2 "MediumCompensated") ----
+ * The ApodizationMethod.calc_apodization seam with its `params` argument read: amplitudes that know the attenuation
+ * every element's straight ray crosses on its way to the focus,
+ *   h_e = exp(-A_e) [S_e / max(d_e, dmin) with spreading],  A_e = the straight-ray sum of section 7 over a [Np/m],
+ *   apod_e = b_e (min_active h / h_e)  (OLX_COMP_EQUALIZE)   or   b_e (h_e / max_active h)  (OLX_COMP_MATCHED),
+ * b = kernel 1's apodization, active = { b_e > 0 }, S_e = area_m2 of olx_set_elements.  Set the attenuation:
+ * attenuation_db_cm_mhz [nx*ny*nz] floats on `grid` (C order; NULL = none), in the frame of the foci, converted at
+ * freq_hz with the field model's power law (a = alpha f_MHz^0.9 100 / 8.685889638065035 Np/m, fp64).  Only the planes
+ * with some attenuation != 0 are held, in buffers of their own: a field plan, its medium and its volumes, and the
+ * medium of olx_bf_set_medium are left as they are.  Refused (nothing on the device touched): freq_hz non-finite
+ * or <= 0, an attenuation negative or non-finite, a bad grid. */
+enum { OLX_COMP_EQUALIZE = 0, OLX_COMP_MATCHED = 1 };
+int olx_bf_set_attenuation(olx_ctx *ctx, const float *attenuation_db_cm_mhz, const olx_grid *grid, double freq_hz);
+/* olx_bf_solve's arguments and outputs with the apodization compensated through the attenuation of
+ * olx_bf_set_attenuation; use_delay_medium != 0: and the delays corrected through the medium of olx_bf_set_medium
+ * (olx_bf_solve_medium's, bit for bit; c must equal its c_ref and both media must share one grid), both by ONE walk
+ * of the rays.  Without attenuation on any ray and without spreading the apodization is kernel 1's bit for bit.  An
+ * h_e that underflows to 0 (A_e > 700) is outside the method's range.  The results stay device-resident as the
+ * steering table.  OLX_ESTATE before an attenuation (and, with use_delay_medium, a medium) is set; olx_bf_time is
+ * refused after it, as after olx_bf_solve_medium. */
+int olx_bf_solve_compensated(olx_ctx *ctx, const double *foci_m, int n_foci, const double *M, double c,
+                             int apod_kind, double p0, double p1, int mode, int spreading, int use_delay_medium,
+                             double *delays_out, double *apod_out);
+
 /* Upload externally computed delays / apodizations [F*N] as the steering table
  * (run_simulation's `delays`, `apod` arguments, sim/kwave_if.py:81-83, 98-99). */
 int olx_set_steering(olx_ctx *ctx, const double *delays_s, const double *apod, int n_foci);

@@ -85,7 +85,7 @@ static int report_bounds(olx_ctx* c) {
     struct { const char* name; int (*read)(unsigned*); } units[] = {{"2g (k_coset2.hip)", olx_dbg_bounds_cosetp}, {"2e (k_coset.hip)", olx_dbg_bounds_coset},
                                                                      {"2f (k_toep.hip)", olx_dbg_bounds_toep}, {"2m (k_hmarch.hip)", olx_dbg_bounds_hmarch},
                                                                      {"2p (k_pulse.hip)", olx_dbg_bounds_pulse}, {"3 (k_thermal.hip)", olx_dbg_bounds_thermal},
-                                                                     {"1m (k_bfmed.hip)", olx_dbg_bounds_bfmed}};
+                                                                     {"1m / 1a (k_bfmed.hip)", olx_dbg_bounds_bfmed}};
     int rc = OLX_OK;
     for (auto& u : units) {
         unsigned w[4] = {0, 0, 0, 0};
@@ -294,7 +294,7 @@ int olx_bf_set_medium(olx_ctx* c, const float* sound_speed, const olx_grid* grid
     }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));      // (a solve of the previous medium may still read the buffers)
-    c->bm_set = false;
+    c->bm_set = false; c->bc_valid = false;
     int rc = c->d_bm_sig.reserve(c, sig.size());
     if (!rc) rc = c->d_bm_zp.reserve(c, zp.size());
     if (!rc) rc = c->d_bm_pk.reserve(c, nz);
@@ -309,6 +309,7 @@ int olx_bf_set_medium(olx_ctx* c, const float* sound_speed, const olx_grid* grid
     P.ztol = 1e-6 * P.hz;
     P.c = c_ref;
     P.nx = nx; P.ny = ny; P.nz = nz; P.n_planes = (int)zp.size();
+    c->h_bm_pk.swap(pk);
     c->bm_set = true;
     return OLX_OK;
 }
@@ -336,6 +337,118 @@ int olx_bf_solve_medium(olx_ctx* c, const double* foci_m, int n_foci, const doub
     c->steer_version++;
     c->h_foci.clear();      // not geometric delays: the planner must not take the foci as known (infer_foci decides)
     c->bf_valid = false;    // (olx_bf_time would rewrite the table with kernel 1's delays)
+    return OLX_OK;
+}
+
+// ---- kernel 1a: MediumCompensated apodization through a medium ---------------------------------------------------------
+int olx_bf_set_attenuation(olx_ctx* c, const float* att, const olx_grid* grid, double freq_hz) {
+    if (!c) return OLX_EINVAL;
+    if (!grid) return fail(c, OLX_EINVAL, "olx_bf_set_attenuation: null grid");
+    if (!(freq_hz > 0) || !std::isfinite(freq_hz)) return fail(c, OLX_EINVAL, "olx_bf_set_attenuation: freq_hz must be finite and > 0");
+    for (int a = 0; a < 3; ++a) {
+        if (grid->n[a] < 1) return fail(c, OLX_EINVAL, "olx_bf_set_attenuation: grid sizes must be >= 1");
+        if (!(grid->spacing[a] > 0) || !std::isfinite(grid->spacing[a]) || !std::isfinite(grid->origin[a]))
+            return fail(c, OLX_EINVAL, "olx_bf_set_attenuation: grid spacing must be finite and > 0, origin finite");
+    }
+    const int nx = grid->n[0], ny = grid->n[1], nz = grid->n[2];
+    const size_t nxy = (size_t)nx * ny;
+    if (att)
+        for (size_t o = 0; o < nxy * nz; ++o)
+            if (!(att[o] >= 0.f) || !std::isfinite(att[o])) return fail(c, OLX_EINVAL, "olx_bf_set_attenuation: attenuation must be finite and >= 0");
+    // the held planes: olx_bf_set_medium's rule for the attenuation (a plane with any voxel != 0), a [Np/m] in fp64 (sim/field.py _np_per_m)
+    const double fpow = std::pow(freq_hz * 1e-6, 0.9);
+    std::vector<int> pk(nz, -1);
+    std::vector<double> zp, av;
+    for (int k = 0; k < nz && att; ++k) {
+        bool any = false;
+        for (size_t ij = 0; ij < nxy && !any; ++ij) any = att[ij * nz + k] != 0.f;
+        if (!any) continue;
+        pk[k] = (int)zp.size();
+        zp.push_back(grid->origin[2] + k * grid->spacing[2]);
+        for (size_t ij = 0; ij < nxy; ++ij) av.push_back((double)att[ij * nz + k] * fpow * 100.0 / 8.685889638065035);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a solve of the previous attenuation may still read the buffers)
+    c->ba_set = false; c->bc_valid = false;
+    int rc = c->d_ba_att.reserve(c, av.size());
+    if (!rc) rc = c->d_ba_zp.reserve(c, zp.size());
+    if (!rc) rc = c->d_ba_pk.reserve(c, nz);
+    if (rc) return rc;
+    if (!av.empty()) HIPCHK(c, hipMemcpy(c->d_ba_att, av.data(), sizeof(double) * av.size(), hipMemcpyHostToDevice));
+    if (!zp.empty()) HIPCHK(c, hipMemcpy(c->d_ba_zp, zp.data(), sizeof(double) * zp.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_ba_pk, pk.data(), sizeof(int) * nz, hipMemcpyHostToDevice));
+    BfMedParams& P = c->ba;
+    P.ox = grid->origin[0]; P.oy = grid->origin[1]; P.oz = grid->origin[2];
+    P.hx = grid->spacing[0]; P.hy = grid->spacing[1]; P.hz = grid->spacing[2];
+    P.dmin = 0.5 * std::min(P.hx, std::min(P.hy, P.hz));
+    P.ztol = 1e-6 * P.hz;
+    P.c = freq_hz;
+    P.nx = nx; P.ny = ny; P.nz = nz; P.n_planes = (int)zp.size();
+    c->h_ba_pk.swap(pk);
+    c->ba_set = true;
+    return OLX_OK;
+}
+
+// the planes held by either medium, in z order, with their plane in each: what the one-walk launch of kernels 1m + 1a steps through
+static int build_joint_walk(olx_ctx* c) {
+    const int nz = c->bm.nz;
+    std::vector<double> zp;
+    std::vector<int2> walk;
+    for (int k = 0; k < nz; ++k) {
+        const int ps = c->h_bm_pk[k], pa = c->h_ba_pk[k];
+        if (ps < 0 && pa < 0) continue;
+        zp.push_back(c->bm.oz + k * c->bm.hz);      // (olx_bf_set_medium's expression for its planes)
+        walk.push_back(make_int2(ps, pa));
+    }
+    int rc = c->d_bc_zp.reserve(c, zp.size());
+    if (!rc) rc = c->d_bc_walk.reserve(c, walk.size());
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!zp.empty()) {
+        HIPCHK(c, hipMemcpy(c->d_bc_zp, zp.data(), sizeof(double) * zp.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_bc_walk, walk.data(), sizeof(int2) * walk.size(), hipMemcpyHostToDevice));
+    }
+    c->bc_planes = (int)zp.size();
+    c->bc_valid = true;
+    return OLX_OK;
+}
+
+int olx_bf_solve_compensated(olx_ctx* c, const double* foci_m, int n_foci, const double* M, double cs, int apod_kind,
+                             double p0, double p1, int mode, int spreading, int use_delay_medium, double* delays_out, double* apod_out) {
+    if (!c) return OLX_EINVAL;
+    if (!c->ba_set) return fail(c, OLX_ESTATE, "olx_bf_solve_compensated: call olx_bf_set_attenuation first");
+    if (use_delay_medium && !c->bm_set) return fail(c, OLX_ESTATE, "olx_bf_solve_compensated: call olx_bf_set_medium first (use_delay_medium)");
+    if (c->n_el <= 0) return fail(c, OLX_ESTATE, "olx_bf_solve_compensated: call olx_set_elements first");
+    if (!foci_m || n_foci <= 0) return fail(c, OLX_EINVAL, "olx_bf_solve_compensated: no foci");
+    if (mode != OLX_COMP_EQUALIZE && mode != OLX_COMP_MATCHED) return fail(c, OLX_EINVAL, "olx_bf_solve_compensated: unknown mode %d", mode);
+    if (use_delay_medium) {
+        const BfMedParams &a = c->bm, &b = c->ba;
+        if (cs != a.c) return fail(c, OLX_EINVAL, "olx_bf_solve_compensated: c (%.17g) must be the c_ref of olx_bf_set_medium (%.17g)", cs, a.c);
+        if (a.nx != b.nx || a.ny != b.ny || a.nz != b.nz || a.ox != b.ox || a.oy != b.oy || a.oz != b.oz || a.hx != b.hx || a.hy != b.hy || a.hz != b.hz)
+            return fail(c, OLX_EINVAL, "olx_bf_solve_compensated: the media of olx_bf_set_medium and olx_bf_set_attenuation must share one grid");
+    }
+    for (size_t q = 0; q < 3 * (size_t)n_foci; ++q)
+        if (!std::isfinite(foci_m[q])) return fail(c, OLX_EINVAL, "olx_bf_solve_compensated: focus positions must be finite");
+    for (int q = 0; M && q < 16; ++q)
+        if (!std::isfinite(M[q])) return fail(c, OLX_EINVAL, "olx_bf_solve_compensated: transform must be finite");
+    // kernel 1 (delays, the base apodization, the foci and the transform on the device), then ONE walk of the rays over its table
+    int rc = olx_bf_solve(c, foci_m, n_foci, M, cs, apod_kind, p0, p1, nullptr, nullptr);
+    if (rc) return rc;
+    const size_t fn = (size_t)n_foci * c->n_el;
+    rc = c->d_ba_h.reserve(c, fn);
+    if (!rc && use_delay_medium && !c->bc_valid) rc = build_joint_walk(c);
+    if (rc) { c->n_foci = 0; return rc; }
+    olx_launch_bfapod(c, n_foci, mode, spreading != 0, use_delay_medium != 0);
+    HIPCHK(c, hipGetLastError());
+    if (use_delay_medium) HIPCHK(c, hipMemcpyAsync(c->h_delays.data(), c->d_delays, sizeof(double) * fn, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_apod.data(), c->d_apod, sizeof(double) * fn, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (delays_out) memcpy(delays_out, c->h_delays.data(), sizeof(double) * fn);
+    if (apod_out) memcpy(apod_out, c->h_apod.data(), sizeof(double) * fn);
+    c->steer_version++;
+    if (use_delay_medium) c->h_foci.clear();      // not geometric delays (as olx_bf_solve_medium)
+    else if (!c->h_foci.empty()) c->foci_version = c->steer_version;      // kernel 1's delays: the foci stay known, the planner reads the apodization as data
+    c->bf_valid = false;    // (olx_bf_time would rewrite the table with kernel 1's apodization)
     return OLX_OK;
 }
 

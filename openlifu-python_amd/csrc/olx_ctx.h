@@ -156,6 +156,19 @@ struct olx_ctx {
     DevBuf<double> d_bm_sig;        // [n_planes][nx][ny] sigma = c_ref / c - 1 (fp64)
     DevBuf<double> d_bm_zp;         // [n_planes] z of the held planes [m]
     DevBuf<int> d_bm_pk;            // [nz] held plane of grid plane k, -1 = sigma == 0 there
+    std::vector<int> h_bm_pk;       // host copy of d_bm_pk (the plane pairs of the one-walk launch are merged from it)
+    // MediumCompensated apodization (kernel 1a, olx_bf_set_attenuation / olx_bf_solve_compensated): the non-zero attenuation planes, again in
+    // buffers of their own (ba.c holds the frequency [Hz] the attenuation was converted at)
+    bool ba_set = false; BfMedParams ba{};
+    DevBuf<double> d_ba_att;        // [n_planes][nx][ny] a [Np/m] (fp64)
+    DevBuf<double> d_ba_zp;         // [n_planes] z of the held planes [m]
+    DevBuf<int> d_ba_pk;            // [nz] held plane of grid plane k, -1 = a == 0 there
+    std::vector<int> h_ba_pk;
+    DevBuf<double> d_ba_h;          // [F][N] arrival amplitudes h_e of the last launch (scratch)
+    // ... and the walk of both at once: the planes held by either volume (rebuilt when either medium changes)
+    bool bc_valid = false; int bc_planes = 0;
+    DevBuf<double> d_bc_zp;         // [bc_planes] z [m]
+    DevBuf<int2> d_bc_walk;         // [bc_planes] (sigma plane, attenuation plane), -1 = not held there
     // comm: RCCL communicator, or the direct peer-to-peer transport (exactly one of comm / p2p is set once initialised)
     P2PState* p2p = nullptr;
     bool comm_active() const { return comm != nullptr || p2p != nullptr; }

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("OLX_LIB_PATH") or os.path.join(os.path.dirname(_PKG_D
 
 OLX_OK, OLX_EINVAL, OLX_ESTATE, OLX_EHIP, OLX_ENOMEM, OLX_ECOMM = 0, -1, -2, -3, -4, -5
 APOD_UNIFORM, APOD_MAXANGLE, APOD_PIECEWISE = 0, 1, 2
+COMP_MODES = {"equalize": 0, "matched": 1}   # OLX_COMP_*
 OUT_PMAG, OUT_INTENSITY, OUT_COMPLEX = 1, 2, 4
 OUT_PMAX = 64             # pulsed plans only (olx_field_pulse): also keep p_max; the OUT_PMAG slot then holds p_min
 MEDIUM_MODELS = {"auto": 0, "sampled": 1, "marched": 2}   # OLX_MEDIUM_*
@@ -41,6 +42,7 @@ SYMBOLS = [
     "olx_field_pulse", "olx_field_fetch_pmax", "olx_aggregate_fetch_pmax",
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
     "olx_bf_set_medium", "olx_bf_solve_medium",
+    "olx_bf_set_attenuation", "olx_bf_solve_compensated",
 ]
 
 
@@ -90,6 +92,8 @@ def load(require_gpu: bool = True):
         lib.olx_bf_solve.argtypes = [vp, dp, c_int, dp, c_double, c_int, c_double, c_double, dp, dp]
         lib.olx_bf_set_medium.argtypes = [vp, fp, POINTER(OlxGrid), c_double]
         lib.olx_bf_solve_medium.argtypes = [vp, dp, c_int, dp, c_double, c_int, c_double, c_double, dp, dp]
+        lib.olx_bf_set_attenuation.argtypes = [vp, fp, POINTER(OlxGrid), c_double]
+        lib.olx_bf_solve_compensated.argtypes = [vp, dp, c_int, dp, c_double, c_int, c_double, c_double, c_int, c_int, c_int, dp, dp]
         lib.olx_set_steering.argtypes = [vp, dp, dp, c_int]
         lib.olx_bf_quantize.argtypes = [vp, c_double, c_int, c_void_p, c_void_p, dp, c_void_p]
         lib.olx_field_plan.argtypes = [vp, POINTER(OlxGrid), POINTER(OlxSlab), c_int, c_double, c_double,
@@ -274,6 +278,38 @@ class Context:
         delays, apod = np.empty((F, self.n_el)), np.empty((F, self.n_el))
         self._chk(self._lib.olx_bf_solve_medium(self._h, _dptr(foci_m), F, _dptr(M), float(c), int(apod_kind),
                                                 float(p0), float(p1), _dptr(delays), _dptr(apod)))
+        self.n_foci = F
+        return delays, apod
+
+    # -- kernel 1a (MediumCompensated apodization)
+    def bf_set_attenuation(self, attenuation, origin_m, spacing_m, n, freq_hz):
+        """The attenuation of ``bf_solve_compensated``: [nx,ny,nz] in dB/cm/MHz^0.9 (None = none) on the grid (origin, spacing [m], n), in
+        the frame of the foci, converted to Np/m at ``freq_hz``.  Leaves any field plan, its medium and its volumes, and the medium of
+        ``bf_set_medium`` as they are."""
+        shape = tuple(int(v) for v in n)
+        g = OlxGrid()
+        for a in range(3):
+            g.origin[a] = float(origin_m[a]); g.spacing[a] = float(spacing_m[a]); g.n[a] = shape[a]
+        att = None if attenuation is None else np.ascontiguousarray(attenuation, dtype=np.float32)
+        if att is not None and att.shape != shape:
+            raise ValueError(f"attenuation volume must have the grid shape {shape}, got {att.shape}")
+        self._chk(self._lib.olx_bf_set_attenuation(self._h, _fptr(att), ctypes.byref(g), float(freq_hz)))
+
+    def bf_solve_compensated(self, foci_m, c, matrix=None, apod_kind=APOD_UNIFORM, p0=1.0, p1=0.0, mode="equalize", spreading=False,
+                             use_delay_medium=False):
+        """``bf_solve`` with the apodization compensated through the attenuation of ``bf_set_attenuation`` and, with
+        ``use_delay_medium``, the delays corrected through the medium of ``bf_set_medium`` in the same walk -> (delays, apod) [F,N]."""
+        if mode not in COMP_MODES:
+            raise ValueError(f"mode must be one of {tuple(COMP_MODES)}, got {mode!r}")
+        foci_m = _f64(np.atleast_2d(foci_m))
+        if foci_m.shape[1] != 3:
+            raise ValueError("foci_m must be [F,3]")
+        F = foci_m.shape[0]
+        M = None if matrix is None else _f64(matrix, (4, 4))
+        delays, apod = np.empty((F, self.n_el)), np.empty((F, self.n_el))
+        self._chk(self._lib.olx_bf_solve_compensated(self._h, _dptr(foci_m), F, _dptr(M), float(c), int(apod_kind), float(p0), float(p1),
+                                                     COMP_MODES[mode], int(bool(spreading)), int(bool(use_delay_medium)),
+                                                     _dptr(delays), _dptr(apod)))
         self.n_foci = F
         return delays, apod
 

@@ -276,6 +276,22 @@ class Engine:
         self.ctx.bf_set_medium(sound_speed, origin_m, spacing_m, n, c_ref)
         return self.ctx.bf_solve_medium(focus_positions_m(targets), c_ref, matrix=transform, apod_kind=kind, p0=p0, p1=p1)
 
+    # ---- kernel 1a (alone, or in one walk with 1m) ----------------------------------------------
+    def beamform_compensated(self, arr, targets, c: float, attenuation, origin_m, spacing_m, n, freq_hz: float, transform=None,
+                             apod=(nat.APOD_UNIFORM, 1.0, 0.0), mode="equalize", spreading=False, sound_speed=False):
+        """delays[F,N] (s) and the MediumCompensated apod[F,N] through the attenuation volume (dB/cm/MHz^0.9, None = none) at ``freq_hz``;
+        ``apod`` is the base method's kernel-1 arguments.  ``sound_speed`` other than False (a volume, or None = c everywhere) also
+        corrects the delays as ``beamform_medium`` does (c = the reference speed), by the same walk of the rays.  The table stays
+        resident as the steering table; the field plan, its medium and its volumes are left as they are."""
+        self.bind(arr)
+        kind, p0, p1 = apod
+        with_delays = sound_speed is not False
+        if with_delays:
+            self.ctx.bf_set_medium(sound_speed, origin_m, spacing_m, n, c)
+        self.ctx.bf_set_attenuation(attenuation, origin_m, spacing_m, n, freq_hz)
+        return self.ctx.bf_solve_compensated(focus_positions_m(targets), c, matrix=transform, apod_kind=kind, p0=p0, p1=p1, mode=mode,
+                                             spreading=spreading, use_delay_medium=with_delays)
+
     # ---- kernel 2 -----------------------------------------------------------------------------
     def field(self, arr, delays, apod, origin_m, spacing_m, n, freq, c, rho, p0_pa,
               want=("pmag", "intensity"), slab=None, steering_resident=False, medium=None, fp8_correction=None,

@@ -22,7 +22,7 @@ from typing import Any, Dict, List
 import numpy as np
 
 from .. import bf, seg, sim
-from ..bf.apod_methods import ApodizationMethod
+from ..bf.apod_methods import ApodizationMethod, MediumCompensated
 from ..bf.delay_methods import Direct, StraightRay
 from ..engine import get_engine, gpu_available
 from ..geo import Point
@@ -151,7 +151,10 @@ class Protocol:
 
     def _solve_fused(self, arr, targets, params):
         """(delays[F,N], apod[F,N]) of the built-in methods: kernel 1 (Direct), or kernels 1 + 1m (StraightRay: the corrected delays
-        are what the resident steering table holds)."""
+        are what the resident steering table holds); with MediumCompensated, kernel 1 + ONE walk of the rays for its apodization
+        and StraightRay's delays (kernel 1a), at the pulse's frequency unless the method has its own."""
+        if type(self.apod_method) is MediumCompensated:
+            return self.apod_method.solve(arr, targets, params, frequency=self.pulse.frequency, delay_method=self.delay_method)
         if type(self.delay_method) is StraightRay:
             return self.delay_method.solve(arr, targets, params, apod=self.apod_method.kernel_args())
         return get_engine().beamform(arr, targets, self.delay_method.speed(params), apod=self.apod_method.kernel_args())
