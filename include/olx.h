@@ -48,6 +48,7 @@ extern "C" {
 #define OLX_OUT_INTENSITY 2u /* 1e-4 |p|^2 / (2 rho c) [W/cm^2]  (kwave_if.py:140-144) */
 #define OLX_OUT_COMPLEX 4u   /* (re, im) interleaved, float32 */
 #define OLX_OUT_PMAX 64u     /* pulsed plans (olx_field_pulse) only: also keep the peak positive pressure p_max [Pa] (olx_field_fetch_pmax) */
+#define OLX_OUT_PII 128u     /* pulsed plans only: also keep the pulse intensity integral 1e-4 dt / (rho c) sum_k p(t_k)^2 [J/cm^2] (olx_field_fetch_pii) */
 /* accuracy / speed options of olx_field_plan (OR-ed into flags; see the accuracy note there) */
 #define OLX_FIELD_FP8_CORRECTION 8u   /* accepted for source compatibility: asks for what is the default since ABI v2 */
 #define OLX_FIELD_FP16_CORRECTION 32u /* opt out of the e4m3 correction products: three fp16 products everywhere (<= 2e-6) */
@@ -266,12 +267,28 @@ int olx_field_absorption(olx_ctx *ctx, double np_per_m);
  * OLX_OUT_PMAX asks for p_max = max(0, max_k p) as one more resident volume: olx_field_scale, olx_field_scale_aggregate and the scaling
  * of olx_solution_analyze scale it too, the device aggregate also forms max_f p_max_f (olx_aggregate_fetch_pmax).  Homogeneous media
  * (with olx_field_absorption) and any element geometry; a pulsed plan refuses a slab, a communicator, OLX_FIELD_DIRECTIVITY,
- * OLX_OUT_COMPLEX and olx_field_set_medium.  cycles > 0 and dt > 0 [s] are used as given (the caller applies its defaults). */
+ * OLX_OUT_COMPLEX and olx_field_set_medium.  cycles > 0 and dt > 0 [s] are used as given (the caller applies its defaults).
+ * Two more outputs of the same time axis (neither touches a plan that does not ask for it):
+ *   OLX_OUT_PII   the pulse intensity integral PII_f(v) = 1e-4 dt / (rho c) sum_k p_f(v, t_k)^2 [J/cm^2] as one more resident volume
+ *                 (olx_field_fetch_pii); PII / (cycles / f0) is the pulse-average intensity [W/cm^2].  olx_field_scale, olx_field_scale_aggregate
+ *                 and olx_solution_analyze do NOT scale it and the device aggregate does not aggregate it: a caller that scales the
+ *                 pressures by `factor` multiplies the fetched PII by factor^2.
+ *   olx_field_pulse_trace   the waveform p_f(v_i, t_k), k = 0 .. n_t - 1, at chosen voxels. */
 int olx_field_pulse(olx_ctx *ctx, double cycles, double dt, int n_t);
 /* p_max of every planned focus of the last pulsed launch ([F * voxels] floats), as scaled since. */
 int olx_field_fetch_pmax(olx_ctx *ctx, float *pmax_out);
 /* max_f p_max_f of the last device aggregate of a pulsed plan's volumes ([voxels] floats). */
 int olx_aggregate_fetch_pmax(olx_ctx *ctx, float *pmax_out);
+/* Pulse intensity integral of every planned focus of the last pulsed launch with OLX_OUT_PII ([F * voxels] floats, J/cm^2).  Never scaled
+ * on the device (see olx_field_pulse): multiply by factor^2 after an olx_field_scale by `factor`. */
+int olx_field_fetch_pii(olx_ctx *ctx, float *pii_out);
+/* Waveforms of the current pulsed plan with the current steering table (the plan need not have been launched, and needs no particular
+ * output flag): trace_out[(f * n_points + i) * n_t + k] = p_f(voxels[i], t_k) [Pa], float32, for all planned foci; voxels are linear C-order
+ * indices of the planned grid (OLX_EINVAL outside it).  A sample at which no element has arrived yet, or after the last burst has ended,
+ * is exactly 0.  One wave per (point, focus): meant for tens of points, not for volumes -- more than OLX_PULSE_TRACE_MAX_SAMPLES
+ * samples (F * n_points * n_t) in one call give OLX_EINVAL.  Synchronous. */
+#define OLX_PULSE_TRACE_MAX_SAMPLES (1ll << 26) /* 256 MiB of float32 */
+int olx_field_pulse_trace(olx_ctx *ctx, int n_points, const long long *voxels, float *trace_out);
 
 /* Thermal model (DESIGN.md section 2 "thermal model", kernel 3): Pennes bioheat rise dT above a baseline over a pulse sequence,
  *   rho Cp d(dT)/dt = div(kappa grad dT) - W dT + Q,   Q = 2 alpha 1e4 I_f(v) while a pulse aimed at focus f is on [W/m^3],

@@ -20,6 +20,13 @@
 //      before the pass go to its slot 0, samples after it are dropped), prefix-scan it across the wave (21 contiguous samples per lane,
 //      then a wave scan of the lane totals), evaluate p at every sample of the pass and keep the lane's max / min;
 //   3. wave max / min, one lane stores.
+// Two opt-in instantiations of the same source ("pulse intensity integral" and "traces"; fp64 oracle
+// tests/pulsed_wave_oracle.py); <false, false> is the kernel above (every addition sits under `if constexpr`):
+//   PII    the lane also sums p^2 over its valid samples of all passes (fp32), one wave sum at the end, lane 0 stores
+//          pii_out = 1e-4 dt / (rho c) sum_k p(v, t_k)^2 [J/cm^2];
+//   TRACE  one wave per (point, focus) instead of per voxel, v from a voxel-index list: the lanes store p at their valid samples between
+//          the first arrival and the last burst end (both fp64) to trace[(f n_points + i) n_t + k] and no volume; the launcher zeroes the
+//          trace first, so every other sample is an exact 0.
 // Single-pass capacity: PULSE_L = 64 x 21 = 1344 samples per voxel window (20 cycles at 400 kHz on a 0.25 mm grid with the default
 // dt = 0.5 x 0.25 mm / 1500 m/s: T / dt = 600 samples + the arrival spread of a 256-element array, ~1100 in all).  Longer windows take
 // ceil(window / 1344) passes, each re-walking the elements (the time axis is split, nothing else changes).
@@ -61,13 +68,26 @@ __device__ __forceinline__ float wave_min(float v) {
     for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o));
     return v;
 }
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
 
+// TRACE: pmin_out is the trace buffer [n_foci][n_points][n_t], points the voxel indices, pmax_out / inten_out / pii_out unused
+template <bool PII, bool TRACE>
 __global__ __launch_bounds__(64 * PULSE_WAVES) void field_pulse_k(const double4* __restrict__ tab, const float* __restrict__ wtab, const PulseParams P,
-                                                                  float* __restrict__ pmin_out, float* __restrict__ pmax_out, float* __restrict__ inten_out) {
+                                                                  float* __restrict__ pmin_out, float* __restrict__ pmax_out, float* __restrict__ inten_out,
+                                                                  float* __restrict__ pii_out, const long long* __restrict__ points, int n_points) {
     __shared__ float lds[PULSE_WAVES][2][PULSE_L];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long v = (long long)blockIdx.x * PULSE_WAVES + wave;
-    if (v >= P.vox) return;                      // (whole waves: nothing below synchronises across waves)
+    const long long w = (long long)blockIdx.x * PULSE_WAVES + wave;      // the wave's voxel, or its entry of the point list
+    if (w >= (TRACE ? (long long)n_points : P.vox)) return;            // (whole waves: nothing below synchronises across waves)
+    long long v = w;
+    if constexpr (TRACE) {
+        v = points[w];
+        if (!OLX_IN(v, P.vox, 5)) return;
+    }
     const int f = blockIdx.y;
     float* re = lds[wave][0];
     float* im = lds[wave][1];
@@ -90,17 +110,25 @@ __global__ __launch_bounds__(64 * PULSE_WAVES) void field_pulse_k(const double4*
     umin = wave_min(umin); umax = wave_max(umax);
     const long long vf = (long long)f * P.vox + v;
     if (umin > umax) {                            // no driven element
-        if (lane == 0) { pmin_out[vf] = 0.f; if (pmax_out) pmax_out[vf] = 0.f; if (inten_out) inten_out[vf] = 0.f; }
+        if constexpr (!TRACE) {
+            if (lane == 0 && OLX_IN(vf, P.vox * P.n_foci, 6)) {
+                pmin_out[vf] = 0.f; if (pmax_out) pmax_out[vf] = 0.f; if (inten_out) inten_out[vf] = 0.f;
+                if constexpr (PII) pii_out[vf] = 0.f;
+            }
+        }
         return;
     }
     const double lo = fmax(floor((double)umin) - 2.0, 0.0);
     const double hi = fmin(ceil((double)umax + P.tdt) + 2.0, (double)P.n_t);          // exclusive
 
     float pmax = 0.f, pmin = 0.f;                 // (samples outside the window are 0: they bound both from the zero side)
+    float e2 = 0.f;                               // PII: the lane's sum of p^2 over its samples of all passes
+    float* const trace = pmin_out + ((long long)f * n_points + w) * P.n_t;       // TRACE: this (focus, point)'s row
     const int s0 = lane * PULSE_SEG;
 #pragma unroll
     for (int s = 0; s < PULSE_SEG; ++s) { re[s0 + s] = 0.f; im[s0 + s] = 0.f; }
     for (double base = lo; base < hi; base += PULSE_L) {
+        double kbeg = 1.0e300, kend = -1.0e300;   // TRACE: first arrival, last burst end (the fp64 integers; the same in every pass)
         wave_lds_sync();
         // 2a. scatter the element terms into the difference array of this pass
         for (int e = lane; e < P.n_el; e += 64) {
@@ -111,6 +139,7 @@ __global__ __launch_bounds__(64 * PULSE_WAVES) void field_pulse_k(const double4*
             const double d = fmax(sqrt(fma(dx, dx, fma(dy, dy, dz * dz))), P.dmin);
             const double q = d * P.inv_cdt;
             const double k0 = el.w + ceil(q), k1 = el.w + ceil(q + P.tdt);
+            if constexpr (TRACE) { kbeg = fmin(kbeg, k0); kend = fmax(kend, k1); }
             if (k0 >= base + PULSE_L || k1 <= base || k1 <= k0) continue;      // after this pass, or over before it: nothing here
             double cyc = P.f0dt * ((el.w - lo) + q);
             cyc -= floor(cyc);
@@ -152,21 +181,41 @@ __global__ __launch_bounds__(64 * PULSE_WAVES) void field_pulse_k(const double4*
         cyc -= floor(cyc);
         float er = __builtin_amdgcn_cosf((float)cyc), ei = __builtin_amdgcn_sinf((float)cyc);
         const int nvalid = (int)fmin(fmax(hi - kfirst, 0.0), (double)PULSE_SEG);
+        int sbeg = 0, send = nvalid;              // TRACE: the valid samples at which an element is or has been active
+        if constexpr (TRACE) {
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) { kbeg = fmin(kbeg, __shfl_xor(kbeg, o)); kend = fmax(kend, __shfl_xor(kend, o)); }
+            sbeg = (int)fmin(fmax(kbeg - kfirst, 0.0), (double)PULSE_SEG);
+            send = min(nvalid, (int)fmin(fmax(kend - kfirst, 0.0), (double)PULSE_SEG));
+        }
 #pragma unroll
         for (int s = 0; s < PULSE_SEG; ++s) {
             const float p = er * (cr + sr[s]) - ei * (ci + si[s]);
-            if (s < nvalid) { pmax = fmaxf(pmax, p); pmin = fminf(pmin, p); }
+            if constexpr (TRACE) {
+                if (s >= sbeg && s < send) {
+                    const long long kk = (long long)kfirst + s;
+                    if (OLX_IN(kk, P.n_t, 4)) trace[kk] = p;
+                }
+            } else if (s < nvalid) {
+                pmax = fmaxf(pmax, p); pmin = fminf(pmin, p);
+                if constexpr (PII) e2 = fmaf(p, p, e2);
+            }
             const float nr = er * P.rot_c - ei * P.rot_s;
             ei = fmaf(er, P.rot_s, ei * P.rot_c);
             er = nr;
         }
     }
+    if constexpr (TRACE) return;
     pmax = wave_max(pmax); pmin = wave_min(pmin);
+    if constexpr (PII) e2 = wave_sum(e2);
     if (lane == 0 && OLX_IN(vf, P.vox * P.n_foci, 2)) {
         const float pn = 0.f - pmin;          // (+0 where nothing arrived)
         pmin_out[vf] = pn;
         if (pmax_out) pmax_out[vf] = pmax;
         if (inten_out) inten_out[vf] = P.inten_scale * pn * pn;
+    }
+    if constexpr (PII) {
+        if (lane == 0 && OLX_IN(vf, P.vox * P.n_foci, 3)) pii_out[vf] = P.pii_scale * e2;
     }
 }
 
@@ -176,11 +225,29 @@ OLX_BOUNDS_READER(pulse)
 
 using namespace olx;
 
-void olx_launch_pulse(olx_ctx* c, float* pm) {
-    const PulseParams& P = c->pulse;
+static void launch_pulse_table(olx_ctx* c) {
     const int fn = c->n_el * c->plan_foci;
     hipLaunchKernelGGL(pulse_table_k, dim3((fn + 255) / 256), dim3(256), 0, c->stream, c->d_pos, c->d_area, c->d_delays, c->d_apod, c->n_el,
-                       c->plan_foci, c->pulse_dt, c->p0_pa * c->freq / c->c, c->d_ptab, c->d_pw);
-    hipLaunchKernelGGL(field_pulse_k, dim3((unsigned)((P.vox + PULSE_WAVES - 1) / PULSE_WAVES), c->plan_foci), dim3(64 * PULSE_WAVES), 0, c->stream,
-                       c->d_ptab, c->d_pw, P, pm, (c->flags & OLX_OUT_PMAX) ? c->d_pmax : nullptr, (c->flags & OLX_OUT_INTENSITY) ? c->d_inten : nullptr);
+                       c->plan_foci, c->pulse_plan_dt, c->p0_pa * c->freq / c->c, c->d_ptab, c->d_pw);      // (the dt of the plan, not of a later olx_field_pulse)
+}
+
+void olx_launch_pulse(olx_ctx* c, float* pm) {
+    const PulseParams& P = c->pulse;
+    launch_pulse_table(c);
+    const dim3 grid((unsigned)((P.vox + PULSE_WAVES - 1) / PULSE_WAVES), c->plan_foci);
+    float* const px = (c->flags & OLX_OUT_PMAX) ? (float*)c->d_pmax : nullptr;
+    float* const it = (c->flags & OLX_OUT_INTENSITY) ? (float*)c->d_inten : nullptr;
+    if (c->flags & OLX_OUT_PII)
+        hipLaunchKernelGGL((field_pulse_k<true, false>), grid, dim3(64 * PULSE_WAVES), 0, c->stream, c->d_ptab, c->d_pw, P, pm, px, it, (float*)c->d_pii,
+                           (const long long*)nullptr, 0);
+    else
+        hipLaunchKernelGGL((field_pulse_k<false, false>), grid, dim3(64 * PULSE_WAVES), 0, c->stream, c->d_ptab, c->d_pw, P, pm, px, it, (float*)nullptr,
+                           (const long long*)nullptr, 0);
+}
+
+void olx_launch_pulse_trace(olx_ctx* c, int n_points) {
+    launch_pulse_table(c);      // (the caller has zeroed c->d_ptrace on the stream)
+    hipLaunchKernelGGL((field_pulse_k<false, true>), dim3((unsigned)((n_points + PULSE_WAVES - 1) / PULSE_WAVES), c->plan_foci), dim3(64 * PULSE_WAVES), 0,
+                       c->stream, c->d_ptab, c->d_pw, c->pulse, (float*)c->d_ptrace, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                       (const long long*)c->d_ptrace_vox, n_points);
 }

@@ -1073,8 +1073,8 @@ static int pack_if_needed(olx_ctx* c) {
 // olx_field_plan of a pulsed model (olx_field_pulse, kernel 2p): whole grid, homogeneous medium, one launch of field_pulse_k
 static int plan_pulse(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_foci, double freq, double cs, double rho, double p0_pa,
                       unsigned flags) {
-    if (flags & ~(OLX_OUT_PMAG | OLX_OUT_INTENSITY | OLX_OUT_PMAX | OLX_FIELD_FP8_CORRECTION | OLX_FIELD_FP16_CORRECTION))
-        return fail(c, OLX_EINVAL, "olx_field_plan: a pulsed plan (olx_field_pulse) takes OLX_OUT_PMAG / OLX_OUT_INTENSITY / OLX_OUT_PMAX only "
+    if (flags & ~(OLX_OUT_PMAG | OLX_OUT_INTENSITY | OLX_OUT_PMAX | OLX_OUT_PII | OLX_FIELD_FP8_CORRECTION | OLX_FIELD_FP16_CORRECTION))
+        return fail(c, OLX_EINVAL, "olx_field_plan: a pulsed plan (olx_field_pulse) takes OLX_OUT_PMAG / OLX_OUT_INTENSITY / OLX_OUT_PMAX / OLX_OUT_PII only "
                     "(no complex output, no OLX_FIELD_DIRECTIVITY), flags 0x%x", flags);
     if (slab && !(slab->x_begin == 0 && slab->x_count == g->n[0]))
         return fail(c, OLX_EINVAL, "olx_field_plan: a pulsed plan (olx_field_pulse) covers the whole grid: no slab");
@@ -1091,6 +1091,7 @@ static int plan_pulse(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n
     const size_t fn = (size_t)n_foci * c->n_el;
     int rc = reserve_outputs(c, total, 1, (flags & OLX_OUT_INTENSITY) != 0, false, false);
     if (!rc && (flags & OLX_OUT_PMAX)) rc = c->d_pmax.reserve(c, total);
+    if (!rc && (flags & OLX_OUT_PII)) rc = c->d_pii.reserve(c, total);
     if (!rc) rc = c->d_ptab.reserve(c, fn);
     if (!rc) rc = c->d_pw.reserve(c, fn);
     if (rc) return rc;
@@ -1100,6 +1101,7 @@ static int plan_pulse(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n
     F.flags = (flags & 3u) | OLX_OUT_PMAG; F.inten_scale = (float)(1e-4 / (2.0 * rho * cs));
     PulseParams& P = c->pulse;
     const double dt = c->pulse_dt;
+    c->pulse_plan_dt = dt;
     P.n_el = c->n_el; P.n_foci = n_foci; P.n_t = c->pulse_nt; P.ny = g->n[1]; P.nz = g->n[2];
     P.ox = g->origin[0]; P.oy = g->origin[1]; P.oz = g->origin[2];
     P.hx = g->spacing[0]; P.hy = g->spacing[1]; P.hz = g->spacing[2];
@@ -1111,8 +1113,9 @@ static int plan_pulse(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n
     P.absorb = (float)c->absorb_np_m;
     P.rot_c = (float)std::cos(2.0 * M_PI * P.f0dt); P.rot_s = (float)std::sin(2.0 * M_PI * P.f0dt);
     P.inten_scale = F.inten_scale;
+    P.pii_scale = (float)(1e-4 * dt / (rho * cs));
     P.vox = vox;
-    c->pulsed = true; c->pmax_live = false; c->agg_pmax_valid = false;
+    c->pulsed = true; c->pmax_live = false; c->agg_pmax_valid = false; c->pii_live = false;
     char nm[128];
     snprintf(nm, sizeof nm, "field_pulse_k (pulsed: %d samples, %.4g samples per burst)", c->pulse_nt, P.tdt);
     c->variant = nm;
@@ -1136,6 +1139,7 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
     if (!(flags & (OLX_OUT_PMAG | OLX_OUT_INTENSITY | OLX_OUT_COMPLEX))) return fail(c, OLX_EINVAL, "olx_field_plan: no outputs selected");
     if (c->pulse_nt > 0) return plan_pulse(c, g, slab, n_foci, freq, cs, rho, p0_pa, flags);
     if (flags & OLX_OUT_PMAX) return fail(c, OLX_EINVAL, "olx_field_plan: OLX_OUT_PMAX needs a pulsed plan (olx_field_pulse)");
+    if (flags & OLX_OUT_PII) return fail(c, OLX_EINVAL, "olx_field_plan: OLX_OUT_PII needs a pulsed plan (olx_field_pulse)");
     if (flags & ~(OLX_OUT_PMAG | OLX_OUT_INTENSITY | OLX_OUT_COMPLEX | OLX_FIELD_FP8_CORRECTION | OLX_FIELD_FP16_CORRECTION | OLX_FIELD_DIRECTIVITY)) return fail(c, OLX_EINVAL, "olx_field_plan: unknown flag bits 0x%x", flags);
     if ((flags & OLX_FIELD_DIRECTIVITY) && c->h_xaxis.size() != 3 * (size_t)c->n_el)
         return fail(c, OLX_ESTATE, "olx_field_plan: OLX_FIELD_DIRECTIVITY needs olx_set_element_apertures");
@@ -1160,7 +1164,7 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->grid = *g; c->slab = s; c->plan_foci = n_foci; c->hetero = false;
-    c->pulsed = false; c->pmax_live = false; c->agg_pmax_valid = false;
+    c->pulsed = false; c->pmax_live = false; c->agg_pmax_valid = false; c->pii_live = false;
     c->agg_local = -1; c->agg_total = 0;   // aggregate over all planned foci unless olx_field_aggregate_counts says otherwise
     c->freq = freq; c->c = cs; c->rho = rho; c->p0_pa = p0_pa; c->flags = flags; c->plan_absorb = c->absorb_np_m;
     const long long vox = (long long)s.x_count * g->n[1] * g->n[2];
@@ -1287,13 +1291,14 @@ int olx_field_launch(olx_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
     if (c->pulsed) {     // kernel 2p: its own table from the steering, no variant packing
         if (c->flags & OLX_OUT_PMAX) c->pmax_live = false;
-        c->agg_pmax_valid = false;
+        c->agg_pmax_valid = false; c->pii_live = false;
         const bool prof = c->prof_on && (size_t)(2 * c->prof_n + 1) < c->prof_ev.size();
         if (prof) HIPCHK(c, hipEventRecord(c->prof_ev[2 * c->prof_n], c->stream));
         olx_launch_pulse(c, c->d_pmag[0]);
         HIPCHK(c, hipGetLastError());
         if (prof) { HIPCHK(c, hipEventRecord(c->prof_ev[2 * c->prof_n + 1], c->stream)); c->prof_n++; }
         c->pmax_live = (c->flags & OLX_OUT_PMAX) != 0;
+        c->pii_live = (c->flags & OLX_OUT_PII) != 0;
         c->cur = 0;
         return OLX_OK;
     }
@@ -1512,6 +1517,40 @@ int olx_field_fetch_pmax(olx_ctx* c, float* pmax_out) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return fetch_to_host(c, pmax_out, c->d_pmax, sizeof(float) * (size_t)c->fp.vox * c->plan_foci);
+}
+
+int olx_field_fetch_pii(olx_ctx* c, float* pii_out) {
+    if (!c) return OLX_EINVAL;
+    if (!pii_out) return fail(c, OLX_EINVAL, "olx_field_fetch_pii: null output");
+    if (!c->pii_live) return fail(c, OLX_ESTATE, "olx_field_fetch_pii: no pulse intensity integrals (a launched pulsed plan with OLX_OUT_PII)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return fetch_to_host(c, pii_out, c->d_pii, sizeof(float) * (size_t)c->fp.vox * c->plan_foci);
+}
+
+int olx_field_pulse_trace(olx_ctx* c, int n_points, const long long* voxels, float* trace_out) {
+    if (!c) return OLX_EINVAL;
+    if (!c->planned || c->uploaded || !c->pulsed) return fail(c, OLX_ESTATE, "olx_field_pulse_trace: needs a pulsed plan (olx_field_pulse, then olx_field_plan)");
+    if (c->n_foci != c->plan_foci) return fail(c, OLX_ESTATE, "olx_field_pulse_trace: steering table changed shape since plan");
+    if (n_points < 1 || !voxels || !trace_out) return fail(c, OLX_EINVAL, "olx_field_pulse_trace: n_points must be >= 1, voxels and trace_out not null");
+    for (int i = 0; i < n_points; ++i)
+        if (voxels[i] < 0 || voxels[i] >= c->pulse.vox)
+            return fail(c, OLX_EINVAL, "olx_field_pulse_trace: voxel %d = %lld outside the planned grid of %lld voxels", i, voxels[i], c->pulse.vox);
+    const double total_d = (double)c->plan_foci * n_points * c->pulse.n_t;
+    if (total_d > (double)OLX_PULSE_TRACE_MAX_SAMPLES)
+        return fail(c, OLX_EINVAL, "olx_field_pulse_trace: %g trace samples are more than OLX_PULSE_TRACE_MAX_SAMPLES (trace fewer points per call)", total_d);
+    const size_t total = (size_t)c->plan_foci * n_points * c->pulse.n_t;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int rc = c->d_ptrace_vox.reserve(c, n_points);
+    if (!rc) rc = c->d_ptrace.reserve(c, total);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpy(c->d_ptrace_vox, voxels, sizeof(long long) * n_points, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(c->d_ptrace, 0, sizeof(float) * total, c->stream));
+    olx_launch_pulse_trace(c, n_points);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // (a large fetch runs on streams of its own, not ordered after this one)
+    return fetch_to_host(c, trace_out, c->d_ptrace, sizeof(float) * total);
 }
 
 int olx_field(olx_ctx* c, const olx_grid* g, int n_foci, double freq, double cs, double rho, double p0_pa,
@@ -1754,7 +1793,7 @@ int olx_field_upload(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_
     c->grid = *g; c->slab = s; c->plan_foci = n_foci;
     c->agg_local = -1; c->agg_total = 0;   // like olx_field_plan: the counts of a former padded sweep do not describe these volumes
     c->hetero = false; c->marched = false;
-    c->pulsed = false; c->pmax_live = false; c->agg_pmax_valid = false;    // (an upload holds no p_max)
+    c->pulsed = false; c->pmax_live = false; c->agg_pmax_valid = false; c->pii_live = false;    // (an upload holds no p_max and no PII)
     c->fp.nx = s.x_count; c->fp.ny = g->n[1]; c->fp.nz = g->n[2]; c->fp.vox = vox;
     c->flags = OLX_OUT_PMAG | (intensity ? OLX_OUT_INTENSITY : 0u);
     c->cur = 0; c->nbuf = 1;

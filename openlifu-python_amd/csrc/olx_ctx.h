@@ -135,12 +135,16 @@ struct olx_ctx {
     std::vector<hipEvent_t> prof_ev; int prof_n = 0; bool prof_on = false;
     // pulsed model (kernel 2p): the setting of olx_field_pulse for the plans that follow, and what the current plan holds
     double pulse_cycles = 0, pulse_dt = 0; int pulse_nt = 0;   // n_t = 0: continuous wave
+    double pulse_plan_dt = 0;                  // dt the current pulsed plan was built with (pulse holds everything else of it)
     bool pulsed = false;                       // the current plan is pulsed: d_pmag holds p_min
     bool pmax_live = false;                    // d_pmax holds the launched (and possibly scaled) p_max volumes
     bool agg_pmax_valid = false;               // d_agg_pmax holds max_f p_max_f of them
     PulseParams pulse{};
     DevBuf<float> d_pmax, d_agg_pmax;
     DevBuf<double4> d_ptab; DevBuf<float> d_pw;
+    bool pii_live = false;                     // d_pii holds the pulse intensity integrals of the last launch (OLX_OUT_PII; never scaled)
+    DevBuf<float> d_pii;                       // [F * voxels], allocated only for a plan with OLX_OUT_PII
+    DevBuf<long long> d_ptrace_vox; DevBuf<float> d_ptrace;   // olx_field_pulse_trace: the voxel list and [F][n_points][n_t] samples
     // thermal model (kernel 3, olx_thermal_*): buffers of their own, apart from the field / aggregate volumes
     bool th_planned = false, th_uniform = false; ThermalParams th{};
     double th_rate = 0;                        // max_v (sum_faces K + W) / (rho Cp)_v [1/s]: the FTCS bound is dt <= 1 / th_rate

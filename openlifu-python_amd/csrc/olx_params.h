@@ -153,6 +153,7 @@ struct PulseParams {
     float absorb;                   // uniform absorption [Np/m]; 0 = lossless
     float rot_c, rot_s;             // cos, sin (2 pi f0 dt)
     float inten_scale;              // 1e-4 / (2 rho c)
+    float pii_scale;                // 1e-4 dt / (rho c): sum_k p^2 -> pulse intensity integral [J/cm^2]
     long long vox;
 };
 

@@ -21,6 +21,7 @@ APOD_UNIFORM, APOD_MAXANGLE, APOD_PIECEWISE = 0, 1, 2
 COMP_MODES = {"equalize": 0, "matched": 1}   # OLX_COMP_*
 OUT_PMAG, OUT_INTENSITY, OUT_COMPLEX = 1, 2, 4
 OUT_PMAX = 64             # pulsed plans only (olx_field_pulse): also keep p_max; the OUT_PMAG slot then holds p_min
+OUT_PII = 128             # pulsed plans only: also keep the pulse intensity integral [J/cm^2] (never scaled on the device)
 MEDIUM_MODELS = {"auto": 0, "sampled": 1, "marched": 2}   # OLX_MEDIUM_*
 FIELD_DIRECTIVITY = 16     # opt-in plan flag: far-field piston directivity (needs set_element_apertures; exact per-pair kernel)
 FIELD_FP8_CORRECTION = 8   # (source compatibility: asks for what is the default since ABI v2)
@@ -39,7 +40,7 @@ SYMBOLS = [
     "olx_aggregate_fetch", "olx_field_aggregate_device", "olx_field_analysis_peaks", "olx_field_aggregate_counts", "olx_rccl_path", "olx_bf_time", "olx_field_fetch_all", "olx_field_medium_layering", "olx_field_medium_model", "olx_set_element_apertures",
     "olx_solution_analyze", "olx_scan_time", "olx_comm_export", "olx_comm_import", "olx_comm_transport",
     "olx_field_scale_aggregate", "olx_field_absorption", "olx_comm_ranks_seen",
-    "olx_field_pulse", "olx_field_fetch_pmax", "olx_aggregate_fetch_pmax",
+    "olx_field_pulse", "olx_field_fetch_pmax", "olx_aggregate_fetch_pmax", "olx_field_fetch_pii", "olx_field_pulse_trace",
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
     "olx_bf_set_medium", "olx_bf_solve_medium",
     "olx_bf_set_attenuation", "olx_bf_solve_compensated",
@@ -137,6 +138,8 @@ def load(require_gpu: bool = True):
         lib.olx_field_pulse.argtypes = [vp, c_double, c_double, c_int]
         lib.olx_field_fetch_pmax.argtypes = [vp, fp]
         lib.olx_aggregate_fetch_pmax.argtypes = [vp, fp]
+        lib.olx_field_fetch_pii.argtypes = [vp, fp]
+        lib.olx_field_pulse_trace.argtypes = [vp, c_int, POINTER(ctypes.c_longlong), fp]
         lib.olx_thermal_plan.argtypes = [vp, POINTER(OlxGrid), fp, fp, fp, fp, c_double, c_double, c_double, c_double, c_double, dp]
         lib.olx_thermal_schedule.argtypes = [vp, c_int, POINTER(c_int), POINTER(c_int), dp, c_int, POINTER(ctypes.c_longlong)]
         lib.olx_thermal_source.argtypes = [vp, c_int, fp]
@@ -194,6 +197,8 @@ class Context:
         self._vox = 0
         self._flags = 0
         self._shape = None
+        self._pulse_nt = 0      # n_t of the last field_pulse (0: continuous wave) ...
+        self._plan_nt = 0       # ... and of the current plan
         self.nranks = 1
 
     # -- plumbing
@@ -368,7 +373,8 @@ class Context:
         self._shape = (nx, int(n[1]), int(n[2]))
         self._grid_shape = (int(n[0]), int(n[1]), int(n[2]))
         self._vox = nx * int(n[1]) * int(n[2])
-        self._flags = (int(flags) | OUT_PMAG) & (7 | OUT_PMAX)
+        self._flags = (int(flags) | OUT_PMAG) & (7 | OUT_PMAX | OUT_PII)
+        self._plan_nt = self._pulse_nt     # samples of a pulsed plan's time axis (0: continuous wave)
         self._plan_foci = F
 
     def field_set_medium(self, sound_speed=None, attenuation=None, density=None, alpha_power=0.9, planes_per_layer=1, model="auto"):
@@ -414,6 +420,9 @@ class Context:
         if "pmax" in want:      # pulsed plans with OUT_PMAX: the peak positive pressure
             out["pmax"] = np.empty(shape, dtype=np.float32)
             self._chk(self._lib.olx_field_fetch_pmax(self._h, _fptr(out["pmax"])))
+        if "pii" in want:       # pulsed plans with OUT_PII: the pulse intensity integral [J/cm^2]
+            out["pii"] = np.empty(shape, dtype=np.float32)
+            self._chk(self._lib.olx_field_fetch_pii(self._h, _fptr(out["pii"])))
         return out
 
     def bf_time(self, iters: int = 20) -> np.ndarray:
@@ -444,6 +453,7 @@ class Context:
         self._shape = tuple(int(v) for v in n)
         self._vox = int(np.prod(self._shape))
         self._plan_foci = int(pmag.shape[0])
+        self._plan_nt = 0
         self._flags = OUT_PMAG | (OUT_INTENSITY if it is not None else 0)
 
     def field_time(self, iters: int) -> np.ndarray:
@@ -507,6 +517,15 @@ class Context:
         """Pulsed (tone-burst) model for the plans that follow: ``cycles`` cycles sampled at ``dt`` [s] over ``n_t`` samples;
         ``n_t = 0`` = continuous wave (the default).  A pulsed plan's OUT_PMAG slot holds p_min, OUT_PMAX adds p_max."""
         self._chk(self._lib.olx_field_pulse(self._h, float(cycles), float(dt), int(n_t)))
+        self._pulse_nt = int(n_t)
+
+    def field_pulse_trace(self, voxels) -> np.ndarray:
+        """Waveforms p(t_k) [Pa] of the current pulsed plan and steering at ``voxels`` (linear C-order indices of the planned grid)
+        -> float32 [F, n_points, n_t]; exact zeros before the first arrival and after the last burst end."""
+        vox = np.ascontiguousarray(voxels, dtype=np.int64).ravel()
+        out = np.empty((self._plan_foci, vox.size, self._plan_nt), dtype=np.float32)
+        self._chk(self._lib.olx_field_pulse_trace(self._h, int(vox.size), vox.ctypes.data_as(POINTER(ctypes.c_longlong)), _fptr(out)))
+        return out
 
     # ---- thermal model (kernel 3) ------------------------------------------------------------------------------------------
     def thermal_plan(self, origin_m, spacing_m, n, density, specific_heat, conductivity, absorption, perfusion=0.0) -> float:

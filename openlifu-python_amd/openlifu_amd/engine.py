@@ -295,7 +295,7 @@ class Engine:
     # ---- kernel 2 -----------------------------------------------------------------------------
     def field(self, arr, delays, apod, origin_m, spacing_m, n, freq, c, rho, p0_pa,
               want=("pmag", "intensity"), slab=None, steering_resident=False, medium=None, fp8_correction=None,
-              lazy=False, directivity=False, absorption=0.0, pulse=None):
+              lazy=False, directivity=False, absorption=0.0, pulse=None, trace_voxels=None):
         """Pressure field for F foci -> dict of float32 arrays [F, nx, ny, nz] (fresh, writable,
         caller-owned).  ``steering_resident`` reuses the table the last ``beamform`` left on the
         device instead of uploading ``delays`` / ``apod``.  ``fp8_correction=False`` opts OUT of the e4m3
@@ -305,7 +305,11 @@ class Engine:
         per-pair kernel; homogeneous media).  ``absorption`` [Np/m] > 0: uniform absorbing medium, every term carries exp(-a d)
         (olx_field_absorption).  ``lazy=True`` returns a ``DeviceResult`` instead: the volumes
         stay in HBM until somebody reads them.  ``pulse = (cycles, dt, t_end, cfl)`` selects the pulsed model (olx_field_pulse, time axis by
-        ``pulse_time_axis``): "pmag" then holds p_min and the result carries p_max under "pmax"."""
+        ``pulse_time_axis``): "pmag" then holds p_min and the result carries p_max under "pmax"; "pii" in ``want`` adds the pulse
+        intensity integral [J/cm^2] (OLX_OUT_PII; not for lazy results), ``trace_voxels`` (linear voxel indices) adds the waveforms
+        p(t_k) there under "trace" [F, P, n_t] (olx_field_pulse_trace)."""
+        if pulse is None and ("pii" in want or trace_voxels is not None):
+            raise ValueError('the pulse intensity integral ("pii") and the waveform traces need the pulsed field model')
         if pulse is not None:
             if medium is not None:
                 raise NotImplementedError("pulsed field model: heterogeneous media are not implemented (homogeneous media, with or without uniform absorption, only)")
@@ -315,6 +319,8 @@ class Engine:
                 raise NotImplementedError("pulsed field model: the multi-GPU slab / shard paths are not implemented (whole grid on one GPU only)")
             if "complex" in want:
                 raise ValueError("pulsed field model: there is no complex output (the field is a peak over time)")
+            if ("pii" in want or trace_voxels is not None) and lazy:
+                raise ValueError("pulsed field model: the pulse intensity integral and the traces are not part of a lazy result (the Solution does not carry them)")
             cycles, dt, t_end, cfl = pulse
             dt, n_t = pulse_time_axis(spacing_m, n, dt, t_end, cfl)
             want = tuple(want) + ("pmax",)
@@ -339,6 +345,8 @@ class Engine:
             self.ctx.field_pulse(cycles, dt, n_t)
             self._pulsed = True
             flags |= nat.OUT_PMAX
+            if "pii" in want:
+                flags |= nat.OUT_PII
         elif getattr(self, "_pulsed", False):
             self.ctx.field_pulse(0.0, 0.0, 0)       # back to continuous wave
             self._pulsed = False
@@ -360,7 +368,10 @@ class Engine:
         if "complex" in want:
             outs = [self.ctx.field_fetch(f, want=want) for f in range(self.ctx.n_foci)]
             return {k: np.stack([o[k] for o in outs], axis=0) for k in outs[0]}
-        return self.ctx.field_fetch_all(want=want)
+        out = self.ctx.field_fetch_all(want=want)
+        if trace_voxels is not None:
+            out["trace"] = self.ctx.field_pulse_trace(trace_voxels)
+        return out
 
     # ---- kernel 3 -----------------------------------------------------------------------------
     def thermal(self, origin_m, spacing_m, n, medium, perfusion, schedule, n_foci, dt, baseline, intensity=None, points=None):

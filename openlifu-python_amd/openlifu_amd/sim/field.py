@@ -11,7 +11,10 @@ like ``directivity``):
   * ``"pulsed"``: the time-domain Rayleigh sum of ``cycles``-cycle tone bursts with the delays truncated
     to whole steps of ``dt``, sampled at k dt up to ``t_end``: peak positive / peak negative pressure
     (HIP kernel 2p; definition DESIGN.md section 2, time axis ``pulse_time_axis``).  Homogeneous media
-    only; directivity, impulse responses and the multi-GPU paths raise NotImplementedError.
+    only; directivity, impulse responses and the multi-GPU paths raise NotImplementedError.  Two opt-in outputs of its time axis:
+    ``pulse_intensity_integral=True`` adds PII = 1e-4 dt / (rho c) sum_k p(t_k)^2 [J/cm^2] (PII / (cycles / freq) is the pulse-average
+    intensity; ``run_thermal_simulation(pulse_energy=...)`` heats with it), ``record_points`` [P, 3] in the units of ``params.coords``
+    adds the waveforms p(t_k) at the nearest voxels to the raw dict ("p_trace" [P, n_t], "t" = k dt, "trace_voxels").
 ``bli_tolerance/upsampling_rate`` are accepted and ignored; ``gpu`` is accepted and ignored -- there is
 no CPU path and a missing MI355X raises.
 ``ref_values_only=True`` simulates the homogeneous reference medium whatever ``params`` holds, as sim/kwave_if.py:49-56 does.
@@ -26,7 +29,8 @@ from ..engine import get_engine, grid_from_coords, pulse_time_axis  # noqa: F401
 from ..util import dataset as ds
 
 _ATTRS = {"p_max": {"units": "Pa", "long_name": "PPP"}, "p_min": {"units": "Pa", "long_name": "PNP"},
-          "intensity": {"units": "W/cm^2", "long_name": "Intensity"}}
+          "intensity": {"units": "W/cm^2", "long_name": "Intensity"},
+          "pulse_intensity_integral": {"units": "J/cm^2", "long_name": "Pulse intensity integral"}}
 
 
 ALPHA_POWER = 0.9      # the reference's kWaveMedium(alpha_power=0.9), sim/kwave_if.py:57
@@ -96,10 +100,11 @@ def _medium(params, freq, ref_values_only=False):
 
 def simulate_foci(arr, params, delays, apod, freq, amplitude, want=("pmag", "intensity"),
                   steering_resident=False, slab=None, fp8_correction=None, lazy=False, hetero_planes_per_layer=1,
-                  hetero_model="auto", directivity=False, ref_values_only=False, pulse=None):
+                  hetero_model="auto", directivity=False, ref_values_only=False, pulse=None, trace_voxels=None):
     """Batched core: F foci in one launch -> dict of float32 arrays [F, nx, ny, nz], or with ``lazy`` a
     ``DeviceResult`` whose volumes stay in HBM until read (``lazy_stack`` wraps it in the reference's schema).
-    ``pulse = (cycles, dt, t_end, cfl)``: the pulsed model -- "pmag" holds p_min, "pmax" p_max."""
+    ``pulse = (cycles, dt, t_end, cfl)``: the pulsed model -- "pmag" holds p_min, "pmax" p_max, "pii" in ``want`` adds the pulse intensity
+    integral and ``trace_voxels`` (linear voxel indices) the waveforms there under "trace" [F, P, n_t]."""
     if pulse is not None:
         check_pulsed_supported(arr, directivity)
     coords = params.coords
@@ -114,7 +119,8 @@ def simulate_foci(arr, params, delays, apod, freq, amplitude, want=("pmag", "int
     p0 = float(amplitude) * (1.0 if arr.sensitivity is None else float(arr.sensitivity))
     return get_engine().field(arr, delays, apod, origin, spacing, n, float(freq), c, rho, p0, want=want,
                               slab=slab, steering_resident=steering_resident, medium=medium,
-                              fp8_correction=fp8_correction, lazy=lazy, directivity=directivity, absorption=absorption, pulse=pulse)
+                              fp8_correction=fp8_correction, lazy=lazy, directivity=directivity, absorption=absorption, pulse=pulse,
+                              trace_voxels=trace_voxels)
 
 
 def lazy_stack(result, coords, dim="focal_point_index", internal=False):
@@ -150,17 +156,27 @@ def dataset_from_fields(fields, coords, focus=None):
 def run_simulation(arr, params, delays=None, apod=None, freq: float = 1e6, cycles: float = 20,
                    amplitude: float = 1, dt: float = 0, t_end: float = 0, cfl: float = 0.5,
                    bli_tolerance: float = 0.05, upsampling_rate: int = 5, gpu: bool = True,
-                   ref_values_only: bool = False, directivity: bool = False, field_model: str = "cw"):
+                   ref_values_only: bool = False, directivity: bool = False, field_model: str = "cw",
+                   pulse_intensity_integral: bool = False, record_points=None):
     n = arr.numelements()
     pulse = (float(cycles), float(dt), float(t_end), float(cfl)) if parse_field_model(field_model) == "pulsed" else None
+    if pulse is None and (pulse_intensity_integral or record_points is not None):
+        raise ValueError('pulse_intensity_integral and record_points need field_model="pulsed" (the continuous-wave model has no time axis)')
+    want, trace_voxels = ("pmag", "intensity"), None
+    if pulse_intensity_integral:
+        want += ("pii",)
+    if record_points is not None:
+        from .thermal import _trace_voxels      # (the same nearest-voxel rule as the thermal traces)
+        spacing, shape = grid_from_coords(params.coords)[1:]
+        trace_voxels, _ = _trace_voxels(record_points, params.coords, shape)
     delays = np.zeros(n) if delays is None else np.asarray(delays, dtype=np.float64)
     apod = np.ones(n) if apod is None else np.asarray(apod, dtype=np.float64)
     if delays.shape != (n,) or apod.shape != (n,):
         raise ValueError(f"delays and apod must have shape ({n},), got {delays.shape} and {apod.shape}")
     logging.info("Running simulation")
     # (directivity: this path's extension -- the far-field pattern of the rectangular elements k-Wave models as finite sources)
-    fields = simulate_foci(arr, params, delays[None, :], apod[None, :], freq, amplitude, directivity=directivity,
-                           ref_values_only=ref_values_only, pulse=pulse)
+    fields = simulate_foci(arr, params, delays[None, :], apod[None, :], freq, amplitude, want=want, directivity=directivity,
+                           ref_values_only=ref_values_only, pulse=pulse, trace_voxels=trace_voxels)
     logging.info("Simulation Complete")
     if ref_values_only:
         # The reference then SIMULATES the reference medium (get_medium, sim/kwave_if.py:49-56) but still forms the intensity with
@@ -174,4 +190,12 @@ def run_simulation(arr, params, delays=None, apod=None, freq: float = 1e6, cycle
             fields["intensity"] = (1e-4 * fields["pmag"].astype(np.float64) ** 2 / (2.0 * Z)[None]).astype(np.float32)
     dataset = dataset_from_fields(fields, params.coords, focus=0)
     raw = {"p_max": fields["pmax"][0] if "pmax" in fields else fields["pmag"][0], "p_min": -fields["pmag"][0], "backend": "openlifu_amd/hip-gfx950"}
+    if pulse_intensity_integral:
+        dims = list(params.coords.dims) if hasattr(params.coords, "dims") else list(params.coords.keys())
+        dataset["pulse_intensity_integral"] = ds.make_dataarray(fields["pii"][0], coords=params.coords, dims=dims, name="pulse_intensity_integral",
+                                                                attrs=_ATTRS["pulse_intensity_integral"])
+        raw["pulse_intensity_integral"] = fields["pii"][0]
+    if trace_voxels is not None:
+        step = pulse_time_axis(spacing, shape, pulse[1], pulse[2], pulse[3])[0]
+        raw["p_trace"], raw["t"], raw["trace_voxels"] = fields["trace"][0], np.arange(fields["trace"].shape[-1]) * step, trace_voxels
     return dataset, raw

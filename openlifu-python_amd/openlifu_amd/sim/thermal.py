@@ -172,13 +172,16 @@ def _trace_voxels(record_points, coords, n):
 
 
 def run_thermal_simulation(params, solution, dt: float = 0.0, t_end: float = 0.0, baseline_temperature: float = 37.0,
-                           perfusion: float = 0.0, record_points=None):
+                           perfusion: float = 0.0, record_points=None, pulse_energy=None):
     """Temperature rise of ``solution``'s sequence in the medium ``params`` -> (Dataset{temperature_max [degC],
     temperature_rise_max [K], CEM43 [min]} on ``params.coords``, raw{dt, n_steps, dt_max, t, traces, points_index}).
 
     ``dt = 0``: half the FTCS bound (a larger dt raises ValueError); ``t_end = 0``: the sequence duration (larger adds cool-down);
     ``perfusion`` W [W/m^3/K] is uniform; ``record_points`` [P, 3] in the coordinates' units are snapped to the nearest voxel and
-    traced (one value of T per step).  The intensity is the Solution's (scaled if scaled), read in place while the device still holds it."""
+    traced (one value of T per step).  The intensity is the Solution's (scaled if scaled), read in place while the device still holds it.
+    ``pulse_energy`` [F, nx, ny, nz] in J/cm^2 on ``params.coords`` -- the pulsed model's pulse intensity integral, times factor^2 when the
+    solution was scaled by ``factor`` -- replaces it: focus f then heats with ``pulse_energy[f] / min(duration, pulse_interval)``, so every
+    pulse deposits exactly that energy instead of the continuous-wave estimate I min(duration, pulse_interval)."""
     missing = [k for k in _MEDIUM_KEYS if k not in params]
     if missing:
         raise ValueError(f"thermal simulation: params lacks {missing}")
@@ -196,6 +199,17 @@ def run_thermal_simulation(params, solution, dt: float = 0.0, t_end: float = 0.0
         raise NotImplementedError(f"thermal simulation: multi-GPU / sharded solutions are not implemented "
                                   f"(the solution holds {n_vol} of its {F} focus volumes)")
     origin, spacing, n = grid_from_coords(coords)
+    source = None
+    if pulse_energy is not None:
+        energy = np.asarray(pulse_energy, dtype=np.float64)
+        if energy.shape != (F,) + tuple(int(v) for v in n):
+            raise ValueError(f"thermal simulation: pulse_energy must have shape {(F,) + tuple(int(v) for v in n)}, got {energy.shape}")
+        if not np.all(np.isfinite(energy)) or np.any(energy < 0):
+            raise ValueError("thermal simulation: pulse_energy must be finite and >= 0 everywhere")
+        on_time = min(float(solution.pulse.duration), float(solution.sequence.pulse_interval))     # (the pulse length of pulse_times)
+        if not on_time > 0:
+            raise ValueError("thermal simulation: pulse_energy needs a pulse of non-zero length")
+        source = (energy / on_time).astype(np.float32)
     rho, cp, kap = (_medium_value(params, k) for k in ("density", "specific_heat", "thermal_conductivity"))
     att = _medium_value(params, "attenuation")
     alpha = np.asarray(att, dtype=np.float64) * _np_per_m(1.0, solution.pulse.frequency)
@@ -206,14 +220,16 @@ def run_thermal_simulation(params, solution, dt: float = 0.0, t_end: float = 0.0
     eng = get_engine()
     if getattr(eng.ctx, "nranks", 1) > 1:
         raise NotImplementedError("thermal simulation: multi-GPU is not implemented (the context belongs to a communicator)")
-    resident = solution._device_is_current()
+    resident = source is None and solution._device_is_current()
+    if source is None and not resident:
+        source = np.asarray(inten.data)
     rise, cem, traces = eng.thermal(origin, spacing, n, (rho, cp, kap, alpha), float(perfusion), (row_ptr, focus, tau), F,
-                                    dt, float(baseline_temperature), None if resident else np.asarray(inten.data), pts)
+                                    dt, float(baseline_temperature), source, pts)
     dims = list(coords.dims) if hasattr(coords, "dims") else list(coords.keys())
     tmax = (float(baseline_temperature) + rise.astype(np.float64)).astype(np.float32)
     out = {name: ds.make_dataarray(vol, coords=coords, dims=dims, name=name, attrs=_ATTRS[name])
            for name, vol in (("temperature_max", tmax), ("temperature_rise_max", rise), ("CEM43", cem))}
     raw = {"dt": dt, "n_steps": n_steps, "dt_max": dt_max, "t": (np.arange(n_steps) + 1) * dt,
            "traces": float(baseline_temperature) + traces.astype(np.float64), "points_index": ijk,
-           "source": "resident" if resident else "uploaded", "backend": "openlifu_amd/hip-gfx950"}
+           "source": "pulse_energy" if pulse_energy is not None else "resident" if resident else "uploaded", "backend": "openlifu_amd/hip-gfx950"}
     return ds.make_dataset(out), raw

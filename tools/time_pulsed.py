@@ -1,12 +1,15 @@
 """Launch the pulsed field kernel (2p, field_pulse_k) on the shapes DESIGN.md section 5 reports, for a
 `rocprofv3 --kernel-trace --stats -- python tools/time_pulsed.py` run: 256-element 16 x 16 array (3 mm pitch), 20 cycles at
 400 kHz, default dt / t_end (pulse_time_axis), 0.25 mm grids of 128^3 and 256^3 with one focus, and 256^3 with the 8 foci
-of one shard.  Prints the per-launch time of each shape from HIP events (median of `--iters`)."""
+of one shard.  Prints the per-launch time of each shape from HIP events (median of `--iters`).  `--pii` plans with OUT_PII (the
+<PII> instantiation), `--trace N` also times one olx_field_pulse_trace of N points per shape (host clock around the synchronous call:
+table, memset, kernel and the copy out)."""
 from __future__ import annotations
 
 import argparse
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -26,6 +29,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--only", type=int, default=0, help="one shape only: the single-focus grid of this edge (counter runs)")
+    ap.add_argument("--pii", action="store_true", help="plan with OUT_PII: the pulse intensity integral volume")
+    ap.add_argument("--trace", type=int, default=0, help="also time olx_field_pulse_trace of this many points")
     args = ap.parse_args()
     pos, size, _ = bo.gen_matrix_array(16, 16, 3.0, 0.3)
     pos_m = pos * 1e-3
@@ -38,10 +43,19 @@ def main():
         origin = (-(n - 1) / 2 * h, -(n - 1) / 2 * h, 5e-3)
         dt, n_t = pulse_time_axis([h] * 3, (n, n, n))
         ctx.field_pulse(20, dt, n_t)
-        ctx.field_plan(origin, (h, h, h), (n, n, n), F0, C, RHO, P0, flags=nat.OUT_PMAG | nat.OUT_INTENSITY | nat.OUT_PMAX)
+        ctx.field_plan(origin, (h, h, h), (n, n, n), F0, C, RHO, P0, flags=nat.OUT_PMAG | nat.OUT_INTENSITY | nat.OUT_PMAX | (nat.OUT_PII if args.pii else 0))
         ms = ctx.field_time(args.iters)
-        print(f"{n}^3 x {nfoci} foci: {np.median(ms):.2f} ms per launch ({np.median(ms) / nfoci:.2f} ms per focus), n_t = {n_t}, "
-              f"{ctx.field_variant()}", flush=True)
+        print(f"{n}^3 x {nfoci} foci{' + PII' if args.pii else ''}: {np.median(ms):.2f} ms per launch ({np.median(ms) / nfoci:.2f} ms per focus), "
+              f"n_t = {n_t}, {ctx.field_variant()}", flush=True)
+        if args.trace:
+            vox = np.random.default_rng(7).integers(0, n ** 3, size=args.trace)
+            ctx.field_pulse_trace(vox)          # (warm-up: code object, buffers)
+            ts = []
+            for _ in range(max(args.iters, 3)):
+                t0 = time.perf_counter()
+                ctx.field_pulse_trace(vox)
+                ts.append(1e3 * (time.perf_counter() - t0))
+            print(f"{n}^3 x {nfoci} foci: trace of {args.trace} points {np.median(ts):.2f} ms per call (host clock, copy out included)", flush=True)
     ctx.field_pulse(0.0, 0.0, 0)
     ctx.sync()
 
