@@ -502,8 +502,9 @@ int olx_bf_quantize(olx_ctx* c, double bf_clk_hz, int width_bits, uint16_t* tick
 }
 
 // ---- kernel 2 -----------------------------------------------------------------------------
-// The pure planning code (lattice detection, K-slot map, column packing, block records, store jobs, focus inference) lives in
-// olx_plan.cpp: no HIP in it, so the CPU suite runs it under AddressSanitizer / UBSan (tools/plan_check.cpp, tests/test_plan_host.py).
+// The pure planning code (lattice detection, K-slot map, mirror permutations, column packing, block records, store jobs, focus inference, the
+// e4m3 rule, kernel 2f's block shape) lives in olx_plan.cpp: no HIP in it, so the CPU suite runs it under AddressSanitizer / UBSan
+// (tools/plan_check.cpp, tests/test_plan_host.py).
 using olxplan::build_slot_map;
 using olxplan::coset_tiles16;
 static void detect_lattice(olx_ctx* c, const double lo[3], const double hi[3], double dmin) {
@@ -530,6 +531,7 @@ static int configure_variant(olx_ctx* c) {
 }
 static int configure_variant_impl(olx_ctx* c) {
     const int n = c->n_el, F = c->plan_foci;
+    const char* const fv_env = getenv("OLX_FIELD_VARIANT");      // pins a kernel family / form for A/B runs
     auto steering_symmetric = [&](const std::vector<int>& perm) {
         if (c->h_delays.size() != (size_t)F * n || c->h_apod.size() != (size_t)F * n) return false;
         for (int f = 0; f < F; ++f)
@@ -587,15 +589,7 @@ static int configure_variant_impl(olx_ctx* c) {
         const double rev = c->freq / c->c, lambda = c->c / c->freq;
         const int n_img = c->mx * c->my;
         constexpr int MAXC = MFMA_COLS * MFMA_MAX_NT;
-        std::vector<int> perm((size_t)4 * n);
-        for (int m = 0; m < 4; ++m)
-            for (int e = 0; e < n; ++e) {
-                int o = e;
-                const bool fx = c->mx == 2 && (m & 1), fy = c->my == 2 && (c->mx == 2 ? (m >> 1) : (m & 1));
-                if (m < n_img && fx) o = c->h_px[o];
-                if (m < n_img && fy) o = c->h_py[o];
-                perm[(size_t)m * n + e] = o;
-            }
+        const std::vector<int> perm = olxplan::mirror_perms(n, n_img, c->mx == 2, c->my == 2, c->h_px.data(), c->h_py.data(), 4);
         olxplan::Steering SV;
         SV.n = n; SV.F = F; SV.n_img = n_img; SV.perm = perm.data(); SV.delays = c->h_delays.data(); SV.apod = c->h_apod.data(); SV.area = c->h_area.data(); SV.freq = c->freq;
         typedef olxplan::Col Col;
@@ -611,11 +605,8 @@ static int configure_variant_impl(olx_ctx* c) {
         // (include/olx.h, olx_field_plan): the foci are known (olx_bf_solve in the element frame, or external delays that infer_foci
         // recognises as geometric), every focus lies inside the planned SLAB and has N_eff = (sum w)^2 / sum w^2 >= 256; the plan flag
         // OLX_FIELD_FP16_CORRECTION opts out.  Decided here, before the columns are packed: it also decides the tile width below.
-        // Returns the first plane of the e4m3 products (0: every plane; a multiple of 16 = the plane blocks of kernels 2e / 2f / 2g: the blocks below keep
-        // three fp16 products), or -1: not eligible.  Conditions (i) and (ii) concern the whole planned slab; the near-field condition (iii) is asked
-        // of the planes from the cut on -- the error of a voxel belongs to the arithmetic its OWN plane block runs, and it is measured against the
-        // maximum of the whole volume, which holds the focal peak by (i).  The reference's default SimSetup (z from -4 mm: through the element plane)
-        // thereby loses the e4m3 products for its first plane block(s) only.
+        // The rule itself is olxplan::fp8_first_plane (first plane of the e4m3 products: 0 = every plane, a multiple of 16 = the plane blocks below keep
+        // three fp16 products, -1 = not eligible); the gates that need the context, and resolving the foci, stay here.
         auto fp8_eligible = [&]() -> int {
             if ((c->flags & (OLX_FIELD_FP16_CORRECTION | OLX_OUT_COMPLEX)) || c->modifier() || !c->lat.ok) return -1;
             bool ok = c->h_foci.size() == 3 * (size_t)F && c->foci_version == c->steer_version;
@@ -623,55 +614,9 @@ static int configure_variant_impl(olx_ctx* c) {
                 c->foci_version = c->steer_version;
                 ok = true;
             }
-            double need = 0;        // the largest  FP8_ERR_K wmax_f / (FP8_ERR_BOUND peak_f)  over the foci: sqrt(S2) must stay below 1 / need
-            for (int f = 0; ok && f < F; ++f) {
-                for (int a = 0; a < 3; ++a) {
-                    const int b0 = a == 0 ? c->slab.x_begin : 0, cnt = a == 0 ? c->slab.x_count : c->grid.n[a];
-                    const double lo = c->grid.origin[a] + (b0 - 0.5) * c->grid.spacing[a];
-                    const double hi = c->grid.origin[a] + (b0 + cnt - 0.5) * c->grid.spacing[a];
-                    if (!(c->h_foci[3 * (size_t)f + a] >= lo && c->h_foci[3 * (size_t)f + a] <= hi)) ok = false;
-                }
-                double sw1 = 0, sw2 = 0, wmx = 0, peak = 0;
-                const double* fo = &c->h_foci[3 * (size_t)f];
-                for (int e = 0; e < n; ++e) {
-                    const double w = std::fabs(c->h_apod[(size_t)f * n + e] * c->h_area[e]);
-                    sw1 += w; sw2 += w * w; wmx = std::max(wmx, w);
-                    const double ddx = fo[0] - c->h_pos[e], ddy = fo[1] - c->h_pos[(size_t)n + e], ddz = fo[2] - c->h_pos[2 * (size_t)n + e];
-                    peak += w / std::sqrt(std::max(ddx * ddx + ddy * ddy + ddz * ddz, 1e-30));
-                }
-                if (!(sw2 > 0 && sw1 * sw1 / sw2 >= 255.5) || !(peak > 0)) ok = false;
-                else need = std::max(need, olxplan::FP8_ERR_K * wmx / (olxplan::FP8_ERR_BOUND * peak));
-            }
             if (!ok) return -1;
-            // Voxels ON a symmetry plane of the array see its elements in pairs at exactly the same distance -- the same table entry, the same
-            // rounding error, and for a focus on that plane the same weight: the pair's errors add coherently instead of at random.  On the array's
-            // axis (both planes: grids with an odd voxel count centred on the array, e.g. the reference's default SimSetup) the emulation finds the
-            // largest normalised error 1.5 x that of a grid whose voxels straddle the planes (4.2e-5 against 2.7 - 3.0e-5; the device measured
-            // 9.2e-6 of the peak where the plain rule promised 7.5e-6): the rule's constant is raised by a quarter per plane that carries voxels.
-            {
-                int planes = 0;
-                for (int a = 0; a < 2; ++a) {
-                    const double ctr = (a == 0 ? c->lat.x0 + 0.5 * (c->lat.ax - 1) * c->lat.px : c->lat.y0 + 0.5 * (c->lat.ay - 1) * c->lat.py);
-                    const double idx = (ctr - c->grid.origin[a]) / c->grid.spacing[a];
-                    const int b0 = a == 0 ? c->slab.x_begin : 0, cnt = a == 0 ? c->slab.x_count : c->grid.n[a];
-                    if (std::fabs(idx - std::round(idx)) <= 1e-6 && idx >= b0 - 0.5 && idx <= b0 + cnt - 0.5) ++planes;
-                }
-                need *= 1.0 + 0.25 * planes;
-            }
-            // the near field: the error next to an element is relative to that element's own term (olx_plan.h, FP8_ERR_K): the bound on the worst
-            // voxel of the planes that run the e4m3 products must stay below FP8_ERR_BOUND of every focus' coherent peak.  S2 per first plane block:
-            // derived lazily, once per (element table, planned slab) -- olx_field_plan resets it
-            const int nzb = (c->grid.n[2] + COS_ZB - 1) / COS_ZB;
-            if ((int)c->nf_s2.size() != nzb) c->nf_s2.assign(nzb, -1.0);
-            for (int q = 0; q < nzb; ++q) {
-                if (c->nf_s2[q] < 0) {
-                    const int b0[3] = {c->slab.x_begin, 0, q * COS_ZB}, cnt[3] = {c->slab.x_count, c->grid.n[1], c->grid.n[2] - q * COS_ZB};
-                    c->nf_s2[q] = olxplan::nearfield_s2(n, c->h_pos.data(), c->grid.origin, c->grid.spacing, b0, cnt,
-                                                        0.5 * std::min({c->grid.spacing[0], c->grid.spacing[1], c->grid.spacing[2]}));
-                }
-                if (need * std::sqrt(c->nf_s2[q]) <= 1.0) return q * COS_ZB;
-            }
-            return -1;
+            return olxplan::fp8_first_plane(n, c->h_pos.data(), c->h_area.data(), c->h_apod.data(), F, c->h_foci.data(), c->grid.origin, c->grid.spacing,
+                                            c->grid.n, c->slab.x_begin, c->slab.x_count, c->lat, c->nf_s2);
         };
         // OLX_FP8_CORRECTION=0 (environment) opts out like the plan flag.  "1" FORCES the e4m3 products past the eligibility rule -- results may
         // then miss the 1e-5 gate, so only developer builds (OLX_DEV_PINS: the debug library, A/B timing builds) honour it; the product ignores it.
@@ -680,11 +625,8 @@ static int configure_variant_impl(olx_ctx* c) {
 #ifdef OLX_DEV_PINS
         if (f8env && strcmp(f8env, "0") != 0) fp8_cut = (lat_ok && !c->modifier()) ? 0 : -1;
 #endif
-        // A split launch is two launches and two operand sets: on BASELINE's array it pays from ~8 M (voxel, focus) pairs above the cut
-        // (121 x 121 x 81 planes x 8 foci: -13 %; the same grid with one focus +27 %, 61 x 61 x 33 x 8: +60 %; profiles/r06_time_grid.txt)
-        // -- and only while the cut leaves at least three quarters of the planes above it (cut at plane 48 of 256: -3 ... -12 %; at plane 80: +-0;
-        // profiles/r06_time_grid.txt); otherwise the whole launch keeps three fp16 products
-        if (fp8_cut > 0 && ((double)c->slab.x_count * c->grid.n[1] * (c->grid.n[2] - fp8_cut) * F < 8.0e6 || 4 * fp8_cut > c->grid.n[2])) fp8_cut = -1;
+        // (a split launch is two launches and two operand sets: where it does not pay, the whole launch keeps three fp16 products)
+        if (fp8_cut > 0 && !olxplan::fp8_split_pays(c->slab.x_count, c->grid.n[1], c->grid.n[2], F, fp8_cut)) fp8_cut = -1;
         const bool fp8_want = fp8_cut >= 0;
         c->fp8_kcut = fp8_want ? fp8_cut : 0;
         olxplan::Tiles tiles = pack(MAXC);
@@ -694,9 +636,8 @@ static int configure_variant_impl(olx_ctx* c) {
         // NT = 4 shape when the fp16 corrections run (0.82 against 2 x 0.45 ms) and is cut in two when the e4m3 corrections apply, which
         // the NT = 4 shape has no registers for (2 x 0.39 against 0.86 ms).  OLX_FIELD_VARIANT=lattice keeps the 32-column tiles for A/B runs.
         {
-            const char* fv = getenv("OLX_FIELD_VARIANT");
             const bool wide = tiles.size() == 1 && (int)tiles[0].size() > MFMA_COLS * 2;
-            if ((tiles.size() > 1 || (wide && fp8_want)) && c->use_lattice && !(c->flags & OLX_OUT_COMPLEX) && !fv && coset_fill(2) >= 0.6) {
+            if ((tiles.size() > 1 || (wide && fp8_want)) && c->use_lattice && !(c->flags & OLX_OUT_COMPLEX) && !fv_env && coset_fill(2) >= 0.6) {
                 tiles = pack(MFMA_COLS * 2);
             }
         }
@@ -712,7 +653,7 @@ static int configure_variant_impl(olx_ctx* c) {
         // grids get so small that most of a tile is padding -- then 2d's fixed 2 x 4 x 2 tiles are the better shape
         c->use_coset = false; c->use_toep = false; c->use_cosetp = false;
         if (c->use_lattice) {
-            const char* fv = getenv("OLX_FIELD_VARIANT");
+            const char* fv = fv_env;
             if (c->modifier() && fv && strcmp(fv, "lattice") && strcmp(fv, "lattice2d")) fv = nullptr;   // (the A/B forms carry no per-term factors)
             c->use_coset = !(c->flags & OLX_OUT_COMPLEX) && !(fv && !strcmp(fv, "lattice2d"));
             if (coset_fill(c->nt) > 0 && coset_fill(c->nt) < 0.6 && !(fv && !strcmp(fv, "lattice"))) c->use_coset = false;
@@ -791,48 +732,27 @@ static int configure_variant_impl(olx_ctx* c) {
             L.hz = P.hz; L.dmin2 = P.dmin2; L.flat_ez = P.flat_ez;
             L.g_scale = M.g_scale; L.out_scale = M.out_scale; L.inten_scale = P.inten_scale;
             L.vox = P.vox; L.flags = P.flags;
-            const char* fv = getenv("OLX_FIELD_VARIANT");
             const long long tiles16 = coset_tiles16(P.nx - L.x_lo, P.ny - L.y_lo, A.mx, A.my, c->nt);
             c->fp8corr = fp8_want && c->use_coset && cos_fp8(c->nt) && !c->modifier();      // (decided above, before the columns were packed)
             if (c->use_coset) {
                 CosetParams& Q = c->cp;
                 Q.nx = L.nx; Q.ny = L.ny; Q.nz = L.nz; Q.x_lo = L.x_lo; Q.y_lo = L.y_lo; Q.x_begin = L.x_begin; Q.mx = L.mx; Q.my = L.my;
-                // kernel 2f: 8 positions along x per row tile; arrays up to 17 elements wide take TWO row tiles per block (<= 16 positions: the tiles share
-                // tables and Toeplitz weights, k_toep.hip M2; wider arrays need the table's 32 columns for one tile: (8 - 1) + 24 = 31)
-                int saw_plan = std::min(A.ax, 24);       // element super-block width of kernel 2f (see below)
-#ifdef OLX_DEV_PINS
-                if (const char* e = getenv("OLX_EXP_TOEP_SAW")) { const int v = atoi(e); if (v >= 8 && v <= 24) saw_plan = std::min(A.ax, v); }   // (A/B)
-#endif
-                // (NM = 2 reads the second tile's fragments 8 columns on in the same 32-word rows: arrays up to 17 wide; wider arrays take THREE tiles on 48-word rows
-                // -- ToepShape<3>, k_toep.hip.h: one block per CU -- where that does not add padded position slots: BASELINE configs[3])
-                c->toep_nm = !c->use_toep ? 1 : (saw_plan + 15 <= 32 ? 2 : 1);
                 const int zb = COS_ZB;      // planes per block
                 // positions of a coset along x: two pitches apart for kernels 2e / 2g (their fragment reads are 8-byte aligned that way), ONE for kernel 2f
                 // (round 5: its 8-position row tiles then fill 7 - 8 of 8 slots on BASELINE's grids instead of 5 - 6, and its tables are shared by more rows)
                 Q.xs = c->use_toep ? 1 : 2;
+                // kernel 2f's block shape (one, two or three row tiles of 8 x positions, the element super-block columns and their K-steps): olxplan::toep_plan
+                olxplan::ToepPlan tp{};
+                c->toep_nm = 1;
                 int kyw = COS_KYW;
                 if (c->use_toep) {
-                    const int wxh = Q.nx - Q.x_lo, wyh = Q.ny - Q.y_lo;
-                    const int kxa_max = wxh > 0 ? (wxh - 1) / (Q.xs * Q.mx) + 1 : 0, kya_max = wyh > 0 ? (wyh - 1) / Q.my + 1 : 0;
-                    auto parts = [](int k, int w) { return std::max(1, (k + w - 1) / w); };
-                    if (c->toep_nm == 2) {      // the two-row-tile shape computes both tiles of every block: only where a part holds more than 8 positions along x
-                        if ((kxa_max + parts(kxa_max, 16) - 1) / parts(kxa_max, 16) <= 8) c->toep_nm = 1;
-                    } else if (!c->dir_lattice) {
-                        // position slots the matrix pipe works through, per coset and plane block: x parts x 8 NM, y parts x the wave groups that hold a position
-                        auto slots = [&](int nm, int kyw_, int nky) {
-                            const int px_ = parts(kxa_max, 8 * nm), py_ = parts(kya_max, kyw_);
-                            const int ky_part = (kya_max + py_ - 1) / py_;
-                            return (long long)px_ * 8 * nm * py_ * ((ky_part + nky - 1) / nky) * nky;
-                        };
-                        const char* pin = nullptr;
+                    int saw_pin = 0, nm_pin = 0;
 #ifdef OLX_DEV_PINS
-                        pin = getenv("OLX_EXP_TOEP_NM");      // (A/B: 1 or 3)
+                    if (const char* e = getenv("OLX_EXP_TOEP_SAW")) { const int v = atoi(e); if (v >= 8 && v <= 24) saw_pin = v; }   // (A/B)
+                    if (const char* e = getenv("OLX_EXP_TOEP_NM")) nm_pin = atoi(e) == 3 ? 3 : 1;      // (A/B: 1 or 3)
 #endif
-                        // (one block per CU in that shape: only where the launch still has a block for every CU)
-                        const long long nblk3 = (long long)Q.xs * Q.mx * Q.my * parts(kxa_max, 24) * parts(kya_max, ToepShape<3>::KYW) * ((Q.nz + zb - 1) / zb);
-                        const bool want3 = pin ? atoi(pin) == 3 : (kxa_max > 8 && nblk3 >= 256 && 20 * slots(3, ToepShape<3>::KYW, ToepShape<3>::NKY) <= 21 * slots(1, ToepShape<1>::KYW, ToepShape<1>::NKY));
-                        if (want3) { c->toep_nm = 3; kyw = ToepShape<3>::KYW; }
-                    }
+                    tp = olxplan::toep_plan(A.ax, Q.mx, Q.my, Q.xs, Q.nx - Q.x_lo, Q.ny - Q.y_lo, Q.nz, c->dir_lattice, saw_pin, nm_pin);
+                    c->toep_nm = tp.nm; kyw = tp.kyw;
                 }
                 const int kxw = c->use_toep ? 8 * c->toep_nm : cos_kxw(c->nt);
                 olxplan::coset_partition(Q, kxw, zb, kyw);
@@ -901,25 +821,11 @@ static int configure_variant_impl(olx_ctx* c) {
                 const std::string f8tag = !c->fp8corr ? "" : (c->fp8_kcut > 0 ? ",fp8corr from plane " + std::to_string(c->fp8_kcut) : ",fp8corr");
                 const long long n_dense = (long long)((double)(P.nx - L.x_lo) * (P.ny - L.y_lo) * P.nz * (double)n * total_cols * 4.0 / 8192.0 * corr_units);
                 if (c->use_toep) {   // kernel 2f operands: lattice cell -> element map, Toeplitz weight fragments, the column's store targets
-                    // element super-blocks of kernel 2f along x: the whole row for arrays up to 24 wide, else columns of 24 and the rest -- the table then has
-                    // (KXW - 1) + 24 = 31 <= 32 columns = two K-steps, and a last column of <= 8 elements fills K-step 1 only (ks_mask)
-                    c->toep_saw = saw_plan;
-                    c->toep_nsa = (A.ax + c->toep_saw - 1) / c->toep_saw;
+                    c->toep_saw = tp.saw;
+                    c->toep_nsa = tp.nsa;
                     if (c->toep_nsa > 16) return fail(c, OLX_ESTATE, "kernel 2f: more than 16 super-block columns");      // (ks_mask holds 2 bits per column)
-                    c->toep_ksmask = 0;
-                    int ksteps_total = 0;       // non-zero K-steps over the super-block columns
-                    int e4_units = 0;           // matrix units of the e4m3 instructions per element row and y position, over the columns
-                    for (int sa = 0; sa < c->toep_nsa; ++sa) {
-                        const int wdt = std::min(c->toep_saw, A.ax - sa * c->toep_saw);      // elements of this column
-                        // table columns with weights: ud' = xs kx - al + (saw - 1), al < wdt, kx < KXW  ->  [saw - wdt, saw - 1 + xs (KXW - 1)]
-                        const int lo_c = c->toep_saw - wdt, hi_c = c->toep_saw - 1 + Q.xs * (8 - 1);      // (of ONE row tile: the second tile of M2 reads the same fragments)
-                        unsigned m = 0;
-                        if (lo_c <= 15) m |= 1u;
-                        if (hi_c >= 16) m |= 2u;
-                        c->toep_ksmask |= m << (2 * sa);
-                        ksteps_total += (int)(m & 1u) + (int)(m >> 1);
-                        e4_units += (c->toep_nm == 3 && m == 2u) ? 1 : 2;      // (three row tiles: a column with K-step 1 only takes its element rows in pairs, k_toep.hip)
-                    }
+                    c->toep_ksmask = tp.ks_mask;
+                    const int ksteps_total = tp.ksteps_total, e4_units = tp.e4_units;
                     for (int q = 0; q < 4; ++q) c->toep_targets[q] = tiles[0][0].tgt[q];
                     { int rc = c->d_cell.reserve(c, A.cell.size()); if (rc) return rc; }
                     HIPCHK(c, hipMemcpy(c->d_cell, A.cell.data(), sizeof(int) * A.cell.size(), hipMemcpyHostToDevice));
@@ -977,15 +883,7 @@ static int configure_variant_impl(olx_ctx* c) {
                                     (c->directivity && c->absorb_np_m > 0) ? ", " : "", c->absorb_np_m > 0 ? "uniform absorption" : "");
         else snprintf(nmbuf, sizeof nmbuf, "field_accum_k<4,%s,%s>", c->flat ? "flat" : "general", c->clamp ? "clamp" : (c->near ? "near" : "noclamp"));
     } else {
-        std::vector<int> perm((size_t)nm * n);
-        for (int m = 0; m < nm; ++m)
-            for (int e = 0; e < n; ++e) {
-                int o = e;
-                const bool fx = c->dx == 2 && (m & 1), fy = c->dy == 2 && (c->dx == 2 ? (m >> 1) : (m & 1));
-                if (fx) o = c->h_px[o];
-                if (fy) o = c->h_py[o];
-                perm[(size_t)m * n + e] = o;
-            }
+        const std::vector<int> perm = olxplan::mirror_perms(n, nm, c->dx == 2, c->dy == 2, c->h_px.data(), c->h_py.data(), nm);
         int rc = upload_if_changed(c, c->d_perm, c->up_perm, perm);
         if (!rc) rc = c->d_tab.reserve(c, (size_t)((F + c->nf - 1) / c->nf) * n * (SH_HEAD + 2 * nm * c->nf));  // never trust the plan-time bound
         if (rc) return rc;
@@ -1217,7 +1115,7 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
     // coordinates of ~ 10 wavelengths lose 1e-6 wavelengths, i.e. up to 4e-6 of a term at a quarter wavelength and 1.5e-5 at the clamp distance of a 0.25 mm grid
     c->near = c->clamp || c->min_dist < 0.25 * cs / freq;
     detect_lattice(c, lo, hi, dmin);
-    c->nf_s2.clear();     // near-field sums of the e4m3 error bound: derived lazily by configure_variant (fp8_eligible)
+    c->nf_s2.clear();     // near-field sums of the e4m3 error bound: derived lazily by configure_variant (olxplan::fp8_first_plane)
     // ---- shared-geometry variant: mirror folds (element set symmetric about the grid centre planes)
     auto mirror_perm = [&](int axis, std::vector<int>& perm) -> bool {
         const double ctr = g->origin[axis] + 0.5 * (g->n[axis] - 1) * g->spacing[axis];

@@ -2,6 +2,8 @@
 // -fsanitize=address,undefined into the CPU-side checker (tools/plan_check.cpp).
 #include "olx_plan.h"
 
+#include "k_toep.hip.h"     // ToepShape: constants only, no device code
+
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -100,6 +102,19 @@ long long coset_tiles16(int wx, int wy, int mx, int my, int nt) {
                 }
         }
     return t16;
+}
+
+std::vector<int> mirror_perms(int n, int n_img, bool fold_x, bool fold_y, const int* px, const int* py, int rows) {
+    std::vector<int> perm((size_t)rows * n);
+    for (int m = 0; m < rows; ++m)
+        for (int e = 0; e < n; ++e) {
+            int o = e;
+            const bool fx = fold_x && (m & 1), fy = fold_y && (fold_x ? (m >> 1) : (m & 1));
+            if (m < n_img && fx) o = px[o];
+            if (m < n_img && fy) o = py[o];
+            perm[(size_t)m * n + e] = o;
+        }
+    return perm;
 }
 
 bool same_vector(const Steering& S, int f1, int m1, int f2, int m2) {
@@ -295,6 +310,111 @@ double nearfield_s2(int n, const double* pos, const double origin[3], const doub
         s2max = std::max(s2max, s2);
     }
     return s2max;
+}
+
+int fp8_first_plane(int n, const double* pos, const double* area, const double* apod, int F, const double* foci, const double origin[3],
+                    const double spacing[3], const int gn[3], int x_begin, int x_count, const Lattice& L, std::vector<double>& nf_s2) {
+    bool ok = true;
+    double need = 0;        // the largest  FP8_ERR_K wmax_f / (FP8_ERR_BOUND peak_f)  over the foci: sqrt(S2) must stay below 1 / need
+    for (int f = 0; ok && f < F; ++f) {
+        for (int a = 0; a < 3; ++a) {
+            const int b0 = a == 0 ? x_begin : 0, cnt = a == 0 ? x_count : gn[a];
+            const double lo = origin[a] + (b0 - 0.5) * spacing[a];
+            const double hi = origin[a] + (b0 + cnt - 0.5) * spacing[a];
+            if (!(foci[3 * (size_t)f + a] >= lo && foci[3 * (size_t)f + a] <= hi)) ok = false;
+        }
+        double sw1 = 0, sw2 = 0, wmx = 0, peak = 0;
+        const double* fo = &foci[3 * (size_t)f];
+        for (int e = 0; e < n; ++e) {
+            const double w = std::fabs(apod[(size_t)f * n + e] * area[e]);
+            sw1 += w; sw2 += w * w; wmx = std::max(wmx, w);
+            const double ddx = fo[0] - pos[e], ddy = fo[1] - pos[(size_t)n + e], ddz = fo[2] - pos[2 * (size_t)n + e];
+            peak += w / std::sqrt(std::max(ddx * ddx + ddy * ddy + ddz * ddz, 1e-30));
+        }
+        if (!(sw2 > 0 && sw1 * sw1 / sw2 >= 255.5) || !(peak > 0)) ok = false;
+        else need = std::max(need, FP8_ERR_K * wmx / (FP8_ERR_BOUND * peak));
+    }
+    if (!ok) return -1;
+    // Voxels ON a symmetry plane of the array see its elements in pairs at exactly the same distance -- the same table entry, the same
+    // rounding error, and for a focus on that plane the same weight: the pair's errors add coherently instead of at random.  On the array's
+    // axis (both planes: grids with an odd voxel count centred on the array, e.g. the reference's default SimSetup) the emulation finds the
+    // largest normalised error 1.5 x that of a grid whose voxels straddle the planes (4.2e-5 against 2.7 - 3.0e-5; the device measured
+    // 9.2e-6 of the peak where the plain rule promised 7.5e-6): the rule's constant is raised by a quarter per plane that carries voxels.
+    {
+        int planes = 0;
+        for (int a = 0; a < 2; ++a) {
+            const double ctr = (a == 0 ? L.x0 + 0.5 * (L.ax - 1) * L.px : L.y0 + 0.5 * (L.ay - 1) * L.py);
+            const double idx = (ctr - origin[a]) / spacing[a];
+            const int b0 = a == 0 ? x_begin : 0, cnt = a == 0 ? x_count : gn[a];
+            if (std::fabs(idx - std::round(idx)) <= 1e-6 && idx >= b0 - 0.5 && idx <= b0 + cnt - 0.5) ++planes;
+        }
+        need *= 1.0 + 0.25 * planes;
+    }
+    // the near field: the error next to an element is relative to that element's own term (olx_plan.h, FP8_ERR_K): the bound on the worst
+    // voxel of the planes that run the e4m3 products must stay below FP8_ERR_BOUND of every focus' coherent peak.  S2 per first plane block:
+    // derived lazily, once per (element table, planned slab) -- the caller resets the cache with the plan
+    const int nzb = (gn[2] + COS_ZB - 1) / COS_ZB;
+    if ((int)nf_s2.size() != nzb) nf_s2.assign(nzb, -1.0);
+    for (int q = 0; q < nzb; ++q) {
+        if (nf_s2[q] < 0) {
+            const int b0[3] = {x_begin, 0, q * COS_ZB}, cnt[3] = {x_count, gn[1], gn[2] - q * COS_ZB};
+            nf_s2[q] = nearfield_s2(n, pos, origin, spacing, b0, cnt, 0.5 * std::min({spacing[0], spacing[1], spacing[2]}));
+        }
+        if (need * std::sqrt(nf_s2[q]) <= 1.0) return q * COS_ZB;
+    }
+    return -1;
+}
+
+// A split launch is two launches and two operand sets: on BASELINE's array it pays from ~8 M (voxel, focus) pairs above the cut
+// (121 x 121 x 81 planes x 8 foci: -13 %; the same grid with one focus +27 %, 61 x 61 x 33 x 8: +60 %; profiles/r06_time_grid.txt)
+// -- and only while the cut leaves at least three quarters of the planes above it (cut at plane 48 of 256: -3 ... -12 %; at plane 80: +-0;
+// profiles/r06_time_grid.txt); otherwise the whole launch keeps three fp16 products
+bool fp8_split_pays(int x_count, int ny, int nz, int F, int cut) {
+    return !((double)x_count * ny * (nz - cut) * F < 8.0e6 || 4 * cut > nz);
+}
+
+ToepPlan toep_plan(int ax, int mx, int my, int xs, int wx, int wy, int nz, bool dir_lattice, int saw_pin, int nm_pin) {
+    ToepPlan T{};
+    // kernel 2f: 8 positions along x per row tile; arrays up to 17 elements wide take TWO row tiles per block (<= 16 positions: the tiles share
+    // tables and Toeplitz weights, k_toep.hip M2; wider arrays need the table's 32 columns for one tile: (8 - 1) + 24 = 31)
+    T.saw = std::min(ax, saw_pin ? saw_pin : 24);
+    // (NM = 2 reads the second tile's fragments 8 columns on in the same 32-word rows: arrays up to 17 wide; wider arrays take THREE tiles on 48-word rows
+    // -- ToepShape<3>, k_toep.hip.h: one block per CU -- where that does not add padded position slots: BASELINE configs[3])
+    T.nm = T.saw + 15 <= 32 ? 2 : 1;
+    T.kyw = COS_KYW;
+    const int zb = COS_ZB;      // planes per block
+    const int kxa_max = wx > 0 ? (wx - 1) / (xs * mx) + 1 : 0, kya_max = wy > 0 ? (wy - 1) / my + 1 : 0;
+    auto parts = [](int k, int w) { return std::max(1, (k + w - 1) / w); };
+    if (T.nm == 2) {      // the two-row-tile shape computes both tiles of every block: only where a part holds more than 8 positions along x
+        if ((kxa_max + parts(kxa_max, 16) - 1) / parts(kxa_max, 16) <= 8) T.nm = 1;
+    } else if (!dir_lattice) {
+        // position slots the matrix pipe works through, per coset and plane block: x parts x 8 NM, y parts x the wave groups that hold a position
+        auto slots = [&](int nm, int kyw_, int nky) {
+            const int px_ = parts(kxa_max, 8 * nm), py_ = parts(kya_max, kyw_);
+            const int ky_part = (kya_max + py_ - 1) / py_;
+            return (long long)px_ * 8 * nm * py_ * ((ky_part + nky - 1) / nky) * nky;
+        };
+        // (one block per CU in that shape: only where the launch still has a block for every CU)
+        const long long nblk3 = (long long)xs * mx * my * parts(kxa_max, 24) * parts(kya_max, ToepShape<3>::KYW) * ((nz + zb - 1) / zb);
+        const bool want3 = nm_pin ? nm_pin == 3 : (kxa_max > 8 && nblk3 >= 256 && 20 * slots(3, ToepShape<3>::KYW, ToepShape<3>::NKY) <= 21 * slots(1, ToepShape<1>::KYW, ToepShape<1>::NKY));
+        if (want3) { T.nm = 3; T.kyw = ToepShape<3>::KYW; }
+    }
+    // element super-blocks of kernel 2f along x: the whole row for arrays up to 24 wide, else columns of 24 and the rest -- the table then has
+    // (KXW - 1) + 24 = 31 <= 32 columns = two K-steps, and a last column of <= 8 elements fills K-step 1 only (ks_mask)
+    T.nsa = (ax + T.saw - 1) / T.saw;
+    if (T.nsa > 16) return T;      // (ks_mask holds 2 bits per column)
+    for (int sa = 0; sa < T.nsa; ++sa) {
+        const int wdt = std::min(T.saw, ax - sa * T.saw);      // elements of this column
+        // table columns with weights: ud' = xs kx - al + (saw - 1), al < wdt, kx < KXW  ->  [saw - wdt, saw - 1 + xs (KXW - 1)]
+        const int lo_c = T.saw - wdt, hi_c = T.saw - 1 + xs * (8 - 1);      // (of ONE row tile: the second tile of M2 reads the same fragments)
+        unsigned m = 0;
+        if (lo_c <= 15) m |= 1u;
+        if (hi_c >= 16) m |= 2u;
+        T.ks_mask |= m << (2 * sa);
+        T.ksteps_total += (int)(m & 1u) + (int)(m >> 1);
+        T.e4_units += (T.nm == 3 && m == 2u) ? 1 : 2;      // (three row tiles: a column with K-step 1 only takes its element rows in pairs, k_toep.hip)
+    }
+    return T;
 }
 
 }  // namespace olxplan

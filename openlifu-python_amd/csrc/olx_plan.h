@@ -1,9 +1,10 @@
-// Pure host planning of the lattice kernels (2d / 2e / 2f / 2g): lattice detection, K-slot map, column packing, store-target
-// balancing, block records, store-job lists, focus inference.  No HIP, no device memory, no context: plain C++17 in, plain vectors
-// out.  olx.hip (configure_variant) calls these and uploads what they return; the SAME translation unit is compiled with
+// Pure host planning of the lattice kernels (2d / 2e / 2f / 2g): lattice detection, K-slot map, mirror permutations, column packing,
+// store-target balancing, block records, store-job lists, focus inference, the e4m3 rule (fp8_first_plane, fp8_split_pays) and kernel 2f's
+// block shape (toep_plan).  No HIP, no device memory, no context: plain C++17 in, plain vectors out.  olx.hip (configure_variant) calls these and uploads what they return; the SAME translation unit is compiled with
 // g++ -fsanitize=address,undefined into the CPU-side checker tools/plan_check.cpp, which `pytest -m "not gpu"` drives over fuzz
 // shapes (tests/test_plan_host.py: every (focus, image) stored exactly once, every voxel covered exactly once, records inside the
-// grid, the kernels' magic divisions exact) -- the 500 lines of planning behind kernel 2g run without a GPU.
+// grid, the kernels' magic divisions exact, the e4m3 rule's known decisions and refusals, kernel 2f's known shapes) -- the planning behind
+// kernels 2f / 2g runs without a GPU.
 #pragma once
 #include <string>
 #include <vector>
@@ -35,6 +36,10 @@ void detect_lattice(Lattice& L, bool flat, int n, const double* pos, const doubl
 
 // MFMA row tiles (16 rows) one plane pair of kernel 2e needs over all cosets and parts
 long long coset_tiles16(int wx, int wy, int mx, int my, int nt);
+
+// Element permutations of the mirror images, [rows][n]: image m < n_img folds x (bit 0, where fold_x) and / or y (the next bit) through the
+// axis permutations px / py (read only where their axis is folded); rows from n_img on are the identity.
+std::vector<int> mirror_perms(int n, int n_img, bool fold_x, bool fold_y, const int* px, const int* py, int rows);
 
 // A column = one distinct steering vector W[sigma_m(e), f]; every (focus, mirror image) whose vector equals it is a store TARGET of
 // that column (code = focus * 4 + image), at most 4 per column.
@@ -80,12 +85,36 @@ bool infer_foci(bool flat, int n, int F, const double* pos /*[3][n]*/, const dou
 // (right side: the coherent focal peak, a lower bound of the volume maximum when the focus lies inside the planned volume) and keeps
 // three fp16 products otherwise -- for the whole launch, or (round 6) for the plane blocks below the first one from which the rule holds.
 // Voxels ON a symmetry plane of the array see element pairs at identical distances, whose errors add coherently: the caller raises
-// FP8_ERR_K by a quarter per symmetry plane that carries voxels (olx.hip, fp8_eligible; calibration in tools/emul_fp8_bound.py).
+// FP8_ERR_K by a quarter per symmetry plane that carries voxels (fp8_first_plane below; calibration in tools/emul_fp8_bound.py).
 constexpr double FP8_ERR_K = 3.75e-5;        // 6 sigma_1
 constexpr double FP8_ERR_BOUND = 7.5e-6;     // stated in include/olx.h (olx_field_plan); north_star's gate is 1e-5
 // max over the candidate voxels (the voxel of the planned slab nearest to each element: S2 peaks next to an element) of
 // sum_e 1 / max(d(v, e), dclamp)^2 [1/m^2].  pos = [3][n] (SoA) [m]; voxel i of axis a sits at origin[a] + i spacing[a], i in [begin[a], begin[a] + count[a]).
 // O(n * min(n, 1024)): evaluated once per (element table, planned slab) by the caller.
 double nearfield_s2(int n, const double* pos, const double origin[3], const double spacing[3], const int begin[3], const int count[3], double dclamp);
+
+// The rule itself.  Returns the first plane of the e4m3 products (0: every plane; a multiple of COS_ZB = the plane blocks of kernels 2e / 2f / 2g: the
+// blocks below keep three fp16 products), or -1: not eligible.  (i) every focus lies inside the planned SLAB [x_begin, x_begin + x_count) x ny x nz,
+// (ii) has N_eff = (sum w)^2 / sum w^2 >= 256, and (iii) the near-field condition above holds for the planes from the cut on -- the error of a voxel
+// belongs to the arithmetic its OWN plane block runs, and it is measured against the maximum of the whole volume, which holds the focal peak by (i).
+// pos = [3][n] (SoA) [m], area = [n], apod = [F][n], foci = [F][3] [m] (known: the caller resolves them); L: the array's lattice (x0, px, ax, y0, py, ay:
+// where its symmetry planes lie).  nf_s2 = [plane block q] nearfield_s2 of the planes >= COS_ZB q (< 0 = not derived yet): the caller's cache, filled
+// lazily here, valid for one (element table, planned slab).
+int fp8_first_plane(int n, const double* pos, const double* area, const double* apod, int F, const double* foci, const double origin[3],
+                    const double spacing[3], const int gn[3], int x_begin, int x_count, const Lattice& L, std::vector<double>& nf_s2);
+// whether a launch split at plane `cut` > 0 (fp16 x 3 below, e4m3 from it on) beats three fp16 products throughout
+bool fp8_split_pays(int x_count, int ny, int nz, int F, int cut);
+
+// ---- kernel 2f's block shape (k_toep.hip.h, ToepShape<NM>) ----
+struct ToepPlan {
+    int saw, nsa;            // element super-block width along x, super-block columns (nsa > 16: ks_mask cannot hold them -- the masks stay 0, the caller fails)
+    int nm, kyw;             // row tiles of 8 x positions per block, y positions per block
+    unsigned ks_mask;        // bit (2 sa + s): K-step s of column sa carries non-zero weights
+    int ksteps_total;        // non-zero K-steps over the columns
+    int e4_units;            // matrix units of the e4m3 instructions per element row and y position, over the columns
+};
+// ax = elements along x, mx / my = pitch [voxels], xs = pitches between two positions of a coset along x, wx x wy x nz = computed region [voxels];
+// dir_lattice: the DIR instantiations (no three-tile shape); saw_pin (8 .. 24) / nm_pin (1 | 3) override the choice for A/B runs, 0 = none
+ToepPlan toep_plan(int ax, int mx, int my, int xs, int wx, int wy, int nz, bool dir_lattice, int saw_pin = 0, int nm_pin = 0);
 
 }  // namespace olxplan

@@ -9,6 +9,11 @@
 //                respect the per-part limit, and the kernels' magic division pos / KY is exact for every position
 //   store jobs   the dense job lists name exactly the targets of their columns
 //   foci         geometric delays are recognised and reproduce the foci; scrambled delays are refused
+//   mirrors      every row of mirror_perms is a permutation and an involution, row 0 and the rows past the image count are the identity, the row of
+//                both folds is the composition of the single folds
+//   e4m3 rule    fp8_first_plane / fp8_split_pays: known decisions on BASELINE's array, one case per way the rule refuses, the result against a
+//                restatement that asks nearfield_s2 of every plane block without the cache
+//   kernel 2f    toep_plan: known shapes of the project; the columns cover the array, ks_mask has 1 - 2 bits per column and none beyond
 // Exit code 0 = all shapes passed; any violation prints the shape and exits 1 (sanitizer reports abort on their own).
 #include <algorithm>
 #include <cmath>
@@ -21,6 +26,7 @@
 #include <vector>
 
 #include "../openlifu-python_amd/csrc/olx_plan.h"
+#include "../openlifu-python_amd/csrc/k_toep.hip.h"
 
 using namespace olx;
 using namespace olxplan;
@@ -40,6 +46,34 @@ static bool ref_same_vector(const Steering& S, int f1, int m1, int f2, int m2) {
         if (std::fabs(turns - std::round(turns)) > 1e-6) return false;
     }
     return true;
+}
+
+// mirror_perms: [rows][n]; hpx / hpy = the checker's own axis mirrors of the element set
+static void check_mirror_perms(const std::vector<int>& perm, int n, int n_img, bool fold_x, bool fold_y, const std::vector<int>& hpx, const std::vector<int>& hpy, int rows) {
+    CHECK((int)perm.size() == rows * n, "mirror_perms: %zu entries for %d rows of %d", perm.size(), rows, n);
+    if ((int)perm.size() != rows * n) return;
+    auto at = [&](int m, int e) { return perm[(size_t)m * n + e]; };
+    for (int m = 0; m < rows; ++m) {
+        std::vector<int> seen(n, 0);
+        for (int e = 0; e < n; ++e) {
+            const int o = at(m, e);
+            CHECK(o >= 0 && o < n, "mirror_perms: row %d maps %d to %d", m, e, o);
+            if (o < 0 || o >= n) return;
+            seen[o]++;
+        }
+        for (int e = 0; e < n; ++e) {
+            CHECK(seen[e] == 1, "mirror_perms: row %d is no permutation (element %d hit %d times)", m, e, seen[e]);
+            CHECK(at(m, at(m, e)) == e, "mirror_perms: row %d is no involution at element %d", m, e);
+            if (m == 0 || m >= n_img) CHECK(at(m, e) == e, "mirror_perms: row %d (images %d) is not the identity", m, n_img);
+        }
+    }
+    // image bits: x fold = bit 0 where x is folded, y fold = the next bit
+    const int bx = fold_x ? 1 : 0, by = fold_y ? (fold_x ? 2 : 1) : 0;
+    for (int e = 0; e < n; ++e) {
+        if (bx && bx < std::min(n_img, rows)) CHECK(at(bx, e) == hpx[e], "mirror_perms: the x fold's row is not the x mirror");
+        if (by && by < std::min(n_img, rows)) CHECK(at(by, e) == hpy[e], "mirror_perms: the y fold's row is not the y mirror");
+        if (bx && by && 3 < std::min(n_img, rows)) CHECK(at(3, e) == at(by, at(bx, e)), "mirror_perms: the row of both folds is not the composition of the single folds");
+    }
 }
 
 struct Shape {
@@ -117,15 +151,11 @@ static void check_shape(const Shape& S, std::mt19937_64& rng, int nt_force) {
         return p;
     };
     const std::vector<int> hpx = mirror(0), hpy = mirror(1);
-    std::vector<int> perm((size_t)4 * n);
-    for (int m = 0; m < 4; ++m)
-        for (int e = 0; e < n; ++e) {
-            int o = e;
-            const bool fx = mxf == 2 && (m & 1), fy = myf == 2 && (mxf == 2 ? (m >> 1) : (m & 1));
-            if (m < n_img && fx) o = hpx[o];
-            if (m < n_img && fy) o = hpy[o];
-            perm[(size_t)m * n + e] = o;
-        }
+    const std::vector<int> perm = mirror_perms(n, n_img, mxf == 2, myf == 2, hpx.data(), hpy.data(), 4);
+    check_mirror_perms(perm, n, n_img, mxf == 2, myf == 2, hpx, hpy, 4);
+    // ... the [nm][n] form of kernel 2b (no rows past the images), and both folds whatever this shape folds (the array is symmetric about 0 either way)
+    check_mirror_perms(mirror_perms(n, n_img, mxf == 2, myf == 2, hpx.data(), hpy.data(), n_img), n, n_img, mxf == 2, myf == 2, hpx, hpy, n_img);
+    check_mirror_perms(mirror_perms(n, 4, true, true, hpx.data(), hpy.data(), 4), n, 4, true, true, hpx, hpy, 4);
     Steering SV; SV.n = n; SV.F = F; SV.n_img = n_img; SV.perm = perm.data(); SV.delays = delays.data(); SV.apod = apod.data(); SV.area = area.data(); SV.freq = freq;
     for (int maxc : {32, 16, 8}) {
         Tiles tiles = pack_columns(SV, maxc);
@@ -231,30 +261,118 @@ static void check_shape(const Shape& S, std::mt19937_64& rng, int nt_force) {
     }
 }
 
-// ---- e4m3 error rule (olx_plan.h FP8_ERR_K / FP8_ERR_BOUND, nearfield_s2): known decisions on BASELINE's 16 x 16 @ 3 mm array, uniform drive, focus (0, 0, 40) mm
-// (ratios from tools/emul_fp8_bound.py), and nearfield_s2 against the brute-force maximum over every voxel of the grid's first planes.
+// ---- e4m3 error rule (olx_plan.h: fp8_first_plane, fp8_split_pays, nearfield_s2) on BASELINE's 16 x 16 @ 3 mm array, uniform drive ----
+struct Fp8Case {
+    int na = 16;                               // na x na elements @ 3 mm
+    double h = 0.25e-3, z0 = 5e-3; int nxy = 256, nz = 256;
+    double shift = 0;                          // lateral shift of the grid [voxels]
+    int x_begin = 0, x_count = -1;             // slab (-1: the whole grid)
+    std::vector<double> foci;                  // [F][3]
+    double taper = 0;                          // apodization exp(-taper r^2 / r_max^2)
+};
+static std::vector<double> wheel8() {          // the 8-focus wheel: (0, 0, 40) mm and seven spokes of 5 mm
+    std::vector<double> f = {0, 0, 40e-3};
+    for (int i = 0; i < 7; ++i) { f.push_back(5e-3 * std::cos(2 * M_PI * i / 7)); f.push_back(5e-3 * std::sin(2 * M_PI * i / 7)); f.push_back(40e-3); }
+    return f;
+}
+struct Fp8Result { int cut, restated; double neff_min; int planes; };
+// fp8_first_plane on the case, twice (empty and filled cache), next to the checker's own restatement of the rule: every focus inside the slab,
+// N_eff >= 255.5, FP8_ERR_K (1 + planes / 4) wmax sqrt(S2 of the planes from the cut on) <= FP8_ERR_BOUND peak -- nearfield_s2 asked afresh per plane block
+static Fp8Result run_fp8_case(const Fp8Case& c, const char* what) {
+    const int na = c.na, n = na * na, F = (int)c.foci.size() / 3;
+    std::vector<double> pos(3 * (size_t)n, 0.0), area(n, 7.29e-6), apod((size_t)F * n);
+    const double rmax2 = 2 * std::pow(0.5 * (na - 1) * 3e-3, 2);
+    for (int a = 0; a < na; ++a) for (int b = 0; b < na; ++b) {
+        const int e = a * na + b;
+        pos[e] = (a - 0.5 * (na - 1)) * 3e-3; pos[(size_t)n + e] = (b - 0.5 * (na - 1)) * 3e-3;
+        for (int f = 0; f < F; ++f) apod[(size_t)f * n + e] = std::exp(-c.taper * (pos[e] * pos[e] + pos[(size_t)n + e] * pos[(size_t)n + e]) / rmax2);
+    }
+    const double origin[3] = {(-(c.nxy - 1) / 2.0 + c.shift) * c.h, (-(c.nxy - 1) / 2.0 + c.shift) * c.h, c.z0}, spacing[3] = {c.h, c.h, c.h};
+    const int gn[3] = {c.nxy, c.nxy, c.nz}, xb = c.x_begin, xc = c.x_count < 0 ? c.nxy : c.x_count;
+    const double lo[3] = {origin[0] + xb * c.h, origin[1], origin[2]}, hi[3] = {origin[0] + (xb + xc - 1) * c.h, origin[1] + (c.nxy - 1) * c.h, origin[2] + (c.nz - 1) * c.h};
+    Lattice L;
+    detect_lattice(L, true, n, pos.data(), spacing, lo, hi, 0.5 * c.h);
+    CHECK(L.ok && L.ax == na && L.ay == na, "fp8 rule (%s): lattice not recognised", what);
+    Fp8Result R{-1, -1, 1e300, 0};
+    if (!L.ok) return R;
+    std::vector<double> cache;
+    R.cut = fp8_first_plane(n, pos.data(), area.data(), apod.data(), F, c.foci.data(), origin, spacing, gn, xb, xc, L, cache);
+    const std::vector<double> filled = cache;
+    const int again = fp8_first_plane(n, pos.data(), area.data(), apod.data(), F, c.foci.data(), origin, spacing, gn, xb, xc, L, cache);
+    CHECK(again == R.cut && cache == filled, "fp8 rule (%s): plane %d with the filled cache, %d without", what, again, R.cut);
+    // the restatement
+    bool ok = true;
+    double worst = 0;      // max_f wmax_f / peak_f
+    for (int f = 0; f < F; ++f) {
+        const double* fo = &c.foci[3 * (size_t)f];
+        if (fo[0] < lo[0] - 0.5 * c.h || fo[0] > hi[0] + 0.5 * c.h || fo[1] < lo[1] - 0.5 * c.h || fo[1] > hi[1] + 0.5 * c.h || fo[2] < lo[2] - 0.5 * c.h || fo[2] > hi[2] + 0.5 * c.h) ok = false;
+        double s1 = 0, s2 = 0, wmax = 0, peak = 0;
+        for (int e = 0; e < n; ++e) {
+            const double w = apod[(size_t)f * n + e] * area[e];
+            s1 += w; s2 += w * w; wmax = std::max(wmax, w);
+            peak += w / std::sqrt(std::pow(fo[0] - pos[e], 2) + std::pow(fo[1] - pos[(size_t)n + e], 2) + fo[2] * fo[2]);
+        }
+        R.neff_min = std::min(R.neff_min, s1 * s1 / s2);
+        worst = std::max(worst, wmax / peak);
+    }
+    if (R.neff_min < 255.5) ok = false;
+    // the array is centred on 0: its symmetry planes are x = 0 and y = 0; a plane carries voxels when 0 is a voxel coordinate of the slab
+    for (int a = 0; a < 2; ++a) {
+        const double idx = -origin[a] / c.h;
+        const int b0 = a == 0 ? xb : 0, cnt = a == 0 ? xc : c.nxy;
+        if (std::fabs(idx - std::round(idx)) < 1e-6 && idx > b0 - 0.5 && idx < b0 + cnt - 0.5) ++R.planes;
+    }
+    if (ok)
+        for (int k = 0; k < c.nz && R.restated < 0; k += COS_ZB) {
+            const int b0[3] = {xb, 0, k}, cnt[3] = {xc, c.nxy, c.nz - k};
+            const double s2 = nearfield_s2(n, pos.data(), origin, spacing, b0, cnt, 0.5 * c.h);
+            if (k / COS_ZB < (int)filled.size() && filled[k / COS_ZB] >= 0) CHECK(filled[k / COS_ZB] == s2, "fp8 rule (%s): cached S2 of plane block %d differs from nearfield_s2", what, k / COS_ZB);
+            if (FP8_ERR_K * (1.0 + 0.25 * R.planes) * worst * std::sqrt(s2) <= FP8_ERR_BOUND) R.restated = k;
+        }
+    CHECK(R.cut == R.restated, "fp8 rule (%s): fp8_first_plane gives plane %d, the restated rule plane %d (N_eff %.1f, %d symmetry plane(s) with voxels)", what, R.cut, R.restated, R.neff_min, R.planes);
+    return R;
+}
+
+// Known decisions (the cut planes are what the rule computes; DESIGN 5.2 quotes them), one case per way the rule refuses, and nearfield_s2 against
+// the brute-force maximum over every voxel of the grid's first planes (ratios from tools/emul_fp8_bound.py).
 static void check_fp8_rule() {
     const int na = 16, n = na * na;
     std::vector<double> pos(3 * (size_t)n, 0.0);
     for (int a = 0; a < na; ++a) for (int b = 0; b < na; ++b) { pos[(size_t)a * na + b] = (a - 7.5) * 3e-3; pos[(size_t)n + a * na + b] = (b - 7.5) * 3e-3; }
     double peak = 0;
     for (int e = 0; e < n; ++e) peak += 1.0 / std::sqrt(pos[e] * pos[e] + pos[(size_t)n + e] * pos[(size_t)n + e] + 40e-3 * 40e-3);
-    struct G { double h, z0; int nxy, nz; bool admit; double ratio; } grids[] = {
-        {0.25e-3, 5e-3, 256, 256, true, 0.188},       // the headline grid
-        {0.5e-3, 5e-3, 128, 128, true, 0.188},        // configs[1]
-        {1e-3, -4e-3, 61, 65, false, 0.340},          // the reference's default SimSetup: through the element plane
-        {0.5e-3, -4e-3, 121, 129, false, 0.730},      // (odd counts: a voxel sits ON every element -- the clamp distance)
-        {0.25e-3, -4e-3, 241, 257, false, 1.403},
-        {0.25e-3, 0.25e-3, 256, 256, false, 0.61},    // one voxel above the element plane
-        {0.25e-3, 1e-3, 256, 256, false, 0.285},
+    // cut1 / cut8: first plane of the e4m3 products with the on-axis focus (0, 0, 40) mm / the 8-focus wheel; pays1 / pays8: fp8_split_pays at that cut
+    struct G { double h, z0; int nxy, nz; double ratio; int cut1, cut8; bool pays1, pays8; } grids[] = {
+        {0.25e-3, 5e-3, 256, 256, 0.188, 0, 0, true, true},             // the headline grid
+        {0.5e-3, 5e-3, 128, 128, 0.188, 0, 0, true, true},              // configs[1]
+        {1e-3, -4e-3, 61, 65, 0.340, 32, 32, false, false},             // the reference's default SimSetup: through the element plane
+        {0.5e-3, -4e-3, 121, 129, 0.730, 48, 48, false, false},          // (odd counts: a voxel sits ON every element -- the clamp distance -- and on both symmetry planes)
+        {0.25e-3, -4e-3, 241, 257, 1.403, 80, 80, false, false},
+        {0.25e-3, 0.25e-3, 256, 256, 0.61, 16, 16, true, true},      // one voxel above the element plane
+        {0.25e-3, 1e-3, 256, 256, 0.285, 16, 16, true, true},
+        {0.5e-3, 0.5e-3, 128, 128, 0.0, 16, 16, false, true},         // ... on a grid below 8 M (voxel, focus) pairs with one focus
     };
     for (const G& g : grids) {
         const double origin[3] = {-(g.nxy - 1) / 2.0 * g.h, -(g.nxy - 1) / 2.0 * g.h, g.z0}, spacing[3] = {g.h, g.h, g.h};
         const int b0[3] = {0, 0, 0}, cnt[3] = {g.nxy, g.nxy, g.nz};
         const double s2 = nearfield_s2(n, pos.data(), origin, spacing, b0, cnt, 0.5 * g.h);
         const double ratio = std::sqrt(s2) / peak;
-        CHECK(std::fabs(ratio - g.ratio) <= 0.03 * g.ratio + 0.005, "fp8 rule: ratio %.4f, expected %.3f (h %.2g z0 %.2g)", ratio, g.ratio, g.h, g.z0);
-        CHECK((FP8_ERR_K * ratio <= FP8_ERR_BOUND) == g.admit, "fp8 rule: h %.2g z0 %.2g admitted = %d, expected %d", g.h, g.z0, (int)(FP8_ERR_K * ratio <= FP8_ERR_BOUND), (int)g.admit);
+        if (g.ratio > 0) CHECK(std::fabs(ratio - g.ratio) <= 0.03 * g.ratio + 0.005, "fp8 rule: ratio %.4f, expected %.3f (h %.2g z0 %.2g)", ratio, g.ratio, g.h, g.z0);
+        // the rule itself: on-axis focus and the 8-focus wheel
+        Fp8Case c; c.h = g.h; c.z0 = g.z0; c.nxy = g.nxy; c.nz = g.nz;
+        for (int F : {1, 8}) {
+            c.foci = F == 1 ? std::vector<double>{0, 0, 40e-3} : wheel8();
+            const Fp8Result R = run_fp8_case(c, F == 1 ? "known grid, on-axis focus" : "known grid, 8-focus wheel");
+            const int want = F == 1 ? g.cut1 : g.cut8;
+            if (R.planes > 0 && want > 0) CHECK(R.cut == want, "fp8 rule, symmetry-plane factor: h %.2g z0 %.2g (voxels on %d symmetry planes), %d foci: first plane %d, expected %d", g.h, g.z0, R.planes, F, R.cut, want);
+            else CHECK(R.cut == want, "fp8 rule: h %.2g z0 %.2g, %d foci: first plane %d, expected %d", g.h, g.z0, F, R.cut, want);
+            if (R.cut > 0) {
+                CHECK(R.cut % COS_ZB == 0, "fp8 rule: cut %d is no multiple of the plane block", R.cut);
+                const bool pays = fp8_split_pays(g.nxy, g.nxy, g.nz, F, R.cut);
+                CHECK(pays == (F == 1 ? g.pays1 : g.pays8), "fp8 rule: h %.2g z0 %.2g, %d foci: a split at plane %d pays = %d, expected %d", g.h, g.z0, F, R.cut, (int)pays, (int)(F == 1 ? g.pays1 : g.pays8));
+            }
+        }
+        if (g.ratio <= 0) continue;
         // brute force over the three planes nearest to the elements (a quadrant: the array and the grid are symmetric)
         double brute = 0;
         int kn = (int)std::llround((0.0 - g.z0) / g.h); kn = std::max(0, std::min(kn, g.nz - 1));
@@ -271,10 +389,87 @@ static void check_fp8_rule() {
                 }
         CHECK(s2 <= brute * (1 + 1e-12) && s2 >= 0.97 * brute, "nearfield_s2 %.6g vs brute-force maximum %.6g (h %.2g z0 %.2g)", s2, brute, g.h, g.z0);
     }
+    // the split condition alone: 8 M (voxel, focus) pairs above the cut, and at least three quarters of the planes above it
+    CHECK(fp8_split_pays(121, 121, 129, 8, 32) && !fp8_split_pays(121, 121, 129, 1, 32) && !fp8_split_pays(61, 61, 65, 8, 32), "fp8 rule: split condition, pairs above the cut");
+    CHECK(fp8_split_pays(256, 256, 256, 8, 64) && !fp8_split_pays(256, 256, 256, 8, 80) && !fp8_split_pays(241, 241, 257, 8, 80), "fp8 rule: split condition, planes above the cut");
+    // ---- one case per way the rule refuses
+    {   // a focus half a voxel outside the slab along x: refused there, admitted in the slab that holds it
+        Fp8Case c; c.foci = {0.125e-3, 0, 40e-3};      // slab [0, 128) ends at x = 0 (its last voxel's upper face)
+        c.x_begin = 0; c.x_count = 128;
+        CHECK(run_fp8_case(c, "focus outside the slab").cut == -1, "fp8 rule, focus inside the slab: a focus half a voxel outside along x admitted");
+        c.x_begin = 128;
+        CHECK(run_fp8_case(c, "focus inside the slab").cut >= 0, "fp8 rule, focus inside the slab: the slab that holds the focus refused");
+    }
+    {   // 15 x 15 elements: N_eff = 225
+        Fp8Case c; c.na = 15; c.foci = {0, 0, 40e-3};
+        const Fp8Result R = run_fp8_case(c, "15 x 15 elements");
+        CHECK(R.cut == -1 && std::fabs(R.neff_min - 225.0) < 1e-6, "fp8 rule, N_eff threshold: 15 x 15 equally driven elements (N_eff %.1f < 255.5) admitted from plane %d", R.neff_min, R.cut);
+    }
+    {   // a strongly tapered apodization on 16 x 16
+        Fp8Case c; c.taper = 3.0; c.foci = {0, 0, 40e-3};
+        const Fp8Result R = run_fp8_case(c, "tapered apodization");
+        CHECK(R.cut == -1 && R.neff_min < 255.5, "fp8 rule, N_eff threshold: tapered drive (N_eff %.1f) admitted from plane %d", R.neff_min, R.cut);
+        c.taper = 1e-4;      // ... and a taper that leaves N_eff at 256 to within the threshold's margin is admitted
+        const Fp8Result R2 = run_fp8_case(c, "barely tapered apodization");
+        CHECK(R2.cut == 0 && R2.neff_min >= 255.5 && R2.neff_min < 256.0, "fp8 rule, N_eff threshold: barely tapered drive (N_eff %.3f) refused (%d)", R2.neff_min, R2.cut);
+    }
+    for (const G& g : grids) {   // the grids through the element plane shifted by half a voxel laterally: no voxel on a symmetry plane
+        if (!(g.z0 < 0)) continue;
+        Fp8Case c; c.h = g.h; c.z0 = g.z0; c.nxy = g.nxy; c.nz = g.nz; c.foci = {0, 0, 40e-3};
+        const Fp8Result ctr = run_fp8_case(c, "centred odd grid");
+        c.shift = 0.5;
+        const Fp8Result sh = run_fp8_case(c, "grid shifted by half a voxel");
+        CHECK(ctr.planes == 2 && sh.planes == 0 && sh.cut >= 0 && sh.cut <= ctr.cut, "fp8 rule, symmetry-plane factor: h %.2g: centred (%d planes with voxels) from plane %d, shifted (%d) from plane %d",
+              g.h, ctr.planes, ctr.cut, sh.planes, sh.cut);
+    }
     {   // a slab beside the array sees the clamped nearest voxel, not the element's own position
         const double origin[3] = {-31.875e-3, -31.875e-3, 5e-3}, spacing[3] = {0.25e-3, 0.25e-3, 0.25e-3};
         const int b0[3] = {192, 0, 0}, cnt[3] = {64, 256, 256}, whole0[3] = {0, 0, 0}, whole[3] = {256, 256, 256};
         CHECK(nearfield_s2(n, pos.data(), origin, spacing, b0, cnt, 0.125e-3) < nearfield_s2(n, pos.data(), origin, spacing, whole0, whole, 0.125e-3), "slab beside the centre must see a smaller sum");
+    }
+}
+
+// ---- kernel 2f's block shape (toep_plan): known shapes of the project and invariants over fuzzed widths
+static int popcount(unsigned v) { int c = 0; for (; v; v &= v - 1) ++c; return c; }
+static void check_toep_plan(std::mt19937_64& rng) {
+    auto ri = [&](int lo, int hi) { return (int)(lo + rng() % (unsigned long long)(hi - lo + 1)); };
+    // 16-wide arrays: one column of 16; two row tiles where a part holds more than 8 x positions (kx positions of a coset along x, cut into parts of <= 16)
+    for (int kx = 1; kx <= 40; ++kx) {
+        const ToepPlan T = toep_plan(16, 3, 3, 1, 3 * kx, 60, 64, false);
+        const int parts = std::max(1, (kx + 15) / 16), per_part = (kx + parts - 1) / parts;
+        CHECK(T.saw == 16 && T.nsa == 1 && T.nm == (per_part > 8 ? 2 : 1) && T.kyw == ToepShape<1>::KYW && T.ks_mask == 3u && T.ksteps_total == 2 && T.e4_units == 2,
+              "toep_plan: 16-wide array, %d x positions: saw %d nsa %d nm %d kyw %d mask %x", kx, T.saw, T.nsa, T.nm, T.kyw, T.ks_mask);
+    }
+    {   // the headline array with one on-axis focus (16 x 16 @ 12 voxels, 256^3 folded: 11 x positions) and configs[1] (6 voxels, 128^3: 11)
+        CHECK(toep_plan(16, 12, 12, 1, 128, 128, 256, false).nm == 2 && toep_plan(16, 6, 6, 1, 64, 64, 128, false).nm == 2 && toep_plan(16, 6, 6, 1, 32, 32, 48, false).nm == 1, "toep_plan: BASELINE's 16 x 16 array");
+    }
+    {   // BASELINE configs[3]: 32 x 32 @ 12 voxels on 512^3 (folded: 256 x 256 computed voxels)
+        const ToepPlan T = toep_plan(32, 12, 12, 1, 256, 256, 512, false);
+        CHECK(T.saw == 24 && T.nsa == 2 && T.nm == 3 && T.kyw == ToepShape<3>::KYW, "toep_plan: configs[3]: saw %d nsa %d nm %d kyw %d", T.saw, T.nsa, T.nm, T.kyw);
+        CHECK(T.ks_mask == (3u | (2u << 2)) && T.ksteps_total == 3 && T.e4_units == 3, "toep_plan: configs[3]: mask %x (the second column fills K-step 1 only), %d K-steps, %d e4m3 units", T.ks_mask, T.ksteps_total, T.e4_units);
+        const ToepPlan D = toep_plan(32, 12, 12, 1, 256, 256, 512, true);      // the DIR instantiations have no three-tile shape
+        CHECK(D.nm == 1 && D.kyw == ToepShape<1>::KYW && D.ks_mask == T.ks_mask && D.e4_units == 4, "toep_plan: configs[3] with per-term factors: nm %d", D.nm);
+        const ToepPlan P1 = toep_plan(32, 12, 12, 1, 256, 256, 512, false, 0, 1), P16 = toep_plan(32, 12, 12, 1, 256, 256, 512, false, 16, 0);      // the A/B pins
+        CHECK(P1.nm == 1 && P1.saw == 24 && P16.saw == 16 && P16.nsa == 2 && P16.nm == 2 && P16.ks_mask == 0xfu, "toep_plan: pins: nm %d / saw %d nsa %d nm %d mask %x", P1.nm, P16.saw, P16.nsa, P16.nm, P16.ks_mask);
+    }
+    {   // a 20-wide array (20 x 20 @ 6 voxels on 206 x 206 x 320, folded): one column of 20, three row tiles; on a small grid (fewer than 256 blocks) one
+        const ToepPlan T = toep_plan(20, 6, 6, 1, 103, 103, 320, false), S = toep_plan(20, 6, 6, 1, 36, 36, 40, false);
+        CHECK(T.saw == 20 && T.nsa == 1 && T.nm == 3 && T.kyw == ToepShape<3>::KYW && T.ks_mask == 3u && T.ksteps_total == 2 && T.e4_units == 2, "toep_plan: 20-wide array: saw %d nsa %d nm %d mask %x", T.saw, T.nsa, T.nm, T.ks_mask);
+        CHECK(S.saw == 20 && S.nm == 1, "toep_plan: 20-wide array on a small grid: nm %d", S.nm);
+    }
+    {   // more than 16 super-block columns: reported through nsa, no masks (the caller fails)
+        const ToepPlan T = toep_plan(400, 2, 2, 1, 100, 100, 32, false);
+        CHECK(T.saw == 24 && T.nsa == 17 && T.ks_mask == 0u && T.ksteps_total == 0, "toep_plan: 400-wide array: nsa %d mask %x", T.nsa, T.ks_mask);
+    }
+    for (int k = 0; k < 2000; ++k) {
+        const int ax = ri(4, 40), xs = ri(1, 2), mx = ri(1, 12), my = ri(1, 12), wx = ri(1, 300), wy = ri(1, 300), nz = ri(1, 520), saw_pin = rng() % 4 ? 0 : ri(8, 24), nm_pin = rng() % 8 ? 0 : (rng() & 1 ? 3 : 1);
+        const ToepPlan T = toep_plan(ax, mx, my, xs, wx, wy, nz, rng() % 4 == 0, saw_pin, nm_pin);
+        bool ok = T.saw >= 1 && T.saw <= TOEP_SA_MAX && T.nsa >= 1 && T.nsa * T.saw >= ax && (T.nsa - 1) * T.saw < ax && T.nm >= 1 && T.nm <= TOEP_MAX_NM && T.kyw >= 1 && T.kyw <= COS_KYW;
+        ok = ok && (T.nm != 2 || T.saw + 15 <= 32);      // two row tiles read the second tile 8 columns on in 32-word rows
+        for (int sa = 0; ok && sa < T.nsa; ++sa) ok = ((T.ks_mask >> (2 * sa)) & 3u) != 0;
+        ok = ok && (T.nsa >= 16 || (T.ks_mask >> (2 * T.nsa)) == 0) && T.ksteps_total == popcount(T.ks_mask) && T.e4_units >= T.nsa && T.e4_units <= 2 * T.nsa;
+        CHECK(ok, "toep_plan(ax %d, pitch %dx%d, xs %d, %dx%dx%d, pins %d %d): saw %d nsa %d nm %d kyw %d mask %x, %d K-steps, %d e4m3 units", ax, mx, my, xs, wx, wy, nz, saw_pin, nm_pin,
+              T.saw, T.nsa, T.nm, T.kyw, T.ks_mask, T.ksteps_total, T.e4_units);
     }
 }
 
@@ -283,6 +478,10 @@ int main(int argc, char** argv) {
     const int cases = argc > 1 ? atoi(argv[1]) : 200;
     const unsigned long long seed = argc > 2 ? strtoull(argv[2], nullptr, 10) : 147;
     std::mt19937_64 rng(seed);
+    {
+        std::mt19937_64 rng2(seed);      // (a stream of its own: the shapes below stay the ones each seed always drew)
+        check_toep_plan(rng2);
+    }
     auto ri = [&](int lo, int hi) { return (int)(lo + rng() % (unsigned long long)(hi - lo + 1)); };
     int done = 0;
     // BASELINE's shapes first: 16 x 16 @ 12 voxels on 256^3 (8-focus shard, 64-focus sweep, 4-GPU x-slab), 32 x 32 @ 12 on 512^3 (coarse: plane count cut)
