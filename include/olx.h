@@ -271,17 +271,33 @@ int olx_field_absorption(olx_ctx *ctx, double np_per_m);
  * Two more outputs of the same time axis (neither touches a plan that does not ask for it):
  *   OLX_OUT_PII   the pulse intensity integral PII_f(v) = 1e-4 dt / (rho c) sum_k p_f(v, t_k)^2 [J/cm^2] as one more resident volume
  *                 (olx_field_fetch_pii); PII / (cycles / f0) is the pulse-average intensity [W/cm^2].  olx_field_scale, olx_field_scale_aggregate
- *                 and olx_solution_analyze do NOT scale it and the device aggregate does not aggregate it: a caller that scales the
- *                 pressures by `factor` multiplies the fetched PII by factor^2.
+ *                 and olx_solution_analyze do NOT scale it and the device aggregate does not aggregate it: olx_pii_post (below) is the
+ *                 only thing that scales it (by factor^2 for pressures scaled by `factor`) and forms its sum and maximum over foci.
  *   olx_field_pulse_trace   the waveform p_f(v_i, t_k), k = 0 .. n_t - 1, at chosen voxels. */
 int olx_field_pulse(olx_ctx *ctx, double cycles, double dt, int n_t);
 /* p_max of every planned focus of the last pulsed launch ([F * voxels] floats), as scaled since. */
 int olx_field_fetch_pmax(olx_ctx *ctx, float *pmax_out);
 /* max_f p_max_f of the last device aggregate of a pulsed plan's volumes ([voxels] floats). */
 int olx_aggregate_fetch_pmax(olx_ctx *ctx, float *pmax_out);
-/* Pulse intensity integral of every planned focus of the last pulsed launch with OLX_OUT_PII ([F * voxels] floats, J/cm^2).  Never scaled
- * on the device (see olx_field_pulse): multiply by factor^2 after an olx_field_scale by `factor`. */
+/* Pulse intensity integral of every focus of the last pulsed launch with OLX_OUT_PII, or of olx_pii_upload ([F * voxels] floats, J/cm^2),
+ * as scaled since by olx_pii_post (nothing else scales it, see olx_field_pulse). */
 int olx_field_fetch_pii(olx_ctx *ctx, float *pii_out);
+/* One pass over the resident PII volumes (a pulsed plan with OLX_OUT_PII that has been launched, or olx_pii_upload), at most 8 foci
+ * (DESIGN.md section 2 "pulse energy"):
+ *   scale_per_focus [F] or NULL   PII_f *= (float)(s_f * s_f) in place (the product in fp64, rounded once; one fp32 multiply per voxel)
+ *   weights [F] or NULL           the weighted volume sum_f w_f PII_f (fp32, f ascending, acc = fmaf((float)w_f, PII_f, acc) from 0, over
+ *                                 the scaled values): the dose of a pulse train for w_f = pulses aimed at focus f; NULL = no weighted volume
+ *   A [F * 12] or NULL            focal frames and masks as olx_field_analysis_peaks (every selection is the fp64 one): peaks_out[F * 4 + 1] =
+ *                                 per focus {mainlobe PII, sidelobe PII, global PII, mainlobe weighted}, then the global (z > zmin) peak of
+ *                                 the weighted volume (the weighted peaks are 0 without weights); NULL = no peaks, aspect / peaks_out unused
+ * and always max_f PII_f.  OLX_ESTATE without resident PII, OLX_EINVAL when n_foci is not the resident volumes' count.  Synchronous. */
+int olx_pii_post(olx_ctx *ctx, const double *scale_per_focus, const double *weights, int n_foci,
+                 const double *A, const double *aspect, double r_main_m, double r_side_m, double zmin_m, float *peaks_out);
+int olx_pii_fetch_weighted(olx_ctx *ctx, float *out);   /* sum_f w_f PII_f of the last olx_pii_post with weights ([voxels] floats); OLX_ESTATE once the PII has been scaled or replaced since */
+int olx_pii_fetch_max(olx_ctx *ctx, float *out);        /* max_f PII_f of the last olx_pii_post ([voxels] floats) */
+/* Host PII volumes ([n_foci * voxels] floats) onto the grid of the current plan / upload: the resident PII from then on, until the next
+ * plan, upload or pulsed launch. */
+int olx_pii_upload(olx_ctx *ctx, int n_foci, const float *pii);
 /* Waveforms of the current pulsed plan with the current steering table (the plan need not have been launched, and needs no particular
  * output flag): trace_out[(f * n_points + i) * n_t + k] = p_f(voxels[i], t_k) [Pa], float32, for all planned foci; voxels are linear C-order
  * indices of the planned grid (OLX_EINVAL outside it).  A sample at which no element has arrived yet, or after the last burst has ended,
@@ -308,6 +324,9 @@ int olx_thermal_schedule(olx_ctx *ctx, int n_steps, const int *row_ptr, const in
 /* The intensity volumes I_f [W/cm^2] the schedule's focus indices refer to: [n_foci * voxels] floats uploaded once, or NULL = the
  * context's resident intensity (a whole-grid result of n_foci foci on the thermal grid, read in place at every olx_thermal_run). */
 int olx_thermal_source(olx_ctx *ctx, int n_foci, const float *intensity);
+/* Kernel 3 reads the resident PII volumes [J/cm^2] in place as its per-focus source volumes (whole-grid, n_foci foci, on the thermal grid:
+ * checked at every olx_thermal_run).  The step kernel is the same: the caller folds 1 / (pulse on-time) into the schedule's tau. */
+int olx_thermal_source_pii(olx_ctx *ctx, int n_foci);
 /* Steps [first_step, first_step + n_steps) of the schedule with time step dt [s] (<= the FTCS bound) and baseline temperature [deg C];
  * first_step = 0 starts from dT = 0, any other first_step continues the last run.  Per voxel it keeps the maximum rise [K] and
  * CEM43 = sum_n dt / 60 R^(43 - T) [min] (T = baseline + dT after the step, R = 0.5 at T >= 43, 0.25 below).  Asynchronous. */
@@ -344,6 +363,9 @@ int olx_profile_end(olx_ctx *ctx, float *ms_each, int capacity, int *n_recorded)
 #define OLX_SCAN_OFFSET_GRID 4
 #define OLX_SCAN_WEIGHTED_SUM 5
 #define OLX_SCAN_FUSED_POST 6   /* scale + aggregate + six peaks + time-average volume in ONE pass (<= 8 foci): V (16 F + 12) bytes */
+#define OLX_SCAN_PII_SCALE 7    /* olx_pii_post over the resident PII (not the planned volumes), factors only: V (8 F + 4) bytes -- 4 more than the scaling
+                                 * alone needs, on purpose: every form stores max_f PII_f, so olx_pii_fetch_max is current after every scaling */
+#define OLX_SCAN_PII_FULL 8     /* ... factors, weights and peaks: V (8 F + 8) bytes */
 int olx_scan_time(olx_ctx *ctx, int kernel, int iters, float *ms_each, double *bytes_per_launch);
 
 /* Name of the field kernel variant the current plan dispatches to (for profiles). */

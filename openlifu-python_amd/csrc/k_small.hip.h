@@ -1187,6 +1187,167 @@ __global__ __launch_bounds__(256, OLX_SCAN_WPE_FIELD_SCALE_AGG_ANALYZE_K) void f
 }
 
 // ------------------------------------------------------------------------------------
+// olx_pii_post: the pulse intensity integrals PII_f [J/cm^2] of a pulsed result in ONE pass: SCALE: PII_f *= g_f in
+// place (g_f = (float)(s_f^2), one fp32 multiply), WTS: the weighted volume sum_f w_f PII_f (fp32, f ascending, acc = fmaf(w_f, PII_f, acc)
+// from 0 over the ROUNDED scaled values -- the train dose for w_f = n_f), always max_f PII_f, PEAKS: per focus the mainlobe / sidelobe / global
+// peak of PII_f and the mainlobe peak of the weighted volume under that focus' mask, and once the global peak (z > zmin) of the weighted volume.
+// The form of field_scale_agg_analyze_k: a lane owns a quad of z voxels of ALL (<= 8) foci, non-temporal 16-byte loads (plain stores: see
+// OLX_SAA_ST), quad_decode, the masks' fp32 pre-test with the exact fp64 test inside the band (every decision is the fp64 one), peaks reduced
+// in the wave and then by atomicMax on the bit patterns (all values >= 0).  ROWQ: row quads with a partial last quad, for nz % 4 != 0.
+// A call that only scales instantiates no mask and no weight arithmetic.  peaks[4 f + k], wpeak: zeroed by the host.
+// Debug library sites: 0 PII quad, 1 weighted / max quad.
+// ------------------------------------------------------------------------------------
+constexpr int PII_MAXF = 8;
+template <bool SCALE, bool WTS, bool PEAKS, bool ROWQ>
+__global__ __launch_bounds__(256) void pii_post_k(float* __restrict__ pii, const float* __restrict__ gain, const float* __restrict__ wts,
+                                                   const double* __restrict__ A, int n_foci, const PeakParams P /*radius = r_main*/, double r_side,
+                                                   float* __restrict__ wvol, float* __restrict__ mvol, unsigned* __restrict__ peaks /*[F][4]*/,
+                                                   unsigned* __restrict__ wpeak) {
+    __shared__ double sA[PEAKS ? PII_MAXF : 1][12];
+    __shared__ MaskFast sM[PEAKS ? PII_MAXF : 1];
+    __shared__ float s_red[4][PII_MAXF * 4 + 1];
+    if constexpr (PEAKS) {       // the focal frames: staged once per block
+        for (int q = threadIdx.x; q < 12 * n_foci; q += blockDim.x) sA[q / 12][q % 12] = A[q];
+        __syncthreads();
+        if ((int)threadIdx.x < n_foci) mask_fast_prepare(sM[threadIdx.x], sA[threadIdx.x], P, P.radius, r_side, true);
+        __syncthreads();
+    }
+    const int nzq = P.nz >> 2, nyzq = P.ny * nzq, nq = P.nx * nyzq;            // WHOLE quads of the rows (host: nx ny ceil(nz / 4) < 2^31)
+    const float inv_nyzq = 1.0f / (float)max(nyzq, 1), inv_nzq = 1.0f / (float)max(nzq, 1);
+    const double rm2 = P.radius * P.radius, rm2lo = rm2 * (1.0 - 1e-12), rm2hi = rm2 * (1.0 + 1e-12);
+    const double rs2 = r_side * r_side, rs2lo = rs2 * (1.0 - 1e-12), rs2hi = rs2 * (1.0 + 1e-12);
+    const int iz_first = PEAKS ? sM[0].iz_first : 0;     // (zmin and the grid are the same for every focus)
+    const float ox = (float)P.ox, oy = (float)P.oy, oz = (float)P.oz, hx = (float)P.hx, hy = (float)P.hy, hz = (float)P.hz;   // (= MaskFast's)
+    float pk[PII_MAXF][4];
+#pragma unroll
+    for (int f = 0; f < PII_MAXF; ++f)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pk[f][k] = 0.f;
+    float wmax = 0.f;
+    const int stride = gridDim.x * blockDim.x;
+    const long long total = (long long)n_foci * P.vox;
+    auto quad = [&](const int ix, const int iy, const int iz0, auto whole_c) __attribute__((always_inline)) {
+        constexpr bool WHOLE = decltype(whole_c)::value != 0;
+        const int cnt = WHOLE ? 4 : P.nz - iz0;                               // < 4 only behind a row's last whole quad (nz % 4 != 0)
+        const long long vo = ((long long)ix * P.ny + iy) * P.nz + iz0;        // first voxel of the quad
+        const float fx = fmaf((float)ix, hx, ox), fy = fmaf((float)iy, hy, oy);
+        float fz[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) fz[e] = fmaf((float)(iz0 + e), hz, oz);
+        float4 m = make_float4(0.f, 0.f, 0.f, 0.f), ws = m;
+        unsigned main_bits = 0;                                               // bit 4 f + e: voxel e lies in focus f's mainlobe mask
+#pragma unroll
+        for (int f = 0; f < PII_MAXF; ++f) {
+            if (f >= n_foci) break;                      // uniform
+            float* const pp = pii + (long long)f * P.vox + vo;
+            if (!OLX_IN((long long)f * P.vox + vo + cnt - 1, total, 0)) continue;
+            float4 p4;
+            if constexpr (ROWQ && WHOLE) p4 = ld4u(pp, 4);
+            else if constexpr (ROWQ) p4 = ld4u(pp, cnt);
+            else p4 = OLX_SAA_LD(reinterpret_cast<const float4*>(pp));
+            if constexpr (SCALE) {
+                const float g = gain[f];
+                p4.x = __fmul_rn(p4.x, g); p4.y = __fmul_rn(p4.y, g); p4.z = __fmul_rn(p4.z, g); p4.w = __fmul_rn(p4.w, g);
+                if constexpr (ROWQ) st4u(pp, p4, cnt);
+                else OLX_SAA_ST(reinterpret_cast<float4*>(pp), p4);
+            }
+            m.x = fmaxf(m.x, p4.x); m.y = fmaxf(m.y, p4.y); m.z = fmaxf(m.z, p4.z); m.w = fmaxf(m.w, p4.w);
+            if constexpr (WTS) {
+                const float w = wts[f];
+                ws.x = fmaf(w, p4.x, ws.x); ws.y = fmaf(w, p4.y, ws.y); ws.z = fmaf(w, p4.z, ws.z); ws.w = fmaf(w, p4.w, ws.w);
+            }
+            if constexpr (PEAKS) {       // field_analysis_peaks4_k's decisions
+                const MaskFast& M = sM[f];
+                const float b0 = fmaf(M.a[1], fy, fmaf(M.a[0], fx, M.a[3])), b1 = fmaf(M.a[5], fy, fmaf(M.a[4], fx, M.a[7])), b2 = fmaf(M.a[9], fy, fmaf(M.a[8], fx, M.a[11]));
+                int in_main[4], in_side[4], undecided = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float g0 = fmaf(M.a[2], fz[e], b0), g1 = fmaf(M.a[6], fz[e], b1), g2 = fmaf(M.a[10], fz[e], b2);
+                    const float d2f = fmaf(g2, g2, fmaf(g1, g1, g0 * g0));
+                    in_main[e] = mask_fast_side(d2f, M.rin2[0], M.rout2[0]);
+                    in_side[e] = mask_fast_side(d2f, M.rin2[1], M.rout2[1]);
+                    undecided |= (in_main[e] == 0 || in_side[e] == 0) ? (1 << e) : 0;
+                }
+                if (undecided) {
+                    const double x = P.ox + ix * P.hx, y = P.oy + iy * P.hy;
+                    const double* a = sA[f];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (!((undecided >> e) & 1)) continue;
+                        const double z = P.oz + (iz0 + e) * P.hz;
+                        const double q0 = (a[0] * x + a[1] * y + a[2] * z + a[3]) * P.ia0;
+                        const double q1 = (a[4] * x + a[5] * y + a[6] * z + a[7]) * P.ia1;
+                        const double q2 = (a[8] * x + a[9] * y + a[10] * z + a[11]) * P.ia2;
+                        const double d2 = q0 * q0 + q1 * q1 + q2 * q2;
+                        in_main[e] = mask_cmp<0>(d2, P.radius, rm2lo, rm2hi) ? 1 : -1;
+                        in_side[e] = mask_cmp<2>(d2, r_side, rs2lo, rs2hi) ? -1 : 1;
+                    }
+                }
+                const float pv[4] = {p4.x, p4.y, p4.z, p4.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (e >= cnt) break;                 // (a partial quad's zero fill selects nothing)
+                    const bool zok = (iz0 + e) >= iz_first;
+                    if (in_main[e] > 0) { pk[f][0] = fmaxf(pk[f][0], pv[e]); main_bits |= 1u << (4 * f + e); }
+                    if (zok && in_side[e] < 0) pk[f][1] = fmaxf(pk[f][1], pv[e]);
+                    if (zok) pk[f][2] = fmaxf(pk[f][2], pv[e]);
+                }
+            }
+        }
+        if (!OLX_IN(vo + cnt - 1, P.vox, 1)) return;
+        if constexpr (ROWQ) { st4u(mvol + vo, m, cnt); if constexpr (WTS) st4u(wvol + vo, ws, cnt); }
+        else { OLX_SAA_ST(reinterpret_cast<float4*>(mvol + vo), m); if constexpr (WTS) OLX_SAA_ST(reinterpret_cast<float4*>(wvol + vo), ws); }
+        if constexpr (WTS && PEAKS) {    // the weighted volume is complete here: its peaks under every focus' mainlobe mask, and above zmin
+            const float wsv[4] = {ws.x, ws.y, ws.z, ws.w};
+#pragma unroll
+            for (int f = 0; f < PII_MAXF; ++f)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) if ((main_bits >> (4 * f + e)) & 1u) pk[f][3] = fmaxf(pk[f][3], wsv[e]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (e < cnt && (iz0 + e) >= iz_first) wmax = fmaxf(wmax, wsv[e]);
+        }
+    };
+    for (int iq = blockIdx.x * blockDim.x + threadIdx.x; iq < nq; iq += stride) {
+        int ix, iy, iz0;
+        quad_decode(iq, nzq, nyzq, inv_nyzq, inv_nzq, ix, iy, iz0);
+        quad(ix, iy, iz0, IntC<1>{});
+    }
+    if constexpr (ROWQ) {
+        if (P.nz & 3) {      // the rows' tails: one thread per row
+            const float inv_ny = 1.0f / (float)P.ny;
+            for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < P.nx * P.ny; r += stride) {
+                int ix = (int)((float)r * inv_ny), iy = r - ix * P.ny;
+                if (iy < 0) { --ix; iy += P.ny; } else if (iy >= P.ny) { ++ix; iy -= P.ny; }
+                quad(ix, iy, P.nz & ~3, IntC<0>{});
+            }
+        }
+    }
+    if constexpr (PEAKS) {       // block reduction: 4 F + 1 maxima
+#pragma unroll
+        for (int f = 0; f < PII_MAXF; ++f)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float v = pk[f][k];
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+                if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6][f * 4 + k] = v;
+            }
+        {
+            float v = wmax;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+            if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6][PII_MAXF * 4] = v;
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < 4 * n_foci) {
+            const int k = threadIdx.x;
+            atomicMax(peaks + k, __float_as_uint(fmaxf(fmaxf(s_red[0][k], s_red[1][k]), fmaxf(s_red[2][k], s_red[3][k]))));
+        }
+        if (threadIdx.x == 255) atomicMax(wpeak, __float_as_uint(fmaxf(fmaxf(s_red[0][PII_MAXF * 4], s_red[1][PII_MAXF * 4]), fmaxf(s_red[2][PII_MAXF * 4], s_red[3][PII_MAXF * 4]))));
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // Pieces of the one-call analysis (olx_solution_analyze): everything Solution.analyze reads off the resident volumes is
 // enqueued back to back on the context's stream, the intermediate numbers (mainlobe peaks -> -3 dB centroid cut-offs and beam
 // width cut-offs) never leave the device, and ONE copy brings the per-focus reports to the host.

@@ -17,6 +17,8 @@
 #include "olx_plan.h"
 #include "k_toep.hip.h"
 
+OLX_BOUNDS_READER(small)     // debug library: the bounds words of this unit's kernels (pii_post_k)
+
 // A device table kept with a host copy of what it holds (`held`): uploaded only when `v` differs from that copy.  The copy runs on the
 // context's stream, behind whatever is queued there, and is waited for (`v` may live on the caller's frame).
 template <class T> static int upload_if_changed(olx_ctx* c, DevBuf<T>& d, std::vector<T>& held, const std::vector<T>& v) {
@@ -80,12 +82,12 @@ int olx_ctx_destroy(olx_ctx* c) {
 const char* olx_last_error(const olx_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 #ifdef OLX_DEBUG_BOUNDS   // debug build (k_types.hip.h): the kernels' index checks report here
-extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); int olx_dbg_bounds_bfmed(unsigned*); }
+extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); int olx_dbg_bounds_bfmed(unsigned*); int olx_dbg_bounds_small(unsigned*); }
 static int report_bounds(olx_ctx* c) {
     struct { const char* name; int (*read)(unsigned*); } units[] = {{"2g (k_coset2.hip)", olx_dbg_bounds_cosetp}, {"2e (k_coset.hip)", olx_dbg_bounds_coset},
                                                                      {"2f (k_toep.hip)", olx_dbg_bounds_toep}, {"2m (k_hmarch.hip)", olx_dbg_bounds_hmarch},
                                                                      {"2p (k_pulse.hip)", olx_dbg_bounds_pulse}, {"3 (k_thermal.hip)", olx_dbg_bounds_thermal},
-                                                                     {"1m / 1a (k_bfmed.hip)", olx_dbg_bounds_bfmed}};
+                                                                     {"1m / 1a (k_bfmed.hip)", olx_dbg_bounds_bfmed}, {"pii_post_k (k_small.hip.h)", olx_dbg_bounds_small}};
     int rc = OLX_OK;
     for (auto& u : units) {
         unsigned w[4] = {0, 0, 0, 0};
@@ -987,6 +989,7 @@ static int plan_pulse(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n
     c->freq = freq; c->c = cs; c->rho = rho; c->p0_pa = p0_pa; c->flags = flags; c->plan_absorb = c->absorb_np_m;
     c->directivity = false; c->nbuf = 1; c->cur = 0;
     const size_t fn = (size_t)n_foci * c->n_el;
+    pii_regrid(c, vox);
     int rc = reserve_outputs(c, total, 1, (flags & OLX_OUT_INTENSITY) != 0, false, false);
     if (!rc && (flags & OLX_OUT_PMAX)) rc = c->d_pmax.reserve(c, total);
     if (!rc && (flags & OLX_OUT_PII)) rc = c->d_pii.reserve(c, total);
@@ -1066,6 +1069,7 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
     c->agg_local = -1; c->agg_total = 0;   // aggregate over all planned foci unless olx_field_aggregate_counts says otherwise
     c->freq = freq; c->c = cs; c->rho = rho; c->p0_pa = p0_pa; c->flags = flags; c->plan_absorb = c->absorb_np_m;
     const long long vox = (long long)s.x_count * g->n[1] * g->n[2];
+    pii_regrid(c, vox);
     const size_t total = (size_t)vox * n_foci;
     c->nbuf = c->comm_active() ? olx_ctx::NBUF : 1;
     // outputs (|p| is always materialised: aggregate / allgather consume it)
@@ -1189,14 +1193,14 @@ int olx_field_launch(olx_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
     if (c->pulsed) {     // kernel 2p: its own table from the steering, no variant packing
         if (c->flags & OLX_OUT_PMAX) c->pmax_live = false;
-        c->agg_pmax_valid = false; c->pii_live = false;
+        c->agg_pmax_valid = false; c->pii_live = false; c->pii_w_valid = false; c->pii_max_valid = false;
         const bool prof = c->prof_on && (size_t)(2 * c->prof_n + 1) < c->prof_ev.size();
         if (prof) HIPCHK(c, hipEventRecord(c->prof_ev[2 * c->prof_n], c->stream));
         olx_launch_pulse(c, c->d_pmag[0]);
         HIPCHK(c, hipGetLastError());
         if (prof) { HIPCHK(c, hipEventRecord(c->prof_ev[2 * c->prof_n + 1], c->stream)); c->prof_n++; }
         c->pmax_live = (c->flags & OLX_OUT_PMAX) != 0;
-        c->pii_live = (c->flags & OLX_OUT_PII) != 0;
+        c->pii_live = (c->flags & OLX_OUT_PII) != 0; c->pii_foci = c->plan_foci;
         c->cur = 0;
         return OLX_OK;
     }
@@ -1420,10 +1424,10 @@ int olx_field_fetch_pmax(olx_ctx* c, float* pmax_out) {
 int olx_field_fetch_pii(olx_ctx* c, float* pii_out) {
     if (!c) return OLX_EINVAL;
     if (!pii_out) return fail(c, OLX_EINVAL, "olx_field_fetch_pii: null output");
-    if (!c->pii_live) return fail(c, OLX_ESTATE, "olx_field_fetch_pii: no pulse intensity integrals (a launched pulsed plan with OLX_OUT_PII)");
+    if (!c->pii_live) return fail(c, OLX_ESTATE, "olx_field_fetch_pii: no pulse intensity integrals (a launched pulsed plan with OLX_OUT_PII, or olx_pii_upload)");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return fetch_to_host(c, pii_out, c->d_pii, sizeof(float) * (size_t)c->fp.vox * c->plan_foci);
+    return fetch_to_host(c, pii_out, c->d_pii, sizeof(float) * (size_t)c->fp.vox * c->pii_foci);
 }
 
 int olx_field_pulse_trace(olx_ctx* c, int n_points, const long long* voxels, float* trace_out) {
@@ -1683,6 +1687,7 @@ int olx_field_upload(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const long long vox = (long long)s.x_count * g->n[1] * g->n[2];
+    pii_regrid(c, vox);
     const size_t total = (size_t)vox * n_foci;
     { int rc_ = exported_buffers_quiesce(c, -1); if (rc_) return rc_; }   // (p2p: buffer 0 is rewritten, all of them may be freed)
     { int rc_ = reserve_outputs(c, total, 1, intensity != nullptr, false, false); if (rc_) return rc_; }
@@ -1743,6 +1748,7 @@ static int pmax_post(olx_ctx* c, const float* scale, bool aggregate) {
 }
 }
 static void fill_scan_params(const olx_ctx* c, PeakParams& P, const double* aspect);
+static int pii_scan_time(olx_ctx* c, int kernel, int iters, float* ms_each, double* bytes_per_launch);
 // Blocks per focus of the masked scans: ~2048 blocks in flight over all foci (8 per CU, all resident), each living long enough
 // that its one-thread mask preparation (fp32 frame, band, first plane above zmin) does not count -- with 2048 blocks PER focus a
 // block moved 32 KB and the prologue was most of its life.
@@ -1759,6 +1765,7 @@ int olx_scan_time(olx_ctx* c, int kernel, int iters, float* ms_each, double* byt
     if (!c) return OLX_EINVAL;
     if (iters < 1 || !ms_each || !bytes_per_launch) return fail(c, OLX_EINVAL, "olx_scan_time: iters < 1 or null output");
     if (!c->planned) return fail(c, OLX_ESTATE, "olx_scan_time: nothing planned");
+    if (kernel == OLX_SCAN_PII_SCALE || kernel == OLX_SCAN_PII_FULL) return pii_scan_time(c, kernel, iters, ms_each, bytes_per_launch);
     if (kernel < 0 || kernel > OLX_SCAN_FUSED_POST) return fail(c, OLX_EINVAL, "olx_scan_time: unknown kernel %d", kernel);
     if (kernel == OLX_SCAN_FUSED_POST && (c->plan_foci > SAA_MAXF || (long long)c->fp.nx * c->fp.ny * ((c->fp.nz + 3) / 4) >= (1ll << 31))) return fail(c, OLX_ESTATE, "olx_scan_time: the fused pass needs <= 8 foci and < 2^31 row quads");
     if (!(c->flags & OLX_OUT_INTENSITY)) return fail(c, OLX_ESTATE, "olx_scan_time: intensity not planned");
@@ -2063,6 +2070,166 @@ static void fill_scan_params(const olx_ctx* c, PeakParams& P, const double* aspe
     P.hx = c->grid.spacing[0]; P.hy = c->grid.spacing[1]; P.hz = c->grid.spacing[2];
     P.ia0 = aspect ? 1.0 / aspect[0] : 1.0; P.ia1 = aspect ? 1.0 / aspect[1] : 1.0; P.ia2 = aspect ? 1.0 / aspect[2] : 1.0;
     P.radius = 0; P.op = 0; P.use_zmin = 0; P.zmin = 0; P.vox = c->fp.vox; P.vol_stride = c->fp.vox;
+}
+
+// ---- pulse intensity integrals (pii_post_k) ---------------------------------------------------------------------------------------
+}   // extern "C"
+template <bool SCALE, bool WTS, bool PEAKS> static void launch_pii_post(olx_ctx* c, const PeakParams& P, double r_side, unsigned blocks, int F) {
+    float* const gw = c->d_pii_gw;
+    unsigned* const pk = c->d_pii_peak;
+    if (P.nz & 3) hipLaunchKernelGGL((pii_post_k<SCALE, WTS, PEAKS, true>), dim3(blocks), dim3(256), 0, c->stream, (float*)c->d_pii, gw, gw + PII_MAXF,
+                                     (const double*)c->d_pii_A, F, P, r_side, (float*)c->d_pii_w, (float*)c->d_pii_max, pk, pk + 4 * PII_MAXF);
+    else hipLaunchKernelGGL((pii_post_k<SCALE, WTS, PEAKS, false>), dim3(blocks), dim3(256), 0, c->stream, (float*)c->d_pii, gw, gw + PII_MAXF,
+                            (const double*)c->d_pii_A, F, P, r_side, (float*)c->d_pii_w, (float*)c->d_pii_max, pk, pk + 4 * PII_MAXF);
+}
+extern "C" {
+
+int olx_pii_post(olx_ctx* c, const double* scale_per_focus, const double* weights, int n_foci, const double* A, const double* aspect,
+                 double r_main_m, double r_side_m, double zmin_m, float* peaks_out) {
+    if (!c) return OLX_EINVAL;
+    if (!c->planned || !c->pii_live) return fail(c, OLX_ESTATE, "olx_pii_post: no resident pulse intensity integrals (a launched pulsed plan with OLX_OUT_PII, or olx_pii_upload)");
+    if (n_foci != c->pii_foci) return fail(c, OLX_EINVAL, "olx_pii_post: %d foci given, the resident pulse intensity integrals have %d", n_foci, c->pii_foci);
+    if (A && (!aspect || !peaks_out)) return fail(c, OLX_EINVAL, "olx_pii_post: focal frames need aspect and peaks_out");
+    const int F = n_foci;
+    if (F > PII_MAXF) return fail(c, OLX_EINVAL, "olx_pii_post: at most %d foci", PII_MAXF);
+    const long long quads = (long long)c->fp.nx * c->fp.ny * ((c->fp.nz + 3) / 4);
+    if (quads >= (1ll << 31)) return fail(c, OLX_EINVAL, "olx_pii_post: grid too large (2^31 row quads or more)");
+    float gw[2 * PII_MAXF] = {0};
+    for (int f = 0; f < F; ++f) {
+        if (scale_per_focus && !std::isfinite(scale_per_focus[f])) return fail(c, OLX_EINVAL, "olx_pii_post: scale factor %d is not finite", f);
+        if (weights && !(weights[f] >= 0 && std::isfinite(weights[f]))) return fail(c, OLX_EINVAL, "olx_pii_post: weight %d must be finite and >= 0", f);
+        gw[f] = scale_per_focus ? (float)(scale_per_focus[f] * scale_per_focus[f]) : 1.f;
+        gw[PII_MAXF + f] = weights ? (float)weights[f] : 0.f;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    {
+        const size_t vox = (size_t)c->fp.vox;
+        int rc = c->d_pii_gw.reserve(c, 2 * PII_MAXF);
+        if (!rc) rc = c->d_pii_A.reserve(c, 12 * PII_MAXF);
+        if (!rc) rc = c->d_pii_peak.reserve(c, 4 * PII_MAXF + 1);
+        if (!rc) rc = c->d_pii_max.reserve(c, vox);
+        if (!rc && weights) rc = c->d_pii_w.reserve(c, vox);
+        if (rc) return rc;
+    }
+    if (scale_per_focus || weights) c->pii_w_valid = false;      // (scaled volumes leave an older weighted volume behind)
+    c->pii_max_valid = false;
+    HIPCHK(c, hipMemcpyAsync(c->d_pii_gw, gw, sizeof gw, hipMemcpyHostToDevice, c->stream));
+    PeakParams P;
+    fill_scan_params(c, P, aspect);
+    if (A) {
+        HIPCHK(c, hipMemcpyAsync(c->d_pii_A, A, sizeof(double) * 12 * F, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_pii_peak, 0, sizeof(unsigned) * (4 * PII_MAXF + 1), c->stream));
+        P.radius = r_main_m; P.use_zmin = 1; P.zmin = zmin_m;
+    }
+    const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>((quads + 255) / 256, 2048));
+    const int form = (scale_per_focus ? 4 : 0) | (weights ? 2 : 0) | (A ? 1 : 0);
+    switch (form) {
+        case 0: launch_pii_post<false, false, false>(c, P, r_side_m, blocks, F); break;
+        case 1: launch_pii_post<false, false, true>(c, P, r_side_m, blocks, F); break;
+        case 2: launch_pii_post<false, true, false>(c, P, r_side_m, blocks, F); break;
+        case 3: launch_pii_post<false, true, true>(c, P, r_side_m, blocks, F); break;
+        case 4: launch_pii_post<true, false, false>(c, P, r_side_m, blocks, F); break;
+        case 5: launch_pii_post<true, false, true>(c, P, r_side_m, blocks, F); break;
+        case 6: launch_pii_post<true, true, false>(c, P, r_side_m, blocks, F); break;
+        default: launch_pii_post<true, true, true>(c, P, r_side_m, blocks, F); break;
+    }
+    HIPCHK(c, hipGetLastError());
+    unsigned pk[4 * PII_MAXF + 1];
+    if (A) HIPCHK(c, hipMemcpyAsync(pk, c->d_pii_peak, sizeof pk, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (gw and pk live on this frame)
+    if (A) {
+        memcpy(peaks_out, pk, sizeof(float) * 4 * F);
+        memcpy(peaks_out + 4 * F, pk + 4 * PII_MAXF, sizeof(float));
+    }
+    c->pii_max_valid = true;
+    if (weights) c->pii_w_valid = true;
+    return OLX_OK;
+}
+
+}   // extern "C"
+// olx_scan_time of pii_post_k over the resident PII: the scale-only form (factors 1.0f: exact, the volumes stay as they are) or the full form
+// (factors, weights 1 / F, a mainlobe-sized mask at the grid centre), `iters` launches back to back with a HIP event between each
+static int pii_scan_time(olx_ctx* c, int kernel, int iters, float* ms_each, double* bytes_per_launch) {
+    if (!c->pii_live) return fail(c, OLX_ESTATE, "olx_scan_time: no resident pulse intensity integrals");
+    const int F = c->pii_foci;
+    const long long quads = (long long)c->fp.nx * c->fp.ny * ((c->fp.nz + 3) / 4);
+    if (F > PII_MAXF || quads >= (1ll << 31)) return fail(c, OLX_ESTATE, "olx_scan_time: pii_post_k needs <= %d foci and < 2^31 row quads", PII_MAXF);
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool full = kernel == OLX_SCAN_PII_FULL;
+    {
+        const size_t vox = (size_t)c->fp.vox;
+        int rc = c->d_pii_gw.reserve(c, 2 * PII_MAXF);
+        if (!rc) rc = c->d_pii_A.reserve(c, 12 * PII_MAXF);
+        if (!rc) rc = c->d_pii_peak.reserve(c, 4 * PII_MAXF + 1);
+        if (!rc) rc = c->d_pii_max.reserve(c, vox);
+        if (!rc && full) rc = c->d_pii_w.reserve(c, vox);
+        if (rc) return rc;
+    }
+    c->pii_w_valid = false; c->pii_max_valid = false;
+    float gw[2 * PII_MAXF];
+    for (int f = 0; f < PII_MAXF; ++f) { gw[f] = 1.0f; gw[PII_MAXF + f] = 1.0f / (float)F; }
+    double hA[12 * PII_MAXF] = {0};
+    const double ctr[3] = {c->grid.origin[0] + (c->slab.x_begin + 0.5 * (c->fp.nx - 1)) * c->grid.spacing[0],
+                           c->grid.origin[1] + 0.5 * (c->fp.ny - 1) * c->grid.spacing[1], c->grid.origin[2] + 0.5 * (c->fp.nz - 1) * c->grid.spacing[2]};
+    for (int f = 0; f < F; ++f) for (int a = 0; a < 3; ++a) { hA[12 * f + 4 * a + a] = 1.0; hA[12 * f + 4 * a + 3] = -ctr[a]; }
+    HIPCHK(c, hipMemcpy(c->d_pii_gw, gw, sizeof gw, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_pii_A, hA, sizeof hA, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(c->d_pii_peak, 0, sizeof(unsigned) * (4 * PII_MAXF + 1)));
+    const double asp[3] = {1.0, 1.0, 5.0};
+    PeakParams P; fill_scan_params(c, P, asp);
+    P.radius = 2.5e-3; P.op = 0; P.use_zmin = 1; P.zmin = c->grid.origin[2] + c->grid.spacing[2];
+    const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>((quads + 255) / 256, 2048));
+    struct Events {
+        std::vector<hipEvent_t> ev;
+        ~Events() { for (auto e : ev) if (e) hipEventDestroy(e); }
+    } T;
+    T.ev.assign(iters + 1, nullptr);
+    for (auto& e : T.ev) HIPCHK(c, hipEventCreate(&e));
+    HIPCHK(c, hipEventRecord(T.ev[0], c->stream));
+    for (int i = 0; i < iters; ++i) {
+        if (full) launch_pii_post<true, true, true>(c, P, 5e-3, blocks, F);
+        else launch_pii_post<true, false, false>(c, P, 5e-3, blocks, F);
+        HIPCHK(c, hipEventRecord(T.ev[i + 1], c->stream));
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < iters; ++i) HIPCHK(c, hipEventElapsedTime(&ms_each[i], T.ev[i], T.ev[i + 1]));
+    *bytes_per_launch = (double)c->fp.vox * (8.0 * F + (full ? 8.0 : 4.0));
+    c->pii_max_valid = true; c->pii_w_valid = full;
+    return OLX_OK;
+}
+extern "C" {
+
+int olx_pii_fetch_weighted(olx_ctx* c, float* out) {
+    if (!c) return OLX_EINVAL;
+    if (!out) return fail(c, OLX_EINVAL, "olx_pii_fetch_weighted: null output");
+    if (!c->pii_live || !c->pii_w_valid) return fail(c, OLX_ESTATE, "olx_pii_fetch_weighted: no weighted volume of the resident pulse intensity integrals (olx_pii_post with weights)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return fetch_to_host(c, out, c->d_pii_w, sizeof(float) * (size_t)c->fp.vox);
+}
+
+int olx_pii_fetch_max(olx_ctx* c, float* out) {
+    if (!c) return OLX_EINVAL;
+    if (!out) return fail(c, OLX_EINVAL, "olx_pii_fetch_max: null output");
+    if (!c->pii_live || !c->pii_max_valid) return fail(c, OLX_ESTATE, "olx_pii_fetch_max: no maximum over foci of the resident pulse intensity integrals (olx_pii_post)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return fetch_to_host(c, out, c->d_pii_max, sizeof(float) * (size_t)c->fp.vox);
+}
+
+int olx_pii_upload(olx_ctx* c, int n_foci, const float* pii) {
+    if (!c) return OLX_EINVAL;
+    if (!c->planned) return fail(c, OLX_ESTATE, "olx_pii_upload: no grid (olx_field_plan or olx_field_upload first)");
+    if (!pii || n_foci < 1) return fail(c, OLX_EINVAL, "olx_pii_upload: null volume or n_foci < 1");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t total = (size_t)c->fp.vox * n_foci;
+    c->pii_live = false; c->pii_w_valid = false; c->pii_max_valid = false;
+    { int rc_ = c->d_pii.reserve(c, total); if (rc_) return rc_; }
+    HIPCHK(c, hipMemcpy(c->d_pii, pii, sizeof(float) * total, hipMemcpyHostToDevice));
+    c->pii_live = true; c->pii_foci = n_foci;
+    return OLX_OK;
 }
 
 int olx_field_masked_moments(olx_ctx* c, const double* A, const double* aspect, double radius_m, const float* cutoff,
@@ -2641,7 +2808,7 @@ int olx_thermal_plan(olx_ctx* c, const olx_grid* g, const float* density, const 
     if (dt_max_out) *dt_max_out = 1.0 / c->th_rate;
     c->th_planned = true;
     c->th_steps = 0; c->th_npts = 0; c->th_next = -1;
-    c->th_src_foci = 0; c->th_src_resident = false;
+    c->th_src_foci = 0; c->th_src_resident = false; c->th_src_pii = false;
     return OLX_OK;
 }
 
@@ -2695,6 +2862,16 @@ int olx_thermal_source(olx_ctx* c, int n_foci, const float* intensity) {
     } else {
         c->th_src_resident = true;     // checked against the resident result at every olx_thermal_run
     }
+    c->th_src_foci = n_foci; c->th_src_pii = false;
+    return OLX_OK;
+}
+
+int olx_thermal_source_pii(olx_ctx* c, int n_foci) {
+    if (!c) return OLX_EINVAL;
+    if (!c->th_planned) return fail(c, OLX_ESTATE, "olx_thermal_source_pii: no thermal plan");
+    if (!c->pii_live) return fail(c, OLX_ESTATE, "olx_thermal_source_pii: no resident pulse intensity integrals (a launched pulsed plan with OLX_OUT_PII, or olx_pii_upload)");
+    if (n_foci != c->pii_foci) return fail(c, OLX_EINVAL, "olx_thermal_source_pii: %d foci given, the resident pulse intensity integrals have %d", n_foci, c->pii_foci);
+    c->th_src_resident = true; c->th_src_pii = true;     // checked against the resident volumes at every olx_thermal_run
     c->th_src_foci = n_foci;
     return OLX_OK;
 }
@@ -2707,7 +2884,12 @@ int olx_thermal_run(olx_ctx* c, double dt, double baseline, int first_step, int 
     if (n_steps < 0 || first_step < 0 || first_step + n_steps > c->th_steps) return fail(c, OLX_EINVAL, "olx_thermal_run: steps [%d, %d) outside the schedule's %d", first_step, first_step + n_steps, c->th_steps);
     if (first_step > 0 && first_step != c->th_next) return fail(c, OLX_ESTATE, "olx_thermal_run: step %d does not continue the last run (next step %d)", first_step, c->th_next);
     const float* inten = c->d_th_I;
-    if (c->th_src_resident) {
+    if (c->th_src_resident && c->th_src_pii) {
+        const bool whole = c->planned && c->pii_live && c->d_pii && c->slab.x_begin == 0 && c->slab.x_count == c->grid.n[0] &&
+                           c->grid.n[0] == c->th.nx && c->grid.n[1] == c->th.ny && c->grid.n[2] == c->th.nz && c->pii_foci == c->th_src_foci;
+        if (!whole) return fail(c, OLX_ESTATE, "olx_thermal_run: no resident whole-grid pulse intensity integrals of %d foci on the thermal grid", c->th_src_foci);
+        inten = c->d_pii;
+    } else if (c->th_src_resident) {
         const bool whole = c->planned && c->d_inten && (c->flags & OLX_OUT_INTENSITY) && c->slab.x_begin == 0 && c->slab.x_count == c->grid.n[0] &&
                            c->grid.n[0] == c->th.nx && c->grid.n[1] == c->th.ny && c->grid.n[2] == c->th.nz && c->plan_foci == c->th_src_foci;
         if (!whole) return fail(c, OLX_ESTATE, "olx_thermal_run: the resident result holds no whole-grid intensity of %d foci on the thermal grid", c->th_src_foci);

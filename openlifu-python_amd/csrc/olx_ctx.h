@@ -142,8 +142,15 @@ struct olx_ctx {
     PulseParams pulse{};
     DevBuf<float> d_pmax, d_agg_pmax;
     DevBuf<double4> d_ptab; DevBuf<float> d_pw;
-    bool pii_live = false;                     // d_pii holds the pulse intensity integrals of the last launch (OLX_OUT_PII; never scaled)
-    DevBuf<float> d_pii;                       // [F * voxels], allocated only for a plan with OLX_OUT_PII
+    bool pii_live = false;                     // d_pii holds the pulse intensity integrals of the last launch (OLX_OUT_PII) or of olx_pii_upload, as scaled since by olx_pii_post
+    int pii_foci = 0;                          // ... of this many foci
+    long long pii_vox = 0;                     // voxels per volume the PII group below is sized for (pii_regrid frees it when the grid changes)
+    DevBuf<float> d_pii;                       // [F * voxels], allocated only for a plan with OLX_OUT_PII / by olx_pii_upload
+    bool pii_w_valid = false, pii_max_valid = false;   // d_pii_w / d_pii_max hold sum_f w_f PII_f / max_f PII_f of the volumes as they are now
+    DevBuf<float> d_pii_w, d_pii_max;          // [voxels] each, created by the first olx_pii_post that forms them
+    DevBuf<float> d_pii_gw;                    // [2 * PII_MAXF] olx_pii_post: the gains g_f = (float)(s_f^2), then the weights
+    DevBuf<double> d_pii_A;                    // [PII_MAXF * 12] ... its focal frames
+    DevBuf<unsigned> d_pii_peak;               // [4 * PII_MAXF + 1] ... its peaks (bit patterns)
     DevBuf<long long> d_ptrace_vox; DevBuf<float> d_ptrace;   // olx_field_pulse_trace: the voxel list and [F][n_points][n_t] samples
     // thermal model (kernel 3, olx_thermal_*): buffers of their own, apart from the field / aggregate volumes
     bool th_planned = false, th_uniform = false; ThermalParams th{};
@@ -153,6 +160,7 @@ struct olx_ctx {
     int th_steps = 0, th_max_focus = -1; std::vector<int> th_row; DevBuf<int> d_th_sf; DevBuf<float> d_th_tau;
     int th_npts = 0; DevBuf<long long> d_th_pts; DevBuf<float> d_th_trace;
     int th_src_foci = 0; bool th_src_resident = false; DevBuf<float> d_th_I;
+    bool th_src_pii = false;                   // with th_src_resident: the resident PII volumes (olx_thermal_source_pii), not the intensity
     int th_next = -1;                          // the step the next olx_thermal_run continues with (-1: nothing run since the last plan / schedule)
     // StraightRay delays (kernel 1m, olx_bf_set_medium / olx_bf_solve_medium): the non-trivial sigma planes in buffers of their own, apart from
     // the field plan's medium and volumes
@@ -231,6 +239,14 @@ static inline int reserve_aggregate(olx_ctx* c, bool with_p, bool with_i) {
     int rc = with_p ? c->d_agg_p.reserve(c, n) : OLX_OK;
     if (!rc && with_i) rc = c->d_agg_i.reserve(c, n);
     return rc;
+}
+
+// A plan or an upload puts a grid of `vox` voxels there: no PII is resident any more, and the PII group (the volumes, the weighted and
+// the max volume) is freed when it was sized for another grid
+static inline void pii_regrid(olx_ctx* c, long long vox) {
+    c->pii_live = false; c->pii_w_valid = false; c->pii_max_valid = false;
+    if (c->pii_vox != vox) { c->d_pii.release(); c->d_pii_w.release(); c->d_pii_max.release(); }
+    c->pii_vox = vox;
 }
 
 // call-scoped device scratch: freed on every return path

@@ -21,7 +21,7 @@ APOD_UNIFORM, APOD_MAXANGLE, APOD_PIECEWISE = 0, 1, 2
 COMP_MODES = {"equalize": 0, "matched": 1}   # OLX_COMP_*
 OUT_PMAG, OUT_INTENSITY, OUT_COMPLEX = 1, 2, 4
 OUT_PMAX = 64             # pulsed plans only (olx_field_pulse): also keep p_max; the OUT_PMAG slot then holds p_min
-OUT_PII = 128             # pulsed plans only: also keep the pulse intensity integral [J/cm^2] (never scaled on the device)
+OUT_PII = 128             # pulsed plans only: also keep the pulse intensity integral [J/cm^2] (scaled by pii_post only)
 MEDIUM_MODELS = {"auto": 0, "sampled": 1, "marched": 2}   # OLX_MEDIUM_*
 FIELD_DIRECTIVITY = 16     # opt-in plan flag: far-field piston directivity (needs set_element_apertures; exact per-pair kernel)
 FIELD_FP8_CORRECTION = 8   # (source compatibility: asks for what is the default since ABI v2)
@@ -41,6 +41,7 @@ SYMBOLS = [
     "olx_solution_analyze", "olx_scan_time", "olx_comm_export", "olx_comm_import", "olx_comm_transport",
     "olx_field_scale_aggregate", "olx_field_absorption", "olx_comm_ranks_seen",
     "olx_field_pulse", "olx_field_fetch_pmax", "olx_aggregate_fetch_pmax", "olx_field_fetch_pii", "olx_field_pulse_trace",
+    "olx_pii_post", "olx_pii_fetch_weighted", "olx_pii_fetch_max", "olx_pii_upload", "olx_thermal_source_pii",
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
     "olx_bf_set_medium", "olx_bf_solve_medium",
     "olx_bf_set_attenuation", "olx_bf_solve_compensated",
@@ -140,6 +141,11 @@ def load(require_gpu: bool = True):
         lib.olx_aggregate_fetch_pmax.argtypes = [vp, fp]
         lib.olx_field_fetch_pii.argtypes = [vp, fp]
         lib.olx_field_pulse_trace.argtypes = [vp, c_int, POINTER(ctypes.c_longlong), fp]
+        lib.olx_pii_post.argtypes = [vp, dp, dp, c_int, dp, dp, c_double, c_double, c_double, fp]
+        lib.olx_pii_fetch_weighted.argtypes = [vp, fp]
+        lib.olx_pii_fetch_max.argtypes = [vp, fp]
+        lib.olx_pii_upload.argtypes = [vp, c_int, fp]
+        lib.olx_thermal_source_pii.argtypes = [vp, c_int]
         lib.olx_thermal_plan.argtypes = [vp, POINTER(OlxGrid), fp, fp, fp, fp, c_double, c_double, c_double, c_double, c_double, dp]
         lib.olx_thermal_schedule.argtypes = [vp, c_int, POINTER(c_int), POINTER(c_int), dp, c_int, POINTER(ctypes.c_longlong)]
         lib.olx_thermal_source.argtypes = [vp, c_int, fp]
@@ -461,12 +467,15 @@ class Context:
         self._chk(self._lib.olx_field_time(self._h, int(iters), _fptr(ms)))
         return ms
 
-    SCANS = {"aggregate": 0, "scale": 1, "analysis_peaks": 2, "masked_peak": 3, "offset_grid": 4, "weighted_sum": 5, "fused_post": 6}
+    SCANS = {"aggregate": 0, "scale": 1, "analysis_peaks": 2, "masked_peak": 3, "offset_grid": 4, "weighted_sum": 5, "fused_post": 6,
+             "pii_scale": 7, "pii_full": 8}      # (the last two: pii_post_k over the resident PII)
 
     def scan_time(self, kernel: str, iters: int = 20):
         """(ms per launch [iters], algorithmic bytes per launch) of one streaming scan over the resident result."""
         if kernel in ("aggregate", "fused_post"):      # these rewrite the aggregate buffers: lazily handed-out aggregates are read first
             self._aggregate_overwrite()
+        if kernel in ("pii_scale", "pii_full"):
+            self._pii_overwrite()
         ms = np.empty(int(iters), dtype=np.float32)
         nbytes = c_double(0)
         self._chk(self._lib.olx_scan_time(self._h, self.SCANS[kernel], int(iters), _fptr(ms), ctypes.byref(nbytes)))
@@ -526,6 +535,59 @@ class Context:
         out = np.empty((self._plan_foci, vox.size, self._plan_nt), dtype=np.float32)
         self._chk(self._lib.olx_field_pulse_trace(self._h, int(vox.size), vox.ctypes.data_as(POINTER(ctypes.c_longlong)), _fptr(out)))
         return out
+
+    # ---- pulse intensity integrals (pii_post_k) ------------------------------------------------------------------------------
+    PII_MAX_FOCI = 8
+
+    def pii_post(self, n_foci, scale=None, weights=None, A=None, aspect=None, r_main_m=0.0, r_side_m=0.0, zmin_m=0.0):
+        """One pass over the resident PII volumes (``olx_pii_post``): ``scale`` [F] scales PII_f by float32(s_f^2) in place, ``weights`` [F]
+        forms sum_f w_f PII_f (``pii_fetch_weighted``), max_f PII_f always (``pii_fetch_max``); with the focal frames ``A`` [F, 12] returns
+        (peaks [F, 4] = mainlobe / sidelobe / global PII and mainlobe weighted, global weighted peak), else None."""
+        F = int(n_foci)
+        self._pii_overwrite()
+        sc = None if scale is None else _f64(scale, (F,))
+        w = None if weights is None else _f64(weights, (F,))
+        out = None
+        if A is not None:
+            A = _f64(A, (F, 12)); aspect = _f64(aspect, (3,))
+            out = np.empty(4 * F + 1, dtype=np.float32)
+        self._chk(self._lib.olx_pii_post(self._h, _dptr(sc), _dptr(w), F, _dptr(A), _dptr(aspect), float(r_main_m), float(r_side_m),
+                                         float(zmin_m), _fptr(out)))
+        return None if out is None else (out[:4 * F].reshape(F, 4).copy(), float(out[4 * F]))
+
+    def _pii_overwrite(self):
+        """The weighted / max volumes of the PII are about to be rewritten: whoever handed out lazy arrays on them reads those first."""
+        hook = getattr(self, "before_pii", None)
+        if hook is not None:
+            hook()
+
+    def pii_fetch_weighted(self) -> np.ndarray:
+        out = np.empty(self._shape, dtype=np.float32)
+        self._chk(self._lib.olx_pii_fetch_weighted(self._h, _fptr(out)))
+        return out
+
+    def pii_fetch_max(self) -> np.ndarray:
+        out = np.empty(self._shape, dtype=np.float32)
+        self._chk(self._lib.olx_pii_fetch_max(self._h, _fptr(out)))
+        return out
+
+    def pii_fetch(self, n_foci) -> np.ndarray:
+        """The resident PII volumes [F, nx, ny, nz] (as scaled since by ``pii_post``)."""
+        out = np.empty((int(n_foci),) + self._shape, dtype=np.float32)
+        self._chk(self._lib.olx_field_fetch_pii(self._h, _fptr(out)))
+        return out
+
+    def pii_upload(self, pii):
+        """Host PII volumes [F, nx, ny, nz] onto the grid of the current plan / upload."""
+        pii = np.ascontiguousarray(pii, dtype=np.float32)
+        if pii.ndim != 4 or (self._shape is not None and pii.shape[1:] != tuple(self._shape)):
+            raise ValueError(f"pii must be [F, nx, ny, nz] on the planned grid {self._shape}, got {pii.shape}")
+        self._pii_overwrite()
+        self._chk(self._lib.olx_pii_upload(self._h, int(pii.shape[0]), _fptr(pii)))
+
+    def thermal_source_pii(self, n_foci: int):
+        """Kernel 3 reads the resident PII volumes in place as its per-focus source volumes."""
+        self._chk(self._lib.olx_thermal_source_pii(self._h, int(n_foci)))
 
     # ---- thermal model (kernel 3) ------------------------------------------------------------------------------------------
     def thermal_plan(self, origin_m, spacing_m, n, density, specific_heat, conductivity, absorption, perfusion=0.0) -> float:

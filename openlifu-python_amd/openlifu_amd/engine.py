@@ -173,6 +173,35 @@ class WeightedResult:
         self.retired = True
 
 
+class PiiVolumeResult:
+    """Handle on one volume ``Engine.pii_post`` left in HBM: ``which`` = "max" (max_f PII_f) or "weighted" (sum_f w_f PII_f); same contract
+    as ``WeightedResult``: ``retire()`` reads a lazily handed-out array nobody has read yet before the buffer is rewritten."""
+
+    def __init__(self, engine, shape, which):
+        self.engine, self.shape, self.which = engine, tuple(int(v) for v in shape), which
+        self._lazies = []
+        self.retired = False
+
+    def fetch(self):
+        if self.retired:
+            raise RuntimeError("the device volume this array belongs to has been overwritten")
+        return self.engine.ctx.pii_fetch_max() if self.which == "max" else self.engine.ctx.pii_fetch_weighted()
+
+    def lazy_array(self, make):
+        da = make(self.fetch)
+        self._lazies.append(weakref.ref(da))
+        return da
+
+    def retire(self):
+        if self.retired:
+            return
+        for ref in self._lazies:
+            da = ref()
+            if da is not None and not da.materialized:
+                _ = da.data
+        self.retired = True
+
+
 class Engine:
     def __init__(self, device: int = 0):
         self.ctx = nat.Context(device)
@@ -186,6 +215,35 @@ class Engine:
         self.ctx.before_aggregate = self._retire_aggregate
         self._live_weighted = None
         self.ctx.before_weighted = self._retire_weighted      # (field_weighted_intensity and solution_analyze rewrite the time-average volume)
+        self._live_pii = []            # PiiVolumeResults of the last pii_post
+        self._pii_token = -1           # the result_token the resident PII volumes belong to (pii_resident)
+        self.ctx.before_pii = self._retire_pii
+
+    def _retire_pii(self):
+        live, self._live_pii = self._live_pii, []
+        for h in live:
+            h.retire()
+
+    def pii_resident(self) -> bool:
+        """The device holds PII volumes that belong to the resident result (a pulsed launch with "pii", or ``upload_pii`` since)."""
+        return self._pii_token == self.result_token
+
+    def pii_post(self, n_foci, scale=None, weights=None, frames=None, **masks):
+        """``ctx.pii_post`` over the resident PII -> (peaks | None, {"max": handle, "weighted": handle | absent}): lazy handles on the
+        volumes it left in HBM (those of an earlier call are read to the host first where somebody still holds them unread)."""
+        if not self.pii_resident():
+            raise RuntimeError("no pulse intensity integrals resident for the current device result")
+        peaks = self.ctx.pii_post(n_foci, scale=scale, weights=weights, A=frames, **masks)      # (retires the live handles through the hook)
+        vols = {"max": PiiVolumeResult(self, self.ctx._shape, "max")}
+        if weights is not None:
+            vols["weighted"] = PiiVolumeResult(self, self.ctx._shape, "weighted")
+        self._live_pii = list(vols.values())
+        return peaks, vols
+
+    def upload_pii(self, pii):
+        """Host PII volumes [F, nx, ny, nz] become the resident PII of the current device result."""
+        self.ctx.pii_upload(pii)
+        self._pii_token = self.result_token
 
     def _retire_weighted(self):
         if self._live_weighted is not None:
@@ -203,6 +261,7 @@ class Engine:
             self._live_aggregate.retire()
             self._live_aggregate = None
         self._retire_weighted()
+        self._retire_pii()
         if self._live_result is not None:
             self._live_result.retire()
             self._live_result = None
@@ -306,7 +365,7 @@ class Engine:
         (olx_field_absorption).  ``lazy=True`` returns a ``DeviceResult`` instead: the volumes
         stay in HBM until somebody reads them.  ``pulse = (cycles, dt, t_end, cfl)`` selects the pulsed model (olx_field_pulse, time axis by
         ``pulse_time_axis``): "pmag" then holds p_min and the result carries p_max under "pmax"; "pii" in ``want`` adds the pulse
-        intensity integral [J/cm^2] (OLX_OUT_PII; not for lazy results), ``trace_voxels`` (linear voxel indices) adds the waveforms
+        intensity integral [J/cm^2] (OLX_OUT_PII; a lazy result carries it like p_max, under "pii"), ``trace_voxels`` (linear voxel indices) adds the waveforms
         p(t_k) there under "trace" [F, P, n_t] (olx_field_pulse_trace)."""
         if pulse is None and ("pii" in want or trace_voxels is not None):
             raise ValueError('the pulse intensity integral ("pii") and the waveform traces need the pulsed field model')
@@ -319,8 +378,8 @@ class Engine:
                 raise NotImplementedError("pulsed field model: the multi-GPU slab / shard paths are not implemented (whole grid on one GPU only)")
             if "complex" in want:
                 raise ValueError("pulsed field model: there is no complex output (the field is a peak over time)")
-            if ("pii" in want or trace_voxels is not None) and lazy:
-                raise ValueError("pulsed field model: the pulse intensity integral and the traces are not part of a lazy result (the Solution does not carry them)")
+            if trace_voxels is not None and lazy:
+                raise ValueError("pulsed field model: the traces are not part of a lazy result (the Solution does not carry them)")
             cycles, dt, t_end, cfl = pulse
             dt, n_t = pulse_time_axis(spacing_m, n, dt, t_end, cfl)
             want = tuple(want) + ("pmax",)
@@ -361,6 +420,8 @@ class Engine:
         self.ctx.field_launch()
         self.result_token += 1
         self._pmax_resident = pulse is not None
+        if pulse is not None and "pii" in want:
+            self._pii_token = self.result_token
         if lazy and "complex" not in want:
             nx = int(n[0]) if slab is None else int(slab[1])
             self._live_result = DeviceResult(self, self.ctx.n_foci, (nx, int(n[1]), int(n[2])), want)
@@ -374,14 +435,19 @@ class Engine:
         return out
 
     # ---- kernel 3 -----------------------------------------------------------------------------
-    def thermal(self, origin_m, spacing_m, n, medium, perfusion, schedule, n_foci, dt, baseline, intensity=None, points=None):
+    def thermal(self, origin_m, spacing_m, n, medium, perfusion, schedule, n_foci, dt, baseline, intensity=None, points=None, pii_source=False):
         """Thermal model (sim/thermal.py, kernel 3) -> (rise_max [K], CEM43 [min], traces [n_steps, P] rise [K]), float32.
         ``medium = (density, specific_heat, conductivity, absorption [Np/m])``, each a float or a [nx, ny, nz] volume;
         ``schedule = (row_ptr, focus, tau)``; ``intensity`` [F, nx, ny, nz] W/cm^2 is uploaded once, None reads the resident
-        intensity in place.  The field / aggregate volumes and every lazy array over them are left as they are."""
+        intensity in place, ``pii_source`` the resident pulse intensity integrals.  The field / aggregate volumes and every lazy array over them are left as they are."""
         self.ctx.thermal_plan(origin_m, spacing_m, n, *medium, perfusion=perfusion)
         self.ctx.thermal_schedule(*schedule, points=points)
-        self.ctx.thermal_source(n_foci, intensity)
+        if pii_source:      # the resident pulse intensity integrals, read in place (the schedule's on-times carry 1 / pulse length)
+            if not self.pii_resident():
+                raise RuntimeError("no pulse intensity integrals resident for the current device result")
+            self.ctx.thermal_source_pii(n_foci)
+        else:
+            self.ctx.thermal_source(n_foci, intensity)
         self.ctx.thermal_run(dt, baseline)
         return self.ctx.thermal_fetch()
 

@@ -21,12 +21,13 @@ from typing import Any, Dict, List
 
 import numpy as np
 
+from .. import _native as nat
 from .. import bf, seg, sim
 from ..bf.apod_methods import ApodizationMethod, MediumCompensated
 from ..bf.delay_methods import Direct, StraightRay
 from ..engine import get_engine, gpu_available
 from ..geo import Point
-from ..sim.field import dataset_from_fields, lazy_stack, parse_field_model, simulate_foci, _ATTRS
+from ..sim.field import dataset_from_fields, lazy_stack, parse_field_model, parse_pii_option, simulate_foci, _ATTRS
 from ..util import dataset as ds
 from .param_constraint import ParameterConstraint
 from .solution import Solution
@@ -65,6 +66,12 @@ def pulse_from_options(sim_setup, pulse):
     if parse_field_model(getattr(sim_setup, "options", {}).get("field_model", "cw")) != "pulsed":
         return None
     return (pulse_cycles(pulse), float(sim_setup.dt), float(sim_setup.t_end), float(sim_setup.cfl))
+
+
+def pii_from_options(sim_setup) -> bool:
+    """``SimSetup.options["pulse_intensity_integral"]`` (default off; "1" / True on): the Solution also carries the pulsed model's pulse
+    intensity integral.  ValueError unless ``options["field_model"]`` is "pulsed"."""
+    return parse_pii_option(getattr(sim_setup, "options", {}))
 
 
 # module-level seam, as in the reference (plan/protocol.py:24; its tests patch this name)
@@ -211,6 +218,7 @@ class Protocol:
         sim_options = self.sim_setup if sim_options is None else sim_options
         analysis_options = self.analysis_options if analysis_options is None else analysis_options
         self.check_target(target)
+        want_pii = pii_from_options(sim_options)      # (raises when the field model has no time axis)
         custom_seam = run_simulation is not sim.run_simulation  # patched seam (reference tests mock it)
         # `params` never leaves this call on the built-in path.  With xarray installed the Dataset factories hand out real xarray objects, which
         # cannot defer: the uniform reference medium would cost five full volumes (0.3 s at 256^3) nobody reads -- the call then works on the
@@ -222,6 +230,12 @@ class Protocol:
             params = sim_options.setup_sim_scene(self.seg_method, volume=volume)
             out_coords = params.coords
         foci = self.focal_pattern.get_targets(target)
+        if want_pii and simulate:      # refused before anything is simulated
+            if custom_seam:
+                raise ValueError('SimSetup.options["pulse_intensity_integral"] needs the built-in simulation (run_simulation is patched)')
+            if len(foci) > nat.Context.PII_MAX_FOCI:
+                raise ValueError(f'SimSetup.options["pulse_intensity_integral"]: at most {nat.Context.PII_MAX_FOCI} foci (olx_pii_post), '
+                                 f"the focal pattern has {len(foci)}")
         if self.sequence.pulse_count % len(foci) != 0:
             self.fix_pulse_mismatch(on_pulse_mismatch, foci)
 
@@ -243,7 +257,7 @@ class Protocol:
                                    self.pulse.amplitude * voltage, steering_resident=resident, fp8_correction=fp8, lazy=True,
                                    hetero_planes_per_layer=int(getattr(sim_options, "options", {}).get("hetero_planes_per_layer", 1)),
                                    directivity=str(getattr(sim_options, "options", {}).get("directivity", "0")).lower() in ("1", "true", "yes"),
-                                   pulse=pulse)
+                                   pulse=pulse, want=("pmag", "intensity") + (("pii",) if want_pii else ()))
             coords = params.coords
             stacked = lazy_stack(fields, _standin_coords(coords) if ds.HAVE_XARRAY else coords, internal=ds.HAVE_XARRAY)
         elif simulate:
@@ -290,6 +304,14 @@ class Protocol:
         coords = out_coords
         dims = list(coords.dims) if hasattr(coords, "dims") else list(coords.keys())
         shape = agg.shape
+        pii_max = None
+        if want_pii and fields is not None:
+            # the pulse intensity integrals, after the fused analysis: ONE pass (olx_pii_post) forms their maximum over foci and, where
+            # Solution.scale deferred the device's volumes to this call (the factors it returned), scales them by the squares of what the
+            # pressures were scaled by
+            deferred = fused_agg if isinstance(fused_agg, np.ndarray) and solution._pii_on_device() else None
+            _, pii_vols = solution._pii_bind().pii_post(len(foci), scale=deferred)
+            pii_max = pii_vols["max"]
         eager_out = ds.HAVE_XARRAY and fields is not None
         if ds.HAVE_XARRAY and not eager_out:
             # (a patched run_simulation seam: its Datasets are whatever it returned) real xarray objects cannot defer: fetch now
@@ -300,6 +322,10 @@ class Protocol:
                                                                           attrs=_ATTRS[name]))
             aggregated = ds.make_dataset({"p_min": lazy("p_min", "pmag"), "p_max": lazy("p_max", "pmax" if agg.pulsed else "pmag"),
                                           "intensity": lazy("intensity", "intensity")})
+            if pii_max is not None:
+                name = "pulse_intensity_integral"
+                aggregated[name] = pii_max.lazy_array(lambda fetch: ds.LazyDataArray(shape, np.float32, fetch, coords=coords, dims=dims, name=name,
+                                                                                     attrs=_ATTRS[name]))
         if analysis is None:
             analysis = solution.analyze(options=analysis_options, param_constraints=self.param_constraints, _host_unchanged=True)
         if eager_out:
@@ -307,6 +333,10 @@ class Protocol:
             # when xarray is installed): ONE fetch of the final per-focus volumes and of the aggregate (xa.Dataset cannot hold a
             # LazyDataArray: MissingDimensionsError)
             res = solution.simulation_result
-            solution.simulation_result = ds.stack_foci({k: (np.asarray(res[k].data), coords, _ATTRS[k]) for k in ("p_max", "p_min", "intensity")})
+            keys = ("p_max", "p_min", "intensity") + (("pulse_intensity_integral",) if pii_max is not None else ())
+            solution.simulation_result = ds.stack_foci({k: (np.asarray(res[k].data), coords, _ATTRS[k]) for k in keys})
             aggregated = aggregate_dataset_eager(agg, coords, dims)
+            if pii_max is not None:
+                aggregated["pulse_intensity_integral"] = ds.make_dataarray(pii_max.fetch(), coords=coords, dims=dims, name="pulse_intensity_integral",
+                                                                           attrs=_ATTRS["pulse_intensity_integral"])
         return solution, aggregated, analysis

@@ -25,7 +25,24 @@ from ..util import dataset as ds
 from ..util import netcdf
 from ..util.units import getunitconversion
 from ..xdc import Transducer
-from .solution_analysis import SolutionAnalysis, SolutionAnalysisOptions, beam_bounds_from_samples, focus_frames, get_focus_matrix
+from .solution_analysis import (PulseEnergyAnalysis, SolutionAnalysis, SolutionAnalysisOptions, beam_bounds_from_samples, focus_frames,
+                                get_focus_matrix)
+
+PII = "pulse_intensity_integral"      # the variable Protocol.calc_solution adds with SimSetup.options["pulse_intensity_integral"]
+_JOULE_PREFIX = {"": 1.0, "m": 1e-3, "u": 1e-6, "µ": 1e-6, "μ": 1e-6, "n": 1e-9, "k": 1e3}
+
+
+def dose_unit_scale(units) -> float:
+    """Factor from J/cm^2 to ``units`` = "<prefix>J/<area>" ("J/cm^2", "mJ/cm^2", "J/m^2", ...); ValueError for anything else.  (The unit
+    table of util/units.py mirrors the reference's and has no joule: the energy prefix is read here, the area goes through the table.)"""
+    energy, sep, area = str(units).partition("/")
+    if not sep or not energy.endswith("J") or energy[:-1] not in _JOULE_PREFIX:
+        raise ValueError(f'pulse dose units must be an energy per area such as "J/cm^2" or "mJ/cm^2", got {units!r}')
+    try:
+        per_area = getunitconversion("cm^2", area)
+    except (ValueError, KeyError, IndexError) as err:
+        raise ValueError(f'pulse dose units must be an energy per area such as "J/cm^2" or "mJ/cm^2", got {units!r}') from err
+    return 1.0 / (_JOULE_PREFIX[energy[:-1]] * per_area)
 
 
 def _default_nc_path(json_filepath: Path) -> Path:
@@ -300,6 +317,82 @@ class Solution:
         an.param_constraints = param_constraints or {}
         return an
 
+    # ---- pulse energy (DESIGN.md section 2 "pulse energy") ---------------------------------------------
+    def _require_pii(self):
+        res = self.simulation_result
+        if res is None or PII not in res:
+            raise ValueError(f'the solution carries no "{PII}": compute it with SimSetup.options["pulse_intensity_integral"] = "1" '
+                             '(and options["field_model"] = "pulsed")')
+        return res[PII]
+
+    def pulses_per_focus(self) -> np.ndarray:
+        """n_f [F]: pulses of one train aimed at focus f -- pulse k = 0 .. pulse_count - 1 aims at focus (k - 1) mod F, the assignment of
+        ``get_ita``'s pulse_seq and of ``sim.thermal.thermal_schedule``."""
+        F = self.num_foci()
+        return np.bincount((np.arange(self.sequence.pulse_count) - 1) % F, minlength=F).astype(np.int64)
+
+    def sequence_period(self) -> float:
+        """P [s] of the energy time-average: pulse_train_interval, or pulse_count pulse_interval when that is 0 (the thermal model's period)."""
+        s = self.sequence
+        return float(s.pulse_train_interval if s.pulse_train_interval != 0 else s.pulse_count * s.pulse_interval)
+
+    def pulse_length(self) -> float:
+        """T = cycles / f0 [s] of the pulsed model's tone burst (cycles = min(round(duration f0), 20), as calc_solution plans them)."""
+        return float(np.min([np.round(self.pulse.duration * self.pulse.frequency), 20])) / float(self.pulse.frequency)
+
+    def _pii_on_device(self) -> bool:
+        """True while the GPU holds THIS solution's pulse intensity integrals and the host cannot have changed them (``_device_is_current``
+        for this variable: the engine's PII belongs to the result this solution is resident as, and nobody has read the lazy array)."""
+        r = getattr(self, "_resident", None)
+        if r is None or r[0] is not get_engine() or r[1] != r[0].result_token or not r[0].pii_resident():
+            return False
+        da = self.simulation_result[PII]
+        return isinstance(da, ds.LazyDataArray) and not da.materialized
+
+    def _pii_bind(self):
+        """Make sure the GPU holds this solution's CURRENT pulse intensity integrals, on the grid ``_bind_device`` put there."""
+        da = self._require_pii()
+        eng = self._bind_device()[0]
+        if not self._pii_on_device():
+            eng.upload_pii(np.asarray(da.data))
+        return eng
+
+    def get_pulse_dose(self, units: str = "J/cm^2"):
+        """Energy one pulse train delivers per area, D(v) = sum_f n_f PII_f(v) (``pulses_per_focus``), as an [x, y, z] DataArray in
+        ``units``: one pass over the volumes on the device (``olx_pii_post``; fp32, f ascending)."""
+        da = self._require_pii()
+        scale = dose_unit_scale(units)
+        eng = self._pii_bind()
+        _, vols = eng.pii_post(self.num_foci(), weights=self.pulses_per_focus().astype(np.float64))
+        dose = vols["weighted"].fetch()
+        if scale != 1:
+            dose = dose * scale
+        dims = tuple(d for d in da.dims if d != "focal_point_index")
+        attrs = {"units": units, "long_name": "Pulse train dose"}
+        return ds.make_dataarray(dose, coords={d: da.coords[d] for d in dims if d in da.coords}, dims=dims, name="pulse_dose", attrs=attrs)
+
+    def analyze_pulse_energy(self, options: SolutionAnalysisOptions | None = None) -> PulseEnergyAnalysis:
+        """Dose numbers of the burst off the pulse intensity integrals, under the masks of ``analyze`` (one ``olx_pii_post``): per focus the
+        mainlobe / sidelobe / global peak of PII_f, the pulse-average intensity (mainlobe PII peak) / T, and the mainlobe and global peaks of
+        the energy time-average intensity I_ta = sum_f n_f PII_f / P."""
+        options = SolutionAnalysisOptions() if options is None else options
+        self._require_pii()
+        eng = self._pii_bind()
+        F = self.num_foci()
+        to_m = getunitconversion(options.distance_units, "m")
+        n_f, period, length = self.pulses_per_focus(), self.sequence_period(), self.pulse_length()
+        (peaks, glob), _ = eng.pii_post(F, weights=n_f / period, frames=self._focus_frames(), aspect=options.mainlobe_aspect_ratio,
+                                        r_main_m=options.mainlobe_radius * to_m, r_side_m=options.sidelobe_radius * to_m,
+                                        zmin_m=options.sidelobe_zmin * to_m)
+        an = PulseEnergyAnalysis(pulses_per_focus=[int(v) for v in n_f], pulse_length_s=length, sequence_period_s=period)
+        for f in range(F):
+            main, side, glb, main_ta = (float(v) for v in peaks[f])
+            an.mainlobe_pii_mJcm2.append(main * 1e3); an.sidelobe_pii_mJcm2.append(side * 1e3); an.global_pii_mJcm2.append(glb * 1e3)
+            an.mainlobe_isppa_Wcm2.append(main / length)
+            an.mainlobe_ispta_mWcm2.append(main_ta * 1e3)
+        an.global_ispta_mWcm2 = float(glob) * 1e3
+        return an
+
     def compute_scaling_factors(self, focal_pattern: FocalPattern, analysis: SolutionAnalysis) -> Tuple[np.ndarray, float, float]:
         """plan/solution.py:283-311."""
         target_mpa = focal_pattern.target_pressure * getunitconversion(focal_pattern.units, "MPa")
@@ -327,6 +420,10 @@ class Solution:
             for i in range(self.num_foci()):
                 da[i].data *= factors[i] ** power
             self._uploaded = None             # host copy edited: whatever the device holds of it is stale
+        pii_on_device = PII in res and self._pii_on_device()
+        if PII in res and not pii_on_device:      # on the host: the device's arithmetic, one fp32 multiply by float32(s_f^2)
+            for i in range(self.num_foci()):
+                res[PII][i].data *= np.float32(float(factors[i]) * float(factors[i]))
         for i in range(self.num_foci()):
             self.apodizations[i] = self.apodizations[i] * apod_factors[i]
         fused = None
@@ -339,6 +436,10 @@ class Solution:
                 fused = self._resident[0].scale_aggregate_lazy(factors)
             else:
                 self._resident[0].ctx.field_scale(factors)
+        if pii_on_device and not isinstance(fused, np.ndarray):
+            # (a deferred scale -- the factors returned below -- leaves the device's PII to the caller as it leaves the pressures:
+            # calc_solution scales and aggregates it in one olx_pii_post after its fused analysis)
+            self._resident[0].pii_post(self.num_foci(), scale=factors)
         self.voltage = v1
         return fused
 

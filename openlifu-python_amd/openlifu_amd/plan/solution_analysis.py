@@ -151,6 +151,21 @@ class SolutionAnalysis(DictMixin):
         return json.dumps(d, separators=(",", ":")) if compact else json.dumps(d, indent=4)
 
 
+@dataclass
+class PulseEnergyAnalysis(DictMixin):
+    """``Solution.analyze_pulse_energy``: the dose numbers of a burst, read off the pulse intensity integrals PII_f [J/cm^2] of a pulsed
+    Solution under the masks of ``SolutionAnalysisOptions`` (DESIGN.md section 2 "pulse energy").  Per-focus lists unless noted."""
+    mainlobe_pii_mJcm2: list = field(default_factory=list)      # peak of PII_f inside the mainlobe mask
+    sidelobe_pii_mJcm2: list = field(default_factory=list)      # ... outside the sidelobe radius, z > zmin
+    global_pii_mJcm2: list = field(default_factory=list)        # ... over z > zmin
+    mainlobe_isppa_Wcm2: list = field(default_factory=list)     # pulse-average intensity: mainlobe PII peak / pulse_length_s
+    mainlobe_ispta_mWcm2: list = field(default_factory=list)    # peak of I_ta = sum_f n_f PII_f / sequence_period_s under focus f's mainlobe mask
+    global_ispta_mWcm2: float | None = None                     # peak of I_ta over z > zmin
+    pulses_per_focus: list = field(default_factory=list)        # n_f: pulses of one train aimed at focus f
+    pulse_length_s: float | None = None                         # T = cycles / f0
+    sequence_period_s: float | None = None                      # P = pulse_train_interval, or pulse_count pulse_interval when that is 0
+
+
 def beam_bounds_from_samples(offsets: np.ndarray, values: np.ndarray, cutoff: float):
     """get_beam_bounds (plan/solution_analysis.py:488-535) on a sampled line: last offset <= 0 and first
     offset >= 0 whose value is below ``cutoff`` (NaN samples -- outside the grid -- never qualify)."""

@@ -104,7 +104,7 @@ def simulate_foci(arr, params, delays, apod, freq, amplitude, want=("pmag", "int
     """Batched core: F foci in one launch -> dict of float32 arrays [F, nx, ny, nz], or with ``lazy`` a
     ``DeviceResult`` whose volumes stay in HBM until read (``lazy_stack`` wraps it in the reference's schema).
     ``pulse = (cycles, dt, t_end, cfl)``: the pulsed model -- "pmag" holds p_min, "pmax" p_max, "pii" in ``want`` adds the pulse intensity
-    integral and ``trace_voxels`` (linear voxel indices) the waveforms there under "trace" [F, P, n_t]."""
+    integral and ``trace_voxels`` (linear voxel indices) the waveforms there under "trace" [F, P, n_t] (not with ``lazy``)."""
     if pulse is not None:
         check_pulsed_supported(arr, directivity)
     coords = params.coords
@@ -123,6 +123,24 @@ def simulate_foci(arr, params, delays, apod, freq, amplitude, want=("pmag", "int
                               trace_voxels=trace_voxels)
 
 
+def parse_pii_option(options) -> bool:
+    """``SimSetup.options["pulse_intensity_integral"]``: "1" / "true" / "yes" / True turn it on (default off); it needs
+    ``options["field_model"] = "pulsed"`` (the continuous-wave model has no time axis)."""
+    options = options or {}
+    value = options.get("pulse_intensity_integral", False)
+    if isinstance(value, str):
+        text = value.strip().lower()
+        if text not in ("", "0", "1", "false", "true", "no", "yes"):
+            raise ValueError(f'options["pulse_intensity_integral"] must be one of "0" / "1" / "false" / "true" / "no" / "yes", got {value!r}')
+        on = text in ("1", "true", "yes")
+    else:
+        on = bool(value)
+    if on and parse_field_model(options.get("field_model", "cw")) != "pulsed":
+        raise ValueError('options["pulse_intensity_integral"] needs options["field_model"] = "pulsed" '
+                         f'(got field_model = {options.get("field_model", "cw")!r}: the continuous-wave model has no time axis)')
+    return on
+
+
 def lazy_stack(result, coords, dim="focal_point_index", internal=False):
     """Dataset{p_max, p_min, intensity}[focal_point_index, x, y, z] (plan/protocol.py:341-347) over a DeviceResult:
     three independent LazyDataArrays (p_max and p_min are separate host arrays once read, as callers scale them
@@ -135,6 +153,10 @@ def lazy_stack(result, coords, dim="focal_point_index", internal=False):
     for name, key in (("p_max", "pmax" if "pmax" in result.keys else "pmag"), ("p_min", "pmag"), ("intensity", "intensity")):
         out[name] = result.lazy_array(key, lambda fetch, name=name: ds.LazyDataArray(
             result.shape, np.float32, fetch, coords=c, dims=dims, name=name, attrs=_ATTRS[name]))
+    if "pii" in result.keys:       # (Protocol.calc_solution with options["pulse_intensity_integral"]: the Solution carries it)
+        name = "pulse_intensity_integral"
+        out[name] = result.lazy_array("pii", lambda fetch: ds.LazyDataArray(result.shape, np.float32, fetch, coords=c, dims=dims, name=name,
+                                                                            attrs=_ATTRS[name]))
     # (internal: the stand-in Dataset whatever the factories hand out -- calc_solution's working copy when xarray is installed)
     return ds.Dataset(out) if internal else ds.make_dataset(out)
 

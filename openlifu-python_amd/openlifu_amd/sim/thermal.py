@@ -181,7 +181,9 @@ def run_thermal_simulation(params, solution, dt: float = 0.0, t_end: float = 0.0
     traced (one value of T per step).  The intensity is the Solution's (scaled if scaled), read in place while the device still holds it.
     ``pulse_energy`` [F, nx, ny, nz] in J/cm^2 on ``params.coords`` -- the pulsed model's pulse intensity integral, times factor^2 when the
     solution was scaled by ``factor`` -- replaces it: focus f then heats with ``pulse_energy[f] / min(duration, pulse_interval)``, so every
-    pulse deposits exactly that energy instead of the continuous-wave estimate I min(duration, pulse_interval)."""
+    pulse deposits exactly that energy instead of the continuous-wave estimate I min(duration, pulse_interval).  ``pulse_energy="solution"``
+    takes the Solution's own "pulse_intensity_integral" (``SimSetup.options["pulse_intensity_integral"]``): read in place while the device
+    still holds it (raw["source"] = "pulse_energy_resident"), else from the host variable as an array would be."""
     missing = [k for k in _MEDIUM_KEYS if k not in params]
     if missing:
         raise ValueError(f"thermal simulation: params lacks {missing}")
@@ -200,7 +202,19 @@ def run_thermal_simulation(params, solution, dt: float = 0.0, t_end: float = 0.0
                                   f"(the solution holds {n_vol} of its {F} focus volumes)")
     origin, spacing, n = grid_from_coords(coords)
     source = None
-    if pulse_energy is not None:
+    pii_resident = False
+    if isinstance(pulse_energy, str):      # "solution": the Solution's own pulse intensity integral (scaled if scaled)
+        if pulse_energy != "solution":
+            raise ValueError(f'thermal simulation: pulse_energy must be an array or "solution", got {pulse_energy!r}')
+        pii = solution._require_pii()
+        pii_resident = solution._pii_on_device()
+        if not pii_resident:
+            pulse_energy = np.asarray(pii.data)
+    if pii_resident:
+        on_time = min(float(solution.pulse.duration), float(solution.sequence.pulse_interval))
+        if not on_time > 0:
+            raise ValueError("thermal simulation: pulse_energy needs a pulse of non-zero length")
+    elif pulse_energy is not None:
         energy = np.asarray(pulse_energy, dtype=np.float64)
         if energy.shape != (F,) + tuple(int(v) for v in n):
             raise ValueError(f"thermal simulation: pulse_energy must have shape {(F,) + tuple(int(v) for v in n)}, got {energy.shape}")
@@ -220,16 +234,18 @@ def run_thermal_simulation(params, solution, dt: float = 0.0, t_end: float = 0.0
     eng = get_engine()
     if getattr(eng.ctx, "nranks", 1) > 1:
         raise NotImplementedError("thermal simulation: multi-GPU is not implemented (the context belongs to a communicator)")
-    resident = source is None and solution._device_is_current()
-    if source is None and not resident:
+    if pii_resident:      # read in place [J/cm^2]: 1 / (pulse on-time) goes into the on-times of the schedule instead of into the volumes
+        tau = tau / on_time
+    resident = source is None and not pii_resident and solution._device_is_current()
+    if source is None and not resident and not pii_resident:
         source = np.asarray(inten.data)
     rise, cem, traces = eng.thermal(origin, spacing, n, (rho, cp, kap, alpha), float(perfusion), (row_ptr, focus, tau), F,
-                                    dt, float(baseline_temperature), source, pts)
+                                    dt, float(baseline_temperature), source, pts, pii_source=pii_resident)
     dims = list(coords.dims) if hasattr(coords, "dims") else list(coords.keys())
     tmax = (float(baseline_temperature) + rise.astype(np.float64)).astype(np.float32)
     out = {name: ds.make_dataarray(vol, coords=coords, dims=dims, name=name, attrs=_ATTRS[name])
            for name, vol in (("temperature_max", tmax), ("temperature_rise_max", rise), ("CEM43", cem))}
     raw = {"dt": dt, "n_steps": n_steps, "dt_max": dt_max, "t": (np.arange(n_steps) + 1) * dt,
            "traces": float(baseline_temperature) + traces.astype(np.float64), "points_index": ijk,
-           "source": "pulse_energy" if pulse_energy is not None else "resident" if resident else "uploaded", "backend": "openlifu_amd/hip-gfx950"}
+           "source": "pulse_energy_resident" if pii_resident else "pulse_energy" if pulse_energy is not None else "resident" if resident else "uploaded", "backend": "openlifu_amd/hip-gfx950"}
     return ds.make_dataset(out), raw
