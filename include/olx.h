@@ -334,6 +334,26 @@ int olx_thermal_run(olx_ctx *ctx, double dt, double baseline, int first_step, in
 /* The maximum rise and CEM43 volumes ([voxels] floats) and the traces ([steps run * n_points] floats, step-major); any may be NULL. */
 int olx_thermal_fetch(olx_ctx *ctx, float *rise_max, float *cem43, float *traces);
 
+/* ---- kernel 4: steering map (DESIGN.md section 2 "Steering map") ---------------------------------------
+ * Where can the array steer?  Every voxel of `grid` is a candidate target, in the frame of the element table (kernel 1 with
+ * M = identity): with w = r_v - g_e, d = |w|, d' = max(d, min(spacing) / 2) and theta = kernel 1's folded angle,
+ *   pfocal_out[v]   = (p0_pa / lambda) sum_e a_e S_e D_e(v) exp(-absorption d') / d'   [Pa]
+ *   n_active_out[v] = #{ e : a_e > 0 }
+ * a_e = the apodization of olx_bf_solve (apod_kind, p0, p1; OLX_APOD_RADIANS honoured), S_e = area_m2 of olx_set_elements, D_e = the
+ * piston factor of olx_set_element_apertures with flags = OLX_FIELD_DIRECTIVITY (1 with flags = 0), absorption_np_m >= 0 a uniform
+ * absorption.  pfocal is the CW |p| of olx_field_* at v when the array is steered to v with untruncated Direct delays and this
+ * apodization.  fp32 results within 1e-5 of the volume maximum; the a_e > 0 decisions are made in fp64.
+ * Uses the resident element table (OLX_ESTATE without one, or without apertures when directivity is flagged).  Both volumes
+ * ([nx*ny*nz], C order; n_active_out may be NULL) are buffers of the context's own, created by the first call and reused: the
+ * current plan, the steering table and every resident result are left untouched.  Synchronous. */
+int olx_steer_map(olx_ctx *ctx, const olx_grid *grid, double freq, double c, double p0_pa,
+                  int apod_kind, double p0, double p1, double absorption_np_m,
+                  unsigned flags /* 0 | OLX_FIELD_DIRECTIVITY */,
+                  float *pfocal_out, int *n_active_out /* may be NULL */);
+/* Times `iters` repeats of the last olx_steer_map's map kernel (same grid and options, results rewritten with equal values) with
+ * HIP events on the context's stream; ms_each[iters] = milliseconds per launch (tools/time_steer.py).  OLX_ESTATE before a map. */
+int olx_steer_time(olx_ctx *ctx, int iters, float *ms_each);
+
 /* Bind host volumes (e.g. a Solution loaded from disk) as the context's resident result so
  * that the aggregate / scale / masked-peak entry points can run on them: [n_foci * slab voxels]
  * floats each; intensity may be NULL.  Needs no element or steering table; olx_field_launch is

@@ -82,12 +82,12 @@ int olx_ctx_destroy(olx_ctx* c) {
 const char* olx_last_error(const olx_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 #ifdef OLX_DEBUG_BOUNDS   // debug build (k_types.hip.h): the kernels' index checks report here
-extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); int olx_dbg_bounds_bfmed(unsigned*); int olx_dbg_bounds_small(unsigned*); }
+extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); int olx_dbg_bounds_bfmed(unsigned*); int olx_dbg_bounds_small(unsigned*); int olx_dbg_bounds_steer(unsigned*); }
 static int report_bounds(olx_ctx* c) {
     struct { const char* name; int (*read)(unsigned*); } units[] = {{"2g (k_coset2.hip)", olx_dbg_bounds_cosetp}, {"2e (k_coset.hip)", olx_dbg_bounds_coset},
                                                                      {"2f (k_toep.hip)", olx_dbg_bounds_toep}, {"2m (k_hmarch.hip)", olx_dbg_bounds_hmarch},
                                                                      {"2p (k_pulse.hip)", olx_dbg_bounds_pulse}, {"3 (k_thermal.hip)", olx_dbg_bounds_thermal},
-                                                                     {"1m / 1a (k_bfmed.hip)", olx_dbg_bounds_bfmed}, {"pii_post_k (k_small.hip.h)", olx_dbg_bounds_small}};
+                                                                     {"1m / 1a (k_bfmed.hip)", olx_dbg_bounds_bfmed}, {"pii_post_k (k_small.hip.h)", olx_dbg_bounds_small}, {"4 (k_steer.hip)", olx_dbg_bounds_steer}};
     int rc = OLX_OK;
     for (auto& u : units) {
         unsigned w[4] = {0, 0, 0, 0};
@@ -183,6 +183,7 @@ int olx_set_elements(olx_ctx* c, const double* pos_m, const double* normal, cons
     c->h_nrm.assign(normal, normal + 3 * (size_t)n);
     c->h_xaxis.clear(); c->h_size.clear();     // apertures belong to an element table
     c->n_el = n;
+    c->sm_valid = false;
     c->n_foci = 0;      // steering shape depends on N
     c->planned = false;
     c->steer_version++;
@@ -1453,6 +1454,89 @@ int olx_field_pulse_trace(olx_ctx* c, int n_points, const long long* voxels, flo
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));     // (a large fetch runs on streams of its own, not ordered after this one)
     return fetch_to_host(c, trace_out, c->d_ptrace, sizeof(float) * total);
+}
+
+// ---- kernel 4: steering map (DESIGN.md section 2 "Steering map") ---------------------------------------------------
+// Reads the element table (and the apertures), writes buffers of its own: the plan, the steering table and every resident result stay as they are.
+int olx_steer_map(olx_ctx* c, const olx_grid* g, double freq, double cs, double p0_pa, int apod_kind, double p0, double p1,
+                  double absorption_np_m, unsigned flags, float* pfocal_out, int* n_active_out) {
+    if (!c) return OLX_EINVAL;
+    if (!g || !pfocal_out) return fail(c, OLX_EINVAL, "olx_steer_map: null grid or output");
+    if (c->n_el <= 0) return fail(c, OLX_ESTATE, "olx_steer_map: call olx_set_elements first");
+    if (flags & ~(unsigned)OLX_FIELD_DIRECTIVITY) return fail(c, OLX_EINVAL, "olx_steer_map: flags must be 0 or OLX_FIELD_DIRECTIVITY");
+    const bool dir = (flags & OLX_FIELD_DIRECTIVITY) != 0;
+    if (dir && c->h_xaxis.empty()) return fail(c, OLX_ESTATE, "olx_steer_map: OLX_FIELD_DIRECTIVITY needs olx_set_element_apertures");
+    if (!(freq > 0) || !(cs > 0) || !std::isfinite(freq) || !std::isfinite(cs) || !std::isfinite(p0_pa))
+        return fail(c, OLX_EINVAL, "olx_steer_map: freq and c must be finite and > 0, p0_pa finite");
+    if (!(absorption_np_m >= 0) || !std::isfinite(absorption_np_m)) return fail(c, OLX_EINVAL, "olx_steer_map: absorption must be finite and >= 0");
+    double hmin = 1e300;
+    for (int a = 0; a < 3; ++a) {
+        if (g->n[a] < 1) return fail(c, OLX_EINVAL, "olx_steer_map: grid sizes must be >= 1");
+        if (!(g->spacing[a] > 0) || !std::isfinite(g->spacing[a]) || !std::isfinite(g->origin[a]))
+            return fail(c, OLX_EINVAL, "olx_steer_map: grid spacing must be finite and > 0, origin finite");
+        hmin = std::min(hmin, g->spacing[a]);
+    }
+    const double to_rad = (apod_kind & OLX_APOD_RADIANS) ? 1.0 : (3.14159265358979323846 / 180.0);
+    const int kind = apod_kind & ~OLX_APOD_RADIANS;
+    if (kind < 0 || kind > 2) return fail(c, OLX_EINVAL, "olx_steer_map: unknown apod_kind %d", apod_kind);
+    if (!std::isfinite(p0) || (kind != OLX_APOD_UNIFORM && !(p0 >= 0))) return fail(c, OLX_EINVAL, "olx_steer_map: apodization parameter must be finite (angles >= 0)");
+    if (kind == OLX_APOD_PIECEWISE && !(p1 < p0 && p1 >= 0)) return fail(c, OLX_EINVAL, "olx_steer_map: rolloff must be >= 0 and < zero angle");
+    SteerParams P{};
+    P.n_el = c->n_el;
+    P.nx = g->n[0]; P.ny = g->n[1]; P.nz = g->n[2];
+    P.vox = (long long)P.nx * P.ny * P.nz;
+    if ((long long)P.nx * P.ny * ((P.nz + 3) / 4) > (long long)INT_MAX * 128) return fail(c, OLX_EINVAL, "olx_steer_map: grid too large");
+    P.ox = g->origin[0]; P.oy = g->origin[1]; P.oz = g->origin[2];
+    P.hx = g->spacing[0]; P.hy = g->spacing[1]; P.hz = g->spacing[2];
+    P.dmin2 = (float)(0.25 * hmin * hmin);
+    P.value = kind == OLX_APOD_UNIFORM ? (float)p0 : 1.0f;
+    P.lim2 = 2.0;      // every angle passes
+    if (kind != OLX_APOD_UNIFORM) {
+        const double lim = p0 * to_rad, half_pi = 1.5707963267948966;
+        if (kind == OLX_APOD_MAXANGLE ? lim < half_pi : lim <= half_pi) { const double s = std::sin(lim); P.lim2 = s * s; }
+        if (kind == OLX_APOD_PIECEWISE) { const double span = (p0 - p1) * to_rad; P.pw_scale = (float)(1.0 / span); P.pw_off = (float)(lim / span); }
+    }
+    P.absorb_l2 = (float)(absorption_np_m * 1.4426950408889634);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)c->n_el;
+    int rc = c->d_sm_p.reserve(c, (size_t)P.vox);
+    if (!rc) rc = c->d_sm_n.reserve(c, (size_t)P.vox);
+    if (!rc) rc = c->d_sm_tabd.reserve(c, n * STEER_TD);
+    if (!rc) rc = c->d_sm_tabf.reserve(c, n * STEER_TF);
+    if (!rc && dir) rc = c->d_sm_ap.reserve(c, n * 5);
+    if (rc) return rc;
+    if (dir) {
+        HIPCHK(c, hipMemcpyAsync(c->d_sm_ap, c->h_xaxis.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync((double*)c->d_sm_ap + 3 * n, c->h_size.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    }
+    olx_launch_steer_table(c, dir ? (const double*)c->d_sm_ap : nullptr, p0_pa * freq / cs, 0.5 * freq / cs);
+    HIPCHK(c, hipGetLastError());
+    olx_launch_steer_map(c, P, kind, dir);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // (a large fetch runs on streams of its own, not ordered after this one)
+    c->sm = P; c->sm_kind = kind; c->sm_dir = dir; c->sm_valid = true;
+    rc = fetch_to_host(c, pfocal_out, c->d_sm_p, sizeof(float) * (size_t)P.vox);
+    if (!rc && n_active_out) rc = fetch_to_host(c, n_active_out, c->d_sm_n, sizeof(int) * (size_t)P.vox);
+    return rc;
+}
+
+int olx_steer_time(olx_ctx* c, int iters, float* ms_each) {
+    if (!c) return OLX_EINVAL;
+    if (iters < 1 || !ms_each) return fail(c, OLX_EINVAL, "olx_steer_time: iters < 1 or null output");
+    if (!c->sm_valid) return fail(c, OLX_ESTATE, "olx_steer_time: no olx_steer_map to repeat");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<hipEvent_t> ev(iters + 1, nullptr);
+    for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
+    HIPCHK(c, hipEventRecord(ev[0], c->stream));
+    for (int i = 0; i < iters; ++i) {   // the element records are still those of the last map: olx_set_elements clears sm_valid
+        olx_launch_steer_map(c, c->sm, c->sm_kind, c->sm_dir);
+        HIPCHK(c, hipEventRecord(ev[i + 1], c->stream));
+    }
+    hipError_t e = hipStreamSynchronize(c->stream);
+    for (int i = 0; i < iters && e == hipSuccess; ++i) e = hipEventElapsedTime(&ms_each[i], ev[i], ev[i + 1]);
+    for (auto& v : ev) hipEventDestroy(v);
+    if (e != hipSuccess) return fail(c, OLX_EHIP, "olx_steer_time: %s", hipGetErrorString(e));
+    return OLX_OK;
 }
 
 int olx_field(olx_ctx* c, const olx_grid* g, int n_foci, double freq, double cs, double rho, double p0_pa,

@@ -162,6 +162,11 @@ struct olx_ctx {
     int th_src_foci = 0; bool th_src_resident = false; DevBuf<float> d_th_I;
     bool th_src_pii = false;                   // with th_src_resident: the resident PII volumes (olx_thermal_source_pii), not the intensity
     int th_next = -1;                          // the step the next olx_thermal_run continues with (-1: nothing run since the last plan / schedule)
+    // steering map (kernel 4, olx_steer_map): result volumes and element records of their own -- they never alias the field, aggregate or PII buffers
+    DevBuf<float> d_sm_p; DevBuf<int> d_sm_n;          // [voxels] focal pressure [Pa], active elements; created by the first call, reused by later ones
+    DevBuf<double> d_sm_tabd; DevBuf<float> d_sm_tabf; // [N * STEER_TD], [N * STEER_TF] element records (olx_params.h)
+    DevBuf<double> d_sm_ap;                            // [N * 5] local x axes and sizes (directivity)
+    bool sm_valid = false; SteerParams sm{}; int sm_kind = 0; bool sm_dir = false;   // the last olx_steer_map (olx_steer_time repeats it; olx_set_elements ends it)
     // StraightRay delays (kernel 1m, olx_bf_set_medium / olx_bf_solve_medium): the non-trivial sigma planes in buffers of their own, apart from
     // the field plan's medium and volumes
     bool bm_set = false; BfMedParams bm{};

@@ -183,6 +183,21 @@ struct BfMedParams {
     int nx, ny, nz, n_planes;       // grid; non-trivial sigma planes held
 };
 
+// kernel 4 (steer_table_k / steer_map_k, k_steer.hip): focal pressure when steered to each voxel (olx_steer_map)
+constexpr int STEER_TD = 8;          // fp64 record per element: { gx, gy, gz, 0 | nx, ny, nz, 0 }  (position [m], unit normal)
+constexpr int STEER_TF = 16;         // fp32 record: { nx, ny, nz, P0 S / lambda | ex (local x axis), w / (2 lambda) | ey = n x ex, l / (2 lambda) | 0 x 4 }
+struct SteerParams {
+    int n_el;
+    int nx, ny, nz;
+    long long vox;
+    double ox, oy, oz, hx, hy, hz;  // voxel (0,0,0) position and spacing [m]
+    double lim2;                    // MaxAngle: sin^2(theta_max); PiecewiseLinear: sin^2(zero angle); 2 = every angle passes (>= 90 deg)
+    float dmin2;                    // (min(spacing) / 2)^2 [m^2]: the distance clamp
+    float value;                    // Uniform: the apodization value
+    float pw_scale, pw_off;         // PiecewiseLinear: a = clip(pw_off - pw_scale theta, 0, 1), theta [rad]
+    float absorb_l2;                // uniform absorption as log2(e) Np/m
+};
+
 struct PeakParams {
     int nx, ny, nz;
     double ox, oy, oz, hx, hy, hz;  // slab voxel (0,0,0) position and spacing [m]

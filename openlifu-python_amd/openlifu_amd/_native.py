@@ -45,6 +45,7 @@ SYMBOLS = [
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
     "olx_bf_set_medium", "olx_bf_solve_medium",
     "olx_bf_set_attenuation", "olx_bf_solve_compensated",
+    "olx_steer_map", "olx_steer_time",
 ]
 
 
@@ -146,6 +147,8 @@ def load(require_gpu: bool = True):
         lib.olx_pii_fetch_max.argtypes = [vp, fp]
         lib.olx_pii_upload.argtypes = [vp, c_int, fp]
         lib.olx_thermal_source_pii.argtypes = [vp, c_int]
+        lib.olx_steer_time.argtypes = [vp, c_int, fp]
+        lib.olx_steer_map.argtypes = [vp, POINTER(OlxGrid), c_double, c_double, c_double, c_int, c_double, c_double, c_double, c_uint, fp, POINTER(c_int32)]
         lib.olx_thermal_plan.argtypes = [vp, POINTER(OlxGrid), fp, fp, fp, fp, c_double, c_double, c_double, c_double, c_double, dp]
         lib.olx_thermal_schedule.argtypes = [vp, c_int, POINTER(c_int), POINTER(c_int), dp, c_int, POINTER(ctypes.c_longlong)]
         lib.olx_thermal_source.argtypes = [vp, c_int, fp]
@@ -323,6 +326,30 @@ class Context:
                                                      _dptr(delays), _dptr(apod)))
         self.n_foci = F
         return delays, apod
+
+    # -- kernel 4 (steering map)
+    def steer_map(self, origin_m, spacing_m, n, freq, c, p0_pa=1.0, apod_kind=APOD_UNIFORM, p0=1.0, p1=0.0, absorption=0.0,
+                  directivity=False):
+        """Focal pressure [Pa] when steered to each voxel of the grid, and the number of elements that contribute there ->
+        (float32 [nx,ny,nz], int32 [nx,ny,nz]).  Uses the resident element table (and apertures, with ``directivity``); leaves the plan,
+        the steering table and every resident result as they are (olx_steer_map)."""
+        shape = tuple(int(v) for v in n)
+        g = OlxGrid()
+        for a in range(3):
+            g.origin[a] = float(origin_m[a]); g.spacing[a] = float(spacing_m[a]); g.n[a] = shape[a]
+        if min(shape) < 1:
+            raise ValueError(f"grid sizes must be >= 1, got {shape}")
+        pf = np.empty(shape, dtype=np.float32); na = np.empty(shape, dtype=np.int32)
+        self._chk(self._lib.olx_steer_map(self._h, ctypes.byref(g), float(freq), float(c), float(p0_pa), int(apod_kind), float(p0), float(p1),
+                                          float(absorption), FIELD_DIRECTIVITY if directivity else 0, _fptr(pf),
+                                          na.ctypes.data_as(POINTER(c_int32))))
+        return pf, na
+
+    def steer_time(self, iters: int) -> np.ndarray:
+        """Milliseconds of ``iters`` repeats of the last ``steer_map``'s kernel (HIP events)."""
+        ms = np.empty(int(iters), dtype=np.float32)
+        self._chk(self._lib.olx_steer_time(self._h, int(iters), _fptr(ms)))
+        return ms
 
     def set_steering(self, delays_s, apod):
         delays_s = _f64(np.atleast_2d(delays_s)); apod = _f64(np.atleast_2d(apod))

@@ -434,6 +434,24 @@ class Engine:
             out["trace"] = self.ctx.field_pulse_trace(trace_voxels)
         return out
 
+    # ---- kernel 4 -----------------------------------------------------------------------------
+    def steering_map(self, arr, origin_m, spacing_m, n, freq, c, p0_pa, apod=(nat.APOD_UNIFORM, 1.0, 0.0), absorption=0.0, directivity=False):
+        """Focal pressure [Pa] when ``arr`` is steered to each voxel of the grid and the number of contributing elements there ->
+        (float32 [nx, ny, nz], int32 [nx, ny, nz]) (olx_steer_map, kernel 4).  ``apod`` = the apodization's kernel-1 arguments,
+        ``absorption`` [Np/m] a uniform absorption, ``directivity`` the elements' piston factor.  The volumes are buffers of their own:
+        the plan, the steering table and the resident results stay as they are -- unless the element table (or, with ``directivity``,
+        the apertures) has to be uploaded, which un-plans the context: arrays handed out lazily are brought to the host first."""
+        if self.ctx.comm_transport():
+            raise NotImplementedError("steering map: a context that belongs to a communicator is not supported (one GPU, whole grid)")
+        if directivity or self._table_of(arr)[3] != self._table_key:
+            self.retire_results()
+        self.bind(arr)
+        if directivity:
+            self.ctx.set_element_apertures(*arr.element_apertures())
+        kind, p0, p1 = apod
+        return self.ctx.steer_map(origin_m, spacing_m, n, freq, c, p0_pa=p0_pa, apod_kind=kind, p0=p0, p1=p1, absorption=absorption,
+                                  directivity=directivity)
+
     # ---- kernel 3 -----------------------------------------------------------------------------
     def thermal(self, origin_m, spacing_m, n, medium, perfusion, schedule, n_foci, dt, baseline, intensity=None, points=None, pii_source=False):
         """Thermal model (sim/thermal.py, kernel 3) -> (rise_max [K], CEM43 [min], traces [n_steps, P] rise [K]), float32.

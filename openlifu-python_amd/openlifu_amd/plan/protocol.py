@@ -190,6 +190,17 @@ class Protocol:
             if tc.dim in target.dims:
                 tc.check_bounds(target.get_position(dim=tc.dim, units=tc.units))
 
+    # ---- steering map (DESIGN.md section 2 "Steering map") ------------------------------------------
+    def calc_steering_map(self, transducer, params=None, reference=None):
+        """Where can ``transducer`` steer under this protocol?  ``SteeringMap`` on ``params.coords`` (None: the protocol's ``sim_setup``
+        grid in the UniformWater scene) with the protocol's ``apod_method`` and the pulse's frequency and amplitude; ``reference`` as in
+        ``plan.calc_steering_map``.  ``SteeringMap.to_target_constraints`` gives boxes for ``target_constraints``."""
+        from .steering import calc_steering_map
+        if params is None:
+            params = self.sim_setup.setup_sim_scene(seg.seg_methods.UniformWater())
+        return calc_steering_map(transducer, params, apod_method=self.apod_method, freq=self.pulse.frequency, amplitude=self.pulse.amplitude,
+                                 reference=reference)
+
     def fix_pulse_mismatch(self, on_pulse_mismatch, foci: List[Point]):
         if on_pulse_mismatch is OnPulseMismatchAction.ERROR:
             raise ValueError(f"Pulse Count {self.sequence.pulse_count} is not a multiple of the number of foci {len(foci)}")
