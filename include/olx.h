@@ -210,10 +210,24 @@ int olx_bf_quantize(olx_ctx *ctx, double bf_clk_hz, int width_bits, uint16_t *ti
  *   blocks next to the array, 17-32 columns in one tile, complex output -- keeps three fp16 products (<= 2e-6).  OLX_FIELD_FP16_CORRECTION
  *   in `flags` (or OLX_FP8_CORRECTION=0 in the environment) opts out everywhere; nothing can opt IN past the rule in the
  *   product library (OLX_FP8_CORRECTION=1 is honoured by developer builds only).
- *   olx_field_variant() names the kernel in use ("fp8corr" when the e4m3 products are active). */
+ *   olx_field_variant() names the kernel in use ("fp8corr" when the e4m3 products are active).
+ * intensity (OLX_OUT_INTENSITY): a continuous-wave plan in a homogeneous medium DERIVES it.  Kernel 2 stores |p| only (an intensity-only
+ *   plan stores |p| as well), no intensity volumes are reserved, and every reader -- the fetches, the scans, olx_solution_analyze, the
+ *   aggregates, olx_field_scale (which then scales |p| only) -- forms I = (|p| * |p|) * k from the float32 |p| as it is stored, k =
+ *   (float)(1e-4 / (2 rho c)): two separately rounded fp32 products, the same bits on every path.  The few readers of whole intensity
+ *   volumes (olx_field_masked_peak(which = 1), olx_field_sample(which = 1), the resident source of olx_thermal_run) fill such volumes from
+ *   |p| on their first call; they stay valid until the next launch, scaling or plan.  Pulsed plans, a heterogeneous medium
+ *   (olx_field_set_medium switches the plan back), uploaded results, and any plan made with OLX_INTENSITY_STORED=1 in the environment (read
+ *   by olx_field_plan; the pin for same-binary A/B runs and for callers that need the former bits) keep separately stored volumes, written
+ *   by kernel 2 as m * s_i from the squared magnitude m.  The two forms differ by rounding only: see olx_field_fetch. */
 int olx_field_plan(olx_ctx *ctx, const olx_grid *grid, const olx_slab *slab /*NULL = whole grid*/,
                    int n_foci, double freq, double c, double rho, double p0_pa, unsigned flags);
 int olx_field_launch(olx_ctx *ctx);
+/* One focus' volumes into caller-owned memory (any may be NULL).  intensity of a launched continuous-wave plan in a homogeneous medium
+ * is DEFINED as (|p| * |p|) * k of the float32 |p| this call returns (see olx_field_plan; formed on the device in one volume of scratch, then
+ * copied out) -- no longer a separately rounded product of the squared magnitude.  Measured worst relative difference per voxel between the
+ * two: 3.9e-7 (kernels 2a / 2e / 2f / 2g, tests/test_gpu_derived_intensity.py; worst-case arithmetic: 6.6e-7), fifty times below the
+ * 2e-5 gate against the fp64 definition; |p| is bit-identical. */
 int olx_field_fetch(olx_ctx *ctx, int focus, float *pmag, float *intensity, float *cplx);
 /* All planned focus volumes at once ([F * slab voxels] floats each, either may be NULL): one pipelined transfer through a
  * ring of pinned chunks whose copy-out into the caller's (pageable, caller-owned) arrays runs on several host threads. */

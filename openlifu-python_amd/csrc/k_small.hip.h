@@ -288,6 +288,9 @@ typedef float olx_f4_t __attribute__((ext_vector_type(4)));
 #define OLX_SCAN_WPE_FIELD_MASKED_PEAK_K 4
 #define OLX_SCAN_WPE_FIELD_ANALYSIS_PEAKS4_K 1
 #define OLX_SCAN_WPE_FIELD_SCALE_AGG_ANALYZE_K 1
+// ... except the fused post-pass of a plan that derives its intensity (whole row quads): the compiler's own choice takes 288 registers (one wave per SIMD) and
+// runs 0.533 ms against the stored form's 0.493; held to two waves it spills 64 registers and still runs 0.389 ms (same box, 8 foci x 256^3, 2026-10-18)
+#define OLX_SCAN_WPE_SAA_DERIVE 2
 __device__ __forceinline__ float4 ld4s(const float4* p) {
     const olx_f4_t v = __builtin_nontemporal_load(reinterpret_cast<const olx_f4_t*>(p));
     return make_float4(v.x, v.y, v.z, v.w);
@@ -315,9 +318,13 @@ __device__ __forceinline__ void st4u(float* p, const float4 v, const int cnt) {
 }
 #define OLX_LD4(p) __builtin_nontemporal_load(p)
 #define OLX_ST4(p, v) __builtin_nontemporal_store(v, p)
+// DERIVE (a plan that derives its intensity, olx_ctx::derive_i): no intensity volumes exist -- the mean takes olx_inten(|p|, ik) of the |p| just
+// loaded (pmag is never null then; imean says whether the mean is wanted), the same sum over f of the same rounded values
+template <bool DERIVE>
 __global__ __launch_bounds__(256) void field_aggregate_k(const float* __restrict__ pmag, const float* __restrict__ inten,
-                                  int n_foci, long long vox, float inv /* 1 / total foci (all ranks) */,
+                                  int n_foci, long long vox, float inv /* 1 / total foci (all ranks) */, float ik,
                                   float* __restrict__ pmax, float* __restrict__ imean) {
+    const bool want_i = DERIVE ? imean != nullptr : inten != nullptr;
     const long long stride = (long long)gridDim.x * blockDim.x;
     // 16-byte main loop (every focus volume starts 16-byte aligned when vox % 4 == 0), up to 8 foci = 16 independent loads in
     // flight per lane; the max / sum run over f in the same order as the scalar tail, so both forms give the same bits
@@ -326,8 +333,11 @@ __global__ __launch_bounds__(256) void field_aggregate_k(const float* __restrict
         float4 m = make_float4(0.f, 0.f, 0.f, 0.f), sm = m;
 #pragma unroll 8
         for (int f = 0; f < n_foci; ++f) {
-            if (pmag) { const olx_f4_t p = OLX_LD4(reinterpret_cast<const olx_f4_t*>(pmag + (long long)f * vox) + q); m.x = fmaxf(m.x, p.x); m.y = fmaxf(m.y, p.y); m.z = fmaxf(m.z, p.z); m.w = fmaxf(m.w, p.w); }
-            if (inten) { const olx_f4_t w = OLX_LD4(reinterpret_cast<const olx_f4_t*>(inten + (long long)f * vox) + q); sm.x += w.x; sm.y += w.y; sm.z += w.z; sm.w += w.w; }
+#pragma clang fp contract(off)      // (DERIVE: __fmul_rn is a plain product to the compiler -- the sum must take olx_inten's ROUNDED value, never fuse it)
+            olx_f4_t p = {0.f, 0.f, 0.f, 0.f};
+            if (pmag) { p = OLX_LD4(reinterpret_cast<const olx_f4_t*>(pmag + (long long)f * vox) + q); m.x = fmaxf(m.x, p.x); m.y = fmaxf(m.y, p.y); m.z = fmaxf(m.z, p.z); m.w = fmaxf(m.w, p.w); }
+            if constexpr (DERIVE) { if (want_i) { sm.x += olx_inten(p.x, ik); sm.y += olx_inten(p.y, ik); sm.z += olx_inten(p.z, ik); sm.w += olx_inten(p.w, ik); } }
+            else if (want_i) { const olx_f4_t w = OLX_LD4(reinterpret_cast<const olx_f4_t*>(inten + (long long)f * vox) + q); sm.x += w.x; sm.y += w.y; sm.z += w.z; sm.w += w.w; }
         }
         if (pmax) st4s(reinterpret_cast<float4*>(pmax) + q, m);
         if (imean) st4s(reinterpret_cast<float4*>(imean) + q, make_float4(sm.x * inv, sm.y * inv, sm.z * inv, sm.w * inv));
@@ -335,8 +345,10 @@ __global__ __launch_bounds__(256) void field_aggregate_k(const float* __restrict
     for (long long v = (v4 << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x; v < vox; v += stride) {
         float m = 0.f, s = 0.f;
         for (int f = 0; f < n_foci; ++f) {
-            if (pmag) m = fmaxf(m, pmag[(long long)f * vox + v]);
-            if (inten) s += inten[(long long)f * vox + v];
+#pragma clang fp contract(off)
+            const float p = pmag ? pmag[(long long)f * vox + v] : 0.f;
+            m = fmaxf(m, p);
+            if (want_i) s += DERIVE ? olx_inten(p, ik) : inten[(long long)f * vox + v];
         }
         if (pmax) pmax[v] = m;
         if (imean) imean[v] = s * inv;
@@ -377,8 +389,10 @@ __global__ __launch_bounds__(256) void field_aggregate_p_k(const float* __restri
 // p_f *= s_f, I_f *= s_f^2 written back in place, and max_f p_f / mean_f I_f of the SCALED values written beside them -- the
 // same products, the same order of the max / sum over f as field_scale_k followed by field_aggregate_k (bit-identical), but
 // the volumes cross HBM twice (read + write) instead of three times.  float4 per lane; vox % 4 == 0 (host-checked).
+// DERIVE: only |p| is scaled and stored; the intensity that enters the mean is olx_inten of the scaled |p| (no intensity volume is touched).
+template <bool DERIVE>
 __global__ __launch_bounds__(256) void field_scale_aggregate_k(float* __restrict__ pmag, float* __restrict__ inten, const float* __restrict__ scale,
-                                                                int n_foci, long long vox, float inv, float* __restrict__ pmax, float* __restrict__ imean) {
+                                                                int n_foci, long long vox, float inv, float ik, float* __restrict__ pmax, float* __restrict__ imean) {
     const long long stride = (long long)gridDim.x * blockDim.x, v4 = vox >> 2;
     for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < v4; q += stride) {
         float4 m = make_float4(0.f, 0.f, 0.f, 0.f), sm = m;
@@ -387,11 +401,16 @@ __global__ __launch_bounds__(256) void field_scale_aggregate_k(float* __restrict
 #pragma clang fp contract(off)      // the sums take the ROUNDED products that are stored (what field_aggregate_k reads back), never an fma
             const float s = scale[f], s2 = s * s;
             float4* pp = reinterpret_cast<float4*>(pmag + (long long)f * vox) + q;
-            float4* ip = reinterpret_cast<float4*>(inten + (long long)f * vox) + q;
-            float4 p = ld4s(pp), w = ld4s(ip);
+            float4 p = ld4s(pp), w;
             p.x *= s; p.y *= s; p.z *= s; p.w *= s;
-            w.x *= s2; w.y *= s2; w.z *= s2; w.w *= s2;
-            st4s(pp, p); st4s(ip, w);
+            st4s(pp, p);
+            if constexpr (DERIVE) w = olx_inten4(p, ik);
+            else {
+                float4* ip = reinterpret_cast<float4*>(inten + (long long)f * vox) + q;
+                w = ld4s(ip);
+                w.x *= s2; w.y *= s2; w.z *= s2; w.w *= s2;
+                st4s(ip, w);
+            }
             m.x = fmaxf(m.x, p.x); m.y = fmaxf(m.y, p.y); m.z = fmaxf(m.z, p.z); m.w = fmaxf(m.w, p.w);
             sm.x += w.x; sm.y += w.y; sm.z += w.z; sm.w += w.w;
         }
@@ -613,9 +632,11 @@ __global__ __launch_bounds__(256, OLX_SCAN_WPE_FIELD_MASKED_PEAK_K) void field_m
 // focal-frame arithmetic and comparisons as field_masked_peak_k (ops 0, 2, 4), so the six numbers are bit-identical to six
 // separate scans; out[f][6] = (main p, main I, side p, side I, global p, global I), integer atomicMax of the float bits.
 // ------------------------------------------------------------------------------------
+// DERIVE: the intensity of a voxel is olx_inten(|p|, ik) of the |p| just loaded; `inten` is not read.
+template <bool DERIVE>
 __global__ __launch_bounds__(256) void field_analysis_peaks_k(const float* __restrict__ pmag, const float* __restrict__ inten,
                                                                const double* __restrict__ A, const PeakParams P /*radius = r_main*/,
-                                                               const double r_side, unsigned* __restrict__ out /*[F][6]*/) {
+                                                               const double r_side, const float ik, unsigned* __restrict__ out /*[F][6]*/) {
     const int f = blockIdx.y;
     __shared__ double sA[12];
     __shared__ float s_red[4][6];
@@ -636,7 +657,7 @@ __global__ __launch_bounds__(256) void field_analysis_peaks_k(const float* __res
         const double q2 = (sA[8] * x + sA[9] * y + sA[10] * z + sA[11]) * P.ia2;
         const double dist = sqrt(q0 * q0 + q1 * q1 + q2 * q2);
         const bool zok = z > P.zmin;
-        const float p = vp[i], w = vi[i];
+        const float p = vp[i], w = DERIVE ? olx_inten(p, ik) : vi[i];
         if (dist < P.radius) { m[0] = fmaxf(m[0], p); m[1] = fmaxf(m[1], w); }
         if (zok && dist > r_side) { m[2] = fmaxf(m[2], p); m[3] = fmaxf(m[3], w); }
         if (zok) { m[4] = fmaxf(m[4], p); m[5] = fmaxf(m[5], w); }
@@ -808,8 +829,10 @@ __global__ __launch_bounds__(256) void tof_spread_k(const double* __restrict__ x
 // counts shaped [1, 1, 1, F]) returns every focus' OWN intensity times the two duty cycles, and analyze takes `.where(mask).max()` /
 // `(ita * z_mask).max()` over that whole stack (plan/solution.py:243, 274) -- i.e. the maximum over foci AND voxels.  This volume is the
 // maximum over foci, so that the masked peaks taken from it are the reference's numbers.  (The kernel keeps its round-2 name.)
+// DERIVE: vol holds the |p| volumes and the weighted value is w_f olx_inten(|p_f|, ik).
+template <bool DERIVE>
 __global__ __launch_bounds__(256) void field_weighted_sum_k(const float* __restrict__ vol, const float* __restrict__ wts, int n_foci,
-                                     long long vox, float* __restrict__ out) {
+                                     long long vox, float ik, float* __restrict__ out) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     const long long v4 = (vox & 3) == 0 ? (vox >> 2) : 0;          // 16-byte main loop, scalar tail (same sums)
     for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < v4; q += stride) {
@@ -817,14 +840,15 @@ __global__ __launch_bounds__(256) void field_weighted_sum_k(const float* __restr
 #pragma unroll 8
         for (int f = 0; f < n_foci; ++f) {
             const float w = wts[f];
-            const float4 v = ld4s(reinterpret_cast<const float4*>(vol + (long long)f * vox) + q);
+            float4 v = ld4s(reinterpret_cast<const float4*>(vol + (long long)f * vox) + q);
+            if constexpr (DERIVE) v = olx_inten4(v, ik);
             s.x = fmaxf(s.x, w * v.x); s.y = fmaxf(s.y, w * v.y); s.z = fmaxf(s.z, w * v.z); s.w = fmaxf(s.w, w * v.w);
         }
         st4s(reinterpret_cast<float4*>(out) + q, s);
     }
     for (long long v = (v4 << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x; v < vox; v += stride) {
         float s = 0.f;
-        for (int f = 0; f < n_foci; ++f) s = fmaxf(s, wts[f] * vol[(long long)f * vox + v]);
+        for (int f = 0; f < n_foci; ++f) { const float x = vol[(long long)f * vox + v]; s = fmaxf(s, wts[f] * (DERIVE ? olx_inten(x, ik) : x)); }
         out[v] = s;
     }
 }
@@ -834,9 +858,10 @@ __global__ __launch_bounds__(256) void field_weighted_sum_k(const float* __restr
 // divisions: there is no hardware integer divide) is paid once per 32 bytes of traffic instead of once per 8.  The fp64 focal-frame
 // expression and the comparisons per voxel are the ones of field_analysis_peaks_k, so the peaks are bit-identical.
 // ------------------------------------------------------------------------------------
+template <bool DERIVE>   // (as field_analysis_peaks_k: the intensity from the |p| quad in registers, half the loads)
 __global__ __launch_bounds__(256, OLX_SCAN_WPE_FIELD_ANALYSIS_PEAKS4_K) void field_analysis_peaks4_k(const float* __restrict__ pmag, const float* __restrict__ inten,
                                                                 const double* __restrict__ A, const PeakParams P /*radius = r_main*/,
-                                                                const double r_side, unsigned* __restrict__ out /*[F][6]*/) {
+                                                                const double r_side, const float ik, unsigned* __restrict__ out /*[F][6]*/) {
     const int f = blockIdx.y;
     __shared__ double sA[12];
     __shared__ float s_red[4][6];
@@ -862,7 +887,8 @@ __global__ __launch_bounds__(256, OLX_SCAN_WPE_FIELD_ANALYSIS_PEAKS4_K) void fie
           const long long iu = (long long)ib + (long long)u * stride;
           const bool ok = iu < nq;
           pq[u] = ok ? ld4s(vp + iu) : make_float4(0.f, 0.f, 0.f, 0.f);
-          wq[u] = ok ? ld4s(vi + iu) : make_float4(0.f, 0.f, 0.f, 0.f);
+          if constexpr (DERIVE) wq[u] = pq[u];      // (unused: the intensity peaks follow from the |p| peaks below)
+          else wq[u] = ok ? ld4s(vi + iu) : make_float4(0.f, 0.f, 0.f, 0.f);
       }
 #pragma unroll
       for (int u = 0; u < UQ; ++u) {
@@ -902,12 +928,13 @@ __global__ __launch_bounds__(256, OLX_SCAN_WPE_FIELD_ANALYSIS_PEAKS4_K) void fie
         for (int e = 0; e < 4; ++e) {
             const bool zok = (iz0 + e) >= M.iz_first;
             const float p = pv[e], w = wv[e];
-            if (in_main[e] > 0) { m[0] = fmaxf(m[0], p); m[1] = fmaxf(m[1], w); }
-            if (zok && in_side[e] < 0) { m[2] = fmaxf(m[2], p); m[3] = fmaxf(m[3], w); }
-            if (zok) { m[4] = fmaxf(m[4], p); m[5] = fmaxf(m[5], w); }
+            if (in_main[e] > 0) { m[0] = fmaxf(m[0], p); if constexpr (!DERIVE) m[1] = fmaxf(m[1], w); }
+            if (zok && in_side[e] < 0) { m[2] = fmaxf(m[2], p); if constexpr (!DERIVE) m[3] = fmaxf(m[3], w); }
+            if (zok) { m[4] = fmaxf(m[4], p); if constexpr (!DERIVE) m[5] = fmaxf(m[5], w); }
         }
       }
     }
+    if constexpr (DERIVE) { m[1] = olx_inten(m[0], ik); m[3] = olx_inten(m[2], ik); m[5] = olx_inten(m[4], ik); }   // (olx_inten is non-decreasing in p >= 0: it commutes with max)
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
 #pragma unroll
@@ -999,8 +1026,9 @@ __global__ __launch_bounds__(256) void field_masked_moments_box_k(const float* _
 
 // out[v] = max_f w_f I_f[v] (field_weighted_sum_k) and, in the same pass, the maximum of out over the voxels with z > zmin
 // (field_masked_peak_k with op 4 on that volume): the global time-average intensity peak costs no second scan.
+template <bool DERIVE>   // (as field_weighted_sum_k)
 __global__ __launch_bounds__(256) void field_weighted_sum_peak_k(const float* __restrict__ vol, const float* __restrict__ wts, int n_foci,
-                                                                  const PeakParams P, float* __restrict__ out, unsigned* __restrict__ peak) {
+                                                                  const PeakParams P, const float ik, float* __restrict__ out, unsigned* __restrict__ peak) {
     __shared__ float s_red[4];
     const long long stride = (long long)gridDim.x * blockDim.x;
     float m = 0.f;
@@ -1011,7 +1039,8 @@ __global__ __launch_bounds__(256) void field_weighted_sum_peak_k(const float* __
 #pragma unroll 8
         for (int f = 0; f < n_foci; ++f) {
             const float w = wts[f];
-            const float4 v = ld4s(reinterpret_cast<const float4*>(vol + (long long)f * P.vox) + q);
+            float4 v = ld4s(reinterpret_cast<const float4*>(vol + (long long)f * P.vox) + q);
+            if constexpr (DERIVE) v = olx_inten4(v, ik);
             s.x = fmaxf(s.x, w * v.x); s.y = fmaxf(s.y, w * v.y); s.z = fmaxf(s.z, w * v.z); s.w = fmaxf(s.w, w * v.w);
         }
         st4s(reinterpret_cast<float4*>(out) + q, s);
@@ -1025,7 +1054,7 @@ __global__ __launch_bounds__(256) void field_weighted_sum_peak_k(const float* __
     }
     for (long long v = (v4 << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x; v < P.vox; v += stride) {
         float s = 0.f;
-        for (int f = 0; f < n_foci; ++f) s = fmaxf(s, wts[f] * vol[(long long)f * P.vox + v]);
+        for (int f = 0; f < n_foci; ++f) { const float x = vol[(long long)f * P.vox + v]; s = fmaxf(s, wts[f] * (DERIVE ? olx_inten(x, ik) : x)); }
         out[v] = s;
         const int iz = P.vox < (1ll << 31) ? (int)((unsigned)v % (unsigned)P.nz) : (int)(v % P.nz);
         const double z = P.oz + iz * P.hz;
@@ -1048,10 +1077,11 @@ __global__ __launch_bounds__(256) void field_weighted_sum_peak_k(const float* __
 // fell back to five scalar passes: calc_solution 2.9 instead of 1.7 ms at 241 x 241 x 257 x 8 foci).
 // ------------------------------------------------------------------------------------
 constexpr int SAA_MAXF = 8;
-template <bool ROWQ /*rows of any length: row quads with a partial last quad (the 16-byte aligned form measured 470 us against 790 us with the general one)*/>
-__global__ __launch_bounds__(256, OLX_SCAN_WPE_FIELD_SCALE_AGG_ANALYZE_K) void field_scale_agg_analyze_k(float* __restrict__ pmag, float* __restrict__ inten, const float* __restrict__ scale,
+template <bool ROWQ /*rows of any length: row quads with a partial last quad (the 16-byte aligned form measured 470 us against 790 us with the general one)*/,
+          bool DERIVE /*no intensity volumes: I_f = olx_inten(scaled |p_f|, ik) in registers -- the pass reads and writes |p| only, (8 F + 12) bytes per voxel*/>
+__global__ __launch_bounds__(256, (DERIVE && !ROWQ) ? OLX_SCAN_WPE_SAA_DERIVE : OLX_SCAN_WPE_FIELD_SCALE_AGG_ANALYZE_K) void field_scale_agg_analyze_k(float* __restrict__ pmag, float* __restrict__ inten, const float* __restrict__ scale,
                                                                   const float* __restrict__ wts, const double* __restrict__ A, int n_foci,
-                                                                  const PeakParams P /*radius = r_main*/, double r_side, float inv_n,
+                                                                  const PeakParams P /*radius = r_main*/, double r_side, float inv_n, const float ik,
                                                                   float* __restrict__ pmax, float* __restrict__ imean, float* __restrict__ wint,
                                                                   unsigned* __restrict__ peaks /*[F][6]*/, unsigned* __restrict__ wpeak) {
     __shared__ double sA[SAA_MAXF][12];
@@ -1092,6 +1122,15 @@ __global__ __launch_bounds__(256, OLX_SCAN_WPE_FIELD_SCALE_AGG_ANALYZE_K) void f
             {
 #pragma clang fp contract(off)      // sums of the ROUNDED scaled values (the stored ones), as the separate kernels form them
             float* const pp = pmag + (long long)f * P.vox + vo;
+            if constexpr (DERIVE) {
+                if constexpr (ROWQ && WHOLE) p4 = ld4u(pp, 4);
+                else if constexpr (ROWQ) p4 = ld4u(pp, cnt);
+                else p4 = OLX_SAA_LD(reinterpret_cast<const float4*>(pp));
+                p4.x *= s; p4.y *= s; p4.z *= s; p4.w *= s;
+                if constexpr (ROWQ) st4u(pp, p4, cnt);
+                else OLX_SAA_ST(reinterpret_cast<float4*>(pp), p4);
+                w4 = olx_inten4(p4, ik);
+            } else {
             float* const ip = inten + (long long)f * P.vox + vo;
             if constexpr (ROWQ && WHOLE) { p4 = ld4u(pp, 4); w4 = ld4u(ip, 4); }
             else if constexpr (ROWQ) { p4 = ld4u(pp, cnt); w4 = ld4u(ip, cnt); }
@@ -1100,6 +1139,7 @@ __global__ __launch_bounds__(256, OLX_SCAN_WPE_FIELD_SCALE_AGG_ANALYZE_K) void f
             w4.x *= s2; w4.y *= s2; w4.z *= s2; w4.w *= s2;
             if constexpr (ROWQ) { st4u(pp, p4, cnt); st4u(ip, w4, cnt); }
             else { OLX_SAA_ST(reinterpret_cast<float4*>(pp), p4); OLX_SAA_ST(reinterpret_cast<float4*>(ip), w4); }
+            }
             m.x = fmaxf(m.x, p4.x); m.y = fmaxf(m.y, p4.y); m.z = fmaxf(m.z, p4.z); m.w = fmaxf(m.w, p4.w);
             sm.x += w4.x; sm.y += w4.y; sm.z += w4.z; sm.w += w4.w;
             }
@@ -1135,9 +1175,11 @@ __global__ __launch_bounds__(256, OLX_SCAN_WPE_FIELD_SCALE_AGG_ANALYZE_K) void f
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const bool zok = (iz0 + e) >= iz_first;
-                if (in_main[e] > 0) { pk[f][0] = fmaxf(pk[f][0], pv[e]); pk[f][1] = fmaxf(pk[f][1], wv[e]); }
-                if (zok && in_side[e] < 0) { pk[f][2] = fmaxf(pk[f][2], pv[e]); pk[f][3] = fmaxf(pk[f][3], wv[e]); }
-                if (zok) { pk[f][4] = fmaxf(pk[f][4], pv[e]); pk[f][5] = fmaxf(pk[f][5], wv[e]); }
+                // (DERIVE: olx_inten is non-decreasing in p >= 0 -- two correctly rounded products with factors >= 0 -- so it commutes with max: the
+                // intensity peak under a mask IS olx_inten of the |p| peak under it, bit for bit, and only the |p| peaks are carried)
+                if (in_main[e] > 0) { pk[f][0] = fmaxf(pk[f][0], pv[e]); if constexpr (!DERIVE) pk[f][1] = fmaxf(pk[f][1], wv[e]); }
+                if (zok && in_side[e] < 0) { pk[f][2] = fmaxf(pk[f][2], pv[e]); if constexpr (!DERIVE) pk[f][3] = fmaxf(pk[f][3], wv[e]); }
+                if (zok) { pk[f][4] = fmaxf(pk[f][4], pv[e]); if constexpr (!DERIVE) pk[f][5] = fmaxf(pk[f][5], wv[e]); }
             }
         }
         const float4 mean4 = make_float4(sm.x * inv_n, sm.y * inv_n, sm.z * inv_n, sm.w * inv_n);
@@ -1167,6 +1209,7 @@ __global__ __launch_bounds__(256, OLX_SCAN_WPE_FIELD_SCALE_AGG_ANALYZE_K) void f
     for (int f = 0; f < SAA_MAXF; ++f)
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
+            if (DERIVE && (k & 1)) continue;
             float v = pk[f][k];
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
@@ -1180,8 +1223,10 @@ __global__ __launch_bounds__(256, OLX_SCAN_WPE_FIELD_SCALE_AGG_ANALYZE_K) void f
     }
     __syncthreads();
     if ((int)threadIdx.x < 6 * n_foci) {
-        const int k = threadIdx.x;
-        atomicMax(peaks + k, __float_as_uint(fmaxf(fmaxf(s_red[0][k], s_red[1][k]), fmaxf(s_red[2][k], s_red[3][k]))));
+        const int k = threadIdx.x, ks = DERIVE ? (k & ~1) : k;
+        float r = fmaxf(fmaxf(s_red[0][ks], s_red[1][ks]), fmaxf(s_red[2][ks], s_red[3][ks]));
+        if (DERIVE && (k & 1)) r = olx_inten(r, ik);
+        atomicMax(peaks + k, __float_as_uint(r));
     }
     if (threadIdx.x == 255) atomicMax(wpeak, __float_as_uint(fmaxf(fmaxf(s_red[0][SAA_MAXF * 6], s_red[1][SAA_MAXF * 6]), fmaxf(s_red[2][SAA_MAXF * 6], s_red[3][SAA_MAXF * 6]))));
 }

@@ -59,6 +59,13 @@ __device__ __forceinline__ float table_mod(float dx, float dy, float d, float ri
     return m;
 }
 
+// THE intensity of a launched continuous-wave result in a homogeneous medium whose plan derives it (olx_ctx::derive_i): k |p|^2 of the fp32 |p|
+// as it is stored (after any scaling), k = 1e-4 / (2 rho c) (sim/kwave_if.py:140-141).  Two separately rounded products, never an fma: every
+// reader -- the scans in registers, the fetch, the materialised volumes -- calls this, so all of them give the same bits.  (__fmul_rn is a plain product
+// to the compiler: a caller that ADDS the result does so under `#pragma clang fp contract(off)`, or the sum fuses the second product -- field_aggregate_k.)
+__device__ __forceinline__ float olx_inten(float p, float k) { return __fmul_rn(__fmul_rn(p, p), k); }
+__device__ __forceinline__ float4 olx_inten4(const float4 p, float k) { return make_float4(olx_inten(p.x, k), olx_inten(p.y, k), olx_inten(p.z, k), olx_inten(p.w, k)); }
+
 // Debug build with teeth (build.py -DOLX_DEBUG_BOUNDS --out lib/libolx_dbg.so; tests/test_gpu_debug_bounds.py): every instrumented LDS / global
 // index of the kernels' table fills, fragment reads, ray-sum gathers and epilogue stores is compared with its extent.  A violation does NOT
 // trap (a faulting wave can take the whole node down): the access is skipped, the site's bit and a count go into a per-translation-unit device

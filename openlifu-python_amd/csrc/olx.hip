@@ -155,6 +155,31 @@ static int reserve_outputs(olx_ctx* c, size_t total, int nbuf, bool want_inten, 
     return rc;
 }
 
+// The intensity volumes as a kernel argument: null in a plan that derives its intensity (the scans then form olx_inten from the |p| they load)
+static inline float* inten_arg(const olx_ctx* c) { return c->derive_i ? nullptr : (float*)c->d_inten; }
+
+// out[i] = olx_inten(pmag[i], ik): what a deriving plan's intensity IS, for the readers that want it in memory
+__global__ __launch_bounds__(256) void field_inten_fill_k(const float* __restrict__ pmag, long long n, float ik, float* __restrict__ out) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = olx_inten(pmag[i], ik);
+}
+static inline void inten_fill(olx_ctx* c, const float* pmag, size_t n, float* out) {
+    hipLaunchKernelGGL(field_inten_fill_k, dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)), dim3(256), 0, c->stream, pmag, (long long)n, c->fp.inten_scale, out);
+}
+
+// The rare readers of whole intensity volumes (a masked peak or point samples of the intensity, the thermal source, the fetch of all foci): in a deriving
+// plan d_inten is reserved on their first call and filled from the current |p| volumes; it stays valid until the next launch, scaling or plan.
+// Nothing on Protocol.calc_solution's default path comes here.
+static int materialize_intensity(olx_ctx* c) {
+    if (!c->derive_i || c->inten_live) return OLX_OK;
+    const size_t total = (size_t)c->fp.vox * c->plan_foci;
+    { int rc = c->d_inten.reserve(c, std::max(total, c->d_pmag[0].capacity())); if (rc) return rc; }
+    inten_fill(c, c->d_pmag[c->cur], total, c->d_inten);
+    HIPCHK(c, hipGetLastError());
+    c->inten_live = true;
+    return OLX_OK;
+}
+
 // ---- element table ---------------------------------------------------------------------
 int olx_set_elements(olx_ctx* c, const double* pos_m, const double* normal, const double* area_m2, int n) {
     if (!c) return OLX_EINVAL;
@@ -991,6 +1016,7 @@ static int plan_pulse(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n
     c->directivity = false; c->nbuf = 1; c->cur = 0;
     const size_t fn = (size_t)n_foci * c->n_el;
     pii_regrid(c, vox);
+    c->derive_i = false; c->inten_live = false;      // (a pulsed plan stores its intensity)
     int rc = reserve_outputs(c, total, 1, (flags & OLX_OUT_INTENSITY) != 0, false, false);
     if (!rc && (flags & OLX_OUT_PMAX)) rc = c->d_pmax.reserve(c, total);
     if (!rc && (flags & OLX_OUT_PII)) rc = c->d_pii.reserve(c, total);
@@ -1053,7 +1079,7 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
         // derived below is still valid -- an interactive caller re-plans per target while only the steering changes.  The steering-
         // dependent part (configure_variant + packing) is redone at the next launch anyway when the table changed.
         std::string env;   // the developer switches the plan below reads
-        for (const char* name : {"OLX_FIELD_VARIANT", "OLX_FP8_CORRECTION", "OLX_EXP_TOEP_SAW", "OLX_EXP_TOEP_NM", "OLX_EXP_KGRP"}) { const char* e = getenv(name); env += e ? e : ""; env += '|'; }
+        for (const char* name : {"OLX_FIELD_VARIANT", "OLX_FP8_CORRECTION", "OLX_EXP_TOEP_SAW", "OLX_EXP_TOEP_NM", "OLX_EXP_KGRP", "OLX_INTENSITY_STORED"}) { const char* e = getenv(name); env += e ? e : ""; env += '|'; }
         const bool same = c->planned && !c->uploaded && !c->hetero && !c->pulsed && memcmp(&c->grid, g, sizeof *g) == 0 && c->slab.x_begin == s.x_begin &&
                           c->slab.x_count == s.x_count && c->plan_foci == n_foci && c->freq == freq && c->c == cs && c->rho == rho &&
                           c->p0_pa == p0_pa && c->flags == flags && c->plan_absorb == c->absorb_np_m && c->nbuf == (c->comm_active() ? olx_ctx::NBUF : 1) && c->plan_env == env;
@@ -1074,7 +1100,12 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
     const size_t total = (size_t)vox * n_foci;
     c->nbuf = c->comm_active() ? olx_ctx::NBUF : 1;
     // outputs (|p| is always materialised: aggregate / allgather consume it)
-    { int rc = reserve_outputs(c, total, c->nbuf, (flags & OLX_OUT_INTENSITY) != 0, (flags & OLX_OUT_COMPLEX) != 0, true); if (rc) return rc; }
+    // Intensity: derived from |p| by its readers unless pinned to the stored form (every homogeneous kernel 2 variant drops the store when its own
+    // flags say so, so the mode does not depend on the variant the steering selects later; olx_field_set_medium switches the plan back to stored)
+    { const char* pin = getenv("OLX_INTENSITY_STORED"); c->derive_i = (flags & OLX_OUT_INTENSITY) && !(pin && *pin && strcmp(pin, "0") != 0); }
+    c->inten_live = false;
+    { int rc = reserve_outputs(c, total, c->nbuf, (flags & OLX_OUT_INTENSITY) && !c->derive_i, (flags & OLX_OUT_COMPLEX) != 0, true); if (rc) return rc; }
+    if (c->derive_i) c->d_inten.release();       // (volumes of an earlier, stored plan)
     { int rc = c->d_tab.reserve(c, (size_t)n_foci * c->n_el * TAB_STRIDE); if (rc) return rc; }
     // kernel parameters.  Table origin = grid origin; slab start expressed relative to it.
     FieldParams& P = c->fp;
@@ -1085,7 +1116,7 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
     const double dmin = 0.5 * std::min({g->spacing[0], g->spacing[1], g->spacing[2]});
     P.dmin2 = (float)(dmin * dmin * rev * rev);
     P.inten_scale = (float)(1e-4 / (2.0 * rho * cs));
-    P.vox = vox; P.flags = (flags & 7u) | OLX_OUT_PMAG;
+    P.vox = vox; P.flags = ((flags & 7u) | OLX_OUT_PMAG) & ~(c->derive_i ? (unsigned)OLX_OUT_INTENSITY : 0u);
     c->directivity = (flags & OLX_FIELD_DIRECTIVITY) != 0;
     // variant decisions from host copies (exact, fp64)
     const int n = c->n_el;
@@ -1214,6 +1245,7 @@ int olx_field_launch(olx_ctx* c) {
         c->gather_pending[b] = false;
     }
     float* pm = c->d_pmag[b];
+    c->inten_live = false;
     const bool prof = c->prof_on && (size_t)(2 * c->prof_n + 1) < c->prof_ev.size();
     if (prof) HIPCHK(c, hipEventRecord(c->prof_ev[2 * c->prof_n], c->stream));
     if (c->hetero) { if (c->marched) olx_launch_hmarch(c, pm); else olx_launch_hetero(c, pm); }
@@ -1382,6 +1414,20 @@ static int fetch_to_host(olx_ctx* c, void* dst, const void* src, size_t bytes) {
     return OLX_OK;
 }
 
+// The intensity of foci [first, first + count) of a deriving plan: formed from |p| one focus at a time in a one-volume scratch block, copied out from there
+static int fetch_derived_intensity(olx_ctx* c, float* out, int first, int count) {
+    const size_t vox = (size_t)c->fp.vox;
+    { int rc = c->d_ifetch.reserve(c, vox); if (rc) return rc; }
+    for (int f = first; f < first + count; ++f) {
+        inten_fill(c, c->d_pmag[c->cur] + vox * f, vox, c->d_ifetch);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        const int rc = fetch_to_host(c, out + vox * (size_t)(f - first), c->d_ifetch, sizeof(float) * vox);
+        if (rc) return rc;
+    }
+    return OLX_OK;
+}
+
 extern "C" {
 
 int olx_field_fetch(olx_ctx* c, int focus, float* pmag, float* intensity, float* cplx) {
@@ -1395,7 +1441,10 @@ int olx_field_fetch(olx_ctx* c, int focus, float* pmag, float* intensity, float*
     const size_t vox = (size_t)c->fp.vox, off = vox * focus;
     int rc = OLX_OK;
     if (pmag) rc = fetch_to_host(c, pmag, c->d_pmag[c->cur] + off, sizeof(float) * vox);
-    if (!rc && intensity) rc = fetch_to_host(c, intensity, c->d_inten + off, sizeof(float) * vox);
+    if (!rc && intensity) {
+        if (c->derive_i && !c->inten_live) rc = fetch_derived_intensity(c, intensity, focus, 1);
+        else rc = fetch_to_host(c, intensity, c->d_inten + off, sizeof(float) * vox);
+    }
     if (!rc && cplx) rc = fetch_to_host(c, cplx, c->d_cplx + 2 * off, sizeof(float) * 2 * vox);
     return rc;
 }
@@ -1409,7 +1458,10 @@ int olx_field_fetch_all(olx_ctx* c, float* pmag, float* intensity) {
     const size_t total = (size_t)c->fp.vox * c->plan_foci;
     int rc = OLX_OK;
     if (pmag) rc = fetch_to_host(c, pmag, c->d_pmag[c->cur], sizeof(float) * total);
-    if (!rc && intensity) rc = fetch_to_host(c, intensity, c->d_inten, sizeof(float) * total);
+    if (!rc && intensity) {
+        if (c->derive_i && !c->inten_live) rc = fetch_derived_intensity(c, intensity, 0, c->plan_foci);
+        else rc = fetch_to_host(c, intensity, c->d_inten, sizeof(float) * total);
+    }
     return rc;
 }
 
@@ -1717,6 +1769,11 @@ int olx_field_set_medium(olx_ctx* c, const float* sound_speed, const float* atte
         { int rc = c->d_inv2z.reserve(c, sv); if (rc) return rc; }
         HIPCHK(c, hipMemcpy(c->d_inv2z, iz.data(), sizeof(float) * sv, hipMemcpyHostToDevice));
     }
+    if (c->derive_i) {      // kernels 2h / 2m store their intensity (it may carry a per-voxel impedance): back to the stored form
+        c->derive_i = false; c->inten_live = false;
+        { int rc = c->d_inten.reserve(c, c->d_pmag[0].capacity()); if (rc) return rc; }
+        c->fp.flags |= OLX_OUT_INTENSITY; c->sp.flags |= OLX_OUT_INTENSITY;
+    }
     HeteroParams& H = c->hp;
     H.n_planes = np; H.n_layers = (int)layer_lo.size(); H.n_foci = c->plan_foci; H.nxg = nx; H.nyg = ny; H.xg_begin = c->slab.x_begin;
     H.inv_hx = (float)(1.0 / (g.spacing[0] * rev)); H.inv_hy = (float)(1.0 / (g.spacing[1] * rev));
@@ -1774,6 +1831,7 @@ int olx_field_upload(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_
     pii_regrid(c, vox);
     const size_t total = (size_t)vox * n_foci;
     { int rc_ = exported_buffers_quiesce(c, -1); if (rc_) return rc_; }   // (p2p: buffer 0 is rewritten, all of them may be freed)
+    c->derive_i = false; c->inten_live = false;      // (an uploaded intensity is whatever the caller says it is)
     { int rc_ = reserve_outputs(c, total, 1, intensity != nullptr, false, false); if (rc_) return rc_; }
     HIPCHK(c, hipMemcpy(c->d_pmag[0], pmag, sizeof(float) * total, hipMemcpyHostToDevice));
     if (intensity) HIPCHK(c, hipMemcpy(c->d_inten, intensity, sizeof(float) * total, hipMemcpyHostToDevice));
@@ -1823,8 +1881,8 @@ static int pmax_post(olx_ctx* c, const float* scale, bool aggregate) {
     if (scale) hipLaunchKernelGGL(field_scale_k, dim3(1024, c->plan_foci), dim3(256), 0, c->stream, c->d_pmax, (float*)nullptr, (float*)nullptr, scale, c->fp.vox);
     if (aggregate) {
         { int rc = c->d_agg_pmax.reserve(c, (size_t)c->fp.vox); if (rc) return rc; }
-        hipLaunchKernelGGL(field_aggregate_k, dim3(2048), dim3(256), 0, c->stream, c->d_pmax, (const float*)nullptr, c->plan_foci, (long long)c->fp.vox,
-                           1.0f / (float)c->plan_foci, c->d_agg_pmax, (float*)nullptr);
+        hipLaunchKernelGGL(field_aggregate_k<false>, dim3(2048), dim3(256), 0, c->stream, c->d_pmax, (const float*)nullptr, c->plan_foci, (long long)c->fp.vox,
+                           1.0f / (float)c->plan_foci, 0.f, c->d_agg_pmax, (float*)nullptr);
     }
     HIPCHK(c, hipGetLastError());
     if (aggregate) c->agg_pmax_valid = true;
@@ -1840,6 +1898,13 @@ static unsigned scan_blocks(long long want, int F) {
     const long long per_focus = std::max<long long>(2048 / std::max(F, 1), 128);
     return (unsigned)std::max<long long>(1, std::min(want, per_focus));
 }
+// the fused post-pass for the planned row length and intensity mode
+static auto saa_kernel(const olx_ctx* c) -> decltype(&field_scale_agg_analyze_k<false, false>) {
+    const bool rowq = (c->fp.nz & 3) != 0;
+    if (c->derive_i) return rowq ? field_scale_agg_analyze_k<true, true> : field_scale_agg_analyze_k<false, true>;
+    return rowq ? field_scale_agg_analyze_k<true, false> : field_scale_agg_analyze_k<false, false>;
+}
+
 extern "C" {
 
 // Streaming scans over the resident result, timed like olx_field_time: `iters` back-to-back launches of ONE scan kernel on the
@@ -1904,19 +1969,21 @@ int olx_scan_time(olx_ctx* c, int kernel, int iters, float* ms_each, double* byt
     PeakParams P; fill_scan_params(c, P, asp);
     P.radius = 2.5e-3; P.op = 0; P.use_zmin = 1; P.zmin = c->grid.origin[2] + c->grid.spacing[2];
     const long long want = (P.vox + 255) / 256;
+    const bool D = c->derive_i; const float IK_ = c->fp.inten_scale;
     HIPCHK(c, hipEventRecord(T.ev[0], c->stream));
     for (int i = 0; i < iters; ++i) {
         switch (kernel) {
-        case OLX_SCAN_AGGREGATE: { int rc = aggregate_local(c, true, true); if (rc) return rc; *bytes_per_launch = vox * (8.0 * F + 8.0); break; }
+        // (bytes: what the launched form moves -- a deriving plan reads and writes |p| only, half the per-focus traffic of the stored form)
+        case OLX_SCAN_AGGREGATE: { int rc = aggregate_local(c, true, true); if (rc) return rc; *bytes_per_launch = vox * ((D ? 4.0 : 8.0) * F + 8.0); break; }
         case OLX_SCAN_SCALE:
-            hipLaunchKernelGGL(field_scale_k, dim3(1024, F), dim3(256), 0, c->stream, c->d_pmag[c->cur], c->d_inten, (float*)nullptr, c->d_scale, c->fp.vox);
-            *bytes_per_launch = vox * 16.0 * F; break;
+            hipLaunchKernelGGL(field_scale_k, dim3(1024, F), dim3(256), 0, c->stream, c->d_pmag[c->cur], inten_arg(c), (float*)nullptr, c->d_scale, c->fp.vox);
+            *bytes_per_launch = vox * (D ? 8.0 : 16.0) * F; break;
         case OLX_SCAN_ANALYSIS_PEAKS:      // (the form olx_solution_analyze launches)
             if ((c->fp.nz & 3) == 0 && c->fp.vox < (1ll << 33))
-                hipLaunchKernelGGL(field_analysis_peaks4_k, dim3(scan_blocks(want, F), F), dim3(256), 0, c->stream, c->d_pmag[c->cur], c->d_inten, d_A, P, 5e-3, d_pk);
+                hipLaunchKernelGGL(D ? field_analysis_peaks4_k<true> : field_analysis_peaks4_k<false>, dim3(scan_blocks(want, F), F), dim3(256), 0, c->stream, c->d_pmag[c->cur], inten_arg(c), d_A, P, 5e-3, IK_, d_pk);
             else
-                hipLaunchKernelGGL(field_analysis_peaks_k, dim3((unsigned)std::min<long long>(want, 2048), F), dim3(256), 0, c->stream, c->d_pmag[c->cur], c->d_inten, d_A, P, 5e-3, d_pk);
-            *bytes_per_launch = vox * 8.0 * F; break;
+                hipLaunchKernelGGL(D ? field_analysis_peaks_k<true> : field_analysis_peaks_k<false>, dim3((unsigned)std::min<long long>(want, 2048), F), dim3(256), 0, c->stream, c->d_pmag[c->cur], inten_arg(c), d_A, P, 5e-3, IK_, d_pk);
+            *bytes_per_launch = vox * (D ? 4.0 : 8.0) * F; break;
         case OLX_SCAN_MASKED_PEAK:         // an OUTSIDE mask ('>': every voxel is visited; inside masks only visit their index box)
             P.op = 2;
             hipLaunchKernelGGL(field_masked_peak_k, dim3(scan_blocks(want, F), F), dim3(256), 0, c->stream, c->d_pmag[c->cur], d_A, P, d_pk);
@@ -1927,11 +1994,11 @@ int olx_scan_time(olx_ctx* c, int kernel, int iters, float* ms_each, double* byt
             *bytes_per_launch = vox * 32.0; break;
         case OLX_SCAN_FUSED_POST:          // scale (by 1.0) + aggregate + six peaks + time-average volume in one pass
             P.op = 0;
-            hipLaunchKernelGGL((c->fp.nz & 3) ? field_scale_agg_analyze_k<true> : field_scale_agg_analyze_k<false>, dim3(2048), dim3(256), 0, c->stream, c->d_pmag[c->cur], c->d_inten, c->d_scale, d_w, d_A, F, P, 5e-3,
-                               1.0f / (float)F, c->d_agg_p, c->d_agg_i, c->d_wint, d_pk, d_pk + 6 * (size_t)F - 1);
-            *bytes_per_launch = vox * (16.0 * F + 12.0); break;
+            hipLaunchKernelGGL(saa_kernel(c), dim3(2048), dim3(256), 0, c->stream, c->d_pmag[c->cur], inten_arg(c), c->d_scale, d_w, d_A, F, P, 5e-3,
+                               1.0f / (float)F, IK_, c->d_agg_p, c->d_agg_i, c->d_wint, d_pk, d_pk + 6 * (size_t)F - 1);
+            *bytes_per_launch = vox * ((D ? 8.0 : 16.0) * F + 12.0); break;
         default:
-            hipLaunchKernelGGL(field_weighted_sum_k, dim3(2048), dim3(256), 0, c->stream, c->d_inten, d_w, F, c->fp.vox, c->d_wint);
+            hipLaunchKernelGGL(D ? field_weighted_sum_k<true> : field_weighted_sum_k<false>, dim3(2048), dim3(256), 0, c->stream, D ? c->d_pmag[c->cur] : c->d_inten, d_w, F, c->fp.vox, IK_, c->d_wint);
             *bytes_per_launch = vox * (4.0 * F + 4.0); break;
         }
         HIPCHK(c, hipEventRecord(T.ev[i + 1], c->stream));
@@ -1950,8 +2017,12 @@ static int aggregate_local(olx_ctx* c, bool with_p, bool with_i) {
     { int rc_ = aggregate_buffers_free(c); if (rc_) return rc_; }
     if (with_p) { int rc_ = pmax_post(c, nullptr, true); if (rc_) return rc_; }
     { int rc_ = reserve_aggregate(c, with_p, with_i); if (rc_) return rc_; }
-    hipLaunchKernelGGL(field_aggregate_k, dim3(2048), dim3(256), 0, c->stream, with_p ? c->d_pmag[c->cur] : nullptr,
-                       with_i ? c->d_inten : nullptr, c->plan_foci, (long long)vox, 1.0f / (float)c->plan_foci,
+    if (c->derive_i)     // (the mean of the intensities the |p| volumes define: |p| is read whether or not its maximum is wanted)
+        hipLaunchKernelGGL(field_aggregate_k<true>, dim3(2048), dim3(256), 0, c->stream, c->d_pmag[c->cur], nullptr, c->plan_foci, (long long)vox,
+                           1.0f / (float)c->plan_foci, c->fp.inten_scale, with_p ? c->d_agg_p : nullptr, with_i ? c->d_agg_i : nullptr);
+    else
+    hipLaunchKernelGGL(field_aggregate_k<false>, dim3(2048), dim3(256), 0, c->stream, with_p ? c->d_pmag[c->cur] : nullptr,
+                       with_i ? c->d_inten : nullptr, c->plan_foci, (long long)vox, 1.0f / (float)c->plan_foci, 0.f,
                        with_p ? c->d_agg_p : nullptr, with_i ? c->d_agg_i : nullptr);
     HIPCHK(c, hipGetLastError());
     return OLX_OK;
@@ -1993,8 +2064,9 @@ int olx_field_scale(olx_ctx* c, const double* scale, int n_foci) {
     for (int i = 0; i < n_foci; ++i) s[i] = (float)scale[i];
     HIPCHK(c, hipMemcpyAsync(c->d_scale, s.data(), sizeof(float) * n_foci, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(field_scale_k, dim3(1024, n_foci), dim3(256), 0, c->stream, c->d_pmag[c->cur],
-                       (c->flags & OLX_OUT_INTENSITY) ? c->d_inten : nullptr,
+                       (c->flags & OLX_OUT_INTENSITY) ? inten_arg(c) : nullptr,      // (a deriving plan scales |p| only: intensity x s^2 follows from olx_inten)
                        (c->flags & OLX_OUT_COMPLEX) ? c->d_cplx : nullptr, c->d_scale, c->fp.vox);
+    c->inten_live = false;
     HIPCHK(c, hipGetLastError());
     { int rc_ = pmax_post(c, c->d_scale, false); if (rc_) return rc_; }
     c->agg_pmax_valid = false;
@@ -2023,8 +2095,9 @@ int olx_field_scale_aggregate(olx_ctx* c, const double* scale, int n_foci) {
     std::vector<float> s(n_foci);
     for (int i = 0; i < n_foci; ++i) s[i] = (float)scale[i];
     HIPCHK(c, hipMemcpyAsync(c->d_scale, s.data(), sizeof(float) * n_foci, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(field_scale_aggregate_k, dim3(4096), dim3(256), 0, c->stream, c->d_pmag[c->cur], c->d_inten, c->d_scale, n_foci,
-                       (long long)c->fp.vox, 1.0f / (float)n_foci, c->d_agg_p, c->d_agg_i);
+    hipLaunchKernelGGL(c->derive_i ? field_scale_aggregate_k<true> : field_scale_aggregate_k<false>, dim3(4096), dim3(256), 0, c->stream, c->d_pmag[c->cur], inten_arg(c), c->d_scale, n_foci,
+                       (long long)c->fp.vox, 1.0f / (float)n_foci, c->fp.inten_scale, c->d_agg_p, c->d_agg_i);
+    c->inten_live = false;
     HIPCHK(c, hipGetLastError());
     { int rc_ = pmax_post(c, c->d_scale, true); if (rc_) return rc_; }
     HIPCHK(c, hipStreamSynchronize(c->stream));      // (s lives on this frame)
@@ -2103,6 +2176,7 @@ int olx_field_masked_peak(olx_ctx* c, int which, const double* A, const double* 
     P.vol_stride = which == 2 ? 0 : c->fp.vox;
     const long long want = (P.vox + 255) / 256;
     dim3 grid(scan_blocks(want, F), F);
+    if (which == 1) { int rc = materialize_intensity(c); if (rc) return rc; }
     const float* vol = which == 0 ? c->d_pmag[c->cur] : (which == 1 ? c->d_inten : c->d_wint);
     if (op <= 1) {   // inside-the-ellipsoid masks: only the index box around each focus' ellipsoid is visited (same per-voxel test)
         std::vector<int> boxes(6 * (size_t)F);
@@ -2141,7 +2215,7 @@ int olx_field_analysis_peaks(olx_ctx* c, const double* A, const double* aspect, 
     P.radius = r_main_m; P.op = 0; P.use_zmin = 1; P.zmin = zmin_m; P.vox = c->fp.vox; P.vol_stride = c->fp.vox;
     const long long want = (P.vox + 255) / 256;
     dim3 grid((unsigned)std::min<long long>(want, 2048), F);
-    hipLaunchKernelGGL(field_analysis_peaks_k, grid, dim3(256), 0, c->stream, c->d_pmag[c->cur], c->d_inten, d_A, P, r_side_m, d_out);
+    hipLaunchKernelGGL(c->derive_i ? field_analysis_peaks_k<true> : field_analysis_peaks_k<false>, grid, dim3(256), 0, c->stream, c->d_pmag[c->cur], inten_arg(c), d_A, P, r_side_m, c->fp.inten_scale, d_out);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(peaks_out, d_out, sizeof(float) * 6 * F, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2354,6 +2428,7 @@ int olx_field_sample(olx_ctx* c, int which, int focus, const double* pts_m, int 
     float* d_o = scratch.at<float>(sizeof(double) * 3 * npts);
     HIPCHK(c, hipMemcpyAsync(d_pts, pts_m, sizeof(double) * 3 * npts, hipMemcpyHostToDevice, c->stream));
     PeakParams P; fill_scan_params(c, P, nullptr);
+    if (which == 1) { int rc = materialize_intensity(c); if (rc) return rc; }
     const float* vol = (which == 0 ? c->d_pmag[c->cur] : c->d_inten) + (size_t)focus * c->fp.vox;
     hipLaunchKernelGGL(field_sample_k, dim3((npts + 127) / 128), dim3(128), 0, c->stream, vol, d_pts, npts, P, d_o);
     HIPCHK(c, hipGetLastError());
@@ -2435,7 +2510,7 @@ int olx_field_weighted_intensity(olx_ctx* c, const double* weights, int n_foci) 
     std::vector<float> w(n_foci);
     for (int i = 0; i < n_foci; ++i) w[i] = (float)weights[i];
     HIPCHK(c, hipMemcpyAsync(c->d_scale, w.data(), sizeof(float) * n_foci, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(field_weighted_sum_k, dim3(2048), dim3(256), 0, c->stream, c->d_inten, c->d_scale, n_foci, c->fp.vox, c->d_wint);
+    hipLaunchKernelGGL(c->derive_i ? field_weighted_sum_k<true> : field_weighted_sum_k<false>, dim3(2048), dim3(256), 0, c->stream, c->derive_i ? c->d_pmag[c->cur] : c->d_inten, c->d_scale, n_foci, c->fp.vox, c->fp.inten_scale, c->d_wint);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return OLX_OK;
@@ -2521,19 +2596,20 @@ int olx_solution_analyze_begin(olx_ctx* c, const double* A, const double* ita_we
     // (1) the six masked peaks of |p| and intensity, one pass
     P.radius = o->r_main_m; P.op = 0; P.use_zmin = 1; P.zmin = o->zmin_m;
     const long long want = (P.vox + 255) / 256;
+    const bool D = c->derive_i; const float IK_ = c->fp.inten_scale;      // (a deriving plan: every intensity below is olx_inten of the |p| the scan loads)
     if (fused)      // scale + aggregate + peaks + time-average volume (with its global peak) in one pass
-        hipLaunchKernelGGL((c->fp.nz & 3) ? field_scale_agg_analyze_k<true> : field_scale_agg_analyze_k<false>, dim3(2048), dim3(256), 0, c->stream, c->d_pmag[c->cur], c->d_inten, reinterpret_cast<const float*>(d + in_sc),
-                           reinterpret_cast<const float*>(d + in_w), d_A, F, P, o->r_side_m, 1.0f / (float)F, c->d_agg_p, c->d_agg_i, c->d_wint, d_pk, d_ita + F);
-    if (fused) { int rc_ = pmax_post(c, reinterpret_cast<const float*>(d + in_sc), true); if (rc_) return rc_; }
-    else if (quad) hipLaunchKernelGGL(field_analysis_peaks4_k, dim3(scan_blocks(want, F), F), dim3(256), 0, c->stream, pm, c->d_inten, d_A, P, o->r_side_m, d_pk);
-    else hipLaunchKernelGGL(field_analysis_peaks_k, dim3((unsigned)std::min<long long>(want, 2048), F), dim3(256), 0, c->stream, pm, c->d_inten, d_A, P, o->r_side_m, d_pk);
+        hipLaunchKernelGGL(saa_kernel(c), dim3(2048), dim3(256), 0, c->stream, c->d_pmag[c->cur], inten_arg(c), reinterpret_cast<const float*>(d + in_sc),
+                           reinterpret_cast<const float*>(d + in_w), d_A, F, P, o->r_side_m, 1.0f / (float)F, IK_, c->d_agg_p, c->d_agg_i, c->d_wint, d_pk, d_ita + F);
+    if (fused) { c->inten_live = false; int rc_ = pmax_post(c, reinterpret_cast<const float*>(d + in_sc), true); if (rc_) return rc_; }
+    else if (quad) hipLaunchKernelGGL(D ? field_analysis_peaks4_k<true> : field_analysis_peaks4_k<false>, dim3(scan_blocks(want, F), F), dim3(256), 0, c->stream, pm, inten_arg(c), d_A, P, o->r_side_m, IK_, d_pk);
+    else hipLaunchKernelGGL(D ? field_analysis_peaks_k<true> : field_analysis_peaks_k<false>, dim3((unsigned)std::min<long long>(want, 2048), F), dim3(256), 0, c->stream, pm, inten_arg(c), d_A, P, o->r_side_m, IK_, d_pk);
     // (2) -3 dB centroid of the mainlobe: cut-off from the peak just found
     hipLaunchKernelGGL(analysis_cutoffs_k, dim3((F + 63) / 64), dim3(64), 0, c->stream, d_pk, F, o->centroid_factor, d_cut);
     P.use_zmin = 0; P.zmin = 0;
     hipLaunchKernelGGL(field_masked_moments_box_k, dim3(32, F), dim3(256), 0, c->stream, pm, d_A, d_cut, P, d_box, reinterpret_cast<double*>(d + out_mom));
     // (3) time-average intensity volume, its mainlobe peaks (F masks over the ONE volume) and its global peak above zmin
     P.zmin = o->zmin_m;        // (the global peak above zmin comes out of the same pass that writes the volume)
-    if (!fused) hipLaunchKernelGGL(field_weighted_sum_peak_k, dim3(2048), dim3(256), 0, c->stream, c->d_inten, reinterpret_cast<const float*>(d + in_w), F, P, c->d_wint, d_ita + F);
+    if (!fused) hipLaunchKernelGGL(D ? field_weighted_sum_peak_k<true> : field_weighted_sum_peak_k<false>, dim3(2048), dim3(256), 0, c->stream, D ? pm : (const float*)c->d_inten, reinterpret_cast<const float*>(d + in_w), F, P, IK_, c->d_wint, d_ita + F);
     P.vol_stride = 0; P.zmin = 0;
     hipLaunchKernelGGL(field_masked_peak_box_k, dim3(32, F), dim3(256), 0, c->stream, c->d_wint, d_A, P, d_box, d_ita);
     // (4) beam widths: |p| along the three focal axes of every focus, then the cut-off crossings
@@ -2749,12 +2825,13 @@ static int aggregate_exchange(olx_ctx* c, bool want_scatter) {
     // the local max / sum, and the mean divides by the GLOBAL number of genuine foci (olx_field_aggregate_counts)
     const int n_local = c->agg_local >= 0 ? std::min(c->agg_local, c->plan_foci) : c->plan_foci;
     const float inv_n = 1.0f / (c->agg_total > 0 ? (float)c->agg_total : (float)c->plan_foci * (float)c->nranks);
-    if (!c->uploaded && (vox & 3) == 0)   // launched result: intensity == scale(v) |p|^2, aggregate from |p| alone (half the reads)
+    if (!c->uploaded && !c->derive_i && (vox & 3) == 0)   // launched result with stored volumes: intensity == scale(v) |p|^2, aggregate from |p| alone (half the reads);
+                                                            // a deriving plan takes field_aggregate_k's DERIVE form below: also |p| alone, and the bits of the single-rank aggregate
         hipLaunchKernelGGL(field_aggregate_p_k, dim3(4096), dim3(256), 0, c->stream, c->d_pmag[c->cur], n_local, (long long)vox,
                            inv_n, c->fp.inten_scale, c->hetero ? c->d_inv2z : nullptr, c->d_agg_p, with_i ? c->d_agg_i : nullptr);
     else
-        hipLaunchKernelGGL(field_aggregate_k, dim3(2048), dim3(256), 0, c->stream, c->d_pmag[c->cur], with_i ? c->d_inten : nullptr,
-                           n_local, (long long)vox, inv_n, c->d_agg_p, with_i ? c->d_agg_i : nullptr);
+        hipLaunchKernelGGL(c->derive_i ? field_aggregate_k<true> : field_aggregate_k<false>, dim3(2048), dim3(256), 0, c->stream, c->d_pmag[c->cur], with_i ? inten_arg(c) : nullptr,
+                           n_local, (long long)vox, inv_n, c->fp.inten_scale, c->d_agg_p, with_i ? c->d_agg_i : nullptr);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_agg, c->stream));
     if (c->p2p)     // peer-to-peer transport: the same two shapes, pulled slice by slice over IPC mappings (csrc/olx_p2p.hip)
@@ -2974,13 +3051,17 @@ int olx_thermal_run(olx_ctx* c, double dt, double baseline, int first_step, int 
         if (!whole) return fail(c, OLX_ESTATE, "olx_thermal_run: no resident whole-grid pulse intensity integrals of %d foci on the thermal grid", c->th_src_foci);
         inten = c->d_pii;
     } else if (c->th_src_resident) {
-        const bool whole = c->planned && c->d_inten && (c->flags & OLX_OUT_INTENSITY) && c->slab.x_begin == 0 && c->slab.x_count == c->grid.n[0] &&
+        const bool whole = c->planned && (c->d_inten || c->derive_i) && (c->flags & OLX_OUT_INTENSITY) && c->slab.x_begin == 0 && c->slab.x_count == c->grid.n[0] &&
                            c->grid.n[0] == c->th.nx && c->grid.n[1] == c->th.ny && c->grid.n[2] == c->th.nz && c->plan_foci == c->th_src_foci;
         if (!whole) return fail(c, OLX_ESTATE, "olx_thermal_run: the resident result holds no whole-grid intensity of %d foci on the thermal grid", c->th_src_foci);
         inten = c->d_inten;
     }
     if (c->th_max_focus >= c->th_src_foci) return fail(c, OLX_EINVAL, "olx_thermal_run: the schedule names focus %d, the source has %d", c->th_max_focus, c->th_src_foci);
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->th_src_resident && !c->th_src_pii) {      // (a deriving plan forms its intensity volumes here, once every check of this call has passed)
+        int rc = materialize_intensity(c); if (rc) return rc;
+        inten = c->d_inten;
+    }
     const size_t vox = (size_t)c->th.vox;
     if (first_step == 0) {
         for (float* p : {(float*)c->d_th_T[0], (float*)c->d_th_max, (float*)c->d_th_cem}) HIPCHK(c, hipMemsetAsync(p, 0, sizeof(float) * vox, c->stream));

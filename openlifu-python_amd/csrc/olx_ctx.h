@@ -114,6 +114,12 @@ struct olx_ctx {
     static constexpr int NBUF = 2;
     DevBuf<float> d_pmag[NBUF];               // the output volumes (reserve_outputs): |p| ...
     DevBuf<float> d_inten, d_cplx, d_agg_p, d_agg_i;   // ... and the members created lazily at its capacity
+    // Intensity of a launched continuous-wave plan in a homogeneous medium: DERIVED -- no kernel 2 variant stores it, d_inten is not reserved, and every
+    // reader forms olx_inten(|p|, fp.inten_scale) from the |p| volumes (k_types.hip.h).  Pulsed plans, heterogeneous media, uploaded results and plans
+    // made under OLX_INTENSITY_STORED=1 keep the stored volumes.  `flags` keeps OLX_OUT_INTENSITY either way; the kernels' own flags drop the bit.
+    bool derive_i = false;
+    bool inten_live = false;                  // derive_i: d_inten holds olx_inten of the |p| volumes as they are now (materialize_intensity; a launch, a scaling or a plan ends it)
+    DevBuf<float> d_ifetch;                   // derive_i: one volume of scratch the intensity fetches fill focus by focus (created by the first of them)
     DevBuf<float> d_scale;
     DevBuf<double> d_peakA; DevBuf<unsigned> d_peak;
     DevBuf<float> d_wint;  // weighted-intensity (time-average) volume
