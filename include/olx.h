@@ -368,6 +368,37 @@ int olx_steer_map(olx_ctx *ctx, const olx_grid *grid, double freq, double c, dou
  * HIP events on the context's stream; ms_each[iters] = milliseconds per launch (tools/time_steer.py).  OLX_ESTATE before a map. */
 int olx_steer_time(olx_ctx *ctx, int iters, float *ms_each);
 
+/* ---- kernel 4h: steering map through a heterogeneous medium, straight rays (DESIGN.md section 2 "Steering map through a medium") ----
+ * olx_steer_map with the medium on every ray.  The volumes (float32 [nx*ny*nz] on `grid`, C order; NULL = c_ref everywhere / no
+ * attenuation) are sound speed [m/s] and attenuation [dB/cm/MHz^0.9], converted at `freq` as olx_bf_set_attenuation does.  With w, d, d',
+ * theta, b_e = the base apodization (apod_kind, p0, p1), S_e, D_e and n_active exactly as olx_steer_map's, voxel v = (i, j, kv):
+ *   K_e(v) = the grid planes k != kv strictly between z_e and z_v (kernel 2h's plane bounds, decided on the host in fp64)
+ *   A_e    = 0 if z_v == z_e, else l (a(v) / 2 + sum_{k in K} a_k(crossing_k)),  l = hz d' / |z_v - z_e|,   E_e = the same over c_ref / c - 1
+ *   h_e    = exp(-A_e)  [S_e / d' with spreading]
+ *   c_e    = b_e (OLX_STEER_COMP_NONE) | b_e min_active h / h_e (OLX_COMP_EQUALIZE) | b_e h_e / max_active h (OLX_COMP_MATCHED), active = { b_e > 0 };
+ *            no active element: 0
+ *   pfocal_out[v] = (p0_pa / lambda) sum_e c_e S_e D_e exp(-A_e) / d'                                   (OLX_STEER_DELAYS_STRAIGHTRAY)
+ *                 = (p0_pa / lambda) | sum_e c_e S_e D_e exp(-A_e) / d' exp(j 2 pi E_e / lambda) |      (OLX_STEER_DELAYS_DIRECT), lambda = c_ref / freq
+ * At a grid voxel A_e and E_e are kernel 1a's and 1m's ray sums with the focus at r_v, so pfocal is the |p| at v of the sampled
+ * heterogeneous field (olx_field_set_medium, OLX_MEDIUM_SAMPLED, one plane per layer) when the array is steered to v with
+ * olx_bf_solve_compensated / olx_bf_solve_medium (StraightRay) or olx_bf_solve (Direct).  With both volumes NULL it is olx_steer_map's map
+ * with absorption 0.  fp32 results within 1e-5 of the volume maximum; the b_e > 0 decisions are made in fp64.  An h_e that underflows is
+ * outside the method's range.
+ * Refused like olx_steer_map (no elements; directivity without apertures; a bad grid; freq / c_ref not finite and > 0), and for a sound
+ * speed <= 0 or non-finite, an attenuation negative or non-finite, an unknown comp / delays; a refusal touches nothing on the device.
+ * The stencil, the plane lists, the element records and both result volumes are buffers of the context's own, created by the first call
+ * and reused: the plan and its medium, the steering table, the media of olx_bf_set_medium / olx_bf_set_attenuation and every resident
+ * result are left untouched.  Synchronous; olx_steer_time repeats the last map of either kind. */
+#define OLX_STEER_COMP_NONE (-1)
+enum { OLX_STEER_DELAYS_STRAIGHTRAY = 0, OLX_STEER_DELAYS_DIRECT = 1 };
+int olx_steer_map_medium(olx_ctx *ctx, const olx_grid *grid, double freq, double c_ref, double p0_pa,
+                         int apod_kind, double p0, double p1,
+                         const float *sound_speed /* [nx*ny*nz] or NULL = c_ref */,
+                         const float *attenuation_db_cm_mhz /* or NULL = none */,
+                         int comp /* OLX_STEER_COMP_NONE | OLX_COMP_EQUALIZE | OLX_COMP_MATCHED */, int spreading,
+                         int delays /* OLX_STEER_DELAYS_STRAIGHTRAY | OLX_STEER_DELAYS_DIRECT */,
+                         unsigned flags /* 0 | OLX_FIELD_DIRECTIVITY */, float *pfocal_out, int *n_active_out /* may be NULL */);
+
 /* Bind host volumes (e.g. a Solution loaded from disk) as the context's resident result so
  * that the aggregate / scale / masked-peak entry points can run on them: [n_foci * slab voxels]
  * floats each; intensity may be NULL.  Needs no element or steering table; olx_field_launch is

@@ -82,12 +82,13 @@ int olx_ctx_destroy(olx_ctx* c) {
 const char* olx_last_error(const olx_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 #ifdef OLX_DEBUG_BOUNDS   // debug build (k_types.hip.h): the kernels' index checks report here
-extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); int olx_dbg_bounds_bfmed(unsigned*); int olx_dbg_bounds_small(unsigned*); int olx_dbg_bounds_steer(unsigned*); }
+extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); int olx_dbg_bounds_bfmed(unsigned*); int olx_dbg_bounds_small(unsigned*); int olx_dbg_bounds_steer(unsigned*); int olx_dbg_bounds_steermed(unsigned*); }
 static int report_bounds(olx_ctx* c) {
     struct { const char* name; int (*read)(unsigned*); } units[] = {{"2g (k_coset2.hip)", olx_dbg_bounds_cosetp}, {"2e (k_coset.hip)", olx_dbg_bounds_coset},
                                                                      {"2f (k_toep.hip)", olx_dbg_bounds_toep}, {"2m (k_hmarch.hip)", olx_dbg_bounds_hmarch},
                                                                      {"2p (k_pulse.hip)", olx_dbg_bounds_pulse}, {"3 (k_thermal.hip)", olx_dbg_bounds_thermal},
-                                                                     {"1m / 1a (k_bfmed.hip)", olx_dbg_bounds_bfmed}, {"pii_post_k (k_small.hip.h)", olx_dbg_bounds_small}, {"4 (k_steer.hip)", olx_dbg_bounds_steer}};
+                                                                     {"1m / 1a (k_bfmed.hip)", olx_dbg_bounds_bfmed}, {"pii_post_k (k_small.hip.h)", olx_dbg_bounds_small}, {"4 (k_steer.hip)", olx_dbg_bounds_steer},
+                                                                     {"4h (k_steer_med.hip)", olx_dbg_bounds_steermed}};
     int rc = OLX_OK;
     for (auto& u : units) {
         unsigned w[4] = {0, 0, 0, 0};
@@ -1566,9 +1567,145 @@ int olx_steer_map(olx_ctx* c, const olx_grid* g, double freq, double cs, double 
     olx_launch_steer_map(c, P, kind, dir);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));     // (a large fetch runs on streams of its own, not ordered after this one)
-    c->sm = P; c->sm_kind = kind; c->sm_dir = dir; c->sm_valid = true;
+    c->sm = P; c->sm_kind = kind; c->sm_dir = dir; c->sm_valid = true; c->sm_medium = false;
     rc = fetch_to_host(c, pfocal_out, c->d_sm_p, sizeof(float) * (size_t)P.vox);
     if (!rc && n_active_out) rc = fetch_to_host(c, n_active_out, c->d_sm_n, sizeof(int) * (size_t)P.vox);
+    return rc;
+}
+
+// ---- kernel 4h: steering map through a heterogeneous medium (DESIGN.md section 2 "Steering map through a medium") ----
+// Kernel 4's element records and decisions, kernel 2h's stencil and plane bounds; every buffer it writes is its own (d_smm_*) or kernel 4's element
+// records: the plan and its medium, the steering table, the media of kernels 1m / 1a and every resident result stay as they are.
+int olx_steer_map_medium(olx_ctx* c, const olx_grid* g, double freq, double cs, double p0_pa, int apod_kind, double p0, double p1,
+                         const float* sound_speed, const float* attenuation, int comp, int spreading, int delays, unsigned flags,
+                         float* pfocal_out, int* n_active_out) {
+    if (!c) return OLX_EINVAL;
+    if (!g || !pfocal_out) return fail(c, OLX_EINVAL, "olx_steer_map_medium: null grid or output");
+    if (c->n_el <= 0) return fail(c, OLX_ESTATE, "olx_steer_map_medium: call olx_set_elements first");
+    if (flags & ~(unsigned)OLX_FIELD_DIRECTIVITY) return fail(c, OLX_EINVAL, "olx_steer_map_medium: flags must be 0 or OLX_FIELD_DIRECTIVITY");
+    const bool dir = (flags & OLX_FIELD_DIRECTIVITY) != 0;
+    if (dir && c->h_xaxis.empty()) return fail(c, OLX_ESTATE, "olx_steer_map_medium: OLX_FIELD_DIRECTIVITY needs olx_set_element_apertures");
+    if (!(freq > 0) || !(cs > 0) || !std::isfinite(freq) || !std::isfinite(cs) || !std::isfinite(p0_pa))
+        return fail(c, OLX_EINVAL, "olx_steer_map_medium: freq and c_ref must be finite and > 0, p0_pa finite");
+    if (comp != OLX_STEER_COMP_NONE && comp != OLX_COMP_EQUALIZE && comp != OLX_COMP_MATCHED)
+        return fail(c, OLX_EINVAL, "olx_steer_map_medium: unknown comp %d", comp);
+    if (delays != OLX_STEER_DELAYS_STRAIGHTRAY && delays != OLX_STEER_DELAYS_DIRECT)
+        return fail(c, OLX_EINVAL, "olx_steer_map_medium: unknown delays %d", delays);
+    double hmin = 1e300;
+    for (int a = 0; a < 3; ++a) {
+        if (g->n[a] < 1) return fail(c, OLX_EINVAL, "olx_steer_map_medium: grid sizes must be >= 1");
+        if (!(g->spacing[a] > 0) || !std::isfinite(g->spacing[a]) || !std::isfinite(g->origin[a]))
+            return fail(c, OLX_EINVAL, "olx_steer_map_medium: grid spacing must be finite and > 0, origin finite");
+        hmin = std::min(hmin, g->spacing[a]);
+    }
+    const double to_rad = (apod_kind & OLX_APOD_RADIANS) ? 1.0 : (3.14159265358979323846 / 180.0);
+    const int kind = apod_kind & ~OLX_APOD_RADIANS;
+    if (kind < 0 || kind > 2) return fail(c, OLX_EINVAL, "olx_steer_map_medium: unknown apod_kind %d", apod_kind);
+    if (!std::isfinite(p0) || (kind != OLX_APOD_UNIFORM && !(p0 >= 0))) return fail(c, OLX_EINVAL, "olx_steer_map_medium: apodization parameter must be finite (angles >= 0)");
+    if (kind == OLX_APOD_PIECEWISE && !(p1 < p0 && p1 >= 0)) return fail(c, OLX_EINVAL, "olx_steer_map_medium: rolloff must be >= 0 and < zero angle");
+    const int nx = g->n[0], ny = g->n[1], nz = g->n[2];
+    const size_t nvox = (size_t)nx * ny * nz;
+    // (32-bit byte offsets into a stencil plane of 32 bytes per cell, 24-bit factors; one block per 8 x 8 x 16 voxels)
+    if ((long long)nx * ny > (1ll << 26) || nx >= (1 << 24) || ny >= (1 << 24) ||
+        (long long)((nx + 7) / 8) * ((ny + 7) / 8) * ((nz + 15) / 16) > (long long)INT_MAX)
+        return fail(c, OLX_EINVAL, "olx_steer_map_medium: grid too large");
+    if (sound_speed)
+        for (size_t o = 0; o < nvox; ++o)
+            if (!(sound_speed[o] > 0.f) || !std::isfinite(sound_speed[o])) return fail(c, OLX_EINVAL, "olx_steer_map_medium: sound speed must be finite and > 0");
+    if (attenuation)
+        for (size_t o = 0; o < nvox; ++o)
+            if (!(attenuation[o] >= 0.f) || !std::isfinite(attenuation[o])) return fail(c, OLX_EINVAL, "olx_steer_map_medium: attenuation must be finite and >= 0");
+    const bool phase = delays == OLX_STEER_DELAYS_DIRECT;
+    const float* ssv = phase ? sound_speed : nullptr;      // StraightRay delays put every term in phase: the sound speed does not enter
+    SteerMedParams M{};
+    SteerParams& P = M.S;
+    P.n_el = c->n_el;
+    P.nx = nx; P.ny = ny; P.nz = nz;
+    P.vox = (long long)nvox;
+    P.ox = g->origin[0]; P.oy = g->origin[1]; P.oz = g->origin[2];
+    P.hx = g->spacing[0]; P.hy = g->spacing[1]; P.hz = g->spacing[2];
+    P.dmin2 = (float)(0.25 * hmin * hmin);
+    P.value = kind == OLX_APOD_UNIFORM ? (float)p0 : 1.0f;
+    P.lim2 = 2.0;      // every angle passes
+    if (kind != OLX_APOD_UNIFORM) {
+        const double lim = p0 * to_rad, half_pi = 1.5707963267948966;
+        if (kind == OLX_APOD_MAXANGLE ? lim < half_pi : lim <= half_pi) { const double s = std::sin(lim); P.lim2 = s * s; }
+        if (kind == OLX_APOD_PIECEWISE) { const double span = (p0 - p1) * to_rad; P.pw_scale = (float)(1.0 / span); P.pw_off = (float)(lim / span); }
+    }
+    const double lambda = cs / freq;
+    M.inv_hx = 1.0 / P.hx; M.inv_hy = 1.0 / P.hy;
+    M.hz_w = (float)(P.hz / lambda);
+    M.abs_value = std::fabs(P.value);
+    M.spreading = spreading ? 1 : 0;
+    // non-trivial planes and their pre-gathered stencil (kernel 2h's layout and conversions, power 0.9 as kernel 1a)
+    const double afac = std::pow(freq * 1e-6, 0.9) * 100.0 / 8.685889638065035 * lambda;      // dB/cm/MHz^0.9 -> Np per wavelength
+    std::vector<int> plane_of_k(nz, -1), plane_k;
+    for (int k = 0; k < nz; ++k) {
+        bool any = false;
+        for (size_t ij = 0; ij < (size_t)nx * ny && !any; ++ij) {
+            const size_t o = ij * nz + k;
+            if (ssv && (double)ssv[o] != cs) any = true;
+            if (attenuation && attenuation[o] != 0.f) any = true;
+        }
+        if (any) { plane_of_k[k] = (int)plane_k.size(); plane_k.push_back(k); }
+    }
+    const int np = (int)plane_k.size();
+    M.n_planes = np;
+    std::vector<float> med((size_t)std::max(np, 1) * nx * ny * 8, 0.f);
+    auto term = [&](int i, int j, int k, float* out) {
+        const size_t o = ((size_t)i * ny + j) * nz + k;
+        out[0] = ssv ? (float)(cs / (double)ssv[o] - 1.0) : 0.f;
+        out[1] = attenuation ? (float)((double)attenuation[o] * afac) : 0.f;
+    };
+    for (int p = 0; p < np; ++p)
+        for (int i = 0; i < nx; ++i)
+            for (int j = 0; j < ny; ++j) {
+                float* tx = &med[(((size_t)p * nx + i) * ny + j) * 8];
+                const int i1 = std::min(i + 1, nx - 1), j1 = std::min(j + 1, ny - 1), k = plane_k[p];
+                term(i, j, k, tx); term(i, j1, k, tx + 2); term(i1, j, k, tx + 4); term(i1, j1, k, tx + 6);
+            }
+    // per element: first plane strictly above, last plane strictly below (fp64, z_k = oz + k hz: kernel 2h's table entries), and S_e
+    const size_t n = (size_t)c->n_el;
+    std::vector<float> tabm(n * STEER_TM);
+    for (size_t e = 0; e < n; ++e) {
+        const double ez = c->h_pos[2 * n + e];
+        int kf = 0;
+        while (kf < nz && !(P.oz + kf * P.hz > ez)) ++kf;
+        int kl = nz - 1;
+        while (kl >= 0 && !(P.oz + kl * P.hz < ez)) --kl;
+        float* t = &tabm[e * STEER_TM];
+        memcpy(&t[0], &kf, 4); memcpy(&t[1], &kl, 4);
+        t[2] = (float)c->h_area[e]; t[3] = (float)(1.0 / c->h_area[e]);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = c->d_smm_p.reserve(c, nvox);
+    if (!rc) rc = c->d_smm_n.reserve(c, nvox);
+    if (!rc) rc = c->d_sm_tabd.reserve(c, n * STEER_TD);
+    if (!rc) rc = c->d_sm_tabf.reserve(c, n * STEER_TF);
+    if (!rc) rc = c->d_smm_tabm.reserve(c, n * STEER_TM);
+    if (!rc) rc = c->d_smm_med.reserve(c, med.size() / 4);
+    if (!rc) rc = c->d_smm_plane_k.reserve(c, np);
+    if (!rc) rc = c->d_smm_plane_of_k.reserve(c, nz);
+    if (!rc && dir) rc = c->d_sm_ap.reserve(c, n * 5);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (the pageable copies below must not overtake a map still running on the stream)
+    HIPCHK(c, hipMemcpy(c->d_smm_med, med.data(), sizeof(float) * med.size(), hipMemcpyHostToDevice));
+    if (np) HIPCHK(c, hipMemcpy(c->d_smm_plane_k, plane_k.data(), sizeof(int) * np, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_smm_plane_of_k, plane_of_k.data(), sizeof(int) * nz, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_smm_tabm, tabm.data(), sizeof(float) * tabm.size(), hipMemcpyHostToDevice));
+    if (dir) {
+        HIPCHK(c, hipMemcpy(c->d_sm_ap, c->h_xaxis.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy((double*)c->d_sm_ap + 3 * n, c->h_size.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+    }
+    olx_launch_steer_table(c, dir ? (const double*)c->d_sm_ap : nullptr, p0_pa * freq / cs, 0.5 * freq / cs);
+    HIPCHK(c, hipGetLastError());
+    const int kcomp = comp == OLX_STEER_COMP_NONE ? 0 : (comp == OLX_COMP_EQUALIZE ? 1 : 2);
+    olx_launch_steer_map_medium(c, M, kind, kcomp, phase, dir);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // (a large fetch runs on streams of its own, not ordered after this one)
+    c->smm = M; c->sm_kind = kind; c->sm_dir = dir; c->smm_comp = kcomp; c->smm_phase = phase; c->sm_valid = true; c->sm_medium = true;
+    rc = fetch_to_host(c, pfocal_out, c->d_smm_p, sizeof(float) * nvox);
+    if (!rc && n_active_out) rc = fetch_to_host(c, n_active_out, c->d_smm_n, sizeof(int) * nvox);
     return rc;
 }
 
@@ -1581,7 +1718,8 @@ int olx_steer_time(olx_ctx* c, int iters, float* ms_each) {
     for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
     HIPCHK(c, hipEventRecord(ev[0], c->stream));
     for (int i = 0; i < iters; ++i) {   // the element records are still those of the last map: olx_set_elements clears sm_valid
-        olx_launch_steer_map(c, c->sm, c->sm_kind, c->sm_dir);
+        if (c->sm_medium) olx_launch_steer_map_medium(c, c->smm, c->sm_kind, c->smm_comp, c->smm_phase, c->sm_dir);
+        else olx_launch_steer_map(c, c->sm, c->sm_kind, c->sm_dir);
         HIPCHK(c, hipEventRecord(ev[i + 1], c->stream));
     }
     hipError_t e = hipStreamSynchronize(c->stream);

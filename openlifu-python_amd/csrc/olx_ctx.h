@@ -173,6 +173,12 @@ struct olx_ctx {
     DevBuf<double> d_sm_tabd; DevBuf<float> d_sm_tabf; // [N * STEER_TD], [N * STEER_TF] element records (olx_params.h)
     DevBuf<double> d_sm_ap;                            // [N * 5] local x axes and sizes (directivity)
     bool sm_valid = false; SteerParams sm{}; int sm_kind = 0; bool sm_dir = false;   // the last olx_steer_map (olx_steer_time repeats it; olx_set_elements ends it)
+    // steering map through a medium (kernel 4h, olx_steer_map_medium): kernel 4's element records plus buffers of its own, created by the first call and reused
+    DevBuf<float> d_smm_p; DevBuf<int> d_smm_n;        // [voxels] focal pressure [Pa], active elements
+    DevBuf<float4> d_smm_med;                          // [n_planes][nx][ny][2] pre-gathered { sig, a' } stencil of the non-trivial planes (kernel 2h's layout)
+    DevBuf<int> d_smm_plane_k, d_smm_plane_of_k;       // [n_planes] grid plane of a stencil plane; [nz] stencil plane of a grid plane, -1 = trivial
+    DevBuf<float> d_smm_tabm;                          // [N * STEER_TM] { kfirst, klast, S, 1 / S } per element
+    bool sm_medium = false; SteerMedParams smm{}; int smm_comp = 0; bool smm_phase = false;   // the last map was olx_steer_map_medium's (sm_valid, sm_kind, sm_dir are shared)
     // StraightRay delays (kernel 1m, olx_bf_set_medium / olx_bf_solve_medium): the non-trivial sigma planes in buffers of their own, apart from
     // the field plan's medium and volumes
     bool bm_set = false; BfMedParams bm{};

@@ -24,6 +24,7 @@ void olx_launch_bfmed(olx_ctx* c, int n_foci);      // 1m  bf_med_k (StraightRay
 void olx_launch_bfapod(olx_ctx* c, int n_foci, int mode, int spreading, bool with_delays);   // 1a  bf_med_k<SIG, true> (MediumCompensated apodization; with_delays: one walk with 1m's delays)
 void olx_launch_steer_table(olx_ctx* c, const double* apertures, double wscale, double inv_2lambda);   // 4  steer_table_k (element records into c->d_sm_tabd / d_sm_tabf; apertures = { xaxis [N][3], size [N][2] } on the device, or null)
 void olx_launch_steer_map(olx_ctx* c, const SteerParams& P, int kind, bool directivity);                   // 4  steer_map_k (P and n_active into c->d_sm_p / d_sm_n)
+void olx_launch_steer_map_medium(olx_ctx* c, const SteerMedParams& M, int kind, int comp /* 0 none, 1 equalize, 2 matched */, bool phase, bool directivity);   // 4h steer_map_med_k (P and n_active into c->d_smm_p / d_smm_n)
 void olx_thermal_pack(olx_ctx* c, const float* rho, const float* cp, const float* kap, const float* alpha);   // 3  thermal_pack_k (coefficients, FTCS rate)
 void olx_thermal_step(olx_ctx* c, const float* inten, int step, const ThermalStep& S);                        // 3  thermal_step_k (one step)
 void olx_thermal_trace_last(olx_ctx* c, int step);                                                          //    thermal_trace_k (last trace row)

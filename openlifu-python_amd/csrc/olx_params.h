@@ -198,6 +198,18 @@ struct SteerParams {
     float absorb_l2;                // uniform absorption as log2(e) Np/m
 };
 
+// kernel 4h (steer_map_med_k, k_steer_med.hip): the steering map through a heterogeneous medium (olx_steer_map_medium).  Element records: kernel 4's
+// two, plus one of STEER_TM floats { kfirst, klast (bit-cast ints, kernel 2h's), S_e [m^2], 1 / S_e }
+constexpr int STEER_TM = 4;
+struct SteerMedParams {
+    SteerParams S;                  // kernel 4's parameters (absorb_l2 unused)
+    double inv_hx, inv_hy;          // 1 / spacing [1/m]: crossings in grid index space
+    int n_planes;                   // non-trivial planes of the stencil
+    int spreading;                  // h_e carries S_e / d'
+    float hz_w;                     // hz / lambda: l in wavelengths = hz_w d' / |dz|
+    float abs_value;                // Uniform: |value| (Direct delays: P is a modulus)
+};
+
 struct PeakParams {
     int nx, ny, nz;
     double ox, oy, oz, hx, hy, hz;  // slab voxel (0,0,0) position and spacing [m]

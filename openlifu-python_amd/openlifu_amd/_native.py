@@ -19,6 +19,8 @@ LIB_PATH = os.environ.get("OLX_LIB_PATH") or os.path.join(os.path.dirname(_PKG_D
 OLX_OK, OLX_EINVAL, OLX_ESTATE, OLX_EHIP, OLX_ENOMEM, OLX_ECOMM = 0, -1, -2, -3, -4, -5
 APOD_UNIFORM, APOD_MAXANGLE, APOD_PIECEWISE = 0, 1, 2
 COMP_MODES = {"equalize": 0, "matched": 1}   # OLX_COMP_*
+STEER_COMP_NONE = -1                         # OLX_STEER_COMP_NONE
+STEER_DELAYS = {"straight_ray": 0, "direct": 1}   # OLX_STEER_DELAYS_*
 OUT_PMAG, OUT_INTENSITY, OUT_COMPLEX = 1, 2, 4
 OUT_PMAX = 64             # pulsed plans only (olx_field_pulse): also keep p_max; the OUT_PMAG slot then holds p_min
 OUT_PII = 128             # pulsed plans only: also keep the pulse intensity integral [J/cm^2] (scaled by pii_post only)
@@ -45,7 +47,7 @@ SYMBOLS = [
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
     "olx_bf_set_medium", "olx_bf_solve_medium",
     "olx_bf_set_attenuation", "olx_bf_solve_compensated",
-    "olx_steer_map", "olx_steer_time",
+    "olx_steer_map", "olx_steer_time", "olx_steer_map_medium",
 ]
 
 
@@ -149,6 +151,8 @@ def load(require_gpu: bool = True):
         lib.olx_thermal_source_pii.argtypes = [vp, c_int]
         lib.olx_steer_time.argtypes = [vp, c_int, fp]
         lib.olx_steer_map.argtypes = [vp, POINTER(OlxGrid), c_double, c_double, c_double, c_int, c_double, c_double, c_double, c_uint, fp, POINTER(c_int32)]
+        lib.olx_steer_map_medium.argtypes = [vp, POINTER(OlxGrid), c_double, c_double, c_double, c_int, c_double, c_double, fp, fp, c_int, c_int, c_int, c_uint,
+                                             fp, POINTER(c_int32)]
         lib.olx_thermal_plan.argtypes = [vp, POINTER(OlxGrid), fp, fp, fp, fp, c_double, c_double, c_double, c_double, c_double, dp]
         lib.olx_thermal_schedule.argtypes = [vp, c_int, POINTER(c_int), POINTER(c_int), dp, c_int, POINTER(ctypes.c_longlong)]
         lib.olx_thermal_source.argtypes = [vp, c_int, fp]
@@ -343,6 +347,37 @@ class Context:
         self._chk(self._lib.olx_steer_map(self._h, ctypes.byref(g), float(freq), float(c), float(p0_pa), int(apod_kind), float(p0), float(p1),
                                           float(absorption), FIELD_DIRECTIVITY if directivity else 0, _fptr(pf),
                                           na.ctypes.data_as(POINTER(c_int32))))
+        return pf, na
+
+    # -- kernel 4h (steering map through a medium)
+    def steer_map_medium(self, origin_m, spacing_m, n, freq, c_ref, p0_pa=1.0, apod_kind=APOD_UNIFORM, p0=1.0, p1=0.0, sound_speed=None,
+                         attenuation=None, comp=None, spreading=False, delays="straight_ray", directivity=False):
+        """``steer_map`` through a heterogeneous medium along straight rays -> (float32 [nx,ny,nz], int32 [nx,ny,nz]).  ``sound_speed`` [m/s]
+        and ``attenuation`` [dB/cm/MHz^0.9] are [nx,ny,nz] volumes on the grid (None = c_ref everywhere / none); ``comp`` = None, "equalize"
+        or "matched" (the MediumCompensated modes, with ``spreading``); ``delays`` = "straight_ray" (every term in phase) or "direct" (the
+        residual phase of an uncorrected array).  Leaves the plan and its medium, the steering table, the media of ``bf_set_medium`` /
+        ``bf_set_attenuation`` and every resident result as they are (olx_steer_map_medium)."""
+        shape = tuple(int(v) for v in n)
+        g = OlxGrid()
+        for a in range(3):
+            g.origin[a] = float(origin_m[a]); g.spacing[a] = float(spacing_m[a]); g.n[a] = shape[a]
+        if min(shape) < 1:
+            raise ValueError(f"grid sizes must be >= 1, got {shape}")
+        if comp is not None and comp not in COMP_MODES:
+            raise ValueError(f"comp must be None or one of {tuple(COMP_MODES)}, got {comp!r}")
+        if delays not in STEER_DELAYS:
+            raise ValueError(f"delays must be one of {tuple(STEER_DELAYS)}, got {delays!r}")
+        vols = []
+        for name, v in (("sound speed", sound_speed), ("attenuation", attenuation)):
+            v = None if v is None else np.ascontiguousarray(v, dtype=np.float32)
+            if v is not None and v.shape != shape:
+                raise ValueError(f"{name} volume must have the grid shape {shape}, got {v.shape}")
+            vols.append(v)
+        pf = np.empty(shape, dtype=np.float32); na = np.empty(shape, dtype=np.int32)
+        self._chk(self._lib.olx_steer_map_medium(self._h, ctypes.byref(g), float(freq), float(c_ref), float(p0_pa), int(apod_kind), float(p0), float(p1),
+                                                 _fptr(vols[0]), _fptr(vols[1]), STEER_COMP_NONE if comp is None else COMP_MODES[comp],
+                                                 int(bool(spreading)), STEER_DELAYS[delays], FIELD_DIRECTIVITY if directivity else 0, _fptr(pf),
+                                                 na.ctypes.data_as(POINTER(c_int32))))
         return pf, na
 
     def steer_time(self, iters: int) -> np.ndarray:

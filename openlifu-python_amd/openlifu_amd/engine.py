@@ -435,12 +435,16 @@ class Engine:
         return out
 
     # ---- kernel 4 -----------------------------------------------------------------------------
-    def steering_map(self, arr, origin_m, spacing_m, n, freq, c, p0_pa, apod=(nat.APOD_UNIFORM, 1.0, 0.0), absorption=0.0, directivity=False):
+    def steering_map(self, arr, origin_m, spacing_m, n, freq, c, p0_pa, apod=(nat.APOD_UNIFORM, 1.0, 0.0), absorption=0.0, directivity=False,
+                     medium=None):
         """Focal pressure [Pa] when ``arr`` is steered to each voxel of the grid and the number of contributing elements there ->
         (float32 [nx, ny, nz], int32 [nx, ny, nz]) (olx_steer_map, kernel 4).  ``apod`` = the apodization's kernel-1 arguments,
         ``absorption`` [Np/m] a uniform absorption, ``directivity`` the elements' piston factor.  The volumes are buffers of their own:
         the plan, the steering table and the resident results stay as they are -- unless the element table (or, with ``directivity``,
-        the apertures) has to be uploaded, which un-plans the context: arrays handed out lazily are brought to the host first."""
+        the apertures) has to be uploaded, which un-plans the context: arrays handed out lazily are brought to the host first.
+        ``medium`` = dict(sound_speed=, attenuation= (volumes or None), comp= None | "equalize" | "matched", spreading=, delays= "straight_ray"
+        | "direct") runs the map through the medium along straight rays instead (olx_steer_map_medium, kernel 4h; c = the reference speed,
+        ``absorption`` must be 0: the attenuation is the volume's)."""
         if self.ctx.comm_transport():
             raise NotImplementedError("steering map: a context that belongs to a communicator is not supported (one GPU, whole grid)")
         if directivity or self._table_of(arr)[3] != self._table_key:
@@ -449,6 +453,13 @@ class Engine:
         if directivity:
             self.ctx.set_element_apertures(*arr.element_apertures())
         kind, p0, p1 = apod
+        if medium is not None:
+            if absorption:
+                raise ValueError("steering map: a uniform absorption and a medium exclude each other (put the absorption into the attenuation volume)")
+            return self.ctx.steer_map_medium(origin_m, spacing_m, n, freq, c, p0_pa=p0_pa, apod_kind=kind, p0=p0, p1=p1,
+                                             sound_speed=medium.get("sound_speed"), attenuation=medium.get("attenuation"), comp=medium.get("comp"),
+                                             spreading=bool(medium.get("spreading", False)), delays=medium.get("delays", "straight_ray"),
+                                             directivity=directivity)
         return self.ctx.steer_map(origin_m, spacing_m, n, freq, c, p0_pa=p0_pa, apod_kind=kind, p0=p0, p1=p1, absorption=absorption,
                                   directivity=directivity)
 

@@ -191,13 +191,18 @@ class Protocol:
                 tc.check_bounds(target.get_position(dim=tc.dim, units=tc.units))
 
     # ---- steering map (DESIGN.md section 2 "Steering map") ------------------------------------------
-    def calc_steering_map(self, transducer, params=None, reference=None):
+    def calc_steering_map(self, transducer, params=None, reference=None, medium_model=None):
         """Where can ``transducer`` steer under this protocol?  ``SteeringMap`` on ``params.coords`` (None: the protocol's ``sim_setup``
         grid in the UniformWater scene) with the protocol's ``apod_method`` and the pulse's frequency and amplitude; ``reference`` as in
-        ``plan.calc_steering_map``.  ``SteeringMap.to_target_constraints`` gives boxes for ``target_constraints``."""
+        ``plan.calc_steering_map``.  ``SteeringMap.to_target_constraints`` gives boxes for ``target_constraints``.
+        ``medium_model="straight_ray"``: through the medium of ``params``, with the protocol's ``apod_method`` (``MediumCompensated``
+        included) and ``delay_method`` (``StraightRay`` or ``Direct``)."""
         from .steering import calc_steering_map
         if params is None:
             params = self.sim_setup.setup_sim_scene(seg.seg_methods.UniformWater())
+        if medium_model is not None:
+            return calc_steering_map(transducer, params, apod_method=self.apod_method, freq=self.pulse.frequency, amplitude=self.pulse.amplitude,
+                                     reference=reference, medium_model=medium_model, delay_method=self.delay_method)
         return calc_steering_map(transducer, params, apod_method=self.apod_method, freq=self.pulse.frequency, amplitude=self.pulse.amplitude,
                                  reference=reference)
 
