@@ -24,6 +24,12 @@ namespace olx {
 //     a per-lane base (plane, g) + a wave-uniform tile offset.  Plane stride 364 words (182 = 22 (mod 32) 8-byte slots: 16 planes ->
 //     16 distinct even slots) and row stride 14 words (7 slots: the second k-group of a ds_read_b64 lane group -> the odd slots)
 //     put the 32 lanes of a ds_read_b64 group (16 planes x 2 k-groups) on 32 distinct 8-byte slots.
+//   * Table pairs (sa - 1, sbb0) and (sa, sbb0) of a block cover the columns [-7 - 8 (sa - 1), 4 - 8 (sa - 1)] and 8 further left: they
+//     share 4 of 12 (same integer U, dx, row and plane: the same bits).  Where a pair follows its left neighbour directly (nsbp == 2: every
+//     16-row array) each wave MOVES words 8 .. 11 of its own planes' rows to words 0 .. 3 and evaluates only the 8 new columns on an
+//     8 columns x 8 rows lane map: 7 instead of 11 evaluations per lane for that pair (OLX_EXP_CP_NOREUSE=1 in developer builds: A/B).
+//   * |p| alone (what the product launches since the intensity is derived from |p|) is an instantiation of its own: PONLY -- no intensity
+//     values, 4 instead of 8 ds_bpermute per position, no flag test at the stores.
 // NT = 2 (9 - 16 distinct steering columns), KX <= 3: the shape of BASELINE's 8-focus shard; the other shapes stay with 2e.
 // Measured on the headline shard (8 foci, 256 el x 256^3, alternating runs on one box): 0.404 vs 0.430 ms with fp8 corrections,
 // 0.456 vs 0.499 ms with fp16 corrections (kernel 2e).  A first version was 12 % SLOWER: the read-out loop carried the ragged-nz
@@ -34,6 +40,7 @@ constexpr int CP_TW = 14;                          // words per table row (12 in
 constexpr int CP_TROWS = 26, CP_ROW0 = 15;         // pair table rows; row of offset wd = 0
 constexpr int CP_PSZ = 364;                        // words per plane table = 26 x 14; PSZ / 2 = 22 (mod 32): see above
 constexpr int CP_UW = 12;                          // table columns: ud = 2 kx - a in [-7, 4]
+constexpr int CP_SHARED = 4;                       // columns a pair (sa, sbb0) shares with (sa - 1, sbb0): [-7 - 8 sa, 4 - 8 sa] and its neighbour overlap in 4
 constexpr int CP_MT = 5;                           // tiles (positions) per wave: ceil(33 / 8)
 
 #ifdef OLX_EXP_CUTRACE
@@ -45,15 +52,16 @@ static __device__ unsigned long long g_cutrace[16384][8][5];
 #define OLX_CUTRACE(k, v)
 #endif
 
-template <int MX, int MY, bool CLAMP, bool FP8, bool DIR = false, bool BOTH = true /*|p| and intensity both wanted (the product's case): no flag tests between the stores*/>
+template <int MX, int MY, bool CLAMP, bool FP8, bool DIR = false, bool BOTH = true /*|p| and intensity both wanted: no flag tests between the stores*/,
+          bool PONLY = false /*|p| alone (the product's case since the intensity is derived): no intensity arithmetic, lane exchange or flag test*/>
 __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
     const uint4* __restrict__ bfrag, float* __restrict__ pmag, float* __restrict__ inten,
     const int* __restrict__ targets /*[tiles][32 columns][4]: focus * 4 + mirror image, -1 = none*/,
     const CosetBlock* __restrict__ blocks /*[n_items]*/, const CosetParams P) {
     constexpr int NT = 2, THREADS = COS_NW * 64, PAIR = 2;
+    static_assert(!(BOTH && PONLY), "one output or both");
     constexpr int TROWS = CP_TROWS, ROW0 = CP_ROW0, PSZ = CP_PSZ, MT = CP_MT;   // 26-row pair tables, 364 words per plane, <= 5 tiles per wave
     static_assert((PSZ / 2) % 2 == 0 && ((PSZ / 2) % 32 == 22 || (PSZ / 2) % 32 == 30), "16 planes on 16 distinct even 8-byte slots");
-    constexpr int RPR = 64 / CP_UW, NROUND = (TROWS + RPR - 1) / RPR;       // 5 table rows per generation round: 6 rounds (pairs) / 4
     constexpr int B_KS_U4 = 128;                                                // uint4 per K-step and column tile: hi, lo (64 lanes each)
     constexpr int B_BYTES = PAIR * 4 * NT * B_KS_U4 * 16;                       // PAIR super-blocks of steering fragments
     constexpr int T_WORDS = COS_ZB * PSZ;
@@ -79,7 +87,7 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
     const int ibase = BK.ibase, jbase = BK.jbase;
     const int k0 = BK.k0;
     const int ntile = __builtin_amdgcn_readfirstlane((npos - wave + COS_NW - 1) / COS_NW);      // this wave's positions: wave, wave + 8, ... (wave-uniform, <= MT)
-    // table generation role (planes 2 wave, 2 wave + 1): lane -> (wl = lane / UW < RPR, ui = lane % UW); round r: rows RPR r + wl.
+    // table generation role (planes 2 wave, 2 wave + 1): full form lane -> (wl = lane / 12 < 5, ui = lane % 12), round r: rows 5 r + wl; reuse form 8 x 8 (the fill lambda below).
     // (Its per-lane constants are formed inside the pair loop from an opaque copy of the lane index: hoisted, they would be live
     // across the K-steps, where the fp8 shape has no register to spare -- 5 spilled registers cost 190 MB of scratch traffic.)
     // fragment read offset [words] of a tile's row for K-step (0, 0) = per-lane part (plane, k-group) + the tile's position
@@ -99,6 +107,10 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
         for (int nt = 0; nt < NT; ++nt) acc[t][nt] = floatx4_t{0.f, 0.f, 0.f, 0.f};
     const int nsbp = P.nsbp;                    // even: chunks = table pairs never straddle sa
     const int n_sb = P.nsa * nsbp;
+    bool reuse_ok = nsbp == PAIR;
+#ifdef OLX_DEV_PINS
+    reuse_ok = reuse_ok && P.cp_noreuse == 0;   // OLX_EXP_CP_NOREUSE=1 (A/B): every pair takes the full fill
+#endif
     constexpr int CHUNK_U4 = PAIR * 4 * NT * B_KS_U4, PRE = CHUNK_U4 / THREADS;
     static_assert(CHUNK_U4 % THREADS == 0, "chunk must split evenly over the block");
     uint4 pre[PRE];
@@ -115,6 +127,8 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
         // previous pair consumed: steering stage and tables are free.  (Not before the first pair: nothing to protect yet, and
         // __syncthreads() drains vmcnt -- the wave would wait for its first steering loads before the tables instead of behind them.)
         if (sb0 > 0) __syncthreads();
+        // a pair whose predecessor in this block was (sa - 1, same sbb0) shares 4 of its 12 table columns with it: nsbp == PAIR (one pair per sa)
+        const bool reuse = sb0 > 0 && reuse_ok;      // (block-uniform)
         if (sb0 == 0) OLX_STAMP(1);
         if (sb0 == 2) OLX_STAMP(7);
         // ---- G tables of planes 2 wave, 2 wave + 1: 26 rows x 12 offsets, shared by the pair's two super-blocks
@@ -124,23 +138,14 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
         if (k0 + wave * COS_P < P.nz) {
             int lane_o = lane;
             asm volatile("" : "+v"(lane_o));
-            const int wl = lane_o / CP_UW, ui = lane_o - CP_UW * wl;
-            const bool gen_lane = wl < RPR;
-            const int Ulane = ibase + P.x_begin + P.ux0 + P.mx * (ui - 7);
-            const int Wlane = jbase + P.uy0 + P.my * (wl - ROW0);
-            const int tw_off = (wave * COS_P) * PSZ + wl * CP_TW + (CP_UW - 1 - ui);   // + z PSZ + RPR r TW
             float dz2[COS_P];
 #pragma unroll
             for (int z = 0; z < COS_P; ++z) {
                 const float dz = (float)(k0 + wave * COS_P + z) * P.hz - P.flat_ez;
                 dz2[z] = dz * dz;
             }
-            const float U = (float)(Ulane - 8 * P.mx * sa);
-            const float dx = fmaf(U, P.hx_hi, fmaf(U, P.hx_lo, P.fx0));
-            const float dx2 = dx * dx;
-            const int Wsb = Wlane - 8 * P.my * sbb0;
             // one table entry: G of squared lateral distance r2 on a plane dz2v above the elements -> hi / lo words at table offset o
-            auto entry = [&](const float r2, const float dz2v, const float dy, const int o, const bool ok) __attribute__((always_inline)) {
+            auto entry = [&](const float r2, const float dz2v, const float dx, const float dy, const int o, const bool ok) __attribute__((always_inline)) {
                 float d2 = r2 + dz2v;
                 if (CLAMP) d2 = fmaxf(d2, P.dmin2);
                 const float ri = __builtin_amdgcn_rsqf(d2);
@@ -173,24 +178,74 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
                     s_lo[o] = lo_word;
                 }
             };
-            // rows 0 .. TROWS - 2 in whole rounds of RPR rows x the wave's two planes; the LAST row once for both planes (row group wl takes
-            // plane wl): 11 instead of 12 evaluations per lane and pair
-            static_assert((TROWS - 1) % RPR == 0 && COS_P <= RPR, "the last table row is shared by the planes of a wave");
+            // The fill proper.  FULL form (reuse_c = 0): 12 columns x 5 rows per round -- rows 0 .. TROWS - 2 in whole rounds x the wave's
+            // two planes, the LAST row once for both planes (row group wl takes plane wl): 11 instead of 12 evaluations per lane and pair.
+            // REUSE form (reuse_c = 1, after the move below): only the 8 new columns ui = 0 .. 7, 8 columns x 8 rows per round -- rows 0 .. 23 in
+            // 3 rounds x two planes, rows 24 and 25 of both planes in one more evaluation (lanes 0 .. 31): 7 evaluations per lane and pair.
+            auto fill = [&](auto reuse_c) __attribute__((always_inline)) {
+                constexpr bool RU = decltype(reuse_c)::value != 0;
+                constexpr int CW = RU ? CP_UW - CP_SHARED : CP_UW;                  // columns evaluated
+                constexpr int RPF = 64 / CW;                                        // table rows per round
+                constexpr int NRF = (TROWS - (RU ? COS_P : 1)) / RPF;               // whole rounds
+                static_assert(NRF * RPF == TROWS - (RU ? COS_P : 1) && (RU ? COS_P * COS_P : COS_P) <= RPF, "the tail rows fit one evaluation of the wave's planes");
+                const int wl = lane_o / CW, ui = lane_o - CW * wl;
+                const bool gen_lane = wl < RPF;
+                const int Ulane = ibase + P.x_begin + P.ux0 + P.mx * (ui - 7);
+                const int Wlane = jbase + P.uy0 + P.my * (wl - ROW0);
+                const int tw_off = (wave * COS_P) * PSZ + wl * CP_TW + (CP_UW - 1 - ui);   // + z PSZ + RPF r TW
+                const float U = (float)(Ulane - 8 * P.mx * sa);
+                const float dx = fmaf(U, P.hx_hi, fmaf(U, P.hx_lo, P.fx0));
+                const float dx2 = dx * dx;
+                const int Wsb = Wlane - 8 * P.my * sbb0;
 #pragma unroll 2
-            for (int r = 0; r < NROUND - 1; ++r) {
-                const float W = (float)(Wsb + RPR * P.my * r);
-                const float dy = fmaf(W, P.hy_hi, fmaf(W, P.hy_lo, P.fy0));
-                const float r2 = fmaf(dy, dy, dx2);
+                for (int r = 0; r < NRF; ++r) {
+                    const float W = (float)(Wsb + RPF * P.my * r);
+                    const float dy = fmaf(W, P.hy_hi, fmaf(W, P.hy_lo, P.fy0));
+                    const float r2 = fmaf(dy, dy, dx2);
 #pragma unroll
-                for (int z = 0; z < COS_P; ++z) entry(r2, dz2[z], dy, z * PSZ + tw_off + RPR * r * CP_TW, gen_lane);
-            }
-            if (KY + 14 >= TROWS - 1) {      // (block-uniform: the fragments of KY positions reach table rows 0 .. KY + 14)
-                const float W = (float)(Wsb - P.my * wl + (TROWS - 1) * P.my);
-                const float dy = fmaf(W, P.hy_hi, fmaf(W, P.hy_lo, P.fy0));
-                float dzl = dz2[0];
+                    for (int z = 0; z < COS_P; ++z) entry(r2, dz2[z], dx, dy, z * PSZ + tw_off + RPF * r * CP_TW, gen_lane);
+                }
+                // (block-uniform: the fragments of KY positions reach table rows 0 .. KY + 14)
+                const bool last_row = KY + 14 >= TROWS - 1;
+                if constexpr (RU) {          // row group wl: plane wl / 2, row TROWS - 2 + wl % 2
+                    const int zt = wl >> 1, rowt = TROWS - COS_P + (wl & 1);
+                    const float W = (float)(Wsb - P.my * wl + rowt * P.my);
+                    const float dy = fmaf(W, P.hy_hi, fmaf(W, P.hy_lo, P.fy0));
+                    float dzl = dz2[0];
 #pragma unroll
-                for (int z = 1; z < COS_P; ++z) dzl = wl == z ? dz2[z] : dzl;
-                entry(fmaf(dy, dy, dx2), dzl, dy, (wave * COS_P + wl) * PSZ + (TROWS - 1) * CP_TW + (CP_UW - 1 - ui), wl < COS_P);
+                    for (int z = 1; z < COS_P; ++z) dzl = zt == z ? dz2[z] : dzl;
+                    entry(fmaf(dy, dy, dx2), dzl, dx, dy, (wave * COS_P + zt) * PSZ + rowt * CP_TW + (CP_UW - 1 - ui), zt < COS_P && (last_row || rowt < TROWS - 1));
+                } else if (last_row) {
+                    const float W = (float)(Wsb - P.my * wl + (TROWS - 1) * P.my);
+                    const float dy = fmaf(W, P.hy_hi, fmaf(W, P.hy_lo, P.fy0));
+                    float dzl = dz2[0];
+#pragma unroll
+                    for (int z = 1; z < COS_P; ++z) dzl = wl == z ? dz2[z] : dzl;
+                    entry(fmaf(dy, dy, dx2), dzl, dx, dy, (wave * COS_P + wl) * PSZ + (TROWS - 1) * CP_TW + (CP_UW - 1 - ui), wl < COS_P);
+                }
+            };
+            if (reuse) {
+                // the previous pair (sa - 1, same sbb0) left columns ud = [-7, -4] of THIS pair in words 8 .. 11 of every row (same U, dx, row and
+                // plane: same bits).  Move them to words 0 .. 3: one lane per (plane, row) of the wave's own planes, two 8-byte reads and writes per
+                // array (rows are 8-byte aligned).  The wave's LDS operations complete in order: the reads stay ahead of the fill's stores to words 8 .. 11.
+                static_assert(COS_P * TROWS <= 64 && CP_UW - CP_SHARED == 8 && CP_TW % 2 == 0 && PSZ % 2 == 0, "one lane per (plane, row); aligned 8-byte moves");
+                const int zm = lane_o >= TROWS ? 1 : 0;
+                const int mo = (wave * COS_P + zm) * PSZ + (lane_o - zm * TROWS) * CP_TW;
+                if (lane_o < COS_P * TROWS && OLX_IN(mo, T_WORDS - (CP_UW - 1), 3)) {
+                    unsigned long long mv[4];
+                    __builtin_memcpy(&mv[0], __builtin_assume_aligned(s_hi + mo + 8, 8), 8);
+                    __builtin_memcpy(&mv[1], __builtin_assume_aligned(s_hi + mo + 10, 8), 8);
+                    __builtin_memcpy(&mv[2], __builtin_assume_aligned(s_lo + mo + 8, 8), 8);
+                    __builtin_memcpy(&mv[3], __builtin_assume_aligned(s_lo + mo + 10, 8), 8);
+                    __builtin_memcpy(__builtin_assume_aligned(s_hi + mo, 8), &mv[0], 8);
+                    __builtin_memcpy(__builtin_assume_aligned(s_hi + mo + 2, 8), &mv[1], 8);
+                    __builtin_memcpy(__builtin_assume_aligned(s_lo + mo, 8), &mv[2], 8);
+                    __builtin_memcpy(__builtin_assume_aligned(s_lo + mo + 2, 8), &mv[3], 8);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (no instruction: pins the move ahead of the fill's stores in the compiler's order too)
+                fill(IntC<1>{});
+            } else {
+                fill(IntC<0>{});
             }
         }
         if constexpr (FP8) __builtin_amdgcn_s_setprio(0);
@@ -315,23 +370,26 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
     const int kz = k0 + 4 * (lane_e & 3);
     const int src_lane4 = (16 * (lane_e & 3) + (lane_e >> 2)) * 4;      // byte index of the lane that computed this lane's values
     const float s_p = P.out_scale, s_i = P.out_scale * P.out_scale * P.inten_scale;
-    const bool want_p = (P.flags & 1u) != 0, want_i = (P.flags & 2u) != 0;      // (uniform)
+    const bool want_p = PONLY || (P.flags & 1u) != 0, want_i = !PONLY && (P.flags & 2u) != 0;      // (uniform)
+    constexpr int NOUT = PONLY ? 1 : NT;                 // |p| alone: no intensity values, half the lane exchange
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
         if (t >= ntile) continue;
-        float o[NT][4];
+        float o[NOUT][4];
 #pragma unroll
         for (int r = 0; r < 4; r += 2) {
             const float2_t re = {acc[t][0][r], acc[t][0][r + 1]}, im = {acc[t][1][r], acc[t][1][r + 1]};
             const float2_t m = __builtin_elementwise_fma(re, re, im * im);
             o[0][r] = __builtin_amdgcn_sqrtf(m.x) * s_p;
             o[0][r + 1] = __builtin_amdgcn_sqrtf(m.y) * s_p;
-            const float2_t in = m * float2_t{s_i, s_i};
-            o[1][r] = in.x;
-            o[1][r + 1] = in.y;
+            if constexpr (!PONLY) {
+                const float2_t in = m * float2_t{s_i, s_i};
+                o[1][r] = in.x;
+                o[1][r + 1] = in.y;
+            }
         }
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
+        for (int nt = 0; nt < NOUT; ++nt) {
             floatx4_t v;
             v[0] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src_lane4, __builtin_bit_cast(int, o[nt][0])));
             v[1] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src_lane4, __builtin_bit_cast(int, o[nt][1])));
@@ -371,14 +429,14 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
                 const unsigned off = o00 + (fxm & DX) + (fym & DY);
                 if (!OLX_IN(fb + off + (FULL4 ? 3 : 0), (long long)P.n_foci * P.vox, 2)) continue;
                 if constexpr (FULL4) {
-                    if (BOTH || want_p) *reinterpret_cast<floatx4u_t*>(base_p + off) = floatx4u_t{acc[t][0][0], acc[t][0][1], acc[t][0][2], acc[t][0][3]};
-                    if (BOTH || want_i) *reinterpret_cast<floatx4u_t*>(base_i + off) = floatx4u_t{acc[t][1][0], acc[t][1][1], acc[t][1][2], acc[t][1][3]};
+                    if (BOTH || PONLY || want_p) *reinterpret_cast<floatx4u_t*>(base_p + off) = floatx4u_t{acc[t][0][0], acc[t][0][1], acc[t][0][2], acc[t][0][3]};
+                    if (!PONLY && (BOTH || want_i)) *reinterpret_cast<floatx4u_t*>(base_i + off) = floatx4u_t{acc[t][1][0], acc[t][1][1], acc[t][1][2], acc[t][1][3]};
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
                         if (kz + e < P.nz) {
-                            if (BOTH || want_p) base_p[off + e] = acc[t][0][e];
-                            if (BOTH || want_i) base_i[off + e] = acc[t][1][e];
+                            if (BOTH || PONLY || want_p) base_p[off + e] = acc[t][0][e];
+                            if (!PONLY && (BOTH || want_i)) base_i[off + e] = acc[t][1][e];
                         }
                 }
             }
@@ -420,9 +478,10 @@ static void launch_cosetp(olx_ctx* c, const LatticePart& q, float* pm) {
     float* inten_exp = c->d_inten;
     const bool clamp = c->clamp || c->lat.clamp;
     dim3 grid(q.n_blocks, c->mp.n_tiles), blk(COS_NW * 64);
-    const bool both = (Q.flags & 3u) == 3u;
-#define OLX_CP(CL, F8, DR) do { if (both) hipLaunchKernelGGL((field_cosetp_k<MX, MY, CL, F8, DR, true>), grid, blk, 0, c->stream, q.bfrag, pm, inten_exp, c->d_targets, q.blocks, Q); \
-                                else hipLaunchKernelGGL((field_cosetp_k<MX, MY, CL, F8, DR, false>), grid, blk, 0, c->stream, q.bfrag, pm, inten_exp, c->d_targets, q.blocks, Q); } while (0)
+    const bool both = (Q.flags & 3u) == 3u, ponly = (Q.flags & 3u) == 1u;      // |p| alone (OLX_OUT_PMAG: what the product plans) has its own epilogue
+#define OLX_CP(CL, F8, DR) do { if (both) hipLaunchKernelGGL((field_cosetp_k<MX, MY, CL, F8, DR, true, false>), grid, blk, 0, c->stream, q.bfrag, pm, inten_exp, c->d_targets, q.blocks, Q); \
+                                else if (ponly) hipLaunchKernelGGL((field_cosetp_k<MX, MY, CL, F8, DR, false, true>), grid, blk, 0, c->stream, q.bfrag, pm, inten_exp, c->d_targets, q.blocks, Q); \
+                                else hipLaunchKernelGGL((field_cosetp_k<MX, MY, CL, F8, DR, false, false>), grid, blk, 0, c->stream, q.bfrag, pm, inten_exp, c->d_targets, q.blocks, Q); } while (0)
     if (c->dir_lattice) {   // piston directivity / uniform absorption folded into the geometry tables (fp16 corrections only)
         if (clamp) OLX_CP(true, false, true); else OLX_CP(false, false, true);
     } else if (q.fp8) {

@@ -94,6 +94,9 @@ struct CosetParams {
     long long vox;
     unsigned flags;
     int n_foci;                // planned foci: the output arrays hold n_foci volumes of vox floats (what the debug build's store checks compare with)
+#ifdef OLX_DEV_PINS
+    int cp_noreuse;            // developer builds only (OLX_EXP_CP_NOREUSE=1): kernel 2g fills every pair table in full instead of taking 4 columns from the previous pair
+#endif
 };
 
 // kernels 2g / 2f: one record per blockIdx.x, written by the host (olx.hip, configure) -- the block's share of the coset decomposition.
