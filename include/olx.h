@@ -433,7 +433,11 @@ int olx_profile_end(olx_ctx *ctx, float *ms_each, int capacity, int *n_recorded)
 #define OLX_SCAN_PII_FULL 8     /* ... factors, weights and peaks: V (8 F + 8) bytes */
 int olx_scan_time(olx_ctx *ctx, int kernel, int iters, float *ms_each, double *bytes_per_launch);
 
-/* Name of the field kernel variant the current plan dispatches to (for profiles). */
+/* Name of the field kernel variant the current plan dispatches to (for profiles and tests).  A launch of kernel 2m (OLX_MEDIUM_MARCHED) appends the
+ * launch sequence it ran, rebuilt by every launch: "; 2m: inside|border, lookup0 xN, writer0 x1, lookup xN, writer xN, texel xN" -- inside: every
+ * element at least half a cell inside the lateral grid (no clamp of the look-up coordinates), else border; lookup0 / writer0: look-up launches below
+ * and the writer of the first non-trivial plane (no source sums); lookup / writer: those that read running sums; texel: the one-sum look-ups above
+ * the medium out of the row-pair form; kinds that did not run are left out -- and then, with OLX_MARCH_FUSE, "; fused writers: P planes in L launches". */
 const char *olx_field_variant(const olx_ctx *ctx);
 
 /* ---- aggregation over foci (plan/protocol.py:382-387) ------------------------------

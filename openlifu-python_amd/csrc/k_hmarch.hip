@@ -5,6 +5,7 @@
 #include "olx_launch.h"
 #include <string>
 #include <type_traits>
+#include <utility>
 
 namespace olx {
 
@@ -640,6 +641,7 @@ static void launch_hmarch_nf(olx_ctx* c, float* pm) {
     int fused_planes = 0, fused_launches = 0;
     int ub = 0;           // the U buffer that holds the latest running sums (a writer reads d_U[ub], writes d_U[ub ^ 1])
     int n_written = 0;    // writer launches so far (consecutive ones walk the blocks in alternate directions)
+    int ran_lookup0 = 0, ran_writer0 = 0, ran_lookup = 0, ran_writer = 0, ran_texel = 0;      // field_hmarch_k launches by kind (olx_field_variant names them)
     // p_src: index of the non-trivial plane the source sums live on (-1: none); write: k_lo == k_hi is non-trivial, the next sums go to the other buffer
     auto go = [&](int k_lo, int k_hi, int p_src, bool write, bool tex = false) {
         if (k_hi < k_lo) return;
@@ -663,10 +665,11 @@ static void launch_hmarch_nf(olx_ctx* c, float* pm) {
         if (write) {
             if (c->march_one) { if (c->clamp) OLX_HM(4, true); else OLX_HM(4, false); }
             else              { if (c->clamp) OLX_HM(16, true); else OLX_HM(16, false); }
-            if (p_src >= 0) ub ^= 1;
+            if (p_src >= 0) { ub ^= 1; ++ran_writer; } else ++ran_writer0;
             ++n_written;
         }
         else if (tex) {   // one-sum look-ups out of the texel form of the last running sums
+            ++ran_texel;
 #define OLX_HMT(CL, IN) hipLaunchKernelGGL((field_hmarch_k<NF, 1, CL, true, true, IN, true>), dim3((S.nblocks + 7u) / 8u * 8u, ftiles), dim3(64 * hm_waves<1>()), 0, \
                                            c->stream, c->d_tab, c->d_med, c->d_plane_of_k, src, dst, c->d_inv2z, pm, c->d_inten, c->d_cplx, P, c->hp, S)
             S.nblocks = (unsigned)(tiles * ((k_hi - k_lo + 4) / 4));
@@ -674,7 +677,7 @@ static void launch_hmarch_nf(olx_ctx* c, float* pm) {
             else          { if (inside) OLX_HMT(false, true); else OLX_HMT(false, false); }
 #undef OLX_HMT
         }
-        else       { if (c->clamp) OLX_HM(1, true); else OLX_HM(1, false); }
+        else       { if (c->clamp) OLX_HM(1, true); else OLX_HM(1, false); ++(p_src >= 0 ? ran_lookup : ran_lookup0); }
 #undef OLX_HM
 #undef OLX_HM_
 #undef OLX_HM__
@@ -715,7 +718,19 @@ static void launch_hmarch_nf(olx_ctx* c, float* pm) {
         fused_planes += G; ++fused_launches;
         return true;
     };
-    if (np == 0) { go(0, nz - 1, -1, false); return; }
+    // olx_field_variant names what ran: "...; 2m: inside, lookup0 x1, writer0 x1, lookup x3, writer x11, texel x1; fused writers: 28 planes in 7 launches"
+    // (lookup0 / writer0: no source sums below -- ES = 1, !SRC / the first non-trivial plane; lookup / writer: SRC; texel: the TEX look-ups)
+    auto name_sequence = [&]() {
+        size_t cut = c->variant.find("; 2m:");
+        if (cut == std::string::npos) cut = c->variant.find("; fused writers");
+        if (cut != std::string::npos) c->variant.erase(cut);
+        c->variant += inside ? "; 2m: inside" : "; 2m: border";
+        const std::pair<const char*, int> kinds[] = {{"lookup0", ran_lookup0}, {"writer0", ran_writer0}, {"lookup", ran_lookup}, {"writer", ran_writer}, {"texel", ran_texel}};
+        for (const auto& kd : kinds)
+            if (kd.second) c->variant += std::string(", ") + kd.first + " x" + std::to_string(kd.second);
+        if (fused_launches) c->variant += "; fused writers: " + std::to_string(fused_planes) + " planes in " + std::to_string(fused_launches) + " launches";
+    };
+    if (np == 0) { go(0, nz - 1, -1, false); name_sequence(); return; }
     go(0, c->h_plane_k[0] - 1, -1, false);                   // below the first non-trivial plane: homogeneous rays
     go(c->h_plane_k[0], c->h_plane_k[0], -1, true);          // U_0 = the plane's own term
     for (int p = 1; p < np;) {
@@ -736,11 +751,7 @@ static void launch_hmarch_nf(olx_ctx* c, float* pm) {
                            static_cast<float2*>(c->d_Utex), c->hp.nxg, c->n_el, c->hp.nyg);
     }
     go(top_lo, nz - 1, np - 1, false, tex);
-    {   // olx_field_variant names what ran: "...; fused writers: 28 planes in 7 launches"
-        const size_t cut = c->variant.find("; fused writers");
-        if (cut != std::string::npos) c->variant.erase(cut);
-        if (fused_launches) c->variant += "; fused writers: " + std::to_string(fused_planes) + " planes in " + std::to_string(fused_launches) + " launches";
-    }
+    name_sequence();
 }
 
 void olx_launch_hmarch(olx_ctx* c, float* pm) {

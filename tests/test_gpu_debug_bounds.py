@@ -34,6 +34,21 @@ def test_kernels_stay_inside_their_extents_in_the_debug_library():
 
 
 @pytest.mark.gpu
+def test_marched_matrix_stays_inside_its_extents_in_the_debug_library():
+    """Kernel 2m's cases of tests/test_gpu_hetero_matrix.py (border and half-cell elements, texel look-ups, several ray-table chunks, ragged element
+    tails, medium planes at k = 0 and k = nz - 1) in one child process against the debug library: every case ends with olx_sync, which reports a
+    counted index violation."""
+    env = dict(os.environ, OLX_LIB_PATH=os.path.join(LIB, "libolx_dbg.so"))
+    for v in ("OLX_FIELD_VARIANT", "OLX_MARCH_FUSE", "OLX_MARCH_SUMS", "OLX_MARCH_NO_TEXELS"):
+        env.pop(v, None)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_hetero_matrix.py"), "-q", "-x", "-m", "gpu", "-k", "matrix_case and 2m-",
+                        "-p", "no:cacheprovider"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    tail = (r.stdout + r.stderr)[-3000:]
+    assert r.returncode == 0, tail
+    assert " passed" in tail and "failed" not in tail and "error" not in tail.lower() and "skipped" not in tail, tail
+
+
+@pytest.mark.gpu
 def test_a_wrong_extent_is_reported():
     code = r"""
 import sys
