@@ -42,6 +42,7 @@ constexpr int CP_PSZ = 364;                        // words per plane table = 26
 constexpr int CP_UW = 12;                          // table columns: ud = 2 kx - a in [-7, 4]
 constexpr int CP_SHARED = 4;                       // columns a pair (sa, sbb0) shares with (sa - 1, sbb0): [-7 - 8 sa, 4 - 8 sa] and its neighbour overlap in 4
 constexpr int CP_MT = 5;                           // tiles (positions) per wave: ceil(33 / 8)
+constexpr int CP_AHEAD_N = 7;                      // evaluations per lane of a reuse-form fill: the words a wave holds when it fills ahead
 
 #ifdef OLX_EXP_CUTRACE
 // developer build only (tools/cutrace_cosetp.py): per block and wave {HW_ID, XCC_ID, cycle at entry, at the last store issued, at the
@@ -59,6 +60,10 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
     const int* __restrict__ targets /*[tiles][32 columns][4]: focus * 4 + mirror image, -1 = none*/,
     const CosetBlock* __restrict__ blocks /*[n_items]*/, const CosetParams P) {
     constexpr int NT = 2, THREADS = COS_NW * 64, PAIR = 2;
+    // fill-ahead (below), per instantiation by measurement: the fp8 shape (the headline) has it; with fp16 corrections and in the DIR instantiations the
+    // matrix pipe is the scarcer unit and the reuse fill stays a phase of its own
+    constexpr bool AHEAD = FP8;
+    constexpr bool PRE_LATE = AHEAD;             // the next pair's steering fragments are requested behind the K-steps instead of in front of them (below)
     static_assert(!(BOTH && PONLY), "one output or both");
     constexpr int TROWS = CP_TROWS, ROW0 = CP_ROW0, PSZ = CP_PSZ, MT = CP_MT;   // 26-row pair tables, 364 words per plane, <= 5 tiles per wave
     static_assert((PSZ / 2) % 2 == 0 && ((PSZ / 2) % 32 == 22 || (PSZ / 2) % 32 == 30), "16 planes on 16 distinct even 8-byte slots");
@@ -111,6 +116,101 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
 #ifdef OLX_DEV_PINS
     reuse_ok = reuse_ok && P.cp_noreuse == 0;   // OLX_EXP_CP_NOREUSE=1 (A/B): every pair takes the full fill
 #endif
+    // fill-ahead: a pair that will take the reuse form has its 7 evaluations per lane done in front of the K-steps of the pair before it, behind the
+    // barrier that opens them; the 14 words wait in registers for the barrier that frees the table, and the fill phase between that barrier and the
+    // next shrinks to the 4-column move and 14 LDS writes per lane
+    bool ahead_ok = AHEAD && reuse_ok;          // (block-uniform)
+#ifdef OLX_DEV_PINS
+    ahead_ok = ahead_ok && P.cp_nofillahead == 0;   // OLX_EXP_CP_NOFILLAHEAD=1 (A/B): the reuse fill stays a phase of its own (PRE_LATE is a compile-time choice and stays)
+#endif
+    const bool my_planes = k0 + wave * COS_P < P.nz;      // (wave-uniform) a wave whose planes lie beyond nz fills, moves and evaluates nothing
+    unsigned held_hi[CP_AHEAD_N], held_lo[CP_AHEAD_N];     // written and read under the same wave-uniform condition
+    // dz^2 of plane z of this wave (opaque: every use adds the same rounded square, never a fused dz * dz + r2)
+    auto plane_dz2 = [&](const int z) __attribute__((always_inline)) {
+        const float dz = (float)(k0 + wave * COS_P + z) * P.hz - P.flat_ez;
+        float q = dz * dz;
+        if constexpr (AHEAD) asm volatile("" : "+v"(q));      // (only where two code paths evaluate the same entries: the others keep their code as it was)
+        return q;
+    };
+    // one table entry: G of squared lateral distance r2 on a plane dz2v above the elements -> hi / lo words
+    auto entry = [&](const float r2, const float dz2v, const float dx, const float dy, unsigned& hi_word, unsigned& lo_word) __attribute__((always_inline)) {
+        float d2 = r2 + dz2v;
+        if (CLAMP) d2 = fmaxf(d2, P.dmin2);
+        const float ri = __builtin_amdgcn_rsqf(d2);
+        const float ph = d2 * ri;
+        float rs = ri * P.g_scale;
+        if constexpr (DIR) rs *= table_mod(dx, dy, ph, ri, P.dir_wx, P.dir_wy, P.absorb_l2);      // (own instantiations: the default path never sees this)
+        float gr = rs * __builtin_amdgcn_cosf(ph), gi = rs * __builtin_amdgcn_sinf(ph);
+        asm volatile("" : "+v"(gr), "+v"(gi));      // (two plain multiplies: packed fp32 beside the partner block's matrix instructions measured slower)
+        half2_t hi;
+        if constexpr (FP8) hi = __builtin_convertvector(float2_t{gr, gi}, half2_t);      // to nearest: |lo| <= half an ulp
+        else hi = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_pkrtz(gr, gi));
+        // lo = g - (float)hi in ONE mixed-precision fma per component (the compiler's form: a convert and a subtract)
+        float lr, li;
+        const unsigned hw = __builtin_bit_cast(unsigned, hi);
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lr) : "v"(hw), "v"(gr));
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(li) : "v"(hw), "v"(gi));
+        if constexpr (FP8) {             // e4m3 bytes [lo re, lo im | hi re, hi im], |.| <= 256 (448 overflows to NaN)
+            // (v_cvt_scalef32_pk_fp8_f32 DIVIDES by its power-of-two scale operand -- tools/probe/cvt_scale_probe.hip --
+            // and rounds / saturates as the unscaled convert: the four operand scalings cost no instruction)
+            short2_t w;                  // (both halves are written below)
+            w = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w, lr, li, 1.0f / COS_F8_LO, false);
+            w = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w, gr, gi, 1.0f / COS_F8_HI, true);
+            lo_word = __builtin_bit_cast(unsigned, w);
+        } else {
+            lo_word = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(lr, li));
+        }
+        hi_word = hw;
+    };
+    auto put = [&](const int o, const bool ok, const unsigned hi_word, const unsigned lo_word) __attribute__((always_inline)) {
+        if (ok && OLX_IN(o, T_WORDS, 0)) {
+            s_hi[o] = hi_word;
+            s_lo[o] = lo_word;
+        }
+    };
+    // The REUSE form of the pair (sa_f, sbb_f) on the 8 columns x 8 rows lane map (the fill lambda below, RU), entry by entry: e = 2 r + z for round r,
+    // plane z; e = 6 the tail rows.  The per-lane constants are formed where these are called, from an opaque copy of the lane index: nothing of them
+    // lives across the tiles.  ru_slot: the table offset of entry e and whether the lane's entry exists; ru_eval_all: the words of all entries.
+    constexpr int RU_CW = CP_UW - CP_SHARED, RU_ROWS = 64 / RU_CW, RU_NR = (CP_TROWS - COS_P) / RU_ROWS;
+    static_assert(CP_AHEAD_N == RU_NR * COS_P + 1 && RU_CW == 8 && RU_ROWS == 8 && COS_P == 2, "the reuse form: 3 rounds x 2 planes and the tail rows");
+    auto ru_slot = [&](const int e, const int lane_o, int& o, bool& ok) __attribute__((always_inline)) {
+        const int wl = lane_o >> 3, ui = lane_o & 7;
+        if (e < RU_NR * COS_P) {
+            o = (wave * COS_P + (e & 1)) * PSZ + (wl + RU_ROWS * (e >> 1)) * CP_TW + (CP_UW - 1 - ui);
+            ok = true;
+        } else {
+            const int zt = wl >> 1, rowt = CP_TROWS - COS_P + (wl & 1);
+            o = (wave * COS_P + zt) * PSZ + rowt * CP_TW + (CP_UW - 1 - ui);
+            ok = zt < COS_P && (KY + 14 >= CP_TROWS - 1 || rowt < CP_TROWS - 1);
+        }
+    };
+    auto ru_eval_all = [&](const int sa_f, const int sbb_f, unsigned (&hi_words)[CP_AHEAD_N], unsigned (&lo_words)[CP_AHEAD_N]) __attribute__((always_inline)) {
+        int lane_o = lane;
+        asm volatile("" : "+v"(lane_o));
+        const int wl = lane_o >> 3, ui = lane_o & 7;
+        const float U = (float)(ibase + P.x_begin + P.ux0 + P.mx * (ui - 7) - 8 * P.mx * sa_f);
+        const float dx = fmaf(U, P.hx_hi, fmaf(U, P.hx_lo, P.fx0));
+        const float dx2 = dx * dx;
+        const int Wsb = jbase + P.uy0 + P.my * (wl - ROW0) - 8 * P.my * sbb_f;
+        float dz2[COS_P];
+#pragma unroll
+        for (int z = 0; z < COS_P; ++z) dz2[z] = plane_dz2(z);
+#pragma unroll
+        for (int r = 0; r < RU_NR; ++r) {
+            const float W = (float)(Wsb + RU_ROWS * P.my * r);
+            const float dy = fmaf(W, P.hy_hi, fmaf(W, P.hy_lo, P.fy0));
+            const float r2 = fmaf(dy, dy, dx2);
+#pragma unroll
+            for (int z = 0; z < COS_P; ++z) entry(r2, dz2[z], dx, dy, hi_words[COS_P * r + z], lo_words[COS_P * r + z]);
+        }
+        const int zt = wl >> 1, rowt = CP_TROWS - COS_P + (wl & 1);
+        const float W = (float)(Wsb - P.my * wl + rowt * P.my);
+        const float dy = fmaf(W, P.hy_hi, fmaf(W, P.hy_lo, P.fy0));
+        float dzl = dz2[0];
+#pragma unroll
+        for (int z = 1; z < COS_P; ++z) dzl = zt == z ? dz2[z] : dzl;
+        entry(fmaf(dy, dy, dx2), dzl, dx, dy, hi_words[CP_AHEAD_N - 1], lo_words[CP_AHEAD_N - 1]);
+    };
     constexpr int CHUNK_U4 = PAIR * 4 * NT * B_KS_U4, PRE = CHUNK_U4 / THREADS;
     static_assert(CHUNK_U4 % THREADS == 0, "chunk must split evenly over the block");
     uint4 pre[PRE];
@@ -135,48 +235,17 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
         // (fp8 shape: table generation at raised priority -- the waves a block's K-steps wait for get the VALU first: -2 ... -4 %;
         // with fp16 corrections the matrix pipe is the scarcer resource and the same setting costs 1.5 %, priority on the K-steps 2.5 %)
         if constexpr (FP8) __builtin_amdgcn_s_setprio(1);
-        if (k0 + wave * COS_P < P.nz) {
+        const bool held = reuse && ahead_ok;          // (block-uniform) this pair's new columns were evaluated in front of the K-steps of the pair before it
+        if (my_planes) {
             int lane_o = lane;
             asm volatile("" : "+v"(lane_o));
             float dz2[COS_P];
 #pragma unroll
-            for (int z = 0; z < COS_P; ++z) {
-                const float dz = (float)(k0 + wave * COS_P + z) * P.hz - P.flat_ez;
-                dz2[z] = dz * dz;
-            }
-            // one table entry: G of squared lateral distance r2 on a plane dz2v above the elements -> hi / lo words at table offset o
-            auto entry = [&](const float r2, const float dz2v, const float dx, const float dy, const int o, const bool ok) __attribute__((always_inline)) {
-                float d2 = r2 + dz2v;
-                if (CLAMP) d2 = fmaxf(d2, P.dmin2);
-                const float ri = __builtin_amdgcn_rsqf(d2);
-                const float ph = d2 * ri;
-                float rs = ri * P.g_scale;
-                if constexpr (DIR) rs *= table_mod(dx, dy, ph, ri, P.dir_wx, P.dir_wy, P.absorb_l2);      // (own instantiations: the default path never sees this)
-                float gr = rs * __builtin_amdgcn_cosf(ph), gi = rs * __builtin_amdgcn_sinf(ph);
-                asm volatile("" : "+v"(gr), "+v"(gi));      // (two plain multiplies: packed fp32 beside the partner block's matrix instructions measured slower)
-                half2_t hi;
-                if constexpr (FP8) hi = __builtin_convertvector(float2_t{gr, gi}, half2_t);      // to nearest: |lo| <= half an ulp
-                else hi = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_pkrtz(gr, gi));
-                // lo = g - (float)hi in ONE mixed-precision fma per component (the compiler's form: a convert and a subtract)
-                float lr, li;
-                const unsigned hw = __builtin_bit_cast(unsigned, hi);
-                asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lr) : "v"(hw), "v"(gr));
-                asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(li) : "v"(hw), "v"(gi));
-                unsigned lo_word;
-                if constexpr (FP8) {             // e4m3 bytes [lo re, lo im | hi re, hi im], |.| <= 256 (448 overflows to NaN)
-                    // (v_cvt_scalef32_pk_fp8_f32 DIVIDES by its power-of-two scale operand -- tools/probe/cvt_scale_probe.hip --
-                    // and rounds / saturates as the unscaled convert: the four operand scalings cost no instruction)
-                    short2_t w;                  // (both halves are written below)
-                    w = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w, lr, li, 1.0f / COS_F8_LO, false);
-                    w = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w, gr, gi, 1.0f / COS_F8_HI, true);
-                    lo_word = __builtin_bit_cast(unsigned, w);
-                } else {
-                    lo_word = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(lr, li));
-                }
-                if (ok && OLX_IN(o, T_WORDS, 0)) {
-                    s_hi[o] = __builtin_bit_cast(unsigned, hi);
-                    s_lo[o] = lo_word;
-                }
+            for (int z = 0; z < COS_P; ++z) dz2[z] = plane_dz2(z);
+            auto entry_put = [&](const float r2, const float dz2v, const float dx, const float dy, const int o, const bool ok) __attribute__((always_inline)) {
+                unsigned hw, lw;
+                entry(r2, dz2v, dx, dy, hw, lw);
+                put(o, ok, hw, lw);
             };
             // The fill proper.  FULL form (reuse_c = 0): 12 columns x 5 rows per round -- rows 0 .. TROWS - 2 in whole rounds x the wave's
             // two planes, the LAST row once for both planes (row group wl takes plane wl): 11 instead of 12 evaluations per lane and pair.
@@ -203,7 +272,7 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
                     const float dy = fmaf(W, P.hy_hi, fmaf(W, P.hy_lo, P.fy0));
                     const float r2 = fmaf(dy, dy, dx2);
 #pragma unroll
-                    for (int z = 0; z < COS_P; ++z) entry(r2, dz2[z], dx, dy, z * PSZ + tw_off + RPF * r * CP_TW, gen_lane);
+                    for (int z = 0; z < COS_P; ++z) entry_put(r2, dz2[z], dx, dy, z * PSZ + tw_off + RPF * r * CP_TW, gen_lane);
                 }
                 // (block-uniform: the fragments of KY positions reach table rows 0 .. KY + 14)
                 const bool last_row = KY + 14 >= TROWS - 1;
@@ -214,14 +283,14 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
                     float dzl = dz2[0];
 #pragma unroll
                     for (int z = 1; z < COS_P; ++z) dzl = zt == z ? dz2[z] : dzl;
-                    entry(fmaf(dy, dy, dx2), dzl, dx, dy, (wave * COS_P + zt) * PSZ + rowt * CP_TW + (CP_UW - 1 - ui), zt < COS_P && (last_row || rowt < TROWS - 1));
+                    entry_put(fmaf(dy, dy, dx2), dzl, dx, dy, (wave * COS_P + zt) * PSZ + rowt * CP_TW + (CP_UW - 1 - ui), zt < COS_P && (last_row || rowt < TROWS - 1));
                 } else if (last_row) {
                     const float W = (float)(Wsb - P.my * wl + (TROWS - 1) * P.my);
                     const float dy = fmaf(W, P.hy_hi, fmaf(W, P.hy_lo, P.fy0));
                     float dzl = dz2[0];
 #pragma unroll
                     for (int z = 1; z < COS_P; ++z) dzl = wl == z ? dz2[z] : dzl;
-                    entry(fmaf(dy, dy, dx2), dzl, dx, dy, (wave * COS_P + wl) * PSZ + (TROWS - 1) * CP_TW + (CP_UW - 1 - ui), wl < COS_P);
+                    entry_put(fmaf(dy, dy, dx2), dzl, dx, dy, (wave * COS_P + wl) * PSZ + (TROWS - 1) * CP_TW + (CP_UW - 1 - ui), wl < COS_P);
                 }
             };
             if (reuse) {
@@ -243,7 +312,17 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
                     __builtin_memcpy(__builtin_assume_aligned(s_lo + mo + 2, 8), &mv[3], 8);
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (no instruction: pins the move ahead of the fill's stores in the compiler's order too)
-                fill(IntC<1>{});
+                if (held) {             // the 8 new columns: evaluated ahead, 14 stores per lane
+#pragma unroll
+                    for (int e = 0; e < CP_AHEAD_N; ++e) {
+                        int o;
+                        bool ok;
+                        ru_slot(e, lane_o, o, ok);
+                        put(o, ok, held_hi[e], held_lo[e]);
+                    }
+                } else {
+                    fill(IntC<1>{});
+                }
             } else {
                 fill(IntC<0>{});
             }
@@ -255,13 +334,27 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
         if (sb0 == 0) OLX_STAMP(2);
         __syncthreads();
         if (sb0 == 0) OLX_STAMP(3);
-        {   // next pair's fragments: in flight during the K-steps, drained by the next barrier
+        // next pair's fragments: in flight during the K-steps, drained by the next barrier.  Where the wave holds fill-ahead words on top of the
+        // fp8 shape's fragments (PRE_LATE) the request waits until the K-steps are through: the 16 registers of pre[] are not live across them
+        // (held words + pre[] + the K-steps' 93 registers do not fit 128; requested at the last K-step group they spilled 2 - 6 registers).
+        auto request_next = [&]() __attribute__((always_inline)) {
+            int tid_o = tid;
+            if constexpr (PRE_LATE) asm volatile("" : "+v"(tid_o));             // (opaque: the request stays where it is written)
             const int nxt = (sb0 + PAIR) * 4 * NT * B_KS_U4, lim = n_sb * 4 * NT * B_KS_U4;
 #pragma unroll
             for (int q = 0; q < PRE; ++q) {
-                const int idx = nxt + tid + q * THREADS;
-                if (idx < lim) pre[q] = bsrc[idx];
+                const int idx = nxt + tid_o + q * THREADS;
+                if constexpr (PRE_LATE) pre[q] = idx < lim ? bsrc[idx] : make_uint4(0, 0, 0, 0);      // (assigned either way: pre[] is dead from the stage write above to here)
+                else if (idx < lim) pre[q] = bsrc[idx];
             }
+        };
+        if constexpr (!PRE_LATE) request_next();
+        // fill-ahead: the next pair's reuse-form entries in ONE piece in front of the first tiles, at priority 0, behind a wave-uniform scalar branch.
+        // A wave without tiles still owns two planes of the table and evaluates them; a wave whose planes lie beyond nz evaluates nothing.
+        // (Spread over the four (sl, kb) groups, or placed behind a later group or behind the K-steps, the same evaluations made the launch slower:
+        // DESIGN 5.6.)
+        if constexpr (AHEAD) if (ahead_ok && my_planes && sb0 + PAIR < n_sb) {      // (reuse_ok: the next pair is (sa + 1, sbb0))
+            ru_eval_all(sa + 1, sbb0, held_hi, held_lo);
         }
 #pragma unroll                                          // (unrolled: the pair position becomes part of the immediate table offsets)
         for (int sl = 0; sl < PAIR; ++sl) {
@@ -348,6 +441,7 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
                 }
             }
         }
+        if constexpr (PRE_LATE) request_next();
         if (sb0 == 0) OLX_STAMP(4);
     }
     OLX_STAMP(5);

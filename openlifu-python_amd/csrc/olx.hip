@@ -791,6 +791,7 @@ static int configure_variant_impl(olx_ctx* c) {
                 Q.vox = L.vox; Q.flags = L.flags; Q.n_foci = F;
 #ifdef OLX_DEV_PINS
                 { const char* e = getenv("OLX_EXP_CP_NOREUSE"); Q.cp_noreuse = (e && atoi(e) != 0) ? 1 : 0; }   // (A/B) kernel 2g fills every table pair in full; the variant name says "noreuse"
+                { const char* e = getenv("OLX_EXP_CP_NOFILLAHEAD"); Q.cp_nofillahead = (e && atoi(e) != 0) ? 1 : 0; }   // (A/B) kernel 2g keeps the reuse fill a phase of its own; the variant name says "nofillahead"
 #endif
                 Q.dir_wx = (c->dir_lattice && c->directivity) ? (float)(0.5 * c->h_size[0] / lambda) : 0.f;      // element width / length over 2 lambda (DIR instantiations)
                 Q.dir_wy = (c->dir_lattice && c->directivity) ? (float)(0.5 * c->h_size[1] / lambda) : 0.f;
@@ -896,13 +897,13 @@ static int configure_variant_impl(olx_ctx* c) {
                     n_mfma = (long long)((double)npos_all * Q.kblocks * A.nsa * A.nsb * 4 * c->nt * corr_units * ntiles);
                 }
 #ifdef OLX_DEV_PINS
-                const char* const noreuse_tag = (c->use_cosetp && Q.cp_noreuse) ? ",noreuse" : "";
+                const std::string pin_tags = std::string((c->use_cosetp && Q.cp_noreuse) ? ",noreuse" : "") + ((c->use_cosetp && Q.cp_nofillahead) ? ",nofillahead" : "");
 #else
-                const char* const noreuse_tag = "";
+                const std::string pin_tags;
 #endif
                 snprintf(nmbuf, sizeof nmbuf, "field_coset%s_k<nt%d,mx%d,my%d,flat,%s%s%s> %d columns for %d foci x %d images in %d tile(s); "
                          "%dx%d lattice, pitch %dx%d voxels, %lld MFMA/launch (%lld dense)", c->use_cosetp ? "p" : "", c->nt, c->mx, c->my, lat_clamp ? "clamp" : "noclamp",
-                         f8tag.c_str(), noreuse_tag, total_cols, F, n_img, ntiles, A.ax, A.ay, A.mx, A.my, n_mfma, n_dense);
+                         f8tag.c_str(), pin_tags.c_str(), total_cols, F, n_img, ntiles, A.ax, A.ay, A.mx, A.my, n_mfma, n_dense);
                 }
             } else {
                 const long long n_mfma = (long long)L.tiles_x * L.tiles_y * L.kgroups * A.nsa * A.nsb * 4 * c->lat_mt * c->nt * 3 * ntiles;
@@ -1088,7 +1089,7 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
         // derived below is still valid -- an interactive caller re-plans per target while only the steering changes.  The steering-
         // dependent part (configure_variant + packing) is redone at the next launch anyway when the table changed.
         std::string env;   // the developer switches the plan below reads
-        for (const char* name : {"OLX_FIELD_VARIANT", "OLX_FP8_CORRECTION", "OLX_EXP_TOEP_SAW", "OLX_EXP_TOEP_NM", "OLX_EXP_KGRP", "OLX_INTENSITY_STORED", "OLX_EXP_CP_NOREUSE"}) { const char* e = getenv(name); env += e ? e : ""; env += '|'; }
+        for (const char* name : {"OLX_FIELD_VARIANT", "OLX_FP8_CORRECTION", "OLX_EXP_TOEP_SAW", "OLX_EXP_TOEP_NM", "OLX_EXP_KGRP", "OLX_INTENSITY_STORED", "OLX_EXP_CP_NOREUSE", "OLX_EXP_CP_NOFILLAHEAD"}) { const char* e = getenv(name); env += e ? e : ""; env += '|'; }
         const bool same = c->planned && !c->uploaded && !c->hetero && !c->pulsed && memcmp(&c->grid, g, sizeof *g) == 0 && c->slab.x_begin == s.x_begin &&
                           c->slab.x_count == s.x_count && c->plan_foci == n_foci && c->freq == freq && c->c == cs && c->rho == rho &&
                           c->p0_pa == p0_pa && c->flags == flags && c->plan_absorb == c->absorb_np_m && c->nbuf == (c->comm_active() ? olx_ctx::NBUF : 1) && c->plan_env == env;

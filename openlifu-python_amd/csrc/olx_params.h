@@ -96,6 +96,7 @@ struct CosetParams {
     int n_foci;                // planned foci: the output arrays hold n_foci volumes of vox floats (what the debug build's store checks compare with)
 #ifdef OLX_DEV_PINS
     int cp_noreuse;            // developer builds only (OLX_EXP_CP_NOREUSE=1): kernel 2g fills every pair table in full instead of taking 4 columns from the previous pair
+    int cp_nofillahead;        // developer builds only (OLX_EXP_CP_NOFILLAHEAD=1): kernel 2g evaluates a reuse-form pair in its own fill phase, not in front of the K-steps of the pair before it
 #endif
 };
 
