@@ -281,7 +281,7 @@ int olx_field_absorption(olx_ctx *ctx, double np_per_m);
  * OLX_OUT_PMAX asks for p_max = max(0, max_k p) as one more resident volume: olx_field_scale, olx_field_scale_aggregate and the scaling
  * of olx_solution_analyze scale it too, the device aggregate also forms max_f p_max_f (olx_aggregate_fetch_pmax).  Homogeneous media
  * (with olx_field_absorption) and any element geometry; a pulsed plan refuses a slab, a communicator, OLX_FIELD_DIRECTIVITY,
- * OLX_OUT_COMPLEX and olx_field_set_medium.  cycles > 0 and dt > 0 [s] are used as given (the caller applies its defaults).
+ * OLX_OUT_COMPLEX and olx_field_set_medium (a heterogeneous medium is opt-in: olx_field_pulse_medium below).  cycles > 0 and dt > 0 [s] are used as given (the caller applies its defaults).
  * Two more outputs of the same time axis (neither touches a plan that does not ask for it):
  *   OLX_OUT_PII   the pulse intensity integral PII_f(v) = 1e-4 dt / (rho c) sum_k p_f(v, t_k)^2 [J/cm^2] as one more resident volume
  *                 (olx_field_fetch_pii); PII / (cycles / f0) is the pulse-average intensity [W/cm^2].  olx_field_scale, olx_field_scale_aggregate
@@ -319,6 +319,21 @@ int olx_pii_upload(olx_ctx *ctx, int n_foci, const float *pii);
  * samples (F * n_points * n_t) in one call give OLX_EINVAL.  Synchronous. */
 #define OLX_PULSE_TRACE_MAX_SAMPLES (1ll << 26) /* 256 MiB of float32 */
 int olx_field_pulse_trace(olx_ctx *ctx, int n_points, const long long *voxels, float *trace_out);
+/* Heterogeneous medium for the CURRENT pulsed plan, opt-in (DESIGN.md section 2 "Pulsed model through a medium", kernel 2ph): valid only
+ * after olx_field_plan of a pulsed plan (OLX_ESTATE otherwise), until the next olx_field_plan.  Volumes as olx_field_set_medium's: float32
+ * [nx*ny*nz] of the whole planned grid, C order, NULL = the plan's constant; attenuation in dB/cm/MHz^alpha_power.  olx_field_launch and
+ * olx_field_pulse_trace of the plan then run the pulsed model with the medium on every straight ray (sampled quadrature, one sample per
+ * non-trivial plane, plane bounds and ray sums A_e, E_e exactly as olx_steer_map_medium defines them at a grid voxel):
+ *   t_e = floor(tau_e / dt) dt + (d'_e + E_e) / c_ref,   p(v, t) = sum_e w_e exp(-A_e) / d'_e cos(2 pi f0 (t - t_e)) 1[0 <= t - t_e < T]
+ * p_max, p_min, PII and the traces as in the homogeneous model; the intensity and the PII take the voxel's own rho(v) c(v).  Whether an
+ * element is active at a sample is decided in fp64, E_e included (sigma = c_ref / c - 1 stays fp64 on the device).  olx_field_variant
+ * then reads "field_pulse_med_k (pulsed through a medium: ... samples, ... planes, R = ...)".  Every reader of the result (scale,
+ * aggregate, analysis, olx_pii_post, the thermal sources) sees it exactly as it sees a homogeneous pulsed result.
+ * OLX_EINVAL: a uniform absorption (olx_field_absorption > 0), more than 1024 elements (the kernel caches the ray sums of 16 elements
+ * per lane), volumes that are not finite / positive.  olx_field_set_medium keeps refusing a pulsed plan: that call selects the
+ * continuous-wave kernels. */
+int olx_field_pulse_medium(olx_ctx *ctx, const float *sound_speed, const float *attenuation_db_cm_mhz, const float *density,
+                           double alpha_power);
 
 /* Thermal model (DESIGN.md section 2 "thermal model", kernel 3): Pennes bioheat rise dT above a baseline over a pulse sequence,
  *   rho Cp d(dT)/dt = div(kappa grad dT) - W dT + Q,   Q = 2 alpha 1e4 I_f(v) while a pulse aimed at focus f is on [W/m^3],

@@ -82,13 +82,13 @@ int olx_ctx_destroy(olx_ctx* c) {
 const char* olx_last_error(const olx_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 #ifdef OLX_DEBUG_BOUNDS   // debug build (k_types.hip.h): the kernels' index checks report here
-extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); int olx_dbg_bounds_bfmed(unsigned*); int olx_dbg_bounds_small(unsigned*); int olx_dbg_bounds_steer(unsigned*); int olx_dbg_bounds_steermed(unsigned*); }
+extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); int olx_dbg_bounds_bfmed(unsigned*); int olx_dbg_bounds_small(unsigned*); int olx_dbg_bounds_steer(unsigned*); int olx_dbg_bounds_steermed(unsigned*); int olx_dbg_bounds_pulsemed(unsigned*); }
 static int report_bounds(olx_ctx* c) {
     struct { const char* name; int (*read)(unsigned*); } units[] = {{"2g (k_coset2.hip)", olx_dbg_bounds_cosetp}, {"2e (k_coset.hip)", olx_dbg_bounds_coset},
                                                                      {"2f (k_toep.hip)", olx_dbg_bounds_toep}, {"2m (k_hmarch.hip)", olx_dbg_bounds_hmarch},
                                                                      {"2p (k_pulse.hip)", olx_dbg_bounds_pulse}, {"3 (k_thermal.hip)", olx_dbg_bounds_thermal},
                                                                      {"1m / 1a (k_bfmed.hip)", olx_dbg_bounds_bfmed}, {"pii_post_k (k_small.hip.h)", olx_dbg_bounds_small}, {"4 (k_steer.hip)", olx_dbg_bounds_steer},
-                                                                     {"4h (k_steer_med.hip)", olx_dbg_bounds_steermed}};
+                                                                     {"4h (k_steer_med.hip)", olx_dbg_bounds_steermed}, {"2ph (k_pulse_med.hip)", olx_dbg_bounds_pulsemed}};
     int rc = OLX_OK;
     for (auto& u : units) {
         unsigned w[4] = {0, 0, 0, 0};
@@ -1054,6 +1054,7 @@ static int plan_pulse(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n
     P.pii_scale = (float)(1e-4 * dt / (rho * cs));
     P.vox = vox;
     c->pulsed = true; c->pmax_live = false; c->agg_pmax_valid = false; c->pii_live = false;
+    c->pulse_med = false;      // (olx_field_pulse_medium belongs to the plan it was called on)
     char nm[128];
     snprintf(nm, sizeof nm, "field_pulse_k (pulsed: %d samples, %.4g samples per burst)", c->pulse_nt, P.tdt);
     c->variant = nm;
@@ -1102,6 +1103,7 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->grid = *g; c->slab = s; c->plan_foci = n_foci; c->hetero = false;
+    c->pulse_med = false;
     c->pulsed = false; c->pmax_live = false; c->agg_pmax_valid = false; c->pii_live = false;
     c->agg_local = -1; c->agg_total = 0;   // aggregate over all planned foci unless olx_field_aggregate_counts says otherwise
     c->freq = freq; c->c = cs; c->rho = rho; c->p0_pa = p0_pa; c->flags = flags; c->plan_absorb = c->absorb_np_m;
@@ -1238,7 +1240,7 @@ int olx_field_launch(olx_ctx* c) {
         c->agg_pmax_valid = false; c->pii_live = false; c->pii_w_valid = false; c->pii_max_valid = false;
         const bool prof = c->prof_on && (size_t)(2 * c->prof_n + 1) < c->prof_ev.size();
         if (prof) HIPCHK(c, hipEventRecord(c->prof_ev[2 * c->prof_n], c->stream));
-        olx_launch_pulse(c, c->d_pmag[0]);
+        if (c->pulse_med) olx_launch_pulse_med(c, c->d_pmag[0]); else olx_launch_pulse(c, c->d_pmag[0]);
         HIPCHK(c, hipGetLastError());
         if (prof) { HIPCHK(c, hipEventRecord(c->prof_ev[2 * c->prof_n + 1], c->stream)); c->prof_n++; }
         c->pmax_live = (c->flags & OLX_OUT_PMAX) != 0;
@@ -1512,7 +1514,7 @@ int olx_field_pulse_trace(olx_ctx* c, int n_points, const long long* voxels, flo
     if (rc) return rc;
     HIPCHK(c, hipMemcpy(c->d_ptrace_vox, voxels, sizeof(long long) * n_points, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemsetAsync(c->d_ptrace, 0, sizeof(float) * total, c->stream));
-    olx_launch_pulse_trace(c, n_points);
+    if (c->pulse_med) olx_launch_pulse_med_trace(c, n_points); else olx_launch_pulse_trace(c, n_points);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));     // (a large fetch runs on streams of its own, not ordered after this one)
     return fetch_to_host(c, trace_out, c->d_ptrace, sizeof(float) * total);
@@ -1948,6 +1950,99 @@ int olx_field_pulse(olx_ctx* c, double cycles, double dt, int n_t) {
     return OLX_OK;
 }
 
+// Kernel 2ph: the medium of the CURRENT pulsed plan (DESIGN.md section 2 "Pulsed model through a medium").  Buffers and a flag of its own
+// (pulse_med, d_pm_*): `hetero` selects the CW machinery -- the 2h / 2m launch, the d_inv2z readers -- and stays false.  A pulsed plan stores
+// its intensity, so every scan reads this result as it reads kernel 2p's.
+int olx_field_pulse_medium(olx_ctx* c, const float* sound_speed, const float* attenuation, const float* density, double alpha_power) {
+    if (!c) return OLX_EINVAL;
+    if (!c->planned || c->uploaded || !c->pulsed)
+        return fail(c, OLX_ESTATE, "olx_field_pulse_medium: needs a pulsed plan (olx_field_pulse, then olx_field_plan)");
+    if (c->plan_absorb > 0 || c->absorb_np_m > 0)
+        return fail(c, OLX_EINVAL, "olx_field_pulse_medium: a uniform absorption (olx_field_absorption) and a heterogeneous medium exclude each other: put the absorption into the medium volumes");
+    if (c->n_el != c->pulse.n_el) return fail(c, OLX_ESTATE, "olx_field_pulse_medium: the element table changed since the plan");
+    if (c->n_el > 1024)
+        return fail(c, OLX_EINVAL, "olx_field_pulse_medium: %d elements, kernel 2ph caches the ray sums of at most 1024 (16 per lane)", c->n_el);
+    if (!std::isfinite(alpha_power)) return fail(c, OLX_EINVAL, "olx_field_pulse_medium: alpha_power must be finite");
+    const olx_grid& g = c->grid;
+    const int nx = g.n[0], ny = g.n[1], nz = g.n[2], n = c->n_el;
+    const size_t nvox = (size_t)nx * ny * nz;
+    for (size_t o = 0; o < nvox; ++o) {
+        if (sound_speed && (!(sound_speed[o] > 0.f) || !std::isfinite(sound_speed[o]))) return fail(c, OLX_EINVAL, "olx_field_pulse_medium: sound speed must be finite and > 0");
+        if (attenuation && (!(attenuation[o] >= 0.f) || !std::isfinite(attenuation[o]))) return fail(c, OLX_EINVAL, "olx_field_pulse_medium: attenuation must be finite and >= 0");
+        if (density && (!(density[o] > 0.f) || !std::isfinite(density[o]))) return fail(c, OLX_EINVAL, "olx_field_pulse_medium: density must be finite and > 0");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const double c0 = c->c;
+    const double afac = std::pow(c->freq * 1e-6, alpha_power) * 100.0 / 8.685889638065035;      // dB/cm/MHz^y -> Np/m
+    // non-trivial planes: olx_field_set_medium's rule
+    std::vector<int> plane_of_k(nz, -1), plane_k;
+    for (int k = 0; k < nz; ++k) {
+        bool any = false;
+        for (size_t ij = 0; ij < (size_t)nx * ny && !any; ++ij) {
+            const size_t o = ij * nz + k;
+            if (sound_speed && (double)sound_speed[o] != c0) any = true;
+            if (attenuation && attenuation[o] != 0.f) any = true;
+        }
+        if (any) { plane_of_k[k] = (int)plane_k.size(); plane_k.push_back(k); }
+    }
+    const int np = (int)plane_k.size();
+    const size_t nxy = (size_t)nx * ny;
+    // compact [plane][i][j] arrays: sig = c_ref / c - 1 in fp64 from the float32 volume, a in Np/m rounded once
+    std::vector<double> sig(sound_speed ? std::max<size_t>(np * nxy, 1) : 0);
+    std::vector<float> att(attenuation ? std::max<size_t>(np * nxy, 1) : 0);
+    for (int p = 0; p < np; ++p)
+        for (size_t ij = 0; ij < nxy; ++ij) {
+            const size_t o = ij * nz + plane_k[p];
+            if (sound_speed) sig[p * nxy + ij] = c0 / (double)sound_speed[o] - 1.0;
+            if (attenuation) att[p * nxy + ij] = (float)((double)attenuation[o] * afac);
+        }
+    // per element: first plane strictly above, last plane strictly below (fp64: olx_field_set_medium's loop)
+    std::vector<int2> kb(n);
+    for (int e = 0; e < n; ++e) {
+        const double ez = c->h_pos[2 * (size_t)n + e];
+        int kf = 0;
+        while (kf < nz && !(g.origin[2] + kf * g.spacing[2] > ez)) ++kf;
+        int kl = nz - 1;
+        while (kl >= 0 && !(g.origin[2] + kl * g.spacing[2] < ez)) --kl;
+        kb[e] = make_int2(kf, kl);
+    }
+    c->pulse_med = false;      // (until everything below is in place)
+    int rc = c->d_pm_plane_k.reserve(c, np);
+    if (!rc) rc = c->d_pm_plane_of_k.reserve(c, nz);
+    if (!rc) rc = c->d_pm_kb.reserve(c, n);
+    if (!rc && sound_speed) rc = c->d_pm_sig.reserve(c, sig.size());
+    if (!rc && attenuation) rc = c->d_pm_att.reserve(c, att.size());
+    if (rc) return rc;
+    if (np) HIPCHK(c, hipMemcpy(c->d_pm_plane_k, plane_k.data(), sizeof(int) * np, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_pm_plane_of_k, plane_of_k.data(), sizeof(int) * nz, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_pm_kb, kb.data(), sizeof(int2) * n, hipMemcpyHostToDevice));
+    if (sound_speed) HIPCHK(c, hipMemcpy(c->d_pm_sig, sig.data(), sizeof(double) * sig.size(), hipMemcpyHostToDevice));
+    if (attenuation) HIPCHK(c, hipMemcpy(c->d_pm_att, att.data(), sizeof(float) * att.size(), hipMemcpyHostToDevice));
+    c->pm_has_sig = sound_speed != nullptr; c->pm_has_att = attenuation != nullptr; c->pm_has_z = density || sound_speed;
+    if (c->pm_has_z) {      // per-voxel 1e-4 / (2 rho c) of the intensity and the PII (sim/kwave_if.py:140-141)
+        std::vector<float> iz(nvox);
+        for (size_t o = 0; o < nvox; ++o) {
+            const double rho = density ? (double)density[o] : c->rho, cs = sound_speed ? (double)sound_speed[o] : c0;
+            iz[o] = (float)(1e-4 / (2.0 * rho * cs));
+        }
+        rc = c->d_pm_inv2z.reserve(c, nvox);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpy(c->d_pm_inv2z, iz.data(), sizeof(float) * nvox, hipMemcpyHostToDevice));
+    }
+    PulseMedParams& M = c->pm;
+    M.P = c->pulse;
+    M.nx = nx; M.n_planes = np;
+    M.inv_hx = 1.0 / g.spacing[0]; M.inv_hy = 1.0 / g.spacing[1];
+    M.two_dt = (float)(2.0 * c->pulse_plan_dt);
+    c->pulse_med_R = n <= 256 ? 4 : 16;
+    c->pulse_med = true;      // (resident volumes of an earlier launch of this plan stay what that launch made them)
+    char nm[160];
+    snprintf(nm, sizeof nm, "field_pulse_med_k (pulsed through a medium: %d samples, %d planes, R = %d)", c->pulse.n_t, np, c->pulse_med_R);
+    c->variant = nm;
+    return OLX_OK;
+}
+
 int olx_field_medium_layering(olx_ctx* c, int planes_per_layer) {
     if (!c) return OLX_EINVAL;
     if (planes_per_layer < 1 || planes_per_layer > 4096) return fail(c, OLX_EINVAL, "olx_field_medium_layering: planes_per_layer must be in [1, 4096]");
@@ -1984,7 +2079,7 @@ int olx_field_upload(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_
     if (intensity) HIPCHK(c, hipMemcpy(c->d_inten, intensity, sizeof(float) * total, hipMemcpyHostToDevice));
     c->grid = *g; c->slab = s; c->plan_foci = n_foci;
     c->agg_local = -1; c->agg_total = 0;   // like olx_field_plan: the counts of a former padded sweep do not describe these volumes
-    c->hetero = false; c->marched = false;
+    c->hetero = false; c->marched = false; c->pulse_med = false;
     c->pulsed = false; c->pmax_live = false; c->agg_pmax_valid = false; c->pii_live = false;    // (an upload holds no p_max and no PII)
     c->fp.nx = s.x_count; c->fp.ny = g->n[1]; c->fp.nz = g->n[2]; c->fp.vox = vox;
     c->flags = OLX_OUT_PMAG | (intensity ? OLX_OUT_INTENSITY : 0u);
@@ -2975,7 +3070,7 @@ static int aggregate_exchange(olx_ctx* c, bool want_scatter) {
     if (!c->uploaded && !c->derive_i && (vox & 3) == 0)   // launched result with stored volumes: intensity == scale(v) |p|^2, aggregate from |p| alone (half the reads);
                                                             // a deriving plan takes field_aggregate_k's DERIVE form below: also |p| alone, and the bits of the single-rank aggregate
         hipLaunchKernelGGL(field_aggregate_p_k, dim3(4096), dim3(256), 0, c->stream, c->d_pmag[c->cur], n_local, (long long)vox,
-                           inv_n, c->fp.inten_scale, c->hetero ? c->d_inv2z : nullptr, c->d_agg_p, with_i ? c->d_agg_i : nullptr);
+                           inv_n, c->fp.inten_scale, c->hetero ? (const float*)c->d_inv2z : (c->pulsed && c->pulse_med && c->pm_has_z ? (const float*)c->d_pm_inv2z : nullptr), c->d_agg_p, with_i ? c->d_agg_i : nullptr);
     else
         hipLaunchKernelGGL(c->derive_i ? field_aggregate_k<true> : field_aggregate_k<false>, dim3(2048), dim3(256), 0, c->stream, c->d_pmag[c->cur], with_i ? inten_arg(c) : nullptr,
                            n_local, (long long)vox, inv_n, c->fp.inten_scale, c->d_agg_p, with_i ? c->d_agg_i : nullptr);

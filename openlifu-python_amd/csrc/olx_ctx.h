@@ -158,6 +158,16 @@ struct olx_ctx {
     DevBuf<double> d_pii_A;                    // [PII_MAXF * 12] ... its focal frames
     DevBuf<unsigned> d_pii_peak;               // [4 * PII_MAXF + 1] ... its peaks (bit patterns)
     DevBuf<long long> d_ptrace_vox; DevBuf<float> d_ptrace;   // olx_field_pulse_trace: the voxel list and [F][n_points][n_t] samples
+    // pulsed model through a medium (kernel 2ph, olx_field_pulse_medium): buffers of their own, apart from the CW medium (`hetero`, d_med, d_inv2z ...)
+    bool pulse_med = false;                    // the current pulsed plan launches kernel 2ph (until the next plan or upload)
+    int pulse_med_R = 0;                       // its cache slots per lane: 4 (N <= 256) or 16 (N <= 1024)
+    PulseMedParams pm{};
+    DevBuf<double> d_pm_sig;                   // [n_planes][nx][ny] sigma = c_ref / c - 1 (fp64) of the non-trivial planes; not created without a sound-speed volume
+    DevBuf<float> d_pm_att;                    // [n_planes][nx][ny] a [Np/m]; not created without an attenuation volume
+    bool pm_has_sig = false, pm_has_att = false, pm_has_z = false;
+    DevBuf<int> d_pm_plane_k, d_pm_plane_of_k; // [n_planes] grid plane of a held plane; [nz] held plane of a grid plane, -1 = trivial
+    DevBuf<int2> d_pm_kb;                      // [N] { kfirst, klast } per element (the host's fp64 decisions)
+    DevBuf<float> d_pm_inv2z;                  // [voxels] 1e-4 / (2 rho(v) c(v)); created with a sound-speed or density volume
     // thermal model (kernel 3, olx_thermal_*): buffers of their own, apart from the field / aggregate volumes
     bool th_planned = false, th_uniform = false; ThermalParams th{};
     double th_rate = 0;                        // max_v (sum_faces K + W) / (rho Cp)_v [1/s]: the FTCS bound is dt <= 1 / th_rate

@@ -161,6 +161,15 @@ struct PulseParams {
     long long vox;
 };
 
+// kernel 2ph (field_pulse_med_k, k_pulse_med.hip): kernel 2p through a heterogeneous medium along straight rays (olx_field_pulse_medium)
+struct PulseMedParams {
+    PulseParams P;                  // kernel 2p's parameters of the same plan (absorb is 0: a uniform absorption is refused)
+    int nx;                         // (P carries ny, nz)
+    int n_planes;                   // non-trivial planes held on the device
+    double inv_hx, inv_hy;          // 1 / spacing [1/m]
+    float two_dt;                   // 2 dt [s]: PII scale of a voxel = two_dt x its 1e-4 / (2 rho c)
+};
+
 // kernel 3 (thermal_pack_k / thermal_step_k, k_thermal.hip): Pennes bioheat rise, explicit FTCS (olx_thermal_*)
 struct ThermalParams {
     int nx, ny, nz;

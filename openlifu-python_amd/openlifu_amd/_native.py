@@ -42,7 +42,7 @@ SYMBOLS = [
     "olx_aggregate_fetch", "olx_field_aggregate_device", "olx_field_analysis_peaks", "olx_field_aggregate_counts", "olx_rccl_path", "olx_bf_time", "olx_field_fetch_all", "olx_field_medium_layering", "olx_field_medium_model", "olx_set_element_apertures",
     "olx_solution_analyze", "olx_scan_time", "olx_comm_export", "olx_comm_import", "olx_comm_transport",
     "olx_field_scale_aggregate", "olx_field_absorption", "olx_comm_ranks_seen",
-    "olx_field_pulse", "olx_field_fetch_pmax", "olx_aggregate_fetch_pmax", "olx_field_fetch_pii", "olx_field_pulse_trace",
+    "olx_field_pulse", "olx_field_fetch_pmax", "olx_aggregate_fetch_pmax", "olx_field_fetch_pii", "olx_field_pulse_trace", "olx_field_pulse_medium",
     "olx_pii_post", "olx_pii_fetch_weighted", "olx_pii_fetch_max", "olx_pii_upload", "olx_thermal_source_pii",
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
     "olx_bf_set_medium", "olx_bf_solve_medium",
@@ -144,6 +144,7 @@ def load(require_gpu: bool = True):
         lib.olx_aggregate_fetch_pmax.argtypes = [vp, fp]
         lib.olx_field_fetch_pii.argtypes = [vp, fp]
         lib.olx_field_pulse_trace.argtypes = [vp, c_int, POINTER(ctypes.c_longlong), fp]
+        lib.olx_field_pulse_medium.argtypes = [vp, fp, fp, fp, c_double]
         lib.olx_pii_post.argtypes = [vp, dp, dp, c_int, dp, dp, c_double, c_double, c_double, fp]
         lib.olx_pii_fetch_weighted.argtypes = [vp, fp]
         lib.olx_pii_fetch_max.argtypes = [vp, fp]
@@ -597,6 +598,16 @@ class Context:
         out = np.empty((self._plan_foci, vox.size, self._plan_nt), dtype=np.float32)
         self._chk(self._lib.olx_field_pulse_trace(self._h, int(vox.size), vox.ctypes.data_as(POINTER(ctypes.c_longlong)), _fptr(out)))
         return out
+
+    def field_pulse_medium(self, sound_speed=None, attenuation=None, density=None, alpha_power=0.9):
+        """Per-voxel medium volumes [nx,ny,nz] of the planned grid (None = the plan's constant) for the CURRENT pulsed plan: its launches
+        and traces run the pulsed model along straight rays through the medium (kernel 2ph, olx_field_pulse_medium) until the next plan."""
+        arrs = []
+        for a in (sound_speed, attenuation, density):
+            arrs.append(None if a is None else np.ascontiguousarray(a, dtype=np.float32))
+            if arrs[-1] is not None and arrs[-1].shape != self._grid_shape:
+                raise ValueError(f"medium volumes must have the grid shape {self._grid_shape}, got {arrs[-1].shape}")
+        self._chk(self._lib.olx_field_pulse_medium(self._h, _fptr(arrs[0]), _fptr(arrs[1]), _fptr(arrs[2]), float(alpha_power)))
 
     # ---- pulse intensity integrals (pii_post_k) ------------------------------------------------------------------------------
     PII_MAX_FOCI = 8

@@ -354,7 +354,7 @@ class Engine:
     # ---- kernel 2 -----------------------------------------------------------------------------
     def field(self, arr, delays, apod, origin_m, spacing_m, n, freq, c, rho, p0_pa,
               want=("pmag", "intensity"), slab=None, steering_resident=False, medium=None, fp8_correction=None,
-              lazy=False, directivity=False, absorption=0.0, pulse=None, trace_voxels=None):
+              lazy=False, directivity=False, absorption=0.0, pulse=None, trace_voxels=None, pulsed_medium_model=None):
         """Pressure field for F foci -> dict of float32 arrays [F, nx, ny, nz] (fresh, writable,
         caller-owned).  ``steering_resident`` reuses the table the last ``beamform`` left on the
         device instead of uploading ``delays`` / ``apod``.  ``fp8_correction=False`` opts OUT of the e4m3
@@ -366,11 +366,16 @@ class Engine:
         stay in HBM until somebody reads them.  ``pulse = (cycles, dt, t_end, cfl)`` selects the pulsed model (olx_field_pulse, time axis by
         ``pulse_time_axis``): "pmag" then holds p_min and the result carries p_max under "pmax"; "pii" in ``want`` adds the pulse
         intensity integral [J/cm^2] (OLX_OUT_PII; a lazy result carries it like p_max, under "pii"), ``trace_voxels`` (linear voxel indices) adds the waveforms
-        p(t_k) there under "trace" [F, P, n_t] (olx_field_pulse_trace)."""
+        p(t_k) there under "trace" [F, P, n_t] (olx_field_pulse_trace).  ``pulsed_medium_model="straight_ray"`` lets the pulsed model take a
+        ``medium`` (olx_field_pulse_medium, kernel 2ph); without it a pulsed request with a medium is refused."""
+        if pulsed_medium_model not in (None, "straight_ray"):
+            raise ValueError(f'pulsed_medium_model must be None or "straight_ray", got {pulsed_medium_model!r}')
+        if pulsed_medium_model is not None and pulse is None:
+            raise ValueError("pulsed_medium_model needs the pulsed field model (the continuous-wave model picks its medium kernels by itself)")
         if pulse is None and ("pii" in want or trace_voxels is not None):
             raise ValueError('the pulse intensity integral ("pii") and the waveform traces need the pulsed field model')
         if pulse is not None:
-            if medium is not None:
+            if medium is not None and pulsed_medium_model is None:
                 raise NotImplementedError("pulsed field model: heterogeneous media are not implemented (homogeneous media, with or without uniform absorption, only)")
             if directivity:
                 raise NotImplementedError("pulsed field model: element directivity is not implemented")
@@ -414,7 +419,11 @@ class Engine:
             flags |= nat.FIELD_DIRECTIVITY
         self.ctx.field_absorption(0.0 if medium is not None else absorption)
         self.ctx.field_plan(origin_m, spacing_m, n, freq, c, rho, p0_pa, flags=flags, slab=slab)
-        if medium is not None:  # heterogeneous medium: layered straight-ray kernel
+        if medium is not None and pulse is not None:  # pulsed model through the medium: kernel 2ph (sampled quadrature, one plane per layer)
+            if int(medium.get("planes_per_layer", 1)) > 1:
+                raise NotImplementedError("pulsed field model through a medium: one plane per layer only")
+            self.ctx.field_pulse_medium(medium.get("sound_speed"), medium.get("attenuation"), medium.get("density"))
+        elif medium is not None:  # heterogeneous medium: layered straight-ray kernel
             self.ctx.field_set_medium(medium.get("sound_speed"), medium.get("attenuation"), medium.get("density"),
                                       planes_per_layer=int(medium.get("planes_per_layer", 1)), model=medium.get("model", "auto"))
         self.ctx.field_launch()

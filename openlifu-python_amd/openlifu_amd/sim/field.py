@@ -11,7 +11,9 @@ like ``directivity``):
   * ``"pulsed"``: the time-domain Rayleigh sum of ``cycles``-cycle tone bursts with the delays truncated
     to whole steps of ``dt``, sampled at k dt up to ``t_end``: peak positive / peak negative pressure
     (HIP kernel 2p; definition DESIGN.md section 2, time axis ``pulse_time_axis``).  Homogeneous media
-    only; directivity, impulse responses and the multi-GPU paths raise NotImplementedError.  Two opt-in outputs of its time axis:
+    by default; ``medium_model="straight_ray"`` opts in to a heterogeneous ``params``: the same model with the straight-ray sums of
+    the medium on every (voxel, element) ray, intensity and PII with the voxel's own impedance (HIP kernel 2ph; sampled quadrature,
+    one plane per layer, whole grid on one GPU).  Directivity, impulse responses and the multi-GPU paths raise NotImplementedError.  Two opt-in outputs of its time axis:
     ``pulse_intensity_integral=True`` adds PII = 1e-4 dt / (rho c) sum_k p(t_k)^2 [J/cm^2] (PII / (cycles / freq) is the pulse-average
     intensity; ``run_thermal_simulation(pulse_energy=...)`` heats with it), ``record_points`` [P, 3] in the units of ``params.coords``
     adds the waveforms p(t_k) at the nearest voxels to the raw dict ("p_trace" [P, n_t], "t" = k dt, "trace_voxels").
@@ -35,6 +37,7 @@ _ATTRS = {"p_max": {"units": "Pa", "long_name": "PPP"}, "p_min": {"units": "Pa",
 
 ALPHA_POWER = 0.9      # the reference's kWaveMedium(alpha_power=0.9), sim/kwave_if.py:57
 FIELD_MODELS = ("cw", "pulsed")
+PULSED_MEDIUM_MODELS = ("straight_ray",)      # how the pulsed model crosses a heterogeneous medium, opt-in (kernel 2ph)
 
 
 def parse_field_model(value) -> str:
@@ -42,6 +45,16 @@ def parse_field_model(value) -> str:
     model = "cw" if value is None or str(value).strip() == "" else str(value).strip().lower()
     if model not in FIELD_MODELS:
         raise ValueError(f"field_model must be one of {FIELD_MODELS}, got {value!r}")
+    return model
+
+
+def parse_pulsed_medium_model(value):
+    """``medium_model`` of run_simulation / ``SimSetup.options["pulsed_medium_model"]``: None (default, also for ""), or "straight_ray"."""
+    if value is None or str(value).strip() == "":
+        return None
+    model = str(value).strip().lower()
+    if model not in PULSED_MEDIUM_MODELS:
+        raise ValueError(f"the pulsed model's medium_model must be None or one of {PULSED_MEDIUM_MODELS}, got {value!r}")
     return model
 
 
@@ -100,18 +113,25 @@ def _medium(params, freq, ref_values_only=False):
 
 def simulate_foci(arr, params, delays, apod, freq, amplitude, want=("pmag", "intensity"),
                   steering_resident=False, slab=None, fp8_correction=None, lazy=False, hetero_planes_per_layer=1,
-                  hetero_model="auto", directivity=False, ref_values_only=False, pulse=None, trace_voxels=None):
+                  hetero_model="auto", directivity=False, ref_values_only=False, pulse=None, trace_voxels=None, pulsed_medium_model=None):
     """Batched core: F foci in one launch -> dict of float32 arrays [F, nx, ny, nz], or with ``lazy`` a
     ``DeviceResult`` whose volumes stay in HBM until read (``lazy_stack`` wraps it in the reference's schema).
     ``pulse = (cycles, dt, t_end, cfl)``: the pulsed model -- "pmag" holds p_min, "pmax" p_max, "pii" in ``want`` adds the pulse intensity
-    integral and ``trace_voxels`` (linear voxel indices) the waveforms there under "trace" [F, P, n_t] (not with ``lazy``)."""
+    integral and ``trace_voxels`` (linear voxel indices) the waveforms there under "trace" [F, P, n_t] (not with ``lazy``).
+    ``pulsed_medium_model="straight_ray"`` opts the pulsed model in to a heterogeneous ``params`` (kernel 2ph: sampled quadrature, one plane
+    per layer); without it such a ``params`` is refused, and a homogeneous one runs kernel 2p either way."""
+    pulsed_medium_model = parse_pulsed_medium_model(pulsed_medium_model)
+    if pulsed_medium_model is not None and pulse is None:
+        raise ValueError("pulsed_medium_model needs the pulsed field model (the continuous-wave model picks its medium kernels by itself)")
     if pulse is not None:
         check_pulsed_supported(arr, directivity)
     coords = params.coords
     origin, spacing, n = grid_from_coords(coords)
     c, rho, medium, absorption = _medium(params, freq, ref_values_only)
-    if pulse is not None and medium is not None:
+    if pulse is not None and medium is not None and pulsed_medium_model is None:
         raise NotImplementedError("pulsed field model: heterogeneous media are not implemented (homogeneous media, with or without uniform absorption, only)")
+    if pulse is not None and medium is not None and int(hetero_planes_per_layer) > 1:
+        raise NotImplementedError("pulsed field model through a medium: one plane per layer only (hetero_planes_per_layer > 1 is not implemented)")
     if medium is not None and int(hetero_planes_per_layer) > 1:   # opt-in layered-screen quadrature (DESIGN.md section 7)
         medium["planes_per_layer"] = int(hetero_planes_per_layer)
     if medium is not None:   # "auto": marched ray sums (kernel 2m) when the elements lie below the medium, else sampled (2h)
@@ -120,7 +140,7 @@ def simulate_foci(arr, params, delays, apod, freq, amplitude, want=("pmag", "int
     return get_engine().field(arr, delays, apod, origin, spacing, n, float(freq), c, rho, p0, want=want,
                               slab=slab, steering_resident=steering_resident, medium=medium,
                               fp8_correction=fp8_correction, lazy=lazy, directivity=directivity, absorption=absorption, pulse=pulse,
-                              trace_voxels=trace_voxels)
+                              trace_voxels=trace_voxels, pulsed_medium_model=pulsed_medium_model)
 
 
 def parse_pii_option(options) -> bool:
@@ -139,6 +159,17 @@ def parse_pii_option(options) -> bool:
         raise ValueError('options["pulse_intensity_integral"] needs options["field_model"] = "pulsed" '
                          f'(got field_model = {options.get("field_model", "cw")!r}: the continuous-wave model has no time axis)')
     return on
+
+
+def parse_pulsed_medium_option(options):
+    """``SimSetup.options["pulsed_medium_model"]``: None / "" (default) or "straight_ray" -- the pulsed model through a heterogeneous medium
+    (kernel 2ph); ValueError for anything else.  It needs ``options["field_model"] = "pulsed"``."""
+    options = options or {}
+    model = parse_pulsed_medium_model(options.get("pulsed_medium_model"))
+    if model is not None and parse_field_model(options.get("field_model", "cw")) != "pulsed":
+        raise ValueError('options["pulsed_medium_model"] needs options["field_model"] = "pulsed" '
+                         f'(got field_model = {options.get("field_model", "cw")!r}: the continuous-wave model picks its medium kernels by itself)')
+    return model
 
 
 def lazy_stack(result, coords, dim="focal_point_index", internal=False):
@@ -179,9 +210,12 @@ def run_simulation(arr, params, delays=None, apod=None, freq: float = 1e6, cycle
                    amplitude: float = 1, dt: float = 0, t_end: float = 0, cfl: float = 0.5,
                    bli_tolerance: float = 0.05, upsampling_rate: int = 5, gpu: bool = True,
                    ref_values_only: bool = False, directivity: bool = False, field_model: str = "cw",
-                   pulse_intensity_integral: bool = False, record_points=None):
+                   pulse_intensity_integral: bool = False, record_points=None, medium_model=None):
     n = arr.numelements()
     pulse = (float(cycles), float(dt), float(t_end), float(cfl)) if parse_field_model(field_model) == "pulsed" else None
+    medium_model = parse_pulsed_medium_model(medium_model)
+    if medium_model is not None and pulse is None:
+        raise ValueError('medium_model needs field_model="pulsed" (the continuous-wave model picks its medium kernels by itself)')
     if pulse is None and (pulse_intensity_integral or record_points is not None):
         raise ValueError('pulse_intensity_integral and record_points need field_model="pulsed" (the continuous-wave model has no time axis)')
     want, trace_voxels = ("pmag", "intensity"), None
@@ -198,7 +232,7 @@ def run_simulation(arr, params, delays=None, apod=None, freq: float = 1e6, cycle
     logging.info("Running simulation")
     # (directivity: this path's extension -- the far-field pattern of the rectangular elements k-Wave models as finite sources)
     fields = simulate_foci(arr, params, delays[None, :], apod[None, :], freq, amplitude, want=want, directivity=directivity,
-                           ref_values_only=ref_values_only, pulse=pulse, trace_voxels=trace_voxels)
+                           ref_values_only=ref_values_only, pulse=pulse, trace_voxels=trace_voxels, pulsed_medium_model=medium_model)
     logging.info("Simulation Complete")
     if ref_values_only:
         # The reference then SIMULATES the reference medium (get_medium, sim/kwave_if.py:49-56) but still forms the intensity with
