@@ -95,8 +95,7 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
     // table generation role (planes 2 wave, 2 wave + 1): full form lane -> (wl = lane / 12 < 5, ui = lane % 12), round r: rows 5 r + wl; reuse form 8 x 8 (the fill lambda below).
     // (Its per-lane constants are formed inside the pair loop from an opaque copy of the lane index: hoisted, they would be live
     // across the K-steps, where the fp8 shape has no register to spare -- 5 spilled registers cost 190 MB of scratch traffic.)
-    // fragment read offset [words] of a tile's row for K-step (0, 0) = per-lane part (plane, k-group) + the tile's position
-    // (wave-uniform: kept in scalar registers, added per tile and K-step group -- five registers fewer across the K-steps)
+    // fragment read offset [words] of a tile's row for K-step (0, 0) = per-lane part (plane, k-group) + the tile's position (wave-uniform)
     const int lane_off = p16 * PSZ - g * CP_TW;
     int toff[MT];
 #pragma unroll
@@ -105,6 +104,27 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
         const int kx = (pos * ky_magic) >> 16, ky = pos - kx * KY;                // scalar: pos / KY, exact for pos <= 40 (host checks)
         toff[t] = (ky + ROW0) * CP_TW + (CP_UW - 8 - 2 * kx);
     }
+    // A tile-step (one tile in one (sl, kb) group) issues no vector instruction but its matrix instructions -- inside the K-steps every other one takes an issue
+    // slot from the matrix instructions of the SIMD's other waves.  The byte addresses of the wave's <= 5 tiles are formed here, once per block, and
+    // held across the pairs (opaque: neither re-derived nor sunk into the tile-steps); every fragment read takes its K-step and array offset as an immediate.
+    // Five registers: the e4m3 K-steps leave 21 since PRE_LATE (118 VGPRs with the clamp), the other instantiations have 94.
+    unsigned frag_b[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+        frag_b[t] = (unsigned)(lane_off + toff[t]) << 2;
+        asm volatile("" : "+v"(frag_b[t]));
+    }
+    // ... and the wave-uniform tile guards `t >= ntile` compare an SGPR copy of the tile count that every group of tile-steps takes for itself: shared by all
+    // groups, the compiler kept the four conditions as lane masks and passed them through a v_cndmask / v_cmp pair per tile
+    auto tile_count = [&]() __attribute__((always_inline)) {
+        int n = ntile;
+        asm volatile("" : "+s"(n));
+        return n;
+    };
+    // fragment words of tile t at word offset kso from its K-step (0, 0) position in table array `arr`
+    auto frag_at = [&](const unsigned* const arr, const int t, const int kso) __attribute__((always_inline)) -> const unsigned long long* {
+        return reinterpret_cast<const unsigned long long*>(reinterpret_cast<const unsigned char*>(arr + kso) + frag_b[t]);
+    };
     floatx4_t acc[MT][NT];
 #pragma unroll
     for (int t = 0; t < MT; ++t)
@@ -373,20 +393,19 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
                             b8[nt][4 * ka + 0] = (int)q.x; b8[nt][4 * ka + 1] = (int)q.y; b8[nt][4 * ka + 2] = (int)q.z; b8[nt][4 * ka + 3] = (int)q.w;
                         }
                     }
+                    const int nt_g = tile_count();
 #pragma unroll
                     for (int t = 0; t < MT; ++t) {
-                        if (t >= ntile) continue;            // wave-uniform
+                        if (t >= nt_g) continue;             // wave-uniform
                         Half8Bits ah[2];
                         intx8_t a8;
-                        int lo_t = lane_off;                 // (opaque: formed here, not hoisted into five live registers)
-                        asm volatile("" : "+v"(lo_t));
-                        const int ro = lo_t + toff[t];
+                        const int ro = (int)(frag_b[t] >> 2);      // the word index (read by the debug library's check alone)
 #pragma unroll
                         for (int ka = 0; ka < 2; ++ka) {
                             const int kso = 4 * ka - (4 * kb + 8 * sl) * CP_TW;   // the pair's second super-block reads 8 table rows lower
                             if (!OLX_IN(ro + kso, T_WORDS - 3, 1)) continue;
-                            const unsigned long long* ph2 = reinterpret_cast<const unsigned long long*>(s_hi + ro + kso);
-                            const unsigned long long* pl2 = reinterpret_cast<const unsigned long long*>(s_lo + ro + kso);
+                            const unsigned long long* ph2 = frag_at(s_hi, t, kso);
+                            const unsigned long long* pl2 = frag_at(s_lo, t, kso);
                             const unsigned long long h0 = __hip_atomic_load(ph2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                             const unsigned long long h1 = __hip_atomic_load(ph2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                             const unsigned long long l0 = __hip_atomic_load(pl2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -415,16 +434,15 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
                         bl[nt].u = s_B(sl * 4 + ks, nt, 1)[lane];
                     }
                     const int kso = 4 * ka - (4 * kb + 8 * sl) * CP_TW;
+                    const int nt_g = tile_count();
 #pragma unroll
                     for (int t = 0; t < MT; ++t) {
-                        if (t >= ntile) continue;            // wave-uniform
+                        if (t >= nt_g) continue;             // wave-uniform
                         Half8Bits ah, al;
-                        int lo_t = lane_off;
-                        asm volatile("" : "+v"(lo_t));
-                        const int ro = lo_t + toff[t];
+                        const int ro = (int)(frag_b[t] >> 2);
                         if (!OLX_IN(ro + kso, T_WORDS - 3, 1)) continue;
-                        const unsigned long long* ph2 = reinterpret_cast<const unsigned long long*>(s_hi + ro + kso);
-                        const unsigned long long* pl2 = reinterpret_cast<const unsigned long long*>(s_lo + ro + kso);
+                        const unsigned long long* ph2 = frag_at(s_hi, t, kso);
+                        const unsigned long long* pl2 = frag_at(s_lo, t, kso);
                         const unsigned long long h0 = __hip_atomic_load(ph2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                         const unsigned long long h1 = __hip_atomic_load(ph2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                         const unsigned long long l0 = __hip_atomic_load(pl2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -466,9 +484,10 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
     const float s_p = P.out_scale, s_i = P.out_scale * P.out_scale * P.inten_scale;
     const bool want_p = PONLY || (P.flags & 1u) != 0, want_i = !PONLY && (P.flags & 2u) != 0;      // (uniform)
     constexpr int NOUT = PONLY ? 1 : NT;                 // |p| alone: no intensity values, half the lane exchange
+    const int nt_e = tile_count();
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
-        if (t >= ntile) continue;
+        if (t >= nt_e) continue;
         float o[NOUT][4];
 #pragma unroll
         for (int r = 0; r < 4; r += 2) {
@@ -512,9 +531,10 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
             const long long fb = (long long)(code >> 2) * P.vox + kz;
             float* const base_p = pmag + fb;
             float* const base_i = inten + fb;
+            const int nt_q = tile_count();
 #pragma unroll
             for (int t = 0; t < MT; ++t) {
-                if (t >= ntile) continue;
+                if (t >= nt_q) continue;
                 const int pos = wave + COS_NW * t;
                 const int kx = (pos * ky_magic) >> 16, ky = pos - kx * KY;
                 const int i = ibase + 2 * P.mx * kx, j = jbase + P.my * ky;      // wave-uniform (scalar ALU)
