@@ -49,6 +49,22 @@ def test_marched_matrix_stays_inside_its_extents_in_the_debug_library():
 
 
 @pytest.mark.gpu
+def test_lattice_matrix_stays_inside_its_extents_in_the_debug_library():
+    """The 2e / 2f / 2g cases of tests/test_gpu_lattice_matrix.py (every fold pattern, clamp value, arithmetic, epilogue and row-tile count; padded arrays,
+    unequal parts, ragged plane blocks, several column tiles) in one child process against the debug library, the developer-pin cases (clamp with
+    e4m3 corrections under OLX_FP8_CORRECTION=1, which only such a build honours) among them: every case ends with olx_sync, which reports a
+    counted index violation."""
+    env = dict(os.environ, OLX_LIB_PATH=os.path.join(LIB, "libolx_dbg.so"))
+    for v in ("OLX_FIELD_VARIANT", "OLX_FP8_CORRECTION", "OLX_INTENSITY_STORED", "OLX_EXP_KGRP", "OLX_EXP_TOEP_SAW", "OLX_EXP_TOEP_NM", "OLX_EXP_CP_NOREUSE", "OLX_EXP_CP_NOFILLAHEAD"):
+        env.pop(v, None)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_lattice_matrix.py"), "-q", "-x", "-m", "gpu",
+                        "-k", "(matrix_case or dev_pin_case) and (2e- or 2f- or 2g-)", "-p", "no:cacheprovider"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    tail = (r.stdout + r.stderr)[-3000:]
+    assert r.returncode == 0, tail
+    assert " passed" in tail and "failed" not in tail and "error" not in tail.lower() and "skipped" not in tail, tail
+
+
+@pytest.mark.gpu
 def test_a_wrong_extent_is_reported():
     code = r"""
 import sys

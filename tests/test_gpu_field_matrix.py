@@ -266,22 +266,28 @@ def test_generators_and_table_follow_the_planning_rule():
 
 
 # ---- GPU: every case against the oracle ------------------------------------------------------------------------------------------------------
-def measure(ctx, xs, ys, zs, pos_m, area, delays, ap, outputs, want_variant=None, slab=None, refs=None, label=""):
+def measure(ctx, xs, ys, zs, pos_m, area, delays, ap, outputs, want_variant=None, slab=None, refs=None, label="", extra_flags=0, fragments=(),
+            directivity=None, absorption=0.0, tag="MATRIX"):
     """Plan (whole grid or the x-slab), launch, fetch `outputs` of every focus and compare them with the oracle over the full volume at
-    test_gpu_field.check's gates.  Returns (variant string, worst error per output, fetched volumes, oracle volumes)."""
+    test_gpu_field.check's gates.  Returns (variant string, worst error per output, fetched volumes, oracle volumes).  extra_flags: plan flags beside
+    the outputs (OLX_FIELD_FP16_CORRECTION, OLX_FIELD_DIRECTIVITY); fragments: pieces the variant string must hold after its prefix; directivity /
+    absorption: the oracle's per-term factors (the caller has set them on the context); tag: the first word of the printed line."""
     h = (xs[1] - xs[0], ys[1] - ys[0], zs[1] - zs[0])
     ctx.field_plan((xs[0], ys[0], zs[0]), h, (len(xs), len(ys), len(zs)), F0, C, RHO, P0,
-                   flags=sum({"pmag": nat.OUT_PMAG, "intensity": nat.OUT_INTENSITY, "complex": nat.OUT_COMPLEX}[o] for o in outputs), slab=slab)
+                   flags=extra_flags | sum({"pmag": nat.OUT_PMAG, "intensity": nat.OUT_INTENSITY, "complex": nat.OUT_COMPLEX}[o] for o in outputs), slab=slab)
     name = ctx.field_variant()
     if want_variant:
-        assert name.startswith(want_variant), (name, want_variant)
+        assert name.startswith(want_variant), (label, name, want_variant)
+    for frag in fragments:
+        assert frag in name, (label, frag, name)
     ctx.field_launch()
     sl = slice(None) if slab is None else slice(slab[0], slab[0] + slab[1])
     worst = dict.fromkeys(outputs, 0.0)
     vols, refs_out = [], []
     for f in range(delays.shape[0]):
         out = ctx.field_fetch(f, want=outputs)
-        ref = refs[f] if refs is not None else co.field_on_grid(xs, ys, zs, pos_m, area, delays[f], ap[f], F0, C, P0, dmin=0.5 * min(h))
+        ref = refs[f] if refs is not None else co.field_on_grid(xs, ys, zs, pos_m, area, delays[f], ap[f], F0, C, P0, dmin=0.5 * min(h),
+                                                                directivity=directivity, absorption=absorption)
         vols.append(out); refs_out.append(ref)
         ref = ref[sl]
         mx = np.abs(ref).max()
@@ -292,7 +298,8 @@ def measure(ctx, xs, ys, zs, pos_m, area, delays, ap, outputs, want_variant=None
             err = {"pmag": lambda: np.abs(out[o] - np.abs(ref)).max() / mx, "complex": lambda: np.abs(out[o] - ref).max() / mx,
                    "intensity": lambda: np.abs(out[o] - iref).max() / imx}[o]()
             worst[o] = max(worst[o], float(err)) if np.isfinite(err) else np.inf
-    print(f"MATRIX {label} | {name.split('>')[0]}> | " + " ".join(f"{o}={worst[o]:.2e}" for o in outputs))
+    figures = outputs if tag == "MATRIX" else ("pmag", "intensity", "complex")      # (the later matrices print every column, "-" where not planned)
+    print(f"{tag} {label} | {name.split('>')[0]}> | " + " ".join(f"{o}={worst[o]:.2e}" if o in worst else f"{o}=-" for o in figures))
     for o, tol in (("pmag", TOL_P), ("complex", 3 * TOL_P), ("intensity", TOL_I)):
         assert worst.get(o, 0.0) <= tol, (label, name, o, worst)
     return name, worst, vols, refs_out
