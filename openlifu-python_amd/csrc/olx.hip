@@ -532,10 +532,8 @@ int olx_bf_quantize(olx_ctx* c, double bf_clk_hz, int width_bits, uint16_t* tick
 
 // ---- kernel 2 -----------------------------------------------------------------------------
 // The pure planning code (lattice detection, K-slot map, mirror permutations, column packing, block records, store jobs, focus inference, the
-// e4m3 rule, kernel 2f's block shape) lives in olx_plan.cpp: no HIP in it, so the CPU suite runs it under AddressSanitizer / UBSan
-// (tools/plan_check.cpp, tests/test_plan_host.py).
-using olxplan::build_slot_map;
-using olxplan::coset_tiles16;
+// e4m3 rule, kernel 2f's block shape, and the variant decision that combines them) lives in olx_plan.cpp: no HIP in it, so the CPU suite runs
+// it under AddressSanitizer / UBSan (tools/plan_check.cpp, tests/test_plan_host.py).
 static void detect_lattice(olx_ctx* c, const double lo[3], const double hi[3], double dmin) {
     olxplan::detect_lattice(c->lat, c->flat, c->n_el, c->h_pos.data(), c->grid.spacing, lo, hi, dmin);
 }
@@ -546,395 +544,129 @@ static bool infer_foci(const olx_ctx* c, std::vector<double>& foci) {
                                c->grid.origin[2] + 0.5 * (c->grid.n[2] - 1) * c->grid.spacing[2], foci);
 }
 
-// Steering-dependent part of the kernel-2 variant choice (runs whenever the steering table changed):
-// dx/dy = distinct weight columns along folded axes (1 when every focus' delays and apodization are
-// mirror-symmetric), nf = foci per tile so that dx*dy*nf <= 8 accumulator columns.
-static int configure_variant_impl(olx_ctx* c);
+static_assert(olxplan::FLAG_OUT_PMAG == OLX_OUT_PMAG && olxplan::FLAG_OUT_INTENSITY == OLX_OUT_INTENSITY && olxplan::FLAG_OUT_COMPLEX == OLX_OUT_COMPLEX &&
+              olxplan::FLAG_FP16_CORRECTION == OLX_FIELD_FP16_CORRECTION, "olx_plan.h restates the plan flags");
+
+// The pins of the variant decision, read from the environment once per decision.  OLX_FIELD_VARIANT pins a kernel family / form for A/B runs and
+// OLX_FP8_CORRECTION=0 opts out of the e4m3 products like the plan flag.  Any other value of OLX_FP8_CORRECTION FORCES them past the eligibility
+// rule -- results may then miss the 1e-5 gate, so only developer builds (OLX_DEV_PINS: the debug library, A/B timing builds) honour it, like
+// the OLX_EXP_* switches; the product ignores them.
+static olxplan::Pins read_pins() {
+    olxplan::Pins pins;
+    if (const char* fv = getenv("OLX_FIELD_VARIANT"))
+        pins.family = !strcmp(fv, "lattice") ? olxplan::FamilyPin::lattice : !strcmp(fv, "lattice2d") ? olxplan::FamilyPin::lattice2d : olxplan::FamilyPin::other;
+    const char* f8env = getenv("OLX_FP8_CORRECTION");
+    if (f8env && !strcmp(f8env, "0")) pins.fp8 = -1;
+#ifdef OLX_DEV_PINS
+    if (f8env && strcmp(f8env, "0") != 0) pins.fp8 = 1;
+    if (const char* e = getenv("OLX_EXP_TOEP_SAW")) { const int v = atoi(e); if (v >= 8 && v <= 24) pins.toep_saw = v; }   // (A/B)
+    if (const char* e = getenv("OLX_EXP_TOEP_NM")) pins.toep_nm = atoi(e) == 3 ? 3 : 1;      // (A/B: 1 or 3)
+    if (const char* e = getenv("OLX_EXP_KGRP")) pins.kgrp = std::max(1, atoi(e));
+    { const char* e = getenv("OLX_EXP_CP_NOREUSE"); pins.cp_noreuse = e && atoi(e) != 0; }
+    { const char* e = getenv("OLX_EXP_CP_NOFILLAHEAD"); pins.cp_nofillahead = e && atoi(e) != 0; }
+#endif
+    return pins;
+}
+
+// Steering-dependent part of the kernel-2 variant choice (runs whenever the steering table changed), in two steps.  DECIDE: olxplan::decide_variant
+// (olx_plan.cpp: pure host code) chooses the kernel family and its shape from what olx_field_plan established, the steering table and the pins, and
+// fills the parameter blocks and tables.  APPLY: this function copies the plan into the context fields the launchers read, sizes the device buffers
+// and uploads the tables.  No choice of a family or a shape is made here.
 // (the result is remembered per steering version: olx_field_plan names the variant with it, the launch that follows packs against the same
 // decisions instead of deriving them again -- column packing, block records and their uploads were 0.28 ms of every calc_solution, twice)
 static int configure_variant(olx_ctx* c) {
     c->configured_version = ~0ull;
-    const int rc = configure_variant_impl(c);
-    if (rc == OLX_OK) c->configured_version = c->steer_version;
-    return rc;
-}
-static int configure_variant_impl(olx_ctx* c) {
     const int n = c->n_el, F = c->plan_foci;
-    const char* const fv_env = getenv("OLX_FIELD_VARIANT");      // pins a kernel family / form for A/B runs
-    auto steering_symmetric = [&](const std::vector<int>& perm) {
-        if (c->h_delays.size() != (size_t)F * n || c->h_apod.size() != (size_t)F * n) return false;
-        for (int f = 0; f < F; ++f)
-            for (int e = 0; e < n; ++e) {
-                const size_t a = (size_t)f * n + e, b = (size_t)f * n + perm[e];
-                if (std::fabs(c->h_delays[a] - c->h_delays[b]) * c->freq > 1e-9) return false;
-                if (std::fabs(c->h_apod[a] * c->h_area[e] - c->h_apod[b] * c->h_area[perm[e]]) >
-                    1e-12 * std::fabs(c->h_apod[a] * c->h_area[e])) return false;
-            }
-        return true;
-    };
-    if (c->hetero) {  // kernel 2h: no folds; the ray integrals of a (voxel, element) pair are shared by up to 8 foci per launch tile
-        c->mx = c->my = c->dx = c->dy = c->nt = 1; c->use_mfma = false; c->use_lattice = false;
-        c->nf = 1;
-        while (c->nf * 2 <= F && c->nf < 8) c->nf *= 2;
+    const bool steering = c->h_delays.size() == (size_t)F * n && c->h_apod.size() == (size_t)F * n;
+    olxplan::VariantIn in;
+    in.n = n; in.F = F; in.pos = c->h_pos.data(); in.area = c->h_area.data();
+    in.delays = steering ? c->h_delays.data() : nullptr; in.apod = steering ? c->h_apod.data() : nullptr;
+    in.px = c->h_px.data(); in.py = c->h_py.data();
+    in.freq = c->freq; in.c = c->c; in.p0_pa = c->p0_pa;
+    for (int a = 0; a < 3; ++a) { in.origin[a] = c->grid.origin[a]; in.spacing[a] = c->grid.spacing[a]; in.gn[a] = c->grid.n[a]; }
+    in.x_begin = c->slab.x_begin; in.x_count = c->slab.x_count; in.flags = c->flags; in.fp = c->fp;
+    in.flat = c->flat; in.clamp = c->clamp; in.near = c->near; in.min_dist = c->min_dist; in.mx = c->mx; in.my = c->my;
+    in.allow_shared = c->allow_shared; in.dir_lattice = c->dir_lattice; in.directivity = c->directivity; in.absorb_np_m = c->absorb_np_m;
+    in.force_kind = c->force_kind;
+    if (c->h_size.size() >= 2) { in.size0 = c->h_size[0]; in.size1 = c->h_size[1]; }
+    in.hetero = c->hetero; in.marched = c->marched; in.march_one = c->march_one;
+    in.n_planes = c->hp.n_planes; in.n_layers = c->hp.n_layers; in.planes_per_layer = c->planes_per_layer;
+    in.lat = &c->lat;
+    in.pins = read_pins();
+    if (olxplan::variant_reads_foci(in)) {      // the e4m3 rule wants the foci: known from olx_bf_solve in the element frame, or external delays that are geometric
+        bool known = c->h_foci.size() == 3 * (size_t)F && c->foci_version == c->steer_version;
+        if (!known && infer_foci(c, c->h_foci)) {
+            c->foci_version = c->steer_version;
+            known = true;
+        }
+        if (known) in.foci = c->h_foci.data();
+    }
+    int slot_rows = c->lat.nsbp;
+    const olxplan::VariantPlan p = olxplan::decide_variant(in, c->nf_s2, slot_rows);
+    if (slot_rows != c->lat.nsbp) olxplan::build_slot_map(c->lat, slot_rows);
+
+    c->mx = p.mx; c->my = p.my; c->dx = p.dx; c->dy = p.dy; c->nf = p.nf; c->nt = p.nt;
+    c->allow_shared = p.allow_shared; c->dir_lattice = p.dir_lattice;
+    c->use_mfma = p.use_mfma; c->use_lattice = p.use_lattice; c->use_coset = p.use_coset; c->use_toep = p.use_toep; c->use_cosetp = p.use_cosetp;
+    c->fp8corr = p.fp8corr;
+    if (c->hetero) {
         { int rc = c->d_tab.reserve(c, (size_t)((F + c->nf - 1) / c->nf) * n * (HET_TAB_HEAD + 2 * c->nf)); if (rc) return rc; }
         c->hp.n_foci = F;
-        char hb[160];
-        if (c->marched)
-            snprintf(hb, sizeof hb, "field_hmarch_k<nf%d,%s%s> (%d non-trivial planes, marched ray sums, %d launches)", c->nf,
-                     c->clamp ? "clamp" : "noclamp", c->march_one ? ",one-sum" : "", c->hp.n_planes, 2 * c->hp.n_planes + 1);
-        else if (c->hp.n_layers > 0)
-            snprintf(hb, sizeof hb, "field_hetero_k<4,nf%d,%s,layers> (%d non-trivial planes in %d layers of <= %d)", c->nf,
-                     c->clamp ? "clamp" : "noclamp", c->hp.n_planes, c->hp.n_layers, c->planes_per_layer);
-        else
-            snprintf(hb, sizeof hb, "field_hetero_k<4,nf%d,%s> (%d non-trivial planes)", c->nf, c->clamp ? "clamp" : "noclamp", c->hp.n_planes);
-        c->variant = hb;
-        return OLX_OK;
-    }
-    c->dx = (c->mx == 2 && !steering_symmetric(c->h_px)) ? 2 : 1;
-    c->dy = (c->my == 2 && !steering_symmetric(c->h_py)) ? 2 : 1;
-    const int nm = c->dx * c->dy;
-    c->nf = 1;
-    if (c->allow_shared) while (c->nf * 2 <= F && c->nf * 2 * nm <= 8) c->nf *= 2;
-    char nmbuf[384];
-    // kernel 2d applies when the array is a lattice commensurate with the grid and the pitch-strided row tiles
-    // (4 rows x pitch) do not overhang the computed region by more than 2x per axis
-    auto tile_fill = [](int width, int m) { const int blk = 4 * m; return (double)width / (double)(((width + blk - 1) / blk) * blk); };
-    const bool lat_ok = c->allow_shared && c->lat.ok && (c->force_kind == 0 || c->force_kind == 4) &&
-                        tile_fill(c->fp.nx - (c->mx == 2 ? c->fp.nx / 2 : 0), c->lat.mx) >= 0.5 &&
-                        tile_fill(c->fp.ny - (c->my == 2 ? c->fp.ny / 2 : 0), c->lat.my) >= 0.5;
-    if (c->modifier() && !(lat_ok && c->dir_lattice)) {   // no lattice path for this array / grid: the exact per-pair kernel 2a-d
-        c->allow_shared = false; c->dir_lattice = false;
-        c->mx = c->my = c->dx = c->dy = c->nf = 1;
-    }
-    c->use_mfma = c->allow_shared && c->force_kind != 2 && (c->force_kind == 3 || nm * c->nf >= 2 || lat_ok) && (!c->modifier() || lat_ok);
-    c->use_lattice = c->use_mfma && lat_ok;
-    c->fp8corr = false;
-    c->nt = 1;
-    if (c->use_mfma) {
-        // ---- kernel 2c column plan.  A column = one distinct steering vector W[sigma_m(e), f]; every
-        // (focus, mirror image) whose vector equals it (on-axis foci: all their images; mirror-partner foci of a
-        // Wheel: each other's images) is a store TARGET of that column, so it is accumulated once.  Foci are packed
-        // greedily into launch tiles of at most 32 columns (NT = 4 MFMA column tiles share each geometry fragment).
-        const double rev = c->freq / c->c, lambda = c->c / c->freq;
-        const int n_img = c->mx * c->my;
-        constexpr int MAXC = MFMA_COLS * MFMA_MAX_NT;
-        const std::vector<int> perm = olxplan::mirror_perms(n, n_img, c->mx == 2, c->my == 2, c->h_px.data(), c->h_py.data(), 4);
-        olxplan::Steering SV;
-        SV.n = n; SV.F = F; SV.n_img = n_img; SV.perm = perm.data(); SV.delays = c->h_delays.data(); SV.apod = c->h_apod.data(); SV.area = c->h_area.data(); SV.freq = c->freq;
-        typedef olxplan::Col Col;
-        // A column may store to ANY focus volume, so the search for an equal vector runs over every tile packed so far: mirror-partner
-        // foci share their columns wherever they sit in the sweep (a Wheel in its natural order has them at opposite ends).
-        auto pack = [&](int maxc) { return olxplan::pack_columns(SV, maxc); };
-        auto coset_fill = [&](int nt) {
-            const int wx = c->fp.nx - (c->mx == 2 ? c->fp.nx / 2 : 0), wy = c->fp.ny - (c->my == 2 ? c->fp.ny / 2 : 0);
-            const long long t16 = coset_tiles16(wx, wy, c->lat.mx, c->lat.my, nt);
-            return t16 > 0 ? (double)COS_P * wx * wy / (16.0 * (double)t16) : 0.0;
-        };
-        // e4m3 correction products (kernels 2e / 2f / 2g, NT <= 2) are the default wherever their error bound is a bound on the planned volume
-        // (include/olx.h, olx_field_plan): the foci are known (olx_bf_solve in the element frame, or external delays that infer_foci
-        // recognises as geometric), every focus lies inside the planned SLAB and has N_eff = (sum w)^2 / sum w^2 >= 256; the plan flag
-        // OLX_FIELD_FP16_CORRECTION opts out.  Decided here, before the columns are packed: it also decides the tile width below.
-        // The rule itself is olxplan::fp8_first_plane (first plane of the e4m3 products: 0 = every plane, a multiple of 16 = the plane blocks below keep
-        // three fp16 products, -1 = not eligible); the gates that need the context, and resolving the foci, stay here.
-        auto fp8_eligible = [&]() -> int {
-            if ((c->flags & (OLX_FIELD_FP16_CORRECTION | OLX_OUT_COMPLEX)) || c->modifier() || !c->lat.ok) return -1;
-            bool ok = c->h_foci.size() == 3 * (size_t)F && c->foci_version == c->steer_version;
-            if (!ok && infer_foci(c, c->h_foci)) {   // external delays: geometric?
-                c->foci_version = c->steer_version;
-                ok = true;
-            }
-            if (!ok) return -1;
-            return olxplan::fp8_first_plane(n, c->h_pos.data(), c->h_area.data(), c->h_apod.data(), F, c->h_foci.data(), c->grid.origin, c->grid.spacing,
-                                            c->grid.n, c->slab.x_begin, c->slab.x_count, c->lat, c->nf_s2);
-        };
-        // OLX_FP8_CORRECTION=0 (environment) opts out like the plan flag.  "1" FORCES the e4m3 products past the eligibility rule -- results may
-        // then miss the 1e-5 gate, so only developer builds (OLX_DEV_PINS: the debug library, A/B timing builds) honour it; the product ignores it.
-        const char* f8env = getenv("OLX_FP8_CORRECTION");
-        int fp8_cut = (lat_ok && !(f8env && !strcmp(f8env, "0"))) ? fp8_eligible() : -1;
-#ifdef OLX_DEV_PINS
-        if (f8env && strcmp(f8env, "0") != 0) fp8_cut = (lat_ok && !c->modifier()) ? 0 : -1;
-#endif
-        // (a split launch is two launches and two operand sets: where it does not pay, the whole launch keeps three fp16 products)
-        if (fp8_cut > 0 && !olxplan::fp8_split_pays(c->slab.x_count, c->grid.n[1], c->grid.n[2], F, fp8_cut)) fp8_cut = -1;
-        const bool fp8_want = fp8_cut >= 0;
-        c->fp8_kcut = fp8_want ? fp8_cut : 0;
-        olxplan::Tiles tiles = pack(MAXC);
-        int total_cols = 0;
-        // A sweep that needs SEVERAL launch tiles anyway is cut into tiles of 16 columns instead of 32: kernel 2g (NT = 2) then takes every
-        // tile -- 8 x 0.43 ms against 2e's 4 x 0.92 ms on the 64-focus sweep (127 columns).  One tile of 17 - 32 columns stays with 2e's
-        // NT = 4 shape when the fp16 corrections run (0.82 against 2 x 0.45 ms) and is cut in two when the e4m3 corrections apply, which
-        // the NT = 4 shape has no registers for (2 x 0.39 against 0.86 ms).  OLX_FIELD_VARIANT=lattice keeps the 32-column tiles for A/B runs.
-        {
-            const bool wide = tiles.size() == 1 && (int)tiles[0].size() > MFMA_COLS * 2;
-            if ((tiles.size() > 1 || (wide && fp8_want)) && c->use_lattice && !(c->flags & OLX_OUT_COMPLEX) && !fv_env && coset_fill(2) >= 0.6) {
-                tiles = pack(MFMA_COLS * 2);
-            }
-        }
-        c->nt = 1;
-        for (auto& t : tiles) { total_cols += (int)t.size(); while (c->nt * MFMA_COLS < (int)t.size()) c->nt *= 2; }
-        // kernel 2d saves table arithmetic but pays ~27 % padded MFMA rows on BASELINE's grids; with 4 column tiles per
-        // geometry fragment the MFMAs dominate and kernel 2c's exact z-run tiling wins (measured, steady state, 64-focus
-        // sweep: 4.6 vs 4.9 ms; 8-focus shard: 0.74 vs 0.58 ms) -- unless the family is pinned for A/B runs
-        // Kernel 2e's NT = 4 shape (3 tiles per wave) takes the sweep when its tiles are reasonably full.
-        if (c->use_lattice && c->nt >= 4 && c->force_kind != 4 && ((c->flags & OLX_OUT_COMPLEX) || coset_fill(c->nt) < 0.6)) c->use_lattice = false;
-        // kernel 2e: whole cosets per wave (no row-tile padding, one table per plane); 2d stays for complex output and A/B runs.
-        // MFMA tiles of kernel 2e: per (coset, part, plane pair) ceil(2 KX KY / 16); with very coarse pitches the position
-        // grids get so small that most of a tile is padding -- then 2d's fixed 2 x 4 x 2 tiles are the better shape
-        c->use_coset = false; c->use_toep = false; c->use_cosetp = false;
-        if (c->use_lattice) {
-            const char* fv = fv_env;
-            if (c->modifier() && fv && strcmp(fv, "lattice") && strcmp(fv, "lattice2d")) fv = nullptr;   // (the A/B forms carry no per-term factors)
-            c->use_coset = !(c->flags & OLX_OUT_COMPLEX) && !(fv && !strcmp(fv, "lattice2d"));
-            if (coset_fill(c->nt) > 0 && coset_fill(c->nt) < 0.6 && !(fv && !strcmp(fv, "lattice"))) c->use_coset = false;
-            const int want = (c->use_coset && c->nt <= 2) ? ((c->lat.nsb + 1) & ~1) : c->lat.nsb;
-            if (want != c->lat.nsbp) build_slot_map(c->lat, want);
-            // kernel 2f: ONE distinct steering vector in the whole launch (an on-axis SinglePoint focus on a mirror-symmetric
-            // array): Toeplitz weights stationary, 16 planes per MFMA tile -- 2e would use 2 of 16 matrix columns
-            c->use_toep = c->use_coset && tiles.size() == 1 && total_cols == 1 && !(fv && !strcmp(fv, "lattice"));
-            // kernel 2g: the NT = 2 shape with the planes in the MFMA rows (stores straight from the accumulators, no staging):
-            // 6 - 9 % faster than 2e on the headline shard; OLX_FIELD_VARIANT=lattice pins kernel 2e for A/B runs
-            c->use_cosetp = c->use_coset && !c->use_toep && c->nt == 2 && !(fv && !strcmp(fv, "lattice"));
-            if (c->use_cosetp)   // kernel 2g stores per column slot: a column with 3 - 4 store targets (an on-axis focus) makes every
-                olxplan::balance_store_targets(tiles, c->nt * MFMA_COLS);   // lane wait for its extra passes -- hand half of them to a free column slot (same weights, no extra MFMA)
-        }
-        const int n_pad = c->use_lattice ? c->lat.n_pad : (n + 15) / 16 * 16;
-        const int ntiles = (int)tiles.size();
-        // [column][f, m] then [column][4 store targets]: one table, d_targets points at its second part
-        const size_t n_col = (size_t)ntiles * MAXC;
-        std::vector<int> colinfo(n_col * 6, -1);
-        for (int t = 0; t < ntiles; ++t)
-            for (size_t o = 0; o < tiles[t].size(); ++o) {
-                colinfo[((size_t)t * MAXC + o) * 2] = tiles[t][o].f;
-                colinfo[((size_t)t * MAXC + o) * 2 + 1] = tiles[t][o].m;
-                for (int q = 0; q < 4; ++q) colinfo[n_col * 2 + ((size_t)t * MAXC + o) * 4 + q] = tiles[t][o].tgt[q];
-            }
+    } else if (p.use_mfma) {
         // (uploaded tables are remembered: an interactive caller re-plans per target, and a new target of the same focal pattern leaves the mirror
         // permutations, the columns' representatives and their store targets as they were -- no copies, no wait for the stream)
-        { int rc = upload_if_changed(c, c->d_perm, c->up_perm, perm); if (rc) return rc; }
-        { int rc = upload_if_changed(c, c->d_colinfo, c->up_colinfo, colinfo); if (rc) return rc; }
-        c->d_targets = c->d_colinfo + n_col * 2;
-        c->bfrag_half = (size_t)ntiles * (n_pad / 16) * 128 * c->nt;      // uint4 per K-step and column tile: hi, lo of the 64 lanes
+        { int rc = upload_if_changed(c, c->d_perm, c->up_perm, p.perm); if (rc) return rc; }
+        { int rc = upload_if_changed(c, c->d_colinfo, c->up_colinfo, p.colinfo); if (rc) return rc; }
+        c->d_targets = c->d_colinfo + p.colinfo.size() / 3;      // one table: the store targets are its second part
+        c->fp8_kcut = p.fp8_kcut;
+        c->bfrag_half = (size_t)p.mp.n_tiles * (p.n_pad / 16) * 128 * c->nt;      // uint4 per K-step and column tile: hi, lo of the 64 lanes
         {   // (index, residual) per element: kernel 2c; a second operand set in the other arithmetic for a launch split at fp8_kcut
-            int rc = c->d_coords.reserve(c, 2 * (size_t)n_pad);
+            int rc = c->d_coords.reserve(c, 2 * (size_t)p.n_pad);
             if (!rc) rc = c->d_bfrag.reserve(c, 2 * c->bfrag_half);
             if (rc) return rc;
         }
-        const double dmin_m = 0.5 * std::min({c->grid.spacing[0], c->grid.spacing[1], c->grid.spacing[2]});
-        const bool lat_clamp = c->use_lattice && (c->clamp || c->lat.clamp);
-        const double min_dist = !c->use_lattice ? c->min_dist : (lat_clamp ? dmin_m : std::sqrt(c->lat.min_d2));
-        if (c->use_lattice) {     // (a new steering table alone changes no slot map)
+        if (p.use_lattice) {     // (a new steering table alone changes no slot map)
             int rc = upload_if_changed(c, c->d_slot, c->up_slot, c->lat.slot_elem);
             if (rc) return rc;
+            c->lat_mt = p.lat_mt; c->lp = p.lp;
         }
-        // power-of-two operand scales: |G| <= 1/d'_min, |W| <= wmax  ->  hi parts <= 2^14, lo parts normal
-        const double dmin_w = std::max(min_dist * rev, 1e-6);
-        const double sg = std::exp2(std::floor(std::log2(16384.0 * dmin_w)));
-        double wmax = 0;
-        for (size_t q = 0; q < (size_t)F * n; ++q) wmax = std::max(wmax, std::fabs(c->h_apod[q] * c->h_area[q % n]));
-        wmax *= c->p0_pa / lambda * rev;
-        const double sw = wmax > 0 ? std::exp2(std::floor(std::log2(16384.0 / wmax))) : 1.0;
-        const FieldParams& P = c->fp;
-        MfmaParams& M = c->mp;
-        M.nx = P.nx; M.ny = P.ny; M.nz = P.nz; M.n_el_pad = n_pad; M.x_begin = P.x_begin; M.n_tiles = ntiles;
-        M.hx = P.hx; M.hy = P.hy; M.hz = P.hz; M.dmin2 = P.dmin2; M.flat_ez = P.flat_ez; M.flat_kz = P.flat_kz; M.flat_fz = P.flat_fz;
-        M.g_scale = (float)sg; M.out_scale = (float)(1.0 / (sg * sw)); M.inten_scale = P.inten_scale;
-        M.vox = P.vox; M.flags = P.flags;
-        c->mfma_wscale = c->p0_pa / lambda * rev * sw;
-        if (c->use_lattice) {
-            const olx_ctx::Lattice& A = c->lat;
-            LatParams& L = c->lp;
-            c->lat_mt = 4;   // MFMA tiles per wave (2 planes each)
-            L.nx = P.nx; L.ny = P.ny; L.nz = P.nz;
-            L.x_lo = c->mx == 2 ? P.nx / 2 : 0; L.y_lo = c->my == 2 ? P.ny / 2 : 0; L.x_begin = P.x_begin;
-            L.mx = A.mx; L.my = A.my;
-            L.tiles_x = ((P.nx - L.x_lo + 4 * A.mx - 1) / (4 * A.mx)) * 2 * A.mx;   // 2 x rows two pitches apart per tile
-            L.tiles_y = ((P.ny - L.y_lo + 4 * A.my - 1) / (4 * A.my)) * A.my;       // 4 y rows one pitch apart
-            L.kgroups = (P.nz + 2 * c->lat_mt - 1) / (2 * c->lat_mt);
-            L.nsa = A.nsa; L.nsb = A.nsb; L.nsbp = A.nsbp;
-            // dx(i, a) = (origin - x0) + (i - mx a) h: whole voxels go into the integer part, the rest is |f| <= h/2
-            const double offx = c->grid.origin[0] - A.x0, offy = c->grid.origin[1] - A.y0;
-            L.ux0 = (int)std::llround(offx / c->grid.spacing[0]); L.uy0 = (int)std::llround(offy / c->grid.spacing[1]);
-            L.fx0 = (float)((offx - L.ux0 * c->grid.spacing[0]) * rev); L.fy0 = (float)((offy - L.uy0 * c->grid.spacing[1]) * rev);
-            const double hxw = c->grid.spacing[0] * rev, hyw = c->grid.spacing[1] * rev;
-            L.hx_hi = (float)hxw; L.hx_lo = (float)(hxw - (double)L.hx_hi);
-            L.hy_hi = (float)hyw; L.hy_lo = (float)(hyw - (double)L.hy_hi);
-            L.hz = P.hz; L.dmin2 = P.dmin2; L.flat_ez = P.flat_ez;
-            L.g_scale = M.g_scale; L.out_scale = M.out_scale; L.inten_scale = P.inten_scale;
-            L.vox = P.vox; L.flags = P.flags;
-            const long long tiles16 = coset_tiles16(P.nx - L.x_lo, P.ny - L.y_lo, A.mx, A.my, c->nt);
-            c->fp8corr = fp8_want && c->use_coset && cos_fp8(c->nt) && !c->modifier();      // (decided above, before the columns were packed)
-            if (c->use_coset) {
-                CosetParams& Q = c->cp;
-                Q.nx = L.nx; Q.ny = L.ny; Q.nz = L.nz; Q.x_lo = L.x_lo; Q.y_lo = L.y_lo; Q.x_begin = L.x_begin; Q.mx = L.mx; Q.my = L.my;
-                const int zb = COS_ZB;      // planes per block
-                // positions of a coset along x: two pitches apart for kernels 2e / 2g (their fragment reads are 8-byte aligned that way), ONE for kernel 2f
-                // (round 5: its 8-position row tiles then fill 7 - 8 of 8 slots on BASELINE's grids instead of 5 - 6, and its tables are shared by more rows)
-                Q.xs = c->use_toep ? 1 : 2;
-                // kernel 2f's block shape (one, two or three row tiles of 8 x positions, the element super-block columns and their K-steps): olxplan::toep_plan
-                olxplan::ToepPlan tp{};
-                c->toep_nm = 1;
-                int kyw = COS_KYW;
-                if (c->use_toep) {
-                    int saw_pin = 0, nm_pin = 0;
-#ifdef OLX_DEV_PINS
-                    if (const char* e = getenv("OLX_EXP_TOEP_SAW")) { const int v = atoi(e); if (v >= 8 && v <= 24) saw_pin = v; }   // (A/B)
-                    if (const char* e = getenv("OLX_EXP_TOEP_NM")) nm_pin = atoi(e) == 3 ? 3 : 1;      // (A/B: 1 or 3)
-#endif
-                    tp = olxplan::toep_plan(A.ax, Q.mx, Q.my, Q.xs, Q.nx - Q.x_lo, Q.ny - Q.y_lo, Q.nz, c->dir_lattice, saw_pin, nm_pin);
-                    c->toep_nm = tp.nm; kyw = tp.kyw;
+        c->mp = p.mp; c->mfma_wscale = p.mfma_wscale;
+        if (p.use_lattice && p.use_coset) {
+            c->cp = p.cp; c->toep_nm = p.toep.nm;
+            { int rc = upload_if_changed(c, c->d_jobs, c->up_jobs, p.jobs); if (rc) return rc; }
+            {   // block records: they depend on the partition only, not on the steering table -- a call that changes nothing but the foci finds the
+                // records it uploaded last time still valid
+                std::vector<CosetBlock> blk;
+                if (!c->up_blocks.empty() && memcmp(c->up_blocks_key, p.rec_key, sizeof p.rec_key) == 0) blk = c->up_blocks;
+                else {
+                    std::string why;
+                    if (!olxplan::build_variant_blocks(p, blk, why)) return fail(c, OLX_ESTATE, "kernel 2g: %s", why.c_str());
                 }
-                const int kxw = c->use_toep ? 8 * c->toep_nm : cos_kxw(c->nt);
-                olxplan::coset_partition(Q, kxw, zb, kyw);
-                Q.nsa = L.nsa; Q.nsb = L.nsb; Q.nsbp = L.nsbp; Q.ux0 = L.ux0; Q.uy0 = L.uy0; Q.fx0 = L.fx0; Q.fy0 = L.fy0;
-                Q.hx_hi = L.hx_hi; Q.hx_lo = L.hx_lo; Q.hy_hi = L.hy_hi; Q.hy_lo = L.hy_lo; Q.hz = L.hz;
-                Q.dmin2 = L.dmin2; Q.flat_ez = L.flat_ez; Q.g_scale = L.g_scale; Q.out_scale = L.out_scale; Q.inten_scale = L.inten_scale;
-                Q.vox = L.vox; Q.flags = L.flags; Q.n_foci = F;
-#ifdef OLX_DEV_PINS
-                { const char* e = getenv("OLX_EXP_CP_NOREUSE"); Q.cp_noreuse = (e && atoi(e) != 0) ? 1 : 0; }   // (A/B) kernel 2g fills every table pair in full; the variant name says "noreuse"
-                { const char* e = getenv("OLX_EXP_CP_NOFILLAHEAD"); Q.cp_nofillahead = (e && atoi(e) != 0) ? 1 : 0; }   // (A/B) kernel 2g keeps the reuse fill a phase of its own; the variant name says "nofillahead"
-#endif
-                Q.dir_wx = (c->dir_lattice && c->directivity) ? (float)(0.5 * c->h_size[0] / lambda) : 0.f;      // element width / length over 2 lambda (DIR instantiations)
-                Q.dir_wy = (c->dir_lattice && c->directivity) ? (float)(0.5 * c->h_size[1] / lambda) : 0.f;
-                Q.absorb_l2 = c->dir_lattice ? (float)(c->absorb_np_m * lambda * 1.4426950408889634) : 0.f;   // exp(-a d) = exp2(-a lambda log2(e) d'), d' [wavelengths]
-                {   // dense store-job lists per (launch tile, column tile): job = c16 | image << 4 | focus << 6
-                    const std::vector<int> jobs = olxplan::build_store_jobs(tiles, MFMA_MAX_NT, MFMA_COLS, COS_JOBS, (P.flags & OLX_OUT_PMAG) != 0, (P.flags & OLX_OUT_INTENSITY) != 0);
-                    int rc = upload_if_changed(c, c->d_jobs, c->up_jobs, jobs);
-                    if (rc) return rc;
-                }
-                {   // kernel 2e / 2g / 2f / 2q block records: blockIdx.x -> (coset, part, plane block), in the kernels' former decode order
-                    // (the records depend on the partition only, not on the steering table: a call that changes nothing but the foci finds the
-                    // records it uploaded last time still valid -- 9 216 of them on the headline grid, 0.1 ms to derive and compare)
-                    // Plane blocks of one position set that follow each other on ONE XCD (round-robin dispatch: ids 8 apart): all 16 of them where the
-                    // counts divide -- that XCD's L2 then collects whole 1 KB z lines of every voxel column before it writes them back.  Measured on the
-                    // headline shard, alternating runs on one box: 1 / 2 / 4 / 8 / 16 in a row = 0.406 / 0.392 / 0.392 / 0.390 / 0.383 ms; y cosets
-                    // grouped on top (48 - 192 in a row) 0.384 - 0.388 (profiles/r05_store_path.txt).  A/B: OLX_EXP_KGRP.
-                    // (round 6: any count that divides the plane blocks, not only powers of two -- the reference's SimSetup grids have odd voxel counts,
-                    // 257 planes = 17 plane blocks: without a group their 64-byte runs went to eight different L2s and the launch took 2.5 x as long)
-                    auto pick_grp = [&](int kblocks) {
-                        const unsigned long long nb = (unsigned long long)Q.xs * Q.mx * Q.my * Q.nsx * Q.nsy * kblocks;
-                        for (int g2 = std::min(kblocks, 32); g2 >= 2; --g2) if (kblocks % g2 == 0 && nb % (8ull * g2) == 0) return (unsigned)g2;
-                        return 1u;
-                    };
-                    const int kcut = c->fp8corr ? c->fp8_kcut : 0;      // records of the plane blocks from the cut on come FIRST (a launch of their own in the e4m3 arithmetic)
-                    const int kb_near = kcut / zb, kb_far = Q.kblocks - kb_near;
-                    unsigned kgrp = pick_grp(kb_far), kgrp_near = kb_near > 0 ? pick_grp(kb_near) : 0u;
-#ifdef OLX_DEV_PINS
-                    if (const char* e = getenv("OLX_EXP_KGRP")) { kgrp = (unsigned)std::max(1, atoi(e)); if (kb_near > 0) kgrp_near = kgrp; }
-#endif
-                    const int rec_key[16] = {Q.nx, Q.ny, Q.nz, Q.x_lo, Q.y_lo, Q.mx, Q.my, Q.nsx, Q.nsy, Q.kblocks, zb, (int)kgrp, c->use_cosetp ? 40 : 0, Q.xs, kcut, (int)kgrp_near};
-                    std::vector<CosetBlock> blk;
-                    if (!c->up_blocks.empty() && memcmp(c->up_blocks_key, rec_key, sizeof rec_key) == 0) blk = c->up_blocks;
-                    else {
-                        std::string why;
-                        // each side of the cut gets its own record list (plane blocks of a position set in a row per XCD within the side)
-                        CosetParams Qf = Q; Qf.kblocks = kb_far;
-                        if (!olxplan::build_coset_blocks(Qf, zb, kgrp, c->use_cosetp ? 40 : 0, blk, why))
-                            return fail(c, OLX_ESTATE, "kernel 2g: %s", why.c_str());
-                        for (CosetBlock& b : blk) b.k0 += kcut;
-                        if (kb_near > 0) {
-                            std::vector<CosetBlock> near;
-                            CosetParams Qn = Q; Qn.kblocks = kb_near;
-                            if (!olxplan::build_coset_blocks(Qn, zb, kgrp_near, c->use_cosetp ? 40 : 0, near, why))
-                                return fail(c, OLX_ESTATE, "kernel 2g: %s", why.c_str());
-                            blk.insert(blk.end(), near.begin(), near.end());
-                        }
-                    }
-                    const unsigned nblk = (unsigned)blk.size();
-                    c->cp_nfar = nblk - (unsigned)((unsigned long long)Q.xs * Q.mx * Q.my * Q.nsx * Q.nsy * kb_near);
-                    { int rc = upload_if_changed(c, c->d_cpblocks, c->up_blocks, blk); if (rc) return rc; }
-                    memcpy(c->up_blocks_key, rec_key, sizeof rec_key);
-                    c->cp_nblocks = nblk;
-                }
-                // what the DENSE contraction of this launch needs, in the same units (one v_mfma_f32_16x16x32_f16 = 8192 real multiply-adds): computed
-                // voxels x elements x columns x 4 real products per complex one, times the products of the operand split -- bench.py reports
-                // dense / issued as `mfma_useful` (padding of rows, columns, K slots and the Toeplitz band all show up there)
-                // (a launch split at fp8_kcut: the plane blocks below the cut run three fp16 products -- the matrix units of both parts are weighted by their planes)
-                const double far_frac = c->fp8corr ? (double)std::max(0, P.nz - c->fp8_kcut) / (double)P.nz : 0.0;
-                const double corr_units = 3.0 - far_frac;                                   // 2 with e4m3 corrections everywhere, 3 with fp16 x 3
-                const std::string f8tag = !c->fp8corr ? "" : (c->fp8_kcut > 0 ? ",fp8corr from plane " + std::to_string(c->fp8_kcut) : ",fp8corr");
-                const long long n_dense = (long long)((double)(P.nx - L.x_lo) * (P.ny - L.y_lo) * P.nz * (double)n * total_cols * 4.0 / 8192.0 * corr_units);
-                if (c->use_toep) {   // kernel 2f operands: lattice cell -> element map, Toeplitz weight fragments, the column's store targets
-                    c->toep_saw = tp.saw;
-                    c->toep_nsa = tp.nsa;
-                    if (c->toep_nsa > 16) return fail(c, OLX_ESTATE, "kernel 2f: more than 16 super-block columns");      // (ks_mask holds 2 bits per column)
-                    c->toep_ksmask = tp.ks_mask;
-                    const int ksteps_total = tp.ksteps_total, e4_units = tp.e4_units;
-                    for (int q = 0; q < 4; ++q) c->toep_targets[q] = tiles[0][0].tgt[q];
-                    { int rc = c->d_cell.reserve(c, A.cell.size()); if (rc) return rc; }
-                    HIPCHK(c, hipMemcpy(c->d_cell, A.cell.data(), sizeof(int) * A.cell.size(), hipMemcpyHostToDevice));
-                    c->afrag_half = (size_t)ntiles * c->toep_nsa * 8 * A.nsb * 4 * 64;
-                    { int rc = c->d_afrag.reserve(c, 2 * c->afrag_half); if (rc) return rc; }      // (a second set in the other arithmetic for a launch split at fp8_kcut)
-                    // matrix-pipe units (one v_mfma_f32_16x16x32_f16 = 16 cycles): per block and element row, for each of its KY y positions 2 K-steps x 3 fp16
-                    // products -- or, with e4m3 corrections, 2 fp16 products + one K = 128 e4m3 instruction (2 units)
-                    long long n_mfma = 0;
-                    const int wx = P.nx - L.x_lo, wy = P.ny - L.y_lo;
-                    // per element row and y position: 3 fp16 products per non-zero K-step, or 1 per non-zero K-step + one e4m3 instruction (2 units) per column
-                    // (two row tiles, e4m3: rows in quads with paired K-step-1 operands -- 6 fp16 products + 3 e4m3 instructions per four rows: 3 units per row, k_toep.hip)
-                    const double units_e4m3 = c->toep_nm == 2 ? 3.0 : (double)ksteps_total + (double)e4_units;
-                    const double per_row = far_frac * units_e4m3 + (1.0 - far_frac) * 3.0 * ksteps_total;
-                    for (int rx = 0; rx < Q.xs * A.mx; ++rx)
-                        for (int ry = 0; ry < A.my; ++ry) {
-                            const int kxa = rx < wx ? (wx - 1 - rx) / (Q.xs * A.mx) + 1 : 0, kya = ry < wy ? (wy - 1 - ry) / A.my + 1 : 0;
-                            for (int sx = 0; sx < Q.nsx; ++sx)
-                                for (int sy = 0; sy < Q.nsy; ++sy) {
-                                    const int KX = (sx + 1) * kxa / Q.nsx - sx * kxa / Q.nsx, KY = (sy + 1) * kya / Q.nsy - sy * kya / Q.nsy;
-                                    if (KX > 0 && KY > 0) n_mfma += (long long)((double)KY * per_row * (c->toep_nm > 1 ? 8 * c->toep_nm : 8) * A.nsb * Q.kblocks);      // (row tiles of 8 positions: every tile of the block's shape is computed)
-                                }
-                        }
-                    snprintf(nmbuf, sizeof nmbuf, "field_toep%s_k<mx%d,my%d,flat,%s%s> %d columns for %d foci x %d images in %d tile(s); "
-                             "%dx%d lattice, pitch %dx%d voxels, %lld MFMA/launch (%lld dense), %d row tile(s) x %d y positions per block", "", c->mx, c->my, lat_clamp ? "clamp" : "noclamp", f8tag.c_str(),
-                             total_cols, F, n_img, ntiles, A.ax, A.ay, A.mx, A.my, n_mfma, n_dense, c->toep_nm, kyw);
-                } else {
-                // matrix-pipe time in units of one v_mfma_f32_16x16x32_f16 (16 cycles): 3 fp16 products per K-step, or with fp8
-                // corrections 1 fp16 product per K-step + one K = 128 e4m3 instruction (2 units) per two K-steps
-                long long n_mfma = (long long)((double)tiles16 * ((P.nz + COS_P - 1) / COS_P) * A.nsa * A.nsb * 4 * c->nt * corr_units * ntiles);
-                if (c->use_cosetp) {   // kernel 2g: one row tile per position and 16-plane block, no padded rows
-                    long long npos_all = 0;
-                    const int wx = P.nx - L.x_lo, wy = P.ny - L.y_lo;
-                    for (int rx = 0; rx < 2 * A.mx; ++rx)
-                        for (int ry = 0; ry < A.my; ++ry)
-                            npos_all += (long long)(rx < wx ? (wx - 1 - rx) / (2 * A.mx) + 1 : 0) * (ry < wy ? (wy - 1 - ry) / A.my + 1 : 0);
-                    n_mfma = (long long)((double)npos_all * Q.kblocks * A.nsa * A.nsb * 4 * c->nt * corr_units * ntiles);
-                }
-#ifdef OLX_DEV_PINS
-                const std::string pin_tags = std::string((c->use_cosetp && Q.cp_noreuse) ? ",noreuse" : "") + ((c->use_cosetp && Q.cp_nofillahead) ? ",nofillahead" : "");
-#else
-                const std::string pin_tags;
-#endif
-                snprintf(nmbuf, sizeof nmbuf, "field_coset%s_k<nt%d,mx%d,my%d,flat,%s%s%s> %d columns for %d foci x %d images in %d tile(s); "
-                         "%dx%d lattice, pitch %dx%d voxels, %lld MFMA/launch (%lld dense)", c->use_cosetp ? "p" : "", c->nt, c->mx, c->my, lat_clamp ? "clamp" : "noclamp",
-                         f8tag.c_str(), pin_tags.c_str(), total_cols, F, n_img, ntiles, A.ax, A.ay, A.mx, A.my, n_mfma, n_dense);
-                }
-            } else {
-                const long long n_mfma = (long long)L.tiles_x * L.tiles_y * L.kgroups * A.nsa * A.nsb * 4 * c->lat_mt * c->nt * 3 * ntiles;
-                snprintf(nmbuf, sizeof nmbuf, "field_lattice_k<mt%d,nt%d,mx%d,my%d,flat,%s> %d columns for %d foci x %d images in %d tile(s); "
-                         "%dx%d lattice, pitch %dx%d voxels, %lld MFMA/launch", c->lat_mt, c->nt, c->mx, c->my, lat_clamp ? "clamp" : "noclamp",
-                         total_cols, F, n_img, ntiles, A.ax, A.ay, A.mx, A.my, n_mfma);
+                const unsigned nblk = (unsigned)blk.size();
+                c->cp_nfar = nblk - p.blocks_near;
+                { int rc = upload_if_changed(c, c->d_cpblocks, c->up_blocks, blk); if (rc) return rc; }
+                memcpy(c->up_blocks_key, p.rec_key, sizeof p.rec_key);
+                c->cp_nblocks = nblk;
             }
-        } else {
-            snprintf(nmbuf, sizeof nmbuf, "field_mfma_k<mt%d,nt%d,mx%d,my%d,%s,%s> %d columns for %d foci x %d images in %d tile(s)",
-                     P.nz >= 48 ? 4 : 1, c->nt, c->mx, c->my, c->flat ? "flat" : "general", c->clamp ? "clamp" : (c->near ? "near" : "noclamp"), total_cols, F,
-                     n_img, ntiles);
+            if (p.use_toep) {   // kernel 2f operands: lattice cell -> element map, Toeplitz weight fragments, the column's store targets
+                c->toep_saw = p.toep.saw;
+                c->toep_nsa = p.toep.nsa;
+                if (c->toep_nsa > 16) return fail(c, OLX_ESTATE, "kernel 2f: more than 16 super-block columns");      // (ks_mask holds 2 bits per column)
+                c->toep_ksmask = p.toep.ks_mask;
+                for (int q = 0; q < 4; ++q) c->toep_targets[q] = p.tiles[0][0].tgt[q];
+                { int rc = c->d_cell.reserve(c, c->lat.cell.size()); if (rc) return rc; }
+                HIPCHK(c, hipMemcpy(c->d_cell, c->lat.cell.data(), sizeof(int) * c->lat.cell.size(), hipMemcpyHostToDevice));
+                c->afrag_half = (size_t)p.mp.n_tiles * c->toep_nsa * 8 * c->lat.nsb * 4 * 64;
+                { int rc = c->d_afrag.reserve(c, 2 * c->afrag_half); if (rc) return rc; }      // (a second set in the other arithmetic for a launch split at fp8_kcut)
+            }
         }
-    } else if (c->mx * c->my * c->nf == 1) {
-        if (c->modifier()) snprintf(nmbuf, sizeof nmbuf, "field_accum_dir_k<4,%s> (%s%s%s)", c->clamp ? "clamp" : "noclamp", c->directivity ? "piston directivity" : "",
-                                    (c->directivity && c->absorb_np_m > 0) ? ", " : "", c->absorb_np_m > 0 ? "uniform absorption" : "");
-        else snprintf(nmbuf, sizeof nmbuf, "field_accum_k<4,%s,%s>", c->flat ? "flat" : "general", c->clamp ? "clamp" : (c->near ? "near" : "noclamp"));
-    } else {
-        const std::vector<int> perm = olxplan::mirror_perms(n, nm, c->dx == 2, c->dy == 2, c->h_px.data(), c->h_py.data(), nm);
-        int rc = upload_if_changed(c, c->d_perm, c->up_perm, perm);
-        if (!rc) rc = c->d_tab.reserve(c, (size_t)((F + c->nf - 1) / c->nf) * n * (SH_HEAD + 2 * nm * c->nf));  // never trust the plan-time bound
+    } else if (!p.perm.empty()) {      // kernel 2b
+        int rc = upload_if_changed(c, c->d_perm, c->up_perm, p.perm);
+        if (!rc) rc = c->d_tab.reserve(c, (size_t)((F + c->nf - 1) / c->nf) * n * (SH_HEAD + 2 * c->dx * c->dy * c->nf));  // never trust the plan-time bound
         if (rc) return rc;
-        snprintf(nmbuf, sizeof nmbuf, "field_shared_k<4,mx%d,my%d,dx%d,dy%d,nf%d,%s,%s>", c->mx, c->my, c->dx, c->dy, c->nf,
-                 c->flat ? "flat" : "general", c->clamp ? "clamp" : (c->near ? "near" : "noclamp"));
     }
-    if (c->modifier() && c->use_mfma && !(c->use_lattice && c->use_coset)) {   // only the coset kernels (2e / 2f / 2g) carry per-term factors: fall back to 2a-d
-        c->dir_lattice = false; c->allow_shared = false;
-        return configure_variant_impl(c);
-    }
-    if (c->directivity && c->use_mfma) strncat(nmbuf, " +piston directivity in the tables", sizeof nmbuf - strlen(nmbuf) - 1);
-    if (c->absorb_np_m > 0 && c->use_mfma) strncat(nmbuf, " +uniform absorption in the tables", sizeof nmbuf - strlen(nmbuf) - 1);
-    c->variant = nmbuf;
+    c->variant = p.variant;
+    c->configured_version = c->steer_version;
     return OLX_OK;
 }
 

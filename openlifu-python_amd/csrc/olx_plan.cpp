@@ -7,7 +7,9 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 namespace olxplan {
 
@@ -417,4 +419,331 @@ ToepPlan toep_plan(int ax, int mx, int my, int xs, int wx, int wy, int nz, bool 
     return T;
 }
 
+// ---- the kernel-2 variant decision ----
+bool steering_symmetric(int n, int F, const double* delays, const double* apod, const double* area, double freq, const int* perm) {
+    if (!delays || !apod) return false;
+    for (int f = 0; f < F; ++f)
+        for (int e = 0; e < n; ++e) {
+            const size_t a = (size_t)f * n + e, b = (size_t)f * n + perm[e];
+            if (std::fabs(delays[a] - delays[b]) * freq > 1e-9) return false;
+            if (std::fabs(apod[a] * area[e] - apod[b] * area[perm[e]]) > 1e-12 * std::fabs(apod[a] * area[e])) return false;
+        }
+    return true;
+}
+
+// kernel 2d applies when the array is a lattice commensurate with the grid and the pitch-strided row tiles
+// (4 rows x pitch) do not overhang the computed region by more than 2x per axis
+static bool lattice_fits(const VariantIn& in) {
+    auto tile_fill = [](int width, int m) { const int blk = 4 * m; return (double)width / (double)(((width + blk - 1) / blk) * blk); };
+    return in.allow_shared && in.lat->ok && (in.force_kind == 0 || in.force_kind == 4) &&
+           tile_fill(in.fp.nx - (in.mx == 2 ? in.fp.nx / 2 : 0), in.lat->mx) >= 0.5 &&
+           tile_fill(in.fp.ny - (in.my == 2 ? in.fp.ny / 2 : 0), in.lat->my) >= 0.5;
+}
+
+bool variant_reads_foci(const VariantIn& in) {
+    return !in.hetero && lattice_fits(in) && in.pins.fp8 >= 0 && !(in.flags & (FLAG_FP16_CORRECTION | FLAG_OUT_COMPLEX)) && !in.modifier();
+}
+
+// One pass of the decision over `in` as it stands (decide_variant runs a second one for the fallback to kernels 2a-d).
+// Steering-dependent: dx/dy = distinct weight columns along folded axes (1 when every focus' delays and apodization are
+// mirror-symmetric), nf = foci per tile so that dx*dy*nf <= 8 accumulator columns.
+static VariantPlan decide_pass(const VariantIn& in, std::vector<double>& nf_s2, int& slot_rows) {
+    VariantPlan p;
+    const int n = in.n, F = in.F;
+    const Pins& pins = in.pins;
+    const bool modifier = in.modifier(), cplx = (in.flags & FLAG_OUT_COMPLEX) != 0;
+    p.mx = in.mx; p.my = in.my; p.allow_shared = in.allow_shared; p.dir_lattice = in.dir_lattice;
+    const char* const clamp_tag = in.clamp ? "clamp" : "noclamp";
+    if (in.hetero) {  // kernel 2h: no folds; the ray integrals of a (voxel, element) pair are shared by up to 8 foci per launch tile
+        p.mx = p.my = 1;
+        while (p.nf * 2 <= F && p.nf < 8) p.nf *= 2;
+        char hb[160];
+        if (in.marched)
+            snprintf(hb, sizeof hb, "field_hmarch_k<nf%d,%s%s> (%d non-trivial planes, marched ray sums, %d launches)", p.nf,
+                     clamp_tag, in.march_one ? ",one-sum" : "", in.n_planes, 2 * in.n_planes + 1);
+        else if (in.n_layers > 0)
+            snprintf(hb, sizeof hb, "field_hetero_k<4,nf%d,%s,layers> (%d non-trivial planes in %d layers of <= %d)", p.nf,
+                     clamp_tag, in.n_planes, in.n_layers, in.planes_per_layer);
+        else
+            snprintf(hb, sizeof hb, "field_hetero_k<4,nf%d,%s> (%d non-trivial planes)", p.nf, clamp_tag, in.n_planes);
+        p.variant = hb;
+        return p;
+    }
+    p.dx = (p.mx == 2 && !steering_symmetric(n, F, in.delays, in.apod, in.area, in.freq, in.px)) ? 2 : 1;
+    p.dy = (p.my == 2 && !steering_symmetric(n, F, in.delays, in.apod, in.area, in.freq, in.py)) ? 2 : 1;
+    const int nm = p.dx * p.dy;
+    if (p.allow_shared) while (p.nf * 2 <= F && p.nf * 2 * nm <= 8) p.nf *= 2;
+    char nmbuf[384];
+    const bool lat_ok = lattice_fits(in);
+    if (modifier && !(lat_ok && p.dir_lattice)) {   // no lattice path for this array / grid: the exact per-pair kernel 2a-d
+        p.allow_shared = false; p.dir_lattice = false;
+        p.mx = p.my = p.dx = p.dy = p.nf = 1;
+    }
+    p.use_mfma = p.allow_shared && in.force_kind != 2 && (in.force_kind == 3 || nm * p.nf >= 2 || lat_ok) && (!modifier || lat_ok);
+    p.use_lattice = p.use_mfma && lat_ok;
+    const char* const near_tag = in.clamp ? "clamp" : (in.near ? "near" : "noclamp");
+    if (p.use_mfma) {
+        // ---- kernel 2c column plan.  A column = one distinct steering vector W[sigma_m(e), f]; every
+        // (focus, mirror image) whose vector equals it (on-axis foci: all their images; mirror-partner foci of a
+        // Wheel: each other's images) is a store TARGET of that column, so it is accumulated once.  Foci are packed
+        // greedily into launch tiles of at most 32 columns (NT = 4 MFMA column tiles share each geometry fragment).
+        const Lattice& A = *in.lat;
+        const FieldParams& P = in.fp;
+        const double rev = in.freq / in.c, lambda = in.c / in.freq;
+        const int n_img = p.mx * p.my;
+        constexpr int MAXC = MFMA_COLS * MFMA_MAX_NT;
+        p.perm = mirror_perms(n, n_img, p.mx == 2, p.my == 2, in.px, in.py, 4);
+        Steering SV;
+        SV.n = n; SV.F = F; SV.n_img = n_img; SV.perm = p.perm.data(); SV.delays = in.delays; SV.apod = in.apod; SV.area = in.area; SV.freq = in.freq;
+        const int wx = P.nx - (p.mx == 2 ? P.nx / 2 : 0), wy = P.ny - (p.my == 2 ? P.ny / 2 : 0);      // the computed region
+        auto coset_fill = [&](int nt) {
+            const long long t16 = coset_tiles16(wx, wy, A.mx, A.my, nt);
+            return t16 > 0 ? (double)COS_P * wx * wy / (16.0 * (double)t16) : 0.0;
+        };
+        // e4m3 correction products (kernels 2e / 2f / 2g, NT <= 2) are the default wherever their error bound is a bound on the planned volume
+        // (include/olx.h, olx_field_plan): the foci are known (olx_bf_solve in the element frame, or external delays that infer_foci
+        // recognises as geometric: the caller resolves them), every focus lies inside the planned SLAB and has N_eff = (sum w)^2 / sum w^2 >= 256;
+        // the plan flag OLX_FIELD_FP16_CORRECTION opts out, and so does OLX_FP8_CORRECTION=0.  Decided here, before the columns are packed: it also
+        // decides the tile width below.  The rule itself is fp8_first_plane (first plane of the e4m3 products: 0 = every plane, a multiple of 16 = the
+        // plane blocks below keep three fp16 products, -1 = not eligible).
+        int fp8_cut = (variant_reads_foci(in) && in.foci)
+                          ? fp8_first_plane(n, in.pos, in.area, in.apod, F, in.foci, in.origin, in.spacing, in.gn, in.x_begin, in.x_count, A, nf_s2) : -1;
+        // The pin FORCES the e4m3 products past the eligibility rule -- results may then miss the 1e-5 gate, so only developer builds set it
+        if (pins.fp8 > 0) fp8_cut = (lat_ok && !modifier) ? 0 : -1;
+        // (a split launch is two launches and two operand sets: where it does not pay, the whole launch keeps three fp16 products)
+        if (fp8_cut > 0 && !fp8_split_pays(in.x_count, in.gn[1], in.gn[2], F, fp8_cut)) fp8_cut = -1;
+        const bool fp8_want = fp8_cut >= 0;
+        p.fp8_kcut = fp8_want ? fp8_cut : 0;
+        // A column may store to ANY focus volume, so the search for an equal vector runs over every tile packed so far: mirror-partner
+        // foci share their columns wherever they sit in the sweep (a Wheel in its natural order has them at opposite ends).
+        Tiles& tiles = p.tiles;
+        tiles = pack_columns(SV, MAXC);
+        // A sweep that needs SEVERAL launch tiles anyway is cut into tiles of 16 columns instead of 32: kernel 2g (NT = 2) then takes every
+        // tile -- 8 x 0.43 ms against 2e's 4 x 0.92 ms on the 64-focus sweep (127 columns).  One tile of 17 - 32 columns stays with 2e's
+        // NT = 4 shape when the fp16 corrections run (0.82 against 2 x 0.45 ms) and is cut in two when the e4m3 corrections apply, which
+        // the NT = 4 shape has no registers for (2 x 0.39 against 0.86 ms).  OLX_FIELD_VARIANT=lattice keeps the 32-column tiles for A/B runs.
+        {
+            const bool wide = tiles.size() == 1 && (int)tiles[0].size() > MFMA_COLS * 2;
+            if ((tiles.size() > 1 || (wide && fp8_want)) && p.use_lattice && !cplx && pins.family == FamilyPin::none && coset_fill(2) >= 0.6)
+                tiles = pack_columns(SV, MFMA_COLS * 2);
+        }
+        for (auto& t : tiles) { p.total_cols += (int)t.size(); while (p.nt * MFMA_COLS < (int)t.size()) p.nt *= 2; }
+        const int total_cols = p.total_cols;
+        // kernel 2d saves table arithmetic but pays ~27 % padded MFMA rows on BASELINE's grids; with 4 column tiles per
+        // geometry fragment the MFMAs dominate and kernel 2c's exact z-run tiling wins (measured, steady state, 64-focus
+        // sweep: 4.6 vs 4.9 ms; 8-focus shard: 0.74 vs 0.58 ms) -- unless the family is pinned for A/B runs
+        // Kernel 2e's NT = 4 shape (3 tiles per wave) takes the sweep when its tiles are reasonably full.
+        if (p.use_lattice && p.nt >= 4 && in.force_kind != 4 && (cplx || coset_fill(p.nt) < 0.6)) p.use_lattice = false;
+        // kernel 2e: whole cosets per wave (no row-tile padding, one table per plane); 2d stays for complex output and A/B runs.
+        // MFMA tiles of kernel 2e: per (coset, part, plane pair) ceil(2 KX KY / 16); with very coarse pitches the position
+        // grids get so small that most of a tile is padding -- then 2d's fixed 2 x 4 x 2 tiles are the better shape
+        if (p.use_lattice) {
+            FamilyPin fv = pins.family;
+            if (modifier && fv != FamilyPin::lattice && fv != FamilyPin::lattice2d) fv = FamilyPin::none;   // (the A/B forms carry no per-term factors)
+            p.use_coset = !cplx && fv != FamilyPin::lattice2d;
+            if (coset_fill(p.nt) > 0 && coset_fill(p.nt) < 0.6 && fv != FamilyPin::lattice) p.use_coset = false;
+            slot_rows = (p.use_coset && p.nt <= 2) ? ((A.nsb + 1) & ~1) : A.nsb;
+            // kernel 2f: ONE distinct steering vector in the whole launch (an on-axis SinglePoint focus on a mirror-symmetric
+            // array): Toeplitz weights stationary, 16 planes per MFMA tile -- 2e would use 2 of 16 matrix columns
+            p.use_toep = p.use_coset && tiles.size() == 1 && total_cols == 1 && fv != FamilyPin::lattice;
+            // kernel 2g: the NT = 2 shape with the planes in the MFMA rows (stores straight from the accumulators, no staging):
+            // 6 - 9 % faster than 2e on the headline shard; OLX_FIELD_VARIANT=lattice pins kernel 2e for A/B runs
+            p.use_cosetp = p.use_coset && !p.use_toep && p.nt == 2 && fv != FamilyPin::lattice;
+            if (p.use_cosetp)   // kernel 2g stores per column slot: a column with 3 - 4 store targets (an on-axis focus) makes every
+                balance_store_targets(tiles, p.nt * MFMA_COLS);   // lane wait for its extra passes -- hand half of them to a free column slot (same weights, no extra MFMA)
+        }
+        p.n_pad = p.use_lattice ? A.nsa * slot_rows * 64 : (n + 15) / 16 * 16;
+        const int ntiles = (int)tiles.size();
+        // [column][f, m] then [column][4 store targets]: one table, the store targets are its second part
+        const size_t n_col = (size_t)ntiles * MAXC;
+        p.colinfo.assign(n_col * 6, -1);
+        for (int t = 0; t < ntiles; ++t)
+            for (size_t o = 0; o < tiles[t].size(); ++o) {
+                p.colinfo[((size_t)t * MAXC + o) * 2] = tiles[t][o].f;
+                p.colinfo[((size_t)t * MAXC + o) * 2 + 1] = tiles[t][o].m;
+                for (int q = 0; q < 4; ++q) p.colinfo[n_col * 2 + ((size_t)t * MAXC + o) * 4 + q] = tiles[t][o].tgt[q];
+            }
+        const double dmin_m = 0.5 * std::min({in.spacing[0], in.spacing[1], in.spacing[2]});
+        p.lat_clamp = p.use_lattice && (in.clamp || A.clamp);
+        const char* const lat_tag = p.lat_clamp ? "clamp" : "noclamp";
+        const double min_dist = !p.use_lattice ? in.min_dist : (p.lat_clamp ? dmin_m : std::sqrt(A.min_d2));
+        // power-of-two operand scales: |G| <= 1/d'_min, |W| <= wmax  ->  hi parts <= 2^14, lo parts normal
+        const double dmin_w = std::max(min_dist * rev, 1e-6);
+        const double sg = std::exp2(std::floor(std::log2(16384.0 * dmin_w)));
+        double wmax = 0;
+        for (size_t q = 0; q < (size_t)F * n; ++q) wmax = std::max(wmax, std::fabs(in.apod[q] * in.area[q % n]));
+        wmax *= in.p0_pa / lambda * rev;
+        const double sw = wmax > 0 ? std::exp2(std::floor(std::log2(16384.0 / wmax))) : 1.0;
+        MfmaParams& M = p.mp;
+        M.nx = P.nx; M.ny = P.ny; M.nz = P.nz; M.n_el_pad = p.n_pad; M.x_begin = P.x_begin; M.n_tiles = ntiles;
+        M.hx = P.hx; M.hy = P.hy; M.hz = P.hz; M.dmin2 = P.dmin2; M.flat_ez = P.flat_ez; M.flat_kz = P.flat_kz; M.flat_fz = P.flat_fz;
+        M.g_scale = (float)sg; M.out_scale = (float)(1.0 / (sg * sw)); M.inten_scale = P.inten_scale;
+        M.vox = P.vox; M.flags = P.flags;
+        p.g_scale = sg; p.out_scale = 1.0 / (sg * sw);
+        p.mfma_wscale = in.p0_pa / lambda * rev * sw;
+        if (p.use_lattice) {
+            LatParams& L = p.lp;
+            L.nx = P.nx; L.ny = P.ny; L.nz = P.nz;
+            L.x_lo = p.mx == 2 ? P.nx / 2 : 0; L.y_lo = p.my == 2 ? P.ny / 2 : 0; L.x_begin = P.x_begin;
+            L.mx = A.mx; L.my = A.my;
+            L.tiles_x = ((P.nx - L.x_lo + 4 * A.mx - 1) / (4 * A.mx)) * 2 * A.mx;   // 2 x rows two pitches apart per tile
+            L.tiles_y = ((P.ny - L.y_lo + 4 * A.my - 1) / (4 * A.my)) * A.my;       // 4 y rows one pitch apart
+            L.kgroups = (P.nz + 2 * p.lat_mt - 1) / (2 * p.lat_mt);                 // lat_mt MFMA tiles per wave (2 planes each)
+            L.nsa = A.nsa; L.nsb = A.nsb; L.nsbp = slot_rows;
+            // dx(i, a) = (origin - x0) + (i - mx a) h: whole voxels go into the integer part, the rest is |f| <= h/2
+            const double offx = in.origin[0] - A.x0, offy = in.origin[1] - A.y0;
+            L.ux0 = (int)std::llround(offx / in.spacing[0]); L.uy0 = (int)std::llround(offy / in.spacing[1]);
+            L.fx0 = (float)((offx - L.ux0 * in.spacing[0]) * rev); L.fy0 = (float)((offy - L.uy0 * in.spacing[1]) * rev);
+            const double hxw = in.spacing[0] * rev, hyw = in.spacing[1] * rev;
+            L.hx_hi = (float)hxw; L.hx_lo = (float)(hxw - (double)L.hx_hi);
+            L.hy_hi = (float)hyw; L.hy_lo = (float)(hyw - (double)L.hy_hi);
+            L.hz = P.hz; L.dmin2 = P.dmin2; L.flat_ez = P.flat_ez;
+            L.g_scale = M.g_scale; L.out_scale = M.out_scale; L.inten_scale = P.inten_scale;
+            L.vox = P.vox; L.flags = P.flags;
+            const long long tiles16 = coset_tiles16(P.nx - L.x_lo, P.ny - L.y_lo, A.mx, A.my, p.nt);
+            p.fp8corr = fp8_want && p.use_coset && cos_fp8(p.nt) && !modifier;      // (decided above, before the columns were packed)
+            if (p.use_coset) {
+                CosetParams& Q = p.cp;
+                Q.nx = L.nx; Q.ny = L.ny; Q.nz = L.nz; Q.x_lo = L.x_lo; Q.y_lo = L.y_lo; Q.x_begin = L.x_begin; Q.mx = L.mx; Q.my = L.my;
+                const int zb = COS_ZB;      // planes per block
+                // positions of a coset along x: two pitches apart for kernels 2e / 2g (their fragment reads are 8-byte aligned that way), ONE for kernel 2f
+                // (round 5: its 8-position row tiles then fill 7 - 8 of 8 slots on BASELINE's grids instead of 5 - 6, and its tables are shared by more rows)
+                Q.xs = p.use_toep ? 1 : 2;
+                // kernel 2f's block shape (one, two or three row tiles of 8 x positions, the element super-block columns and their K-steps): toep_plan
+                ToepPlan& tp = p.toep;
+                if (p.use_toep) tp = toep_plan(A.ax, Q.mx, Q.my, Q.xs, Q.nx - Q.x_lo, Q.ny - Q.y_lo, Q.nz, p.dir_lattice, pins.toep_saw, pins.toep_nm);
+                const int kxw = p.use_toep ? 8 * tp.nm : cos_kxw(p.nt);
+                coset_partition(Q, kxw, zb, tp.kyw);
+                Q.nsa = L.nsa; Q.nsb = L.nsb; Q.nsbp = L.nsbp; Q.ux0 = L.ux0; Q.uy0 = L.uy0; Q.fx0 = L.fx0; Q.fy0 = L.fy0;
+                Q.hx_hi = L.hx_hi; Q.hx_lo = L.hx_lo; Q.hy_hi = L.hy_hi; Q.hy_lo = L.hy_lo; Q.hz = L.hz;
+                Q.dmin2 = L.dmin2; Q.flat_ez = L.flat_ez; Q.g_scale = L.g_scale; Q.out_scale = L.out_scale; Q.inten_scale = L.inten_scale;
+                Q.vox = L.vox; Q.flags = L.flags; Q.n_foci = F;
+#ifdef OLX_DEV_PINS
+                Q.cp_noreuse = pins.cp_noreuse ? 1 : 0;             // (A/B) kernel 2g fills every table pair in full; the variant name says "noreuse"
+                Q.cp_nofillahead = pins.cp_nofillahead ? 1 : 0;     // (A/B) kernel 2g keeps the reuse fill a phase of its own; the variant name says "nofillahead"
+#endif
+                Q.dir_wx = (p.dir_lattice && in.directivity) ? (float)(0.5 * in.size0 / lambda) : 0.f;      // element width / length over 2 lambda (DIR instantiations)
+                Q.dir_wy = (p.dir_lattice && in.directivity) ? (float)(0.5 * in.size1 / lambda) : 0.f;
+                Q.absorb_l2 = p.dir_lattice ? (float)(in.absorb_np_m * lambda * 1.4426950408889634) : 0.f;   // exp(-a d) = exp2(-a lambda log2(e) d'), d' [wavelengths]
+                // dense store-job lists per (launch tile, column tile): job = c16 | image << 4 | focus << 6
+                p.jobs = build_store_jobs(tiles, MFMA_MAX_NT, MFMA_COLS, COS_JOBS, (P.flags & FLAG_OUT_PMAG) != 0, (P.flags & FLAG_OUT_INTENSITY) != 0);
+                {   // kernel 2e / 2g / 2f block records: blockIdx.x -> (coset, part, plane block), in the kernels' former decode order.  The records
+                    // themselves stay with the caller (build_coset_blocks, cached against rec_key: they depend on the partition only, not on the
+                    // steering table -- 9 216 of them on the headline grid, 0.1 ms to derive and compare); decided here is their order over the XCDs.
+                    // Plane blocks of one position set that follow each other on ONE XCD (round-robin dispatch: ids 8 apart): all 16 of them where the
+                    // counts divide -- that XCD's L2 then collects whole 1 KB z lines of every voxel column before it writes them back.  Measured on the
+                    // headline shard, alternating runs on one box: 1 / 2 / 4 / 8 / 16 in a row = 0.406 / 0.392 / 0.392 / 0.390 / 0.383 ms; y cosets
+                    // grouped on top (48 - 192 in a row) 0.384 - 0.388 (profiles/r05_store_path.txt).  A/B: OLX_EXP_KGRP.
+                    // (round 6: any count that divides the plane blocks, not only powers of two -- the reference's SimSetup grids have odd voxel counts,
+                    // 257 planes = 17 plane blocks: without a group their 64-byte runs went to eight different L2s and the launch took 2.5 x as long)
+                    auto pick_grp = [&](int kblocks) {
+                        const unsigned long long nb = (unsigned long long)Q.xs * Q.mx * Q.my * Q.nsx * Q.nsy * kblocks;
+                        for (int g2 = std::min(kblocks, 32); g2 >= 2; --g2) if (kblocks % g2 == 0 && nb % (8ull * g2) == 0) return (unsigned)g2;
+                        return 1u;
+                    };
+                    const int kcut = p.fp8corr ? p.fp8_kcut : 0;      // records of the plane blocks from the cut on come FIRST (a launch of their own in the e4m3 arithmetic)
+                    const int kb_near = kcut / zb, kb_far = Q.kblocks - kb_near;
+                    p.kgrp = pick_grp(kb_far); p.kgrp_near = kb_near > 0 ? pick_grp(kb_near) : 0u;
+                    if (pins.kgrp > 0) { p.kgrp = (unsigned)pins.kgrp; if (kb_near > 0) p.kgrp_near = p.kgrp; }
+                    const int rec_key[16] = {Q.nx, Q.ny, Q.nz, Q.x_lo, Q.y_lo, Q.mx, Q.my, Q.nsx, Q.nsy, Q.kblocks, zb, (int)p.kgrp, p.use_cosetp ? 40 : 0, Q.xs, kcut, (int)p.kgrp_near};
+                    memcpy(p.rec_key, rec_key, sizeof rec_key);
+                    p.blocks_near = (unsigned)((unsigned long long)Q.xs * Q.mx * Q.my * Q.nsx * Q.nsy * kb_near);
+                }
+                // what the DENSE contraction of this launch needs, in the same units (one v_mfma_f32_16x16x32_f16 = 8192 real multiply-adds): computed
+                // voxels x elements x columns x 4 real products per complex one, times the products of the operand split -- bench.py reports
+                // dense / issued as `mfma_useful` (padding of rows, columns, K slots and the Toeplitz band all show up there)
+                // (a launch split at fp8_kcut: the plane blocks below the cut run three fp16 products -- the matrix units of both parts are weighted by their planes)
+                const double far_frac = p.fp8corr ? (double)std::max(0, P.nz - p.fp8_kcut) / (double)P.nz : 0.0;
+                const double corr_units = 3.0 - far_frac;                                   // 2 with e4m3 corrections everywhere, 3 with fp16 x 3
+                const std::string f8tag = !p.fp8corr ? "" : (p.fp8_kcut > 0 ? ",fp8corr from plane " + std::to_string(p.fp8_kcut) : ",fp8corr");
+                p.n_dense = (long long)((double)(P.nx - L.x_lo) * (P.ny - L.y_lo) * P.nz * (double)n * total_cols * 4.0 / 8192.0 * corr_units);
+                if (p.use_toep) {
+                    // matrix-pipe units (one v_mfma_f32_16x16x32_f16 = 16 cycles): per block and element row, for each of its KY y positions 2 K-steps x 3 fp16
+                    // products -- or, with e4m3 corrections, 2 fp16 products + one K = 128 e4m3 instruction (2 units)
+                    // per element row and y position: 3 fp16 products per non-zero K-step, or 1 per non-zero K-step + one e4m3 instruction (2 units) per column
+                    // (two row tiles, e4m3: rows in quads with paired K-step-1 operands -- 6 fp16 products + 3 e4m3 instructions per four rows: 3 units per row, k_toep.hip)
+                    const double units_e4m3 = tp.nm == 2 ? 3.0 : (double)tp.ksteps_total + (double)tp.e4_units;
+                    const double per_row = far_frac * units_e4m3 + (1.0 - far_frac) * 3.0 * tp.ksteps_total;
+                    for (int rx = 0; rx < Q.xs * A.mx; ++rx)
+                        for (int ry = 0; ry < A.my; ++ry) {
+                            const int kxa = rx < wx ? (wx - 1 - rx) / (Q.xs * A.mx) + 1 : 0, kya = ry < wy ? (wy - 1 - ry) / A.my + 1 : 0;
+                            for (int sx = 0; sx < Q.nsx; ++sx)
+                                for (int sy = 0; sy < Q.nsy; ++sy) {
+                                    const int KX = (sx + 1) * kxa / Q.nsx - sx * kxa / Q.nsx, KY = (sy + 1) * kya / Q.nsy - sy * kya / Q.nsy;
+                                    if (KX > 0 && KY > 0) p.n_mfma += (long long)((double)KY * per_row * (tp.nm > 1 ? 8 * tp.nm : 8) * A.nsb * Q.kblocks);      // (row tiles of 8 positions: every tile of the block's shape is computed)
+                                }
+                        }
+                    snprintf(nmbuf, sizeof nmbuf, "field_toep%s_k<mx%d,my%d,flat,%s%s> %d columns for %d foci x %d images in %d tile(s); "
+                             "%dx%d lattice, pitch %dx%d voxels, %lld MFMA/launch (%lld dense), %d row tile(s) x %d y positions per block", "", p.mx, p.my, lat_tag, f8tag.c_str(),
+                             total_cols, F, n_img, ntiles, A.ax, A.ay, A.mx, A.my, p.n_mfma, p.n_dense, tp.nm, tp.kyw);
+                } else {
+                    // matrix-pipe time in units of one v_mfma_f32_16x16x32_f16 (16 cycles): 3 fp16 products per K-step, or with fp8
+                    // corrections 1 fp16 product per K-step + one K = 128 e4m3 instruction (2 units) per two K-steps
+                    p.n_mfma = (long long)((double)tiles16 * ((P.nz + COS_P - 1) / COS_P) * A.nsa * A.nsb * 4 * p.nt * corr_units * ntiles);
+                    if (p.use_cosetp) {   // kernel 2g: one row tile per position and 16-plane block, no padded rows
+                        long long npos_all = 0;
+                        for (int rx = 0; rx < 2 * A.mx; ++rx)
+                            for (int ry = 0; ry < A.my; ++ry)
+                                npos_all += (long long)(rx < wx ? (wx - 1 - rx) / (2 * A.mx) + 1 : 0) * (ry < wy ? (wy - 1 - ry) / A.my + 1 : 0);
+                        p.n_mfma = (long long)((double)npos_all * Q.kblocks * A.nsa * A.nsb * 4 * p.nt * corr_units * ntiles);
+                    }
+#ifdef OLX_DEV_PINS
+                    const std::string pin_tags = std::string((p.use_cosetp && pins.cp_noreuse) ? ",noreuse" : "") + ((p.use_cosetp && pins.cp_nofillahead) ? ",nofillahead" : "");
+#else
+                    const std::string pin_tags;      // (the product cannot name the tags: tests/test_gpu_cosetp_fill_ahead.py)
+#endif
+                    snprintf(nmbuf, sizeof nmbuf, "field_coset%s_k<nt%d,mx%d,my%d,flat,%s%s%s> %d columns for %d foci x %d images in %d tile(s); "
+                             "%dx%d lattice, pitch %dx%d voxels, %lld MFMA/launch (%lld dense)", p.use_cosetp ? "p" : "", p.nt, p.mx, p.my, lat_tag,
+                             f8tag.c_str(), pin_tags.c_str(), total_cols, F, n_img, ntiles, A.ax, A.ay, A.mx, A.my, p.n_mfma, p.n_dense);
+                }
+            } else {
+                p.n_mfma = (long long)L.tiles_x * L.tiles_y * L.kgroups * A.nsa * A.nsb * 4 * p.lat_mt * p.nt * 3 * ntiles;
+                snprintf(nmbuf, sizeof nmbuf, "field_lattice_k<mt%d,nt%d,mx%d,my%d,flat,%s> %d columns for %d foci x %d images in %d tile(s); "
+                         "%dx%d lattice, pitch %dx%d voxels, %lld MFMA/launch", p.lat_mt, p.nt, p.mx, p.my, lat_tag,
+                         total_cols, F, n_img, ntiles, A.ax, A.ay, A.mx, A.my, p.n_mfma);
+            }
+        } else {
+            snprintf(nmbuf, sizeof nmbuf, "field_mfma_k<mt%d,nt%d,mx%d,my%d,%s,%s> %d columns for %d foci x %d images in %d tile(s)",
+                     P.nz >= 48 ? 4 : 1, p.nt, p.mx, p.my, in.flat ? "flat" : "general", near_tag, total_cols, F, n_img, ntiles);
+        }
+    } else if (p.mx * p.my * p.nf == 1) {
+        if (modifier) snprintf(nmbuf, sizeof nmbuf, "field_accum_dir_k<4,%s> (%s%s%s)", clamp_tag, in.directivity ? "piston directivity" : "",
+                               (in.directivity && in.absorb_np_m > 0) ? ", " : "", in.absorb_np_m > 0 ? "uniform absorption" : "");
+        else snprintf(nmbuf, sizeof nmbuf, "field_accum_k<4,%s,%s>", in.flat ? "flat" : "general", near_tag);
+    } else {
+        p.perm = mirror_perms(n, nm, p.dx == 2, p.dy == 2, in.px, in.py, nm);
+        snprintf(nmbuf, sizeof nmbuf, "field_shared_k<4,mx%d,my%d,dx%d,dy%d,nf%d,%s,%s>", p.mx, p.my, p.dx, p.dy, p.nf, in.flat ? "flat" : "general", near_tag);
+    }
+    if (in.directivity && p.use_mfma) strncat(nmbuf, " +piston directivity in the tables", sizeof nmbuf - strlen(nmbuf) - 1);
+    if (in.absorb_np_m > 0 && p.use_mfma) strncat(nmbuf, " +uniform absorption in the tables", sizeof nmbuf - strlen(nmbuf) - 1);
+    p.variant = nmbuf;
+    return p;
+}
+
+VariantPlan decide_variant(const VariantIn& in, std::vector<double>& nf_s2, int& slot_rows) {
+    VariantPlan p = decide_pass(in, nf_s2, slot_rows);
+    if (in.modifier() && p.use_mfma && !(p.use_lattice && p.use_coset)) {   // only the coset kernels (2e / 2f / 2g) carry per-term factors: fall back to 2a-d
+        VariantIn exact = in;
+        exact.mx = p.mx; exact.my = p.my; exact.dir_lattice = false; exact.allow_shared = false;
+        p = decide_pass(exact, nf_s2, slot_rows);
+    }
+    return p;
+}
+
+bool build_variant_blocks(const VariantPlan& p, std::vector<CosetBlock>& blk, std::string& msg) {
+    const int zb = COS_ZB, kcut = p.fp8corr ? p.fp8_kcut : 0, kb_near = kcut / zb, max_pos = p.use_cosetp ? 40 : 0;
+    // each side of the cut gets its own record list (plane blocks of a position set in a row per XCD within the side)
+    CosetParams Qf = p.cp; Qf.kblocks = p.cp.kblocks - kb_near;
+    if (!build_coset_blocks(Qf, zb, p.kgrp, max_pos, blk, msg)) return false;
+    for (CosetBlock& b : blk) b.k0 += kcut;
+    if (kb_near > 0) {
+        std::vector<CosetBlock> near;
+        CosetParams Qn = p.cp; Qn.kblocks = kb_near;
+        if (!build_coset_blocks(Qn, zb, p.kgrp_near, max_pos, near, msg)) return false;
+        blk.insert(blk.end(), near.begin(), near.end());
+    }
+    return true;
+}
+
 }  // namespace olxplan
+

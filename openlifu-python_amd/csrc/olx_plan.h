@@ -1,10 +1,12 @@
-// Pure host planning of the lattice kernels (2d / 2e / 2f / 2g): lattice detection, K-slot map, mirror permutations, column packing,
-// store-target balancing, block records, store-job lists, focus inference, the e4m3 rule (fp8_first_plane, fp8_split_pays) and kernel 2f's
-// block shape (toep_plan).  No HIP, no device memory, no context: plain C++17 in, plain vectors out.  olx.hip (configure_variant) calls these and uploads what they return; the SAME translation unit is compiled with
-// g++ -fsanitize=address,undefined into the CPU-side checker tools/plan_check.cpp, which `pytest -m "not gpu"` drives over fuzz
-// shapes (tests/test_plan_host.py: every (focus, image) stored exactly once, every voxel covered exactly once, records inside the
-// grid, the kernels' magic divisions exact, the e4m3 rule's known decisions and refusals, kernel 2f's known shapes) -- the planning behind
-// kernels 2f / 2g runs without a GPU.
+// Pure host planning of kernel 2: lattice detection, K-slot map, mirror permutations, column packing, store-target balancing, block records,
+// store-job lists, focus inference, the e4m3 rule (fp8_first_plane, fp8_split_pays), kernel 2f's block shape (toep_plan) -- and the DECISION that
+// combines them: decide_variant chooses among the eleven field kernels (2a .. 2g, 2h / 2m), their shapes and parameter blocks, and names the variant.
+// No HIP, no device memory, no context, no environment: plain C++17 in, plain vectors out.  olx.hip (configure_variant) reads the pins, calls
+// decide_variant and uploads what it returns; the SAME translation unit is compiled with g++ -fsanitize=address,undefined into the CPU-side
+// checker tools/plan_check.cpp, which `pytest -m "not gpu"` drives over fuzz shapes (tests/test_plan_host.py: every (focus, image) stored exactly
+// once, every voxel covered exactly once, records inside the grid, the kernels' magic divisions exact, the e4m3 rule's known decisions and refusals,
+// kernel 2f's known shapes, the decision's flags, tables and record key consistent with each other), and into tools/plan_query.cpp, through which
+// the parity matrices compare the variant string of every row with the one they expect -- the planning AND the decision run without a GPU.
 #pragma once
 #include <string>
 #include <vector>
@@ -116,5 +118,77 @@ struct ToepPlan {
 // ax = elements along x, mx / my = pitch [voxels], xs = pitches between two positions of a coset along x, wx x wy x nz = computed region [voxels];
 // dir_lattice: the DIR instantiations (no three-tile shape); saw_pin (8 .. 24) / nm_pin (1 | 3) override the choice for A/B runs, 0 = none
 ToepPlan toep_plan(int ax, int mx, int my, int xs, int wx, int wy, int nz, bool dir_lattice, int saw_pin = 0, int nm_pin = 0);
+
+// ---- the kernel-2 variant decision ----
+// Bits of the plan flags the decision reads (include/olx.h: OLX_OUT_PMAG, OLX_OUT_INTENSITY, OLX_OUT_COMPLEX, OLX_FIELD_FP16_CORRECTION; olx.hip asserts the values)
+constexpr unsigned FLAG_OUT_PMAG = 1u, FLAG_OUT_INTENSITY = 2u, FLAG_OUT_COMPLEX = 4u, FLAG_FP16_CORRECTION = 32u;
+
+// What the caller read from the environment.  A product build fills `family` and fp8 = -1 only; the rest are the A/B pins of developer builds (OLX_DEV_PINS).
+enum class FamilyPin { none, lattice, lattice2d, other };      // OLX_FIELD_VARIANT: unset, "lattice", "lattice2d", any other value
+struct Pins {
+    FamilyPin family = FamilyPin::none;
+    int fp8 = 0;                               // OLX_FP8_CORRECTION: -1 = "0" (opts out like the plan flag), 0 = unset, 1 = forced past the e4m3 rule
+    int toep_saw = 0, toep_nm = 0;             // OLX_EXP_TOEP_SAW (8 .. 24), OLX_EXP_TOEP_NM (1 | 3); 0 = none
+    int kgrp = 0;                              // OLX_EXP_KGRP (>= 1); 0 = none
+    bool cp_noreuse = false, cp_nofillahead = false;      // OLX_EXP_CP_NOREUSE, OLX_EXP_CP_NOFILLAHEAD
+};
+
+// What olx_field_plan established and what the steering provides: values and read-only arrays
+struct VariantIn {
+    int n = 0, F = 0;
+    const double* pos = nullptr;               // [3][n] (SoA) [m]
+    const double* area = nullptr;              // [n]
+    const double* delays = nullptr;            // [F][n] s (null: no host copy of the steering table)
+    const double* apod = nullptr;              // [F][n]
+    const int* px = nullptr; const int* py = nullptr;      // [n] axis mirrors of the element set (read where mx / my == 2)
+    double freq = 0, c = 0, p0_pa = 0;
+    double origin[3] = {0, 0, 0}, spacing[3] = {0, 0, 0}; int gn[3] = {0, 0, 0};      // the grid
+    int x_begin = 0, x_count = 0;              // the slab
+    unsigned flags = 0;                        // plan flags (FLAG_*)
+    olx::FieldParams fp{};
+    bool flat = false, clamp = false, near = false;
+    double min_dist = 0;                       // lower bound of any voxel-element distance [m]
+    int mx = 1, my = 1;                        // mirror folds of the geometry
+    bool allow_shared = true, dir_lattice = false, directivity = false;
+    double absorb_np_m = 0;
+    int force_kind = 0;                        // 0 auto, 1 general, 2 shared, 3 mfma, 4 lattice
+    double size0 = 0, size1 = 0;               // width / length of element 0 [m] (directivity on a dir_lattice array: all elements are equal)
+    bool hetero = false, marched = false, march_one = false;      // heterogeneous medium: what the name needs
+    int n_planes = 0, n_layers = 0, planes_per_layer = 1;
+    const Lattice* lat = nullptr;
+    const double* foci = nullptr;              // [F][3] m where the foci are known, else null
+    Pins pins;
+    bool modifier() const { return directivity || absorb_np_m > 0; }
+};
+
+struct VariantPlan {
+    bool use_mfma = false, use_lattice = false, use_coset = false, use_toep = false, use_cosetp = false, fp8corr = false;
+    int fp8_kcut = 0;                          // first plane of the e4m3 products (meaningful while fp8corr)
+    int mx = 1, my = 1, dx = 1, dy = 1, nf = 1, nt = 1, lat_mt = 4;
+    bool allow_shared = true, dir_lattice = false;      // as they end up after the fallback to kernels 2a-d
+    std::vector<int> perm;                     // mirror permutations: [4][n] (kernels 2c - 2g), [dx dy][n] (kernel 2b), empty (2a, 2h / 2m)
+    Tiles tiles; int total_cols = 0;
+    std::vector<int> colinfo;                  // [column][f, m] then [column][4 store targets], tiles x MFMA_COLS x MFMA_MAX_NT columns
+    std::vector<int> jobs;                     // build_store_jobs (use_coset)
+    ToepPlan toep{0, 0, 1, olx::COS_KYW, 0u, 0, 0};
+    int n_pad = 0; bool lat_clamp = false;
+    double g_scale = 0, out_scale = 0, mfma_wscale = 0;
+    olx::MfmaParams mp{}; olx::LatParams lp{}; olx::CosetParams cp{};
+    unsigned kgrp = 1, kgrp_near = 0;          // plane blocks of one position set in a row per XCD, above / below the cut
+    unsigned blocks_near = 0;                  // block records of the plane blocks below the cut (they follow the others)
+    int rec_key[16] = {0};                     // everything build_coset_blocks reads: the caller rebuilds its block records only when this changes
+    long long n_mfma = 0, n_dense = 0;
+    std::string variant;
+};
+
+// dx / dy: whether every focus' delays and apodization are symmetric under the element permutation of a folded axis
+bool steering_symmetric(int n, int F, const double* delays, const double* apod, const double* area, double freq, const int* perm);
+// whether decide_variant will ask the e4m3 rule, i.e. read in.foci (the caller resolves them only then: infer_foci)
+bool variant_reads_foci(const VariantIn& in);
+// The decision.  nf_s2 and slot_rows are the caller's caches: fp8_first_plane's near-field sums, and the rows of the K-slot map the lattice holds
+// (in: in.lat->nsbp; out: what the chosen shape needs -- the caller rebuilds the map when it differs; LatParams / CosetParams carry the new count).
+VariantPlan decide_variant(const VariantIn& in, std::vector<double>& nf_s2, int& slot_rows);
+// The block records of a use_coset plan: those of the plane blocks from the cut on first, then the blocks below it.  False (msg) as build_coset_blocks.
+bool build_variant_blocks(const VariantPlan& p, std::vector<CosetBlock>& blk, std::string& msg);
 
 }  // namespace olxplan

@@ -21,6 +21,7 @@ import pytest
 
 from openlifu_amd import _native as nat
 from oracle import bf_oracle as bo, c_oracle as co
+import plan_query
 import test_gpu_field_matrix as fm
 from test_gpu_field import C, F0, HET_TOL_P, P0, RHO, TOL_I, TOL_P, setup_ctx
 
@@ -365,6 +366,23 @@ def test_table_follows_the_host_rules():
             assert eu.min() >= 0.7 and eu.max() <= len(xs) - 1.7 and ev.min() >= 0.7 and ev.max() <= len(ys) - 1.7, cid
         else:
             assert eu.min() < 0 or eu.max() > len(xs) - 1, cid
+
+
+def test_every_row_reaches_its_prefix_in_the_real_decision():
+    """Without a GPU: the real decision (olxplan::decide_variant, through tools/plan_query.cpp) names, for every row, the nf and the prefix the GPU tests
+    wait for.  What olx_field_set_medium establishes before it asks -- marched or sampled, the one-sum form, the non-trivial planes and their layers --
+    comes from the restated host rules (plan_rule, nontrivial_planes); the decision adds the foci per launch tile and the clamp class, and names them."""
+    for cid, case in CASES.items():
+        pos, _, size = array(case["arr"])
+        prefix, _ = plan_rule(case)
+        planes = nontrivial_planes(*medium(case)[:2])
+        runs = np.split(np.array(planes), np.flatnonzero(np.diff(planes) != 1) + 1) if planes else []
+        layers = sum(-(-len(r) // case["G"]) for r in runs) if "layers" in prefix else 0
+        d, ap = steering(cid)
+        line = plan_query.variant(pos * 1e-3, size[:, 0] * size[:, 1] * 1e-6, d, ap, *grid(case), F0, C, RHO, P0, OUTPUTS[case["out"]],
+                                  medium=(prefix.startswith("field_hmarch_k"), "one-sum" in prefix, len(planes), layers, case["G"]))
+        assert line.split(">")[0] + ">" == case["want"], (cid, line, case["want"])
+        assert f"nf{NF_OF(case['foci'][1])}," in line and f"({len(planes)} non-trivial planes" in line, (cid, line)
 
 
 # ---- the references: computed once per (case, focus), shared, read-only ----------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """Parity matrix of the lattice field kernels -- 2d (field_lattice_k), 2e (field_coset_k), 2g (field_cosetp_k), 2f (field_toep_k) -- against the
 fp64 C oracle, modelled on tests/test_gpu_field_matrix.py (kernels 2a / 2b / 2c).
 
-Every array here is a flat matrix array whose pitch is a whole number of voxels, so the planner (configure_variant in olx.hip, olx_plan.cpp) has to
+Every array here is a flat matrix array whose pitch is a whole number of voxels, so the planner (decide_variant in olx_plan.cpp) has to
 choose among the ~ 180 instantiations of these four kernels from the mirror folds of the geometry, the number of distinct steering vectors, the output
 set, the arithmetic of the correction products, per-term modifiers and the pins.  One table (CASES) names for every case the instantiation it must
 reach -- the string olx_field_variant reports up to '>', and where it matters a later fragment ("in 2 tile(s)", "3 row tile(s)", "piston directivity
@@ -13,9 +13,10 @@ padding, one rolled element under the directivity flag) have rows of their own w
 Fold patterns come from the geometry, never from a pin: grid centred on the array = both folds, shifted by whole voxels along one axis = the other
 fold only, shifted along both = none, an x-slab of a centred grid = the y fold only.
 
-Tests without a GPU: the coverage test (the table's strings reach every instantiation and shape edge the matrix is for, the size caps), the rule test
-(the planner's decision restated in plan_rule predicts every expected string; lattice detection with its clamp bound, column packing, coset_tiles16,
-toep_plan and the e4m3 rule are ASKED of the real olx_plan.cpp through tools/plan_query.cpp, not restated a third time), the oracle alone and the
+Tests without a GPU: the coverage test (the table's strings reach every instantiation and shape edge the matrix is for, the size caps), the decision test
+(the REAL decision, olxplan::decide_variant asked through tools/plan_query.cpp, produces every row's expected string and fragments, and agrees with
+plan_rule on every row), the rule test (the planner's decision restated independently in plan_rule predicts every expected string; lattice detection
+with its clamp bound, column packing, coset_tiles16, toep_plan and the e4m3 rule are ASKED of the real olx_plan.cpp, not restated a third time), the oracle alone and the
 sensitivity test (a dropped element row, an array displaced by one pitch and a mirrored store target each move the reference by more than ten gates).
 
 Left out on purpose: split launches ("fp8corr from plane K").  fp8_split_pays needs >= 8e6 (voxel, focus) pairs above the cut, i.e. more than 2e9
@@ -30,20 +31,18 @@ OLX_FP8_CORRECTION=1, which only a developer build honours, and run in the debug
 the 7.5e-6 promise, so those cases are held to the project's gates only."""
 import ctypes
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from openlifu_amd import _native as nat
 from oracle import bf_oracle as bo, c_oracle as co, field_oracle as fo
+from plan_query import _d, _i, planq, variant as real_variant_of      # the real planning code (olx_plan.cpp) behind a C interface
 from test_gpu_field import C, DEV_LIB, F0, FP8_BOUND, P0, RHO, TOL_I, TOL_P, setup_ctx
 from test_gpu_field_matrix import APODS, FOLDS, OUTPUTS, distance_class, measure
 from test_gpu_cosetp_table_reuse import block_shapes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GATES = {"pmag": TOL_P, "complex": 3 * TOL_P, "intensity": TOL_I}
 CAP, CAP_BIG, MAX_BIG = 2e8, 6e8, 4      # oracle terms (voxels x elements x foci) per case; the named exceptions are the NM = 3 cases of kernel 2f
 SHIFT = (3, -2)                          # whole voxels: the shift that takes a fold away
@@ -266,32 +265,7 @@ BIG = [k for k in ALL_CASES if k.startswith("2f-nm3-")]
 EPILOGUE_SETS = [f"{k}-epi-{{}}-nz{nz}" for k in ("2g", "2e") for nz in (32, 23)]
 
 
-# ---- the real planning code (olx_plan.cpp) behind a C interface ---------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def planq():
-    out = os.path.join(ROOT, "oracle", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libplan_query.so")
-    srcs = [os.path.join(ROOT, "tools", "plan_query.cpp"), os.path.join(ROOT, "openlifu-python_amd", "csrc", "olx_plan.cpp")]
-    deps = srcs + [os.path.join(ROOT, "openlifu-python_amd", "csrc", h) for h in ("olx_plan.h", "olx_params.h", "k_toep.hip.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC"] + srcs + ["-o", so])
-    lib = ctypes.CDLL(so)
-    lib.olq_coset_tiles16.restype = ctypes.c_longlong
-    return lib
-
-
-def _d(a):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
-def _i(a):
-    a = np.ascontiguousarray(a, dtype=np.int32)
-    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-
-
-# ---- the planner's decision for lattice arrays, restated (configure_variant and olx_field_plan in olx.hip) ----------------------------------
+# ---- the planner's decision for lattice arrays, restated (decide_variant in olx_plan.cpp, olx_field_plan in olx.hip) ----------------------------------
 def tile_fill(width, m):
     blk = 4 * m
     return width / (-(-width // blk) * blk)
@@ -417,7 +391,46 @@ def plan_rule(case, report=None):
     return name, tail
 
 
+def real_variant(case):
+    """The whole string of the REAL decision (olxplan::decide_variant, through tools/plan_query.cpp) for the plan run_lcase makes of the case: the same
+    elements, steering, grid, slab, outputs, flags and pins; the foci are known where kernel 1 makes the steering, inferred from the delays otherwise.
+    Developer rows ask the library built with -DOLX_DEV_PINS."""
+    pos, ori, size, xs, ys, zs = geometry(case)
+    delays, ap = steering(case)
+    return real_variant_of(pos * 1e-3, size[:, 0] * size[:, 1] * 1e-6, delays, ap, xs, ys, zs, F0, C, RHO, P0, OUTPUTS[case["out"]],
+                           foci=foci_of(case) if _solve(case) else None, slab=case["slab"], fp16=case["fp16"], directivity=case["dirv"], aligned=not ori.any(),
+                           size=size[0] * 1e-3, absorb=case["absorb"], stored=case["stored"], pin=case["pin"], fp8_pin="1" if case["dev"] else None, dev=case["dev"])
+
+
+def _agrees(case, label):
+    """plan_rule, the independent restatement, against the real decision: the same string up to '>' and every later fragment it predicts."""
+    line = real_variant(case)
+    name, tail = plan_rule(case)
+    assert line.split(">")[0] + ">" == name, (label, line, name)
+    for frag in tail:
+        assert frag in line, (label, frag, line)
+    return line
+
+
 # ---- CPU tests -------------------------------------------------------------------------------------------------------------------------------------
+def test_every_row_reaches_its_variant_in_the_real_decision():
+    """Without a GPU: decide_variant itself produces, for every row of the table (developer rows included), the string the GPU tests wait for -- `want` up
+    to '>' and every entry of `frag` after it -- and plan_rule agrees with it on every row, on the slab sets and on the seeded sweep's draws."""
+    for cid, case in ALL_CASES.items():
+        line = _agrees(case, cid)
+        assert line.split(">")[0] + ">" == case["want"], (cid, line, case["want"])
+        for frag in case["frag"]:
+            assert frag in line, (cid, frag, line)
+        assert "from plane" not in line, (cid, line)
+    for which in SLAB_SETS:
+        case, want_whole, want_part = _slab_case(which)
+        assert real_variant(case).startswith(want_whole), (which, real_variant(case))
+        for slab in ((0, 10), (10, 17), (27, 9)):
+            assert _agrees(dict(case, slab=slab), (which, slab)).startswith(want_part), (which, slab)
+    for q, case in enumerate(_sweep_cases()):
+        _agrees(case, f"sweep-{q}")
+
+
 def _kernel(c):
     return c["want"].split("<")[0]
 

@@ -14,11 +14,16 @@
 //   e4m3 rule    fp8_first_plane / fp8_split_pays: known decisions on BASELINE's array, one case per way the rule refuses, the result against a
 //                restatement that asks nearfield_s2 of every plane block without the cache
 //   kernel 2f    toep_plan: known shapes of the project; the columns cover the array, ks_mask has 1 - 2 bits per column and none beyond
+//   decision     decide_variant on every recognised lattice with 1 / 3 / 8 / 9 / 64 foci, plain and complex output, once with a per-term factor: the
+//                family flags imply each other, e4m3 products only in the NT <= 2 coset shapes, NT covers the widest tile, colinfo / store jobs /
+//                permutations sized as the kernels index them, an even row count of the pair tables for NT <= 2, no per-term factor left with a
+//                kernel that carries none, and the record key names every quantity of the block records (one key, one record list)
 // Exit code 0 = all shapes passed; any violation prints the shape and exits 1 (sanitizer reports abort on their own).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <random>
 #include <set>
@@ -84,6 +89,9 @@ struct Shape {
     int nf;                        // foci
     double h;                      // spacing [m]
 };
+
+struct Geometry { int n; const double* pos; const double* area; const int* px; const int* py; double origin[3]; double h; int gn[3]; int x_begin, x_count, mx, my; const Lattice* L; };
+static void check_decision(const Geometry& G, int F, bool cplx, bool absorb);
 
 static void check_shape(const Shape& S, std::mt19937_64& rng, int nt_force) {
     const int n = S.nax * S.nay;
@@ -259,6 +267,96 @@ static void check_shape(const Shape& S, std::mt19937_64& rng, int nt_force) {
                         CHECK(blk[id + 8].ibase == blk[id].ibase && blk[id + 8].jbase == blk[id].jbase && blk[id + 8].k0 == blk[id].k0 + fm.zb, "line partners not 8 ids apart");
         }
     }
+    // ---- the decision over this lattice: 1 .. 64 foci, plain and complex output, and once with a per-term factor (the fallback to kernels 2a-d)
+    Geometry G{n, pos.data(), area.data(), hpx.data(), hpy.data(), {origin[0], origin[1], origin[2]}, S.h, {S.n[0], S.n[1], S.n[2]}, S.x_begin, S.x_count, mxf, myf, &L};
+    for (int Fd : {1, 3, 8, 9, 64})
+        for (int variation = 0; variation < (Fd == 3 ? 3 : 2); ++variation) check_decision(G, Fd, variation == 1, variation == 2);
+}
+
+// ---- decide_variant: what nobody checks on a GPU -- the flags imply each other, NT covers the widest tile, the tables have the sizes the kernels
+// index them with, the pair tables of the NT <= 2 shapes have an even row count, the fallback leaves no per-term factor with a kernel that cannot
+// carry it, and the record key determines the block records
+static std::map<std::vector<int>, std::vector<CosetBlock>> g_records_of_key;
+static std::map<std::string, int> g_decided;      // kernel name -> decisions that chose it
+static void check_decision(const Geometry& G, int F, bool cplx, bool absorb) {
+    const int n = G.n;
+    std::mt19937_64 rng(1000003ull * n + 131 * F + G.gn[2]);      // (a stream of its own: the shapes stay the ones each seed always drew)
+    std::uniform_real_distribution<double> U(-4e-3, 4e-3), Z(20e-3, 40e-3);
+    std::vector<double> foci(3 * (size_t)F), delays((size_t)F * n), apod((size_t)F * n, 1.0);
+    for (int f = 0; f < F; ++f) {
+        double x = U(rng), y = U(rng), z = Z(rng);
+        if (f % 5 == 0) { x = 0; y = 0; }                 // on the axis: all images share one vector
+        else if (f % 5 == 2 && f >= 3) { x = -foci[3 * (size_t)(f - 1)]; y = foci[3 * (size_t)(f - 1) + 1]; z = foci[3 * (size_t)(f - 1) + 2]; }   // mirror partner of the previous focus
+        foci[3 * (size_t)f] = x; foci[3 * (size_t)f + 1] = y; foci[3 * (size_t)f + 2] = z;
+        double tmax = 0;
+        for (int e = 0; e < n; ++e) {
+            const double dx = x - G.pos[e], dy = y - G.pos[(size_t)n + e];
+            delays[(size_t)f * n + e] = std::sqrt(dx * dx + dy * dy + z * z) / 1500.0; tmax = std::max(tmax, delays[(size_t)f * n + e]);
+        }
+        for (int e = 0; e < n; ++e) delays[(size_t)f * n + e] = tmax - delays[(size_t)f * n + e];
+    }
+    VariantIn in;
+    in.n = n; in.F = F; in.pos = G.pos; in.area = G.area; in.delays = delays.data(); in.apod = apod.data(); in.px = G.px; in.py = G.py; in.foci = foci.data();
+    in.freq = 400e3; in.c = 1500.0; in.p0_pa = 1e5; in.x_begin = G.x_begin; in.x_count = G.x_count;
+    for (int a = 0; a < 3; ++a) { in.origin[a] = G.origin[a]; in.spacing[a] = G.h; in.gn[a] = G.gn[a]; }
+    in.flags = FLAG_OUT_PMAG | FLAG_OUT_INTENSITY | (cplx ? FLAG_OUT_COMPLEX : 0u);
+    const double rev = in.freq / in.c;
+    FieldParams& P = in.fp;
+    P.nx = G.x_count; P.ny = G.gn[1]; P.nz = G.gn[2]; P.n_el = n; P.x_begin = G.x_begin; P.hx = P.hy = P.hz = (float)(G.h * rev);
+    P.dmin2 = (float)(0.25 * G.h * G.h * rev * rev); P.inten_scale = 1e-10f; P.flat_ez = (float)(-G.origin[2] * rev); P.vox = (long long)P.nx * P.ny * P.nz; P.flags = in.flags & 7u;
+    in.flat = true; in.min_dist = G.origin[2];      // (the grid starts 4 mm above the array: neither clamp nor near)
+    in.mx = G.mx; in.my = G.my; in.lat = G.L;
+    if (absorb) { in.absorb_np_m = 5.0; in.dir_lattice = true; }
+    std::vector<double> nf_s2;
+    int slot_rows = G.L->nsbp;
+    const VariantPlan p = decide_variant(in, nf_s2, slot_rows);
+    const char* v = p.variant.c_str();
+    ++g_decided[p.variant.substr(0, p.variant.find('<'))];
+    CHECK(!p.variant.empty() && p.variant.size() < 383, "decision: variant string of %zu characters", p.variant.size());
+    CHECK((!p.use_toep || p.use_coset) && (!p.use_cosetp || p.use_coset) && (!p.use_coset || p.use_lattice) && (!p.use_lattice || p.use_mfma) && !(p.use_toep && p.use_cosetp),
+          "decision: family flags contradict each other (%s)", v);
+    CHECK(!p.fp8corr || (p.use_coset && cos_fp8(p.nt)), "decision: e4m3 products with NT = %d / without a coset kernel (%s)", p.nt, v);
+    CHECK(!(in.modifier() && p.use_mfma && !(p.use_lattice && p.use_coset)), "decision: a per-term factor left with a kernel that carries none (%s)", v);
+    CHECK(in.modifier() || (p.allow_shared && p.mx == in.mx && p.my == in.my), "decision: folds changed without a fallback (%s)", v);
+    if (!p.use_mfma) { CHECK(p.tiles.empty() && p.colinfo.empty() && p.jobs.empty(), "decision: column tables without a matrix kernel (%s)", v); return; }
+    int widest = 0, cols = 0;
+    for (const auto& t : p.tiles) { widest = std::max(widest, (int)t.size()); cols += (int)t.size(); }
+    CHECK((p.nt == 1 || p.nt == 2 || p.nt == 4) && p.nt * MFMA_COLS >= widest && widest >= 1, "decision: tile of %d columns exceeds NT = %d (%s)", widest, p.nt, v);
+    CHECK((p.use_cosetp ? cols >= p.total_cols : cols == p.total_cols) && p.mp.n_tiles == (int)p.tiles.size(), "decision: %d columns counted, %d packed", p.total_cols, cols);      // (kernel 2g: balancing hands store targets to free slots)
+    // colinfo as mfma_pack_k and the kernels index it: [tile][32 columns][f, m], then [tile][32 columns][4 targets]
+    constexpr int MAXC = MFMA_COLS * MFMA_MAX_NT;
+    const size_t n_col = p.tiles.size() * MAXC;
+    CHECK(p.colinfo.size() == n_col * 6 && p.perm.size() == 4 * (size_t)n, "decision: colinfo of %zu entries for %zu tiles, %zu permutation entries", p.colinfo.size(), p.tiles.size(), p.perm.size());
+    if (p.colinfo.size() == n_col * 6)
+        for (size_t t = 0; t < p.tiles.size(); ++t)
+            for (size_t o = 0; o < (size_t)MAXC; ++o) {
+                const int* fm = &p.colinfo[(t * MAXC + o) * 2]; const int* tg = &p.colinfo[n_col * 2 + (t * MAXC + o) * 4];
+                if (o < p.tiles[t].size()) CHECK(fm[0] == p.tiles[t][o].f && fm[1] == p.tiles[t][o].m && std::equal(tg, tg + 4, p.tiles[t][o].tgt), "decision: colinfo of tile %zu column %zu", t, o);
+                else CHECK(fm[0] == -1 && fm[1] == -1 && tg[0] == -1, "decision: colinfo names a column past the tile (%zu, %zu)", t, o);
+            }
+    CHECK(p.n_pad % 16 == 0 && p.n_pad >= n && p.mp.n_el_pad == p.n_pad, "decision: %d padded elements for %d", p.n_pad, n);
+    CHECK(p.g_scale > 0 && p.out_scale > 0 && p.mfma_wscale > 0 && std::isfinite(p.mfma_wscale), "decision: operand scales");
+    if (!p.use_lattice) return;
+    CHECK(slot_rows == p.lp.nsbp && p.n_pad == G.L->nsa * slot_rows * 64 && (slot_rows == G.L->nsb || slot_rows == ((G.L->nsb + 1) & ~1)), "decision: %d rows of the slot map (nsb %d)", slot_rows, G.L->nsb);
+    if (!p.use_coset) { CHECK(p.jobs.empty(), "decision: store jobs without a coset kernel"); return; }
+    const CosetParams& Q = p.cp;
+    CHECK(p.jobs.size() == p.tiles.size() * MFMA_MAX_NT * (COS_JOBS + 1), "decision: %zu store-job entries for %zu tiles", p.jobs.size(), p.tiles.size());
+    CHECK(Q.nsbp == slot_rows && (p.nt > 2 || Q.nsbp % 2 == 0), "decision: NT = %d with %d rows of pair tables", p.nt, Q.nsbp);
+    CHECK(Q.xs == (p.use_toep ? 1 : 2) && Q.n_foci == F && Q.kblocks == (Q.nz + COS_ZB - 1) / COS_ZB, "decision: coset parameters");
+    CHECK(!p.use_toep || (p.total_cols == 1 && p.toep.nm >= 1 && p.toep.nm <= TOEP_MAX_NM), "decision: kernel 2f with %d columns, %d row tiles", p.total_cols, p.toep.nm);
+    // the record key: it names every quantity build_coset_blocks reads, and plans with one key have the same records (what the caller's cache relies on)
+    const int kcut = p.fp8corr ? p.fp8_kcut : 0;
+    const int key[16] = {Q.nx, Q.ny, Q.nz, Q.x_lo, Q.y_lo, Q.mx, Q.my, Q.nsx, Q.nsy, Q.kblocks, COS_ZB, (int)p.kgrp, p.use_cosetp ? 40 : 0, Q.xs, kcut, (int)p.kgrp_near};
+    CHECK(std::equal(key, key + 16, p.rec_key), "decision: the record key misses a quantity the block records depend on (%s)", v);
+    std::vector<CosetBlock> blk;
+    std::string why;
+    const bool ok = build_variant_blocks(p, blk, why);
+    CHECK(ok, "decision: block records refused: %s", why.c_str());
+    if (!ok) return;
+    CHECK(blk.size() == (size_t)Q.xs * Q.mx * Q.my * Q.nsx * Q.nsy * Q.kblocks && p.blocks_near <= blk.size() && p.blocks_near == (size_t)Q.xs * Q.mx * Q.my * Q.nsx * Q.nsy * (kcut / COS_ZB),
+          "decision: %zu block records, %u below the cut", blk.size(), p.blocks_near);
+    const auto hit = g_records_of_key.emplace(std::vector<int>(p.rec_key, p.rec_key + 16), blk);
+    if (!hit.second) CHECK(hit.first->second.size() == blk.size() && !memcmp(hit.first->second.data(), blk.data(), blk.size() * sizeof(CosetBlock)), "decision: two plans with one record key, different block records (%s)", v);
 }
 
 // ---- e4m3 error rule (olx_plan.h: fp8_first_plane, fp8_split_pays, nearfield_s2) on BASELINE's 16 x 16 @ 3 mm array, uniform drive ----
@@ -499,6 +597,9 @@ int main(int argc, char** argv) {
         check_shape(S, rng, 0);
         ++done;
     }
+    printf("plan_check: decisions");
+    for (const auto& kv : g_decided) printf(" %s x%d", kv.first.c_str(), kv.second);
+    printf("\n");
     printf("plan_check: %d shapes (%lld recognised lattices, %lld columns, %lld block records), %d violations\n", done, g_lattices, g_columns, g_records, g_fail);
     return g_fail ? 1 : 0;
 }
