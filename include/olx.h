@@ -363,6 +363,35 @@ int olx_thermal_run(olx_ctx *ctx, double dt, double baseline, int first_step, in
 /* The maximum rise and CEM43 volumes ([voxels] floats) and the traces ([steps run * n_points] floats, step-major); any may be NULL. */
 int olx_thermal_fetch(olx_ctx *ctx, float *rise_max, float *cem43, float *traces);
 
+/* Full-wave model (DESIGN.md section 2 "full-wave model", kernel 5): linear acoustics, first order in (p, v), on a staggered grid --
+ * second order in time, fourth order in space, fp32 state -- with reflection, refraction and transmission loss at every interface of
+ * the medium.  An opt-in model of its own: its buffers are apart from the field plan, the resident result and the thermal buffers, and
+ * a full-wave run changes none of them.
+ * Plan `grid` -- the PADDED grid: the caller's grid plus pml_size voxels of absorbing layer on every side, the medium extended into the
+ * layers by the caller -- and the medium: per-voxel sound speed [m/s], density [kg/m^3] and absorption [Np/m at the drive frequency]
+ * ([nx * ny * nz] floats each, C order), each may be NULL for the uniform value that follows; with all three NULL no coefficient volume
+ * is formed or streamed.  A layer voxel `depth` voxels into the layer of axis a (1 .. pml_size) decays by
+ * exp(-pml_alpha (c_ref / h_a) (depth / pml_size)^4 dt) per step.  dt [s] is the time step of every run of the plan; dt_max_out (may
+ * be NULL) receives the stability bound 6 / (7 c_max sqrt(sum_a 1 / h_a^2)).  OLX_EINVAL before the device is touched: dt above the
+ * bound, a medium that is not finite and > 0 (absorption >= 0), an axis with no interior voxel, 2^31 voxels or more. */
+int olx_fullwave_plan(olx_ctx *ctx, const olx_grid *grid, const float *sound_speed, const float *density, const float *absorption,
+                      double sound_speed0, double density0, double absorption0, double c_ref, int pml_size, double pml_alpha,
+                      double dt, double *dt_max_out);
+/* The source table of the plan: entry s adds amplitude[s] env(u) sin(2 pi freq u), u = (n - 1/2) dt - tau[s], to p at voxels[s]
+ * (linear C-order index of the padded grid) at the start of step n while 0 <= u < cycles / freq (decided in fp64); env is 1, or with
+ * ramp_cycles > 0 a raised-cosine ramp over the first and the last ramp_cycles / freq seconds.  Entries that share a voxel add in
+ * table order.  n_steps is the length of the run (olx_fullwave_run takes steps inside [0, n_steps)); n_points voxels are traced:
+ * olx_fullwave_fetch returns p there after every step. */
+int olx_fullwave_sources(olx_ctx *ctx, int n_entries, const long long *voxels, const double *amplitude, const double *tau,
+                         double freq, double cycles, double ramp_cycles, int n_steps, int n_points, const long long *points);
+/* Steps [first_step, first_step + n_steps); first_step = 0 starts from p = v = 0 and clears the records, any other first_step
+ * continues the last run (OLX_ESTATE when it does not).  Per voxel it keeps p_max = max_n p and p_min = max_n -p (both >= 0) and,
+ * with accumulate_psq != 0, sum_n p^2 (a continued run keeps the choice of its first call).  Asynchronous. */
+int olx_fullwave_run(olx_ctx *ctx, int first_step, int n_steps, int accumulate_psq);
+/* The records of the padded grid ([voxels] floats each) and the traces ([steps run * n_points] floats, step-major); any may be NULL.
+ * OLX_ESTATE: nothing run, or p_sq asked of a run that did not accumulate it. */
+int olx_fullwave_fetch(olx_ctx *ctx, float *p_max, float *p_min, float *p_sq, float *traces);
+
 /* ---- kernel 4: steering map (DESIGN.md section 2 "Steering map") ---------------------------------------
  * Where can the array steer?  Every voxel of `grid` is a candidate target, in the frame of the element table (kernel 1 with
  * M = identity): with w = r_v - g_e, d = |w|, d' = max(d, min(spacing) / 2) and theta = kernel 1's folded angle,

@@ -1,0 +1,179 @@
+// kernel 5 (fullwave_pack_k, fullwave_inject_k, fullwave_vel_k, fullwave_pres_k, fullwave_trace_k): full-wave FDTD field model --
+// linear acoustics, first order in (p, v) on a staggered grid, second order in time, fourth order in space.
+// gfx950 (CDNA4, wave64) only.  Definition: DESIGN.md section 2 ("full-wave model") and section 5.14, fp64 oracle tests/fullwave_oracle.py.
+//
+// p lives at voxel centres, v_a on the + face along axis a, stored at the voxel's index (C order, z fastest); any field read outside
+// the grid is 0.  State (p^n, v^(n - 1/2)), fp32.  Step n, one launch each, in place:
+//   inject    p[vox_s] += amp_s env(u) sin(2 pi f0 u), u = (n - 1/2) dt - tau_s, for the entries with 0 <= u < T (decided, and the phase
+//             reduced, in fp64); ONE thread per distinct source voxel walks its entries in table order (CSR): no atomics, no race
+//   velocity  v_a <- D (v_a - b_a d+_a p),  d+ p[i] = 9/8 (p[i+1] - p[i]) - 1/24 (p[i+2] - p[i-1]),  b_a = dt / (rho_face h_a)
+//             (each lane reads p around it and reads / writes only its own v: in place)
+//   pressure  p~ <- g (p - kp sum_a d-_a v_a / h_a),  d- v[i] = 9/8 (v[i] - v[i-1]) - 1/24 (v[i+1] - v[i-2]),  kp = dt rho c^2, g = D ga,
+//             ga = exp(-2 alpha c dt); then p_max = max(p_max, p~), p_min = max(p_min, -p~) and, opt-in, sum += p~^2 (one fmaf)
+//             (each lane reads v around it and reads / writes only its own p: in place)
+//   trace     opt-in: p~ at the trace voxels into row n
+// D = d_x[i] d_y[j] d_z[k] from three 1-D tables (1 in the interior, the absorbing layers' decay per step outside it).
+// A heterogeneous medium streams five coefficient volumes formed once by fullwave_pack_k (b_x, b_y, b_z for the velocity launch, kp, ga
+// for the pressure launch); the uniform instantiation (UNI) streams none of them.
+#include "k_types.hip.h"
+#include "olx_ctx.h"
+#include "olx_launch.h"
+
+namespace olx {
+
+constexpr int FW_BLOCK = 256;
+constexpr float FW_C1 = 9.0f / 8.0f, FW_C2 = 1.0f / 24.0f;
+
+// (i, j, k) of linear voxel v (vox < 2^31: two 32-bit divisions)
+__device__ __forceinline__ void fw_ijk(unsigned v, const FullwaveParams& P, int& i, int& j, int& k) {
+    const unsigned row = v / (unsigned)P.nz;
+    k = (int)(v - row * (unsigned)P.nz);
+    i = (int)(row / (unsigned)P.ny);
+    j = (int)(row - (unsigned)i * (unsigned)P.ny);
+}
+
+// a[u], u inside the volume by the caller's index test (checked against the extent in the debug library); 0 when the test fails
+__device__ __forceinline__ float fw_ld(const float* __restrict__ a, bool inside, long long u, long long vox, int site) {
+    return (inside && OLX_IN(u, vox, site)) ? a[u] : 0.f;
+}
+
+__device__ __forceinline__ float fw_layer(const float* __restrict__ dtab, const FullwaveParams& P, int i, int j, int k) {
+    const int n = P.nx + P.ny + P.nz;
+    float d = 1.f;
+    if (OLX_IN(i, n, 20) && OLX_IN(P.nx + j, n, 20) && OLX_IN(P.nx + P.ny + k, n, 20)) d = (dtab[i] * dtab[P.nx + j]) * dtab[P.nx + P.ny + k];
+    return d;
+}
+
+// coefficient volumes of a heterogeneous medium (NULL volume = the scalar of FullwaveParams): b_a = dt / (rho_face h_a) with rho_face the
+// mean of the two voxels' rho (the voxel's own on the high boundary), kp = dt rho c^2, ga = exp(-2 alpha c dt)
+__global__ __launch_bounds__(FW_BLOCK) void fullwave_pack_k(const float* __restrict__ cs, const float* __restrict__ rho, const float* __restrict__ alpha,
+                                                            const FullwaveParams P, float* __restrict__ bx, float* __restrict__ by,
+                                                            float* __restrict__ bz, float* __restrict__ kp, float* __restrict__ ga) {
+    const long long v = (long long)blockIdx.x * FW_BLOCK + threadIdx.x;
+    if (v >= P.vox) return;
+    int i, j, k;
+    fw_ijk((unsigned)v, P, i, j, k);
+    const long long pl = (long long)P.ny * P.nz;
+    auto rv = [&](bool inside, long long u, float own) { return rho ? (inside && OLX_IN(u, P.vox, 0) ? rho[u] : own) : P.rho0; };
+    if (!OLX_IN(v, P.vox, 1)) return;
+    const float r = rho ? rho[v] : P.rho0, c = cs ? cs[v] : P.c0, a = alpha ? alpha[v] : P.alpha0;
+    bx[v] = P.dthx / (0.5f * (r + rv(i + 1 < P.nx, v + pl, r)));
+    by[v] = P.dthy / (0.5f * (r + rv(j + 1 < P.ny, v + P.nz, r)));
+    bz[v] = P.dthz / (0.5f * (r + rv(k + 1 < P.nz, v + 1, r)));
+    kp[v] = P.dt * r * c * c;
+    ga[v] = expf(-2.0f * a * c * P.dt);
+}
+
+// the sources of step n: row r of the CSR table is one voxel, its entries add in table order
+__global__ void fullwave_inject_k(float* __restrict__ p, const long long* __restrict__ svox, const int* __restrict__ srow, const double* __restrict__ samp,
+                                  const double* __restrict__ stau, const FullwaveSource S, int n_entries, long long vox, int step) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= S.n_vox || !OLX_IN(r + 1, S.n_vox + 1, 2)) return;
+    const long long at = svox[r];
+    if (!OLX_IN(at, vox, 3)) return;
+    float acc = p[at];
+    bool any = false;
+    for (int e = srow[r]; e < srow[r + 1]; ++e) {
+        if (!OLX_IN(e, n_entries, 4)) break;
+        const double u = ((double)step - 0.5) * S.dt - stau[e];
+        if (!(u >= 0.0 && u < S.T)) continue;
+        double ph = S.freq * u;
+        ph -= floor(ph);
+        double env = 1.0;
+        if (S.Tr > 0.0) {
+            if (u < S.Tr) env *= 0.5 * (1.0 - cos(M_PI * u / S.Tr));
+            if (S.T - u < S.Tr) env *= 0.5 * (1.0 - cos(M_PI * (S.T - u) / S.Tr));
+        }
+        acc += (float)(samp[e] * env * sin(2.0 * M_PI * ph));
+        any = true;
+    }
+    if (any) p[at] = acc;
+}
+
+template <bool UNI>
+__global__ __launch_bounds__(FW_BLOCK) void fullwave_vel_k(const float* __restrict__ p, float* __restrict__ vx, float* __restrict__ vy, float* __restrict__ vz,
+                                                           const float* __restrict__ bx, const float* __restrict__ by, const float* __restrict__ bz,
+                                                           const float* __restrict__ dtab, const FullwaveParams P) {
+    const long long v = (long long)blockIdx.x * FW_BLOCK + threadIdx.x;
+    if (v >= P.vox || !OLX_IN(v, P.vox, 5)) return;
+    int i, j, k;
+    fw_ijk((unsigned)v, P, i, j, k);
+    const long long pl = (long long)P.ny * P.nz, nz = P.nz;
+    const float D = fw_layer(dtab, P, i, j, k);
+    const float pc = p[v];
+    const float dpx = FW_C1 * (fw_ld(p, i + 1 < P.nx, v + pl, P.vox, 6) - pc) - FW_C2 * (fw_ld(p, i + 2 < P.nx, v + 2 * pl, P.vox, 6) - fw_ld(p, i > 0, v - pl, P.vox, 6));
+    const float dpy = FW_C1 * (fw_ld(p, j + 1 < P.ny, v + nz, P.vox, 7) - pc) - FW_C2 * (fw_ld(p, j + 2 < P.ny, v + 2 * nz, P.vox, 7) - fw_ld(p, j > 0, v - nz, P.vox, 7));
+    const float dpz = FW_C1 * (fw_ld(p, k + 1 < P.nz, v + 1, P.vox, 8) - pc) - FW_C2 * (fw_ld(p, k + 2 < P.nz, v + 2, P.vox, 8) - fw_ld(p, k > 0, v - 1, P.vox, 8));
+    const float cbx = UNI ? P.bx0 : bx[v], cby = UNI ? P.by0 : by[v], cbz = UNI ? P.bz0 : bz[v];
+    vx[v] = D * (vx[v] - cbx * dpx);
+    vy[v] = D * (vy[v] - cby * dpy);
+    vz[v] = D * (vz[v] - cbz * dpz);
+}
+
+template <bool UNI, bool PII>
+__global__ __launch_bounds__(FW_BLOCK) void fullwave_pres_k(float* __restrict__ p, const float* __restrict__ vx, const float* __restrict__ vy,
+                                                            const float* __restrict__ vz, const float* __restrict__ kp, const float* __restrict__ ga,
+                                                            const float* __restrict__ dtab, float* __restrict__ pmax, float* __restrict__ pmin,
+                                                            float* __restrict__ psq, const FullwaveParams P) {
+    const long long v = (long long)blockIdx.x * FW_BLOCK + threadIdx.x;
+    if (v >= P.vox || !OLX_IN(v, P.vox, 9)) return;
+    int i, j, k;
+    fw_ijk((unsigned)v, P, i, j, k);
+    const long long pl = (long long)P.ny * P.nz, nz = P.nz;
+    const float D = fw_layer(dtab, P, i, j, k);
+    const float dvx = FW_C1 * (vx[v] - fw_ld(vx, i > 0, v - pl, P.vox, 10)) - FW_C2 * (fw_ld(vx, i + 1 < P.nx, v + pl, P.vox, 10) - fw_ld(vx, i > 1, v - 2 * pl, P.vox, 10));
+    const float dvy = FW_C1 * (vy[v] - fw_ld(vy, j > 0, v - nz, P.vox, 11)) - FW_C2 * (fw_ld(vy, j + 1 < P.ny, v + nz, P.vox, 11) - fw_ld(vy, j > 1, v - 2 * nz, P.vox, 11));
+    const float dvz = FW_C1 * (vz[v] - fw_ld(vz, k > 0, v - 1, P.vox, 12)) - FW_C2 * (fw_ld(vz, k + 1 < P.nz, v + 1, P.vox, 12) - fw_ld(vz, k > 1, v - 2, P.vox, 12));
+    const float div = dvx * P.ihx + dvy * P.ihy + dvz * P.ihz;
+    const float ckp = UNI ? P.kp0 : kp[v], g = D * (UNI ? P.ga0 : ga[v]);
+    const float pn = g * (p[v] - ckp * div);
+    p[v] = pn;
+    pmax[v] = fmaxf(pmax[v], pn);
+    pmin[v] = fmaxf(pmin[v], -pn);
+    if (PII) psq[v] = fmaf(pn, pn, psq[v]);
+}
+
+// row n of the traces: p~ of step n at the trace voxels
+__global__ void fullwave_trace_k(const float* __restrict__ p, const long long* __restrict__ pts, int npts, long long vox, float* __restrict__ row) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < npts && OLX_IN(pts[q], vox, 13)) row[q] = p[pts[q]];
+}
+
+OLX_BOUNDS_READER(fullwave)
+
+}  // namespace olx
+
+using namespace olx;
+
+static inline dim3 fw_grid(const FullwaveParams& P) { return dim3((unsigned)((P.vox + FW_BLOCK - 1) / FW_BLOCK)); }
+
+void olx_fullwave_pack(olx_ctx* c, const float* cs, const float* rho, const float* alpha) {
+    const FullwaveParams& P = c->fw;
+    hipLaunchKernelGGL(fullwave_pack_k, fw_grid(P), dim3(FW_BLOCK), 0, c->stream, cs, rho, alpha, P, c->d_fw_coef[0], c->d_fw_coef[1], c->d_fw_coef[2],
+                       c->d_fw_coef[3], c->d_fw_coef[4]);
+}
+
+void olx_fullwave_step(olx_ctx* c, int step, bool pii) {
+    const FullwaveParams& P = c->fw;
+    const FullwaveSource& S = c->fw_src;
+    float* p = c->d_fw_p;
+    if (S.n_vox > 0)
+        hipLaunchKernelGGL(fullwave_inject_k, dim3((S.n_vox + 63) / 64), dim3(64), 0, c->stream, p, c->d_fw_svox, c->d_fw_srow, c->d_fw_samp, c->d_fw_stau, S,
+                           c->fw_entries, P.vox, step);
+    const dim3 grid = fw_grid(P), block(FW_BLOCK);
+    float *vx = c->d_fw_v[0], *vy = c->d_fw_v[1], *vz = c->d_fw_v[2], *pmax = c->d_fw_pmax, *pmin = c->d_fw_pmin, *psq = c->d_fw_psq;
+    const float* dtab = c->d_fw_dtab;
+    if (c->fw_uniform) {
+        hipLaunchKernelGGL(fullwave_vel_k<true>, grid, block, 0, c->stream, p, vx, vy, vz, nullptr, nullptr, nullptr, dtab, P);
+        if (pii) hipLaunchKernelGGL((fullwave_pres_k<true, true>), grid, block, 0, c->stream, p, vx, vy, vz, nullptr, nullptr, dtab, pmax, pmin, psq, P);
+        else hipLaunchKernelGGL((fullwave_pres_k<true, false>), grid, block, 0, c->stream, p, vx, vy, vz, nullptr, nullptr, dtab, pmax, pmin, nullptr, P);
+    } else {
+        const float *bx = c->d_fw_coef[0], *by = c->d_fw_coef[1], *bz = c->d_fw_coef[2], *kp = c->d_fw_coef[3], *ga = c->d_fw_coef[4];
+        hipLaunchKernelGGL(fullwave_vel_k<false>, grid, block, 0, c->stream, p, vx, vy, vz, bx, by, bz, dtab, P);
+        if (pii) hipLaunchKernelGGL((fullwave_pres_k<false, true>), grid, block, 0, c->stream, p, vx, vy, vz, kp, ga, dtab, pmax, pmin, psq, P);
+        else hipLaunchKernelGGL((fullwave_pres_k<false, false>), grid, block, 0, c->stream, p, vx, vy, vz, kp, ga, dtab, pmax, pmin, nullptr, P);
+    }
+    if (c->fw_npts > 0)
+        hipLaunchKernelGGL(fullwave_trace_k, dim3((c->fw_npts + 255) / 256), dim3(256), 0, c->stream, p, c->d_fw_pts, c->fw_npts, P.vox,
+                           c->d_fw_trace + (size_t)step * c->fw_npts);
+}

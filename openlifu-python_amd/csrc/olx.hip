@@ -82,13 +82,13 @@ int olx_ctx_destroy(olx_ctx* c) {
 const char* olx_last_error(const olx_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 #ifdef OLX_DEBUG_BOUNDS   // debug build (k_types.hip.h): the kernels' index checks report here
-extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); int olx_dbg_bounds_bfmed(unsigned*); int olx_dbg_bounds_small(unsigned*); int olx_dbg_bounds_steer(unsigned*); int olx_dbg_bounds_steermed(unsigned*); int olx_dbg_bounds_pulsemed(unsigned*); }
+extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); int olx_dbg_bounds_bfmed(unsigned*); int olx_dbg_bounds_small(unsigned*); int olx_dbg_bounds_steer(unsigned*); int olx_dbg_bounds_steermed(unsigned*); int olx_dbg_bounds_pulsemed(unsigned*); int olx_dbg_bounds_fullwave(unsigned*); }
 static int report_bounds(olx_ctx* c) {
     struct { const char* name; int (*read)(unsigned*); } units[] = {{"2g (k_coset2.hip)", olx_dbg_bounds_cosetp}, {"2e (k_coset.hip)", olx_dbg_bounds_coset},
                                                                      {"2f (k_toep.hip)", olx_dbg_bounds_toep}, {"2m (k_hmarch.hip)", olx_dbg_bounds_hmarch},
                                                                      {"2p (k_pulse.hip)", olx_dbg_bounds_pulse}, {"3 (k_thermal.hip)", olx_dbg_bounds_thermal},
                                                                      {"1m / 1a (k_bfmed.hip)", olx_dbg_bounds_bfmed}, {"pii_post_k (k_small.hip.h)", olx_dbg_bounds_small}, {"4 (k_steer.hip)", olx_dbg_bounds_steer},
-                                                                     {"4h (k_steer_med.hip)", olx_dbg_bounds_steermed}, {"2ph (k_pulse_med.hip)", olx_dbg_bounds_pulsemed}};
+                                                                     {"4h (k_steer_med.hip)", olx_dbg_bounds_steermed}, {"2ph (k_pulse_med.hip)", olx_dbg_bounds_pulsemed}, {"5 (k_fullwave.hip)", olx_dbg_bounds_fullwave}};
     int rc = OLX_OK;
     for (auto& u : units) {
         unsigned w[4] = {0, 0, 0, 0};
@@ -3064,6 +3064,187 @@ int olx_thermal_fetch(olx_ctx* c, float* rise_max, float* cem43, float* traces) 
     if (rise_max) rc = fetch_to_host(c, rise_max, c->d_th_max, sizeof(float) * vox);
     if (!rc && cem43) rc = fetch_to_host(c, cem43, c->d_th_cem, sizeof(float) * vox);
     if (!rc && traces && c->th_npts > 0) rc = fetch_to_host(c, traces, c->d_th_trace, sizeof(float) * (size_t)c->th_next * c->th_npts);
+    return rc;
+}
+
+}  // extern "C"
+
+// ---- full-wave model (kernel 5, k_fullwave.hip) ------------------------------------------------------------------------------------
+extern "C" {
+
+int olx_fullwave_plan(olx_ctx* c, const olx_grid* g, const float* sound_speed, const float* density, const float* absorption, double sound_speed0,
+                      double density0, double absorption0, double c_ref, int pml_size, double pml_alpha, double dt, double* dt_max_out) {
+    if (!c) return OLX_EINVAL;
+    if (!g) return fail(c, OLX_EINVAL, "olx_fullwave_plan: null grid");
+    double ih2 = 0;
+    for (int a = 0; a < 3; ++a) {
+        if (g->n[a] < 1 || !(g->spacing[a] > 0) || !std::isfinite(g->spacing[a])) return fail(c, OLX_EINVAL, "olx_fullwave_plan: bad grid axis %d", a);
+        ih2 += 1.0 / (g->spacing[a] * g->spacing[a]);
+    }
+    const long long voxll = (long long)g->n[0] * g->n[1] * g->n[2];
+    if (voxll >= (1ll << 31)) return fail(c, OLX_EINVAL, "olx_fullwave_plan: grid of %lld voxels is too large (< 2^31)", voxll);
+    if (pml_size < 0 || !(pml_alpha >= 0) || !std::isfinite(pml_alpha)) return fail(c, OLX_EINVAL, "olx_fullwave_plan: pml_size must be >= 0, pml_alpha finite and >= 0");
+    for (int a = 0; a < 3; ++a)
+        if (2 * pml_size >= g->n[a]) return fail(c, OLX_EINVAL, "olx_fullwave_plan: axis %d of %d voxels holds no interior between two layers of %d", a, g->n[a], pml_size);
+    if (!(c_ref > 0) || !std::isfinite(c_ref)) return fail(c, OLX_EINVAL, "olx_fullwave_plan: c_ref must be finite and > 0");
+    if ((!sound_speed && !(sound_speed0 > 0 && std::isfinite(sound_speed0))) || (!density && !(density0 > 0 && std::isfinite(density0))) ||
+        (!absorption && !(absorption0 >= 0 && std::isfinite(absorption0))))
+        return fail(c, OLX_EINVAL, "olx_fullwave_plan: the scalars of NULL volumes must be finite and > 0 (absorption >= 0)");
+    if (!(dt > 0) || !std::isfinite(dt)) return fail(c, OLX_EINVAL, "olx_fullwave_plan: dt must be finite and > 0");
+    const size_t vox = (size_t)voxll;
+    double c_max = sound_speed ? 0.0 : sound_speed0;
+    for (size_t o = 0; o < vox; ++o) {
+        if (sound_speed) {
+            if (!(sound_speed[o] > 0.f) || !std::isfinite(sound_speed[o])) return fail(c, OLX_EINVAL, "olx_fullwave_plan: sound speed must be finite and > 0");
+            c_max = std::max(c_max, (double)sound_speed[o]);
+        }
+        if (density && (!(density[o] > 0.f) || !std::isfinite(density[o]))) return fail(c, OLX_EINVAL, "olx_fullwave_plan: density must be finite and > 0");
+        if (absorption && (!(absorption[o] >= 0.f) || !std::isfinite(absorption[o]))) return fail(c, OLX_EINVAL, "olx_fullwave_plan: absorption must be finite and >= 0");
+    }
+    const double dt_max = 6.0 / (7.0 * c_max * std::sqrt(ih2));
+    if (dt_max_out) *dt_max_out = dt_max;
+    if (dt > dt_max * (1.0 + 1e-6)) return fail(c, OLX_EINVAL, "olx_fullwave_plan: dt = %g s is above the stability bound %g s", dt, dt_max);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->fw_planned = false; c->fw_sourced = false; c->fw_next = -1;
+    FullwaveParams& P = c->fw;
+    P = FullwaveParams{};
+    P.nx = g->n[0]; P.ny = g->n[1]; P.nz = g->n[2]; P.vox = voxll;
+    P.ihx = (float)(1.0 / g->spacing[0]); P.ihy = (float)(1.0 / g->spacing[1]); P.ihz = (float)(1.0 / g->spacing[2]);
+    P.dthx = (float)(dt / g->spacing[0]); P.dthy = (float)(dt / g->spacing[1]); P.dthz = (float)(dt / g->spacing[2]);
+    P.dt = (float)dt;
+    P.c0 = (float)sound_speed0; P.rho0 = (float)density0; P.alpha0 = (float)absorption0;
+    c->fw_uniform = !sound_speed && !density && !absorption;
+    c->fw_dt = dt; c->fw_dt_max = dt_max;
+    for (DevBuf<float>* b : {&c->d_fw_p, &c->d_fw_v[0], &c->d_fw_v[1], &c->d_fw_v[2], &c->d_fw_pmax, &c->d_fw_pmin}) { int rc = b->reserve(c, vox); if (rc) return rc; }
+    // the layers' decay per step: d_a[i] = exp(-pml_alpha (c_ref / h_a) (depth / pml_size)^4 dt), depth = voxels into the layer (0 inside)
+    const int ntab = P.nx + P.ny + P.nz;
+    std::vector<float> tab(ntab);
+    for (int a = 0, at = 0; a < 3; at += g->n[a], ++a)
+        for (int i = 0; i < g->n[a]; ++i) {
+            const int depth = i < pml_size ? pml_size - i : i >= g->n[a] - pml_size ? i - (g->n[a] - pml_size) + 1 : 0;
+            const double x = pml_size > 0 ? (double)depth / pml_size : 0.0;
+            tab[at + i] = (float)std::exp(-pml_alpha * (c_ref / g->spacing[a]) * x * x * x * x * dt);
+        }
+    { int rc = c->d_fw_dtab.reserve(c, ntab); if (rc) return rc; }
+    HIPCHK(c, hipMemcpy(c->d_fw_dtab, tab.data(), sizeof(float) * ntab, hipMemcpyHostToDevice));
+    if (c->fw_uniform) {
+        P.bx0 = (float)(dt / (density0 * g->spacing[0])); P.by0 = (float)(dt / (density0 * g->spacing[1])); P.bz0 = (float)(dt / (density0 * g->spacing[2]));
+        P.kp0 = (float)(dt * density0 * sound_speed0 * sound_speed0);
+        P.ga0 = (float)std::exp(-2.0 * absorption0 * sound_speed0 * dt);
+    } else {
+        // the volumes go up once, the pack kernel forms the coefficients, the volumes are freed again
+        DevScratch scr;
+        const float* src[3] = {sound_speed, density, absorption};
+        size_t nvol = 0;
+        for (const float* p : src) nvol += p ? 1 : 0;
+        HIPCHK(c, hipMalloc(&scr.p, sizeof(float) * vox * std::max(nvol, (size_t)1)));
+        const float* dv[3] = {nullptr, nullptr, nullptr};
+        size_t at = 0;
+        for (int q = 0; q < 3; ++q) {
+            if (!src[q]) continue;
+            float* d = scr.at<float>(sizeof(float) * vox * at++);
+            HIPCHK(c, hipMemcpy(d, src[q], sizeof(float) * vox, hipMemcpyHostToDevice));
+            dv[q] = d;
+        }
+        for (DevBuf<float>& b : c->d_fw_coef) { int rc = b.reserve(c, vox); if (rc) return rc; }
+        olx_fullwave_pack(c, dv[0], dv[1], dv[2]);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    c->fw_planned = true;
+    c->fw_steps = 0; c->fw_npts = 0; c->fw_entries = 0;
+    return OLX_OK;
+}
+
+int olx_fullwave_sources(olx_ctx* c, int n_entries, const long long* voxels, const double* amplitude, const double* tau_s, double freq, double cycles,
+                         double ramp_cycles, int n_steps, int n_points, const long long* points) {
+    if (!c) return OLX_EINVAL;
+    if (!c->fw_planned) return fail(c, OLX_ESTATE, "olx_fullwave_sources: no full-wave plan");
+    if (n_entries < 0 || (n_entries > 0 && (!voxels || !amplitude || !tau_s))) return fail(c, OLX_EINVAL, "olx_fullwave_sources: n_entries < 0 or null table");
+    if (!(freq > 0) || !std::isfinite(freq) || !(cycles > 0) || !std::isfinite(cycles) || !(ramp_cycles >= 0) || !std::isfinite(ramp_cycles))
+        return fail(c, OLX_EINVAL, "olx_fullwave_sources: freq and cycles must be finite and > 0, ramp_cycles finite and >= 0");
+    if (n_steps < 1 || n_points < 0 || (n_points > 0 && !points)) return fail(c, OLX_EINVAL, "olx_fullwave_sources: n_steps < 1 or bad points");
+    for (int e = 0; e < n_entries; ++e) {
+        if (voxels[e] < 0 || voxels[e] >= c->fw.vox) return fail(c, OLX_EINVAL, "olx_fullwave_sources: entry %d: voxel %lld outside the grid of %lld voxels", e, voxels[e], c->fw.vox);
+        if (!std::isfinite(amplitude[e]) || !std::isfinite(tau_s[e])) return fail(c, OLX_EINVAL, "olx_fullwave_sources: entry %d: amplitude and delay must be finite", e);
+    }
+    for (int p = 0; p < n_points; ++p)
+        if (points[p] < 0 || points[p] >= c->fw.vox) return fail(c, OLX_EINVAL, "olx_fullwave_sources: trace point %d outside the grid", p);
+    if ((double)n_steps * n_points > 268435456.0) return fail(c, OLX_EINVAL, "olx_fullwave_sources: %g trace samples are too many (trace fewer points)", (double)n_steps * n_points);
+    // CSR by voxel: a stable sort keeps the entries of one voxel in table order
+    std::vector<int> order(n_entries);
+    for (int e = 0; e < n_entries; ++e) order[e] = e;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return voxels[a] < voxels[b]; });
+    std::vector<long long> svox; std::vector<int> srow; std::vector<double> samp(n_entries), stau(n_entries);
+    for (int q = 0; q < n_entries; ++q) {
+        const int e = order[q];
+        if (q == 0 || voxels[e] != svox.back()) { svox.push_back(voxels[e]); srow.push_back(q); }
+        samp[q] = amplitude[e]; stau[q] = tau_s[e];
+    }
+    srow.push_back(n_entries);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->fw_sourced = false; c->fw_next = -1;
+    int rc = c->d_fw_svox.reserve(c, svox.size());
+    if (!rc) rc = c->d_fw_srow.reserve(c, srow.size());
+    if (!rc) rc = c->d_fw_samp.reserve(c, n_entries);
+    if (!rc) rc = c->d_fw_stau.reserve(c, n_entries);
+    if (!rc) rc = c->d_fw_pts.reserve(c, n_points);
+    if (!rc) rc = c->d_fw_trace.reserve(c, (size_t)n_steps * n_points);
+    if (rc) return rc;
+    if (n_entries > 0) {
+        HIPCHK(c, hipMemcpy(c->d_fw_svox, svox.data(), sizeof(long long) * svox.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_fw_samp, samp.data(), sizeof(double) * n_entries, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_fw_stau, stau.data(), sizeof(double) * n_entries, hipMemcpyHostToDevice));
+    }
+    HIPCHK(c, hipMemcpy(c->d_fw_srow, srow.data(), sizeof(int) * srow.size(), hipMemcpyHostToDevice));
+    if (n_points > 0) HIPCHK(c, hipMemcpy(c->d_fw_pts, points, sizeof(long long) * n_points, hipMemcpyHostToDevice));
+    FullwaveSource& S = c->fw_src;
+    S = FullwaveSource{};
+    S.freq = freq; S.T = cycles / freq; S.Tr = ramp_cycles / freq; S.dt = c->fw_dt; S.n_vox = (int)svox.size();
+    c->fw_entries = n_entries; c->fw_steps = n_steps; c->fw_npts = n_points;
+    c->fw_sourced = true;
+    return OLX_OK;
+}
+
+int olx_fullwave_run(olx_ctx* c, int first_step, int n_steps, int accumulate_psq) {
+    if (!c) return OLX_EINVAL;
+    if (!c->fw_planned || !c->fw_sourced) return fail(c, OLX_ESTATE, "olx_fullwave_run: needs olx_fullwave_plan and olx_fullwave_sources first");
+    if (n_steps < 0 || first_step < 0 || first_step + n_steps > c->fw_steps) return fail(c, OLX_EINVAL, "olx_fullwave_run: steps [%d, %d) outside the run of %d", first_step, first_step + n_steps, c->fw_steps);
+    if (first_step > 0 && first_step != c->fw_next) return fail(c, OLX_ESTATE, "olx_fullwave_run: step %d does not continue the last run (next step %d)", first_step, c->fw_next);
+    const bool pii = accumulate_psq != 0;
+    if (first_step > 0 && pii != c->fw_pii) return fail(c, OLX_ESTATE, "olx_fullwave_run: a continued run keeps the accumulation of sum p^2 as the run began it");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t vox = (size_t)c->fw.vox;
+    if (first_step == 0) {
+        if (pii) { int rc = c->d_fw_psq.reserve(c, vox); if (rc) return rc; }
+        for (float* p : {(float*)c->d_fw_p, (float*)c->d_fw_v[0], (float*)c->d_fw_v[1], (float*)c->d_fw_v[2], (float*)c->d_fw_pmax, (float*)c->d_fw_pmin})
+            HIPCHK(c, hipMemsetAsync(p, 0, sizeof(float) * vox, c->stream));
+        if (pii) HIPCHK(c, hipMemsetAsync(c->d_fw_psq, 0, sizeof(float) * vox, c->stream));
+        c->fw_pii = pii;
+    }
+    for (int n = first_step; n < first_step + n_steps; ++n) olx_fullwave_step(c, n, pii);
+    HIPCHK(c, hipGetLastError());
+    c->fw_next = first_step + n_steps;
+    return OLX_OK;
+}
+
+int olx_fullwave_fetch(olx_ctx* c, float* p_max, float* p_min, float* p_sq, float* traces) {
+    if (!c) return OLX_EINVAL;
+    if (!c->fw_planned || c->fw_next < 0) return fail(c, OLX_ESTATE, "olx_fullwave_fetch: nothing run");
+    if (p_sq && !c->fw_pii) return fail(c, OLX_ESTATE, "olx_fullwave_fetch: the run did not accumulate sum p^2");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+#ifdef OLX_DEBUG_BOUNDS
+    { int rc_ = report_bounds(c); if (rc_) return rc_; }
+#endif
+    const size_t vox = (size_t)c->fw.vox;
+    int rc = OLX_OK;
+    if (p_max) rc = fetch_to_host(c, p_max, c->d_fw_pmax, sizeof(float) * vox);
+    if (!rc && p_min) rc = fetch_to_host(c, p_min, c->d_fw_pmin, sizeof(float) * vox);
+    if (!rc && p_sq) rc = fetch_to_host(c, p_sq, c->d_fw_psq, sizeof(float) * vox);
+    if (!rc && traces && c->fw_npts > 0 && c->fw_next > 0) rc = fetch_to_host(c, traces, c->d_fw_trace, sizeof(float) * (size_t)c->fw_next * c->fw_npts);
     return rc;
 }
 

@@ -178,6 +178,15 @@ struct olx_ctx {
     int th_src_foci = 0; bool th_src_resident = false; DevBuf<float> d_th_I;
     bool th_src_pii = false;                   // with th_src_resident: the resident PII volumes (olx_thermal_source_pii), not the intensity
     int th_next = -1;                          // the step the next olx_thermal_run continues with (-1: nothing run since the last plan / schedule)
+    // full-wave model (kernel 5, olx_fullwave_*): buffers of their own, apart from the plan, the resident result and the thermal buffers
+    bool fw_planned = false, fw_uniform = false; FullwaveParams fw{}; double fw_dt = 0, fw_dt_max = 0;
+    DevBuf<float> d_fw_p, d_fw_v[3], d_fw_pmax, d_fw_pmin, d_fw_psq;   // [voxels] state p, v_x / v_y / v_z; p_max, p_min; sum p~^2 (created by the first run that asks for it)
+    DevBuf<float> d_fw_coef[5];               // [voxels] b_x, b_y, b_z, kp, ga of a heterogeneous medium (not created for a uniform one)
+    DevBuf<float> d_fw_dtab;                  // [nx + ny + nz] the layers' per-step decay d_x | d_y | d_z
+    bool fw_sourced = false; FullwaveSource fw_src{}; int fw_entries = 0, fw_steps = 0;
+    DevBuf<long long> d_fw_svox; DevBuf<int> d_fw_srow; DevBuf<double> d_fw_samp, d_fw_stau;   // CSR source table: voxel per row, row offsets, entries in table order
+    int fw_npts = 0; DevBuf<long long> d_fw_pts; DevBuf<float> d_fw_trace;   // trace voxels, [fw_steps][fw_npts] samples
+    int fw_next = -1; bool fw_pii = false;    // the step the next olx_fullwave_run continues with (-1: nothing run since the last plan / sources); the run accumulates sum p~^2
     // steering map (kernel 4, olx_steer_map): result volumes and element records of their own -- they never alias the field, aggregate or PII buffers
     DevBuf<float> d_sm_p; DevBuf<int> d_sm_n;          // [voxels] focal pressure [Pa], active elements; created by the first call, reused by later ones
     DevBuf<double> d_sm_tabd; DevBuf<float> d_sm_tabf; // [N * STEER_TD], [N * STEER_TF] element records (olx_params.h)

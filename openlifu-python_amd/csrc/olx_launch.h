@@ -30,3 +30,5 @@ void olx_launch_steer_map_medium(olx_ctx* c, const SteerMedParams& M, int kind, 
 void olx_thermal_pack(olx_ctx* c, const float* rho, const float* cp, const float* kap, const float* alpha);   // 3  thermal_pack_k (coefficients, FTCS rate)
 void olx_thermal_step(olx_ctx* c, const float* inten, int step, const ThermalStep& S);                        // 3  thermal_step_k (one step)
 void olx_thermal_trace_last(olx_ctx* c, int step);                                                          //    thermal_trace_k (last trace row)
+void olx_fullwave_pack(olx_ctx* c, const float* cs, const float* rho, const float* alpha);   // 5  fullwave_pack_k (coefficient volumes of a heterogeneous medium)
+void olx_fullwave_step(olx_ctx* c, int step, bool pii);                                      // 5  fullwave_inject_k, fullwave_vel_k, fullwave_pres_k, fullwave_trace_k (one step)

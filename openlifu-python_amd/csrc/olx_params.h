@@ -187,6 +187,23 @@ struct ThermalStep {
     int npts, n_foci;                // trace points; foci of the source volumes
 };
 
+// kernel 5 (fullwave_*_k, k_fullwave.hip): linear acoustics on a staggered grid, 2nd order in time / 4th in space (olx_fullwave_*)
+struct FullwaveParams {
+    int nx, ny, nz;                  // the padded grid (absorbing layers included)
+    long long vox;
+    float ihx, ihy, ihz;             // 1 / h per axis [1/m]
+    float dthx, dthy, dthz;          // dt / h per axis [s/m]
+    float dt;                        // [s]
+    float c0, rho0, alpha0;          // the scalars of the volumes passed as NULL (alpha in Np/m)
+    float bx0, by0, bz0;             // uniform medium: dt / (rho h) per axis
+    float kp0, ga0;                  // uniform medium: dt rho c^2, exp(-2 alpha c dt)
+};
+struct FullwaveSource {
+    double freq, T, Tr;              // f0 [Hz], burst length cycles / f0 [s], ramp length ramp_cycles / f0 [s] (0: rectangular)
+    double dt;                       // [s]
+    int n_vox;                       // distinct source voxels (CSR rows)
+};
+
 // kernel 1m (bf_med_k, k_bfmed.hip): straight-ray delays through the medium of olx_bf_set_medium (DESIGN.md section 2 "StraightRay")
 struct BfMedParams {
     double ox, oy, oz, hx, hy, hz;  // grid origin and spacing [m]

@@ -45,6 +45,7 @@ SYMBOLS = [
     "olx_field_pulse", "olx_field_fetch_pmax", "olx_aggregate_fetch_pmax", "olx_field_fetch_pii", "olx_field_pulse_trace", "olx_field_pulse_medium",
     "olx_pii_post", "olx_pii_fetch_weighted", "olx_pii_fetch_max", "olx_pii_upload", "olx_thermal_source_pii",
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
+    "olx_fullwave_plan", "olx_fullwave_sources", "olx_fullwave_run", "olx_fullwave_fetch",
     "olx_bf_set_medium", "olx_bf_solve_medium",
     "olx_bf_set_attenuation", "olx_bf_solve_compensated",
     "olx_steer_map", "olx_steer_time", "olx_steer_map_medium",
@@ -159,6 +160,11 @@ def load(require_gpu: bool = True):
         lib.olx_thermal_source.argtypes = [vp, c_int, fp]
         lib.olx_thermal_run.argtypes = [vp, c_double, c_double, c_int, c_int]
         lib.olx_thermal_fetch.argtypes = [vp, fp, fp, fp]
+        lib.olx_fullwave_plan.argtypes = [vp, POINTER(OlxGrid), fp, fp, fp, c_double, c_double, c_double, c_double, c_int, c_double, c_double, dp]
+        lib.olx_fullwave_sources.argtypes = [vp, c_int, POINTER(ctypes.c_longlong), dp, dp, c_double, c_double, c_double, c_int, c_int,
+                                             POINTER(ctypes.c_longlong)]
+        lib.olx_fullwave_run.argtypes = [vp, c_int, c_int, c_int]
+        lib.olx_fullwave_fetch.argtypes = [vp, fp, fp, fp, fp]
         lib.olx_set_element_apertures.argtypes = [vp, dp, dp]
         lib.olx_comm_export.argtypes = [vp, vp]
         lib.olx_comm_import.argtypes = [vp, vp]
@@ -714,6 +720,56 @@ class Context:
         tr = np.empty((self._th_ran, self._th_npts), dtype=np.float32)
         self._chk(self._lib.olx_thermal_fetch(self._h, _fptr(rise), _fptr(cem), _fptr(tr) if tr.size else None))
         return rise, cem, tr
+
+    # ---- full-wave model (kernel 5) ----------------------------------------------------------------------------------------
+    def fullwave_plan(self, spacing_m, n, sound_speed, density, absorption, c_ref, pml_size, pml_alpha, dt) -> float:
+        """Padded grid and medium of the full-wave model; each medium argument is a float (uniform) or a [nx, ny, nz] volume
+        (absorption in Np/m).  Returns the stability bound dt_max [s]."""
+        shape = tuple(int(v) for v in n)
+        g = OlxGrid()
+        for a in range(3):
+            g.origin[a] = 0.0; g.spacing[a] = float(spacing_m[a]); g.n[a] = shape[a]
+        vols, scal = [], []
+        for v in (sound_speed, density, absorption):
+            if np.ndim(v) == 0:
+                vols.append(None); scal.append(float(v))
+            else:
+                a = np.ascontiguousarray(v, dtype=np.float32)
+                if a.shape != shape:
+                    raise ValueError(f"full-wave medium volume must be {shape}, got {a.shape}")
+                vols.append(a); scal.append(0.0)
+        dt_max = c_double(0.0)
+        self._chk(self._lib.olx_fullwave_plan(self._h, ctypes.byref(g), *[_fptr(a) for a in vols], *scal, float(c_ref), int(pml_size),
+                                              float(pml_alpha), float(dt), ctypes.byref(dt_max)))
+        self._fw_shape = shape
+        return float(dt_max.value)
+
+    def fullwave_sources(self, voxels, amplitude, tau, freq, cycles, ramp_cycles, n_steps, points=None):
+        """Source table (linear voxel of the padded grid, amplitude, delay per entry) and trace voxels."""
+        vx = np.ascontiguousarray(voxels, dtype=np.int64)
+        am = np.ascontiguousarray(amplitude, dtype=np.float64)
+        ta = np.ascontiguousarray(tau, dtype=np.float64)
+        if not (vx.ndim == 1 and vx.shape == am.shape == ta.shape):
+            raise ValueError(f"voxels, amplitude and tau must be 1-D of one length, got {vx.shape}, {am.shape}, {ta.shape}")
+        pts = np.ascontiguousarray([] if points is None else points, dtype=np.int64)
+        lp = POINTER(ctypes.c_longlong)
+        self._chk(self._lib.olx_fullwave_sources(self._h, int(vx.size), vx.ctypes.data_as(lp), _dptr(am), _dptr(ta), float(freq), float(cycles),
+                                                 float(ramp_cycles), int(n_steps), int(pts.size), pts.ctypes.data_as(lp)))
+        self._fw_steps, self._fw_npts = int(n_steps), int(pts.size)
+
+    def fullwave_run(self, first_step: int = 0, n_steps=None, psq: bool = False):
+        n_steps = self._fw_steps - int(first_step) if n_steps is None else int(n_steps)
+        self._chk(self._lib.olx_fullwave_run(self._h, int(first_step), n_steps, int(bool(psq))))
+        self._fw_ran, self._fw_psq = int(first_step) + n_steps, bool(psq)
+
+    def fullwave_fetch(self):
+        """(p_max, p_min, sum p^2 | None, traces [steps run, points]) of the padded grid."""
+        pmax = np.empty(self._fw_shape, dtype=np.float32)
+        pmin = np.empty(self._fw_shape, dtype=np.float32)
+        psq = np.empty(self._fw_shape, dtype=np.float32) if self._fw_psq else None
+        tr = np.empty((self._fw_ran, self._fw_npts), dtype=np.float32)
+        self._chk(self._lib.olx_fullwave_fetch(self._h, _fptr(pmax), _fptr(pmin), _fptr(psq), _fptr(tr) if tr.size else None))
+        return pmax, pmin, psq, tr
 
     def field_scale_aggregate(self, scale_per_focus):
         """``field_scale`` + ``field_aggregate_device`` in one pass (identical values)."""

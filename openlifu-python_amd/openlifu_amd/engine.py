@@ -489,6 +489,18 @@ class Engine:
         self.ctx.thermal_run(dt, baseline)
         return self.ctx.thermal_fetch()
 
+    # ---- kernel 5 -----------------------------------------------------------------------------
+    def fullwave(self, spacing_m, n_padded, medium, c_ref, pml_size, pml_alpha, dt, n_steps, sources, freq, cycles, ramp_cycles=0.0,
+                 psq=False, points=None):
+        """Full-wave model (sim/fullwave.py, kernel 5) on the padded grid -> (p_max, p_min, sum p^2 | None, traces [n_steps, P]), float32.
+        ``medium = (sound_speed, density, absorption [Np/m])``, each a float or a padded [nx, ny, nz] volume; ``sources = (voxel, amplitude,
+        tau)`` per entry, voxels and ``points`` as linear indices of the padded grid.  The field / aggregate / thermal volumes and every lazy
+        array over them are left as they are."""
+        self.ctx.fullwave_plan(spacing_m, n_padded, *medium, c_ref=c_ref, pml_size=pml_size, pml_alpha=pml_alpha, dt=dt)
+        self.ctx.fullwave_sources(*sources, freq=freq, cycles=cycles, ramp_cycles=ramp_cycles, n_steps=n_steps, points=points)
+        self.ctx.fullwave_run(0, n_steps, psq=psq)
+        return self.ctx.fullwave_fetch()
+
     def upload_result(self, origin_m, spacing_m, n, pmag, intensity=None):
         """Bind host volumes [F,nx,ny,nz] as the resident result (analysis of a detached Solution)."""
         self.retire_results()
