@@ -233,14 +233,32 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
     };
     constexpr int CHUNK_U4 = PAIR * 4 * NT * B_KS_U4, PRE = CHUNK_U4 / THREADS;
     static_assert(CHUNK_U4 % THREADS == 0, "chunk must split evenly over the block");
+    constexpr int REC_U4 = 4 * NT * B_KS_U4;     // uint4 per super-block: 4 K-step records x NT column tiles
     uint4 pre[PRE];
-    const uint4* const bsrc = bfrag + (size_t)tile * n_sb * (4 * NT * B_KS_U4);
+    const uint4* const bsrc = bfrag + (size_t)tile * n_sb * REC_U4;
     // (the steering fragments do not depend on the item: all items of a launch tile read the same chunks)
+    // A request is one chunk = the PAIR super-blocks of a table pair, THREADS x PRE uint4.  n_sb is even and the launch tile holds n_sb whole
+    // super-blocks (the host refuses a plan where either fails: olx.hip), so a chunk lies inside the tile's records as a whole or not at all:
+    // ONE wave-uniform test per request (the caller's: a scalar compare and branch), no per-lane bounds test, select or zero fill; a lane's
+    // address is a scalar base per q (q x 8192 bytes is beyond a global_load immediate) + its 32-bit byte offset tid x 16 -- one vector
+    // instruction per request.  Per-lane tests and 64-bit per-lane addresses were 33 vector instructions per request, 25 of them executed
+    // even by the last pair that requests nothing.
+    auto request = [&](const int sb_first, const int tid_r) __attribute__((always_inline)) {
+        const unsigned lane_b = (unsigned)tid_r << 4;
 #pragma unroll
-    for (int q = 0; q < PRE; ++q) {
-        const int idx = tid + q * THREADS;
-        pre[q] = idx < n_sb * 4 * NT * B_KS_U4 ? bsrc[idx] : make_uint4(0, 0, 0, 0);
-    }
+        for (int q = 0; q < PRE; ++q) {
+            // (opaque scalar base: left to itself the compiler adds the lane offset first and then q x 8192 to the 64-bit per-lane address)
+            unsigned first_q = (unsigned)(sb_first * REC_U4 + q * THREADS);      // the chunk's entry of lane 0
+            asm volatile("" : "+s"(first_q));
+            // (a typed 16-byte load and four component assignments: a struct copy under the uniform branch stays a memcpy into a private array -- scratch)
+            typedef unsigned uintx4_t __attribute__((ext_vector_type(4)));
+            uintx4_t v = {0u, 0u, 0u, 0u};
+            if (OLX_IN((long long)sb_first * REC_U4 + tid_r + q * THREADS, (long long)n_sb * REC_U4, 4))      // (debug library: the lane's entry inside the launch tile's own records)
+                v = *reinterpret_cast<const uintx4_t*>(reinterpret_cast<const unsigned char*>(bsrc + first_q) + lane_b);
+            pre[q].x = v.x; pre[q].y = v.y; pre[q].z = v.z; pre[q].w = v.w;
+        }
+    };
+    request(0, tid);        // the first pair: always there (n_sb >= PAIR)
     OLX_STAMP(0);
     for (int sb0 = 0; sb0 < n_sb; sb0 += PAIR) {
         const int sa = sb0 / nsbp, sbb0 = sb0 - sa * nsbp;       // the pair (sa, sbb0), (sa, sbb0 + 1)
@@ -359,13 +377,17 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
         // (held words + pre[] + the K-steps' 93 registers do not fit 128; requested at the last K-step group they spilled 2 - 6 registers).
         auto request_next = [&]() __attribute__((always_inline)) {
             int tid_o = tid;
-            if constexpr (PRE_LATE) asm volatile("" : "+v"(tid_o));             // (opaque: the request stays where it is written)
-            const int nxt = (sb0 + PAIR) * 4 * NT * B_KS_U4, lim = n_sb * 4 * NT * B_KS_U4;
+            // (opaque.  PRE_LATE: the request stays where it is written.  The others: the loop-invariant sum of base and lane offset would be hoisted, held
+            // as a 64-bit per-lane address across the pairs, and every part's offset added to it with vector instructions.)
+            asm volatile("" : "+v"(tid_o));
+            if (sb0 + PAIR < n_sb) {                                            // (wave-uniform: the whole next chunk or nothing)
+                request(sb0 + PAIR, tid_o);
+            } else if constexpr (PRE_LATE) {
+                // no next pair: nothing is issued.  pre[] still counts as assigned on this path (no instruction) -- it is dead from the stage
+                // write above to here, and a path that left it alone would keep its 16 registers live across the K-steps.  The stage write at
+                // the top of the loop is never reached with these values.
 #pragma unroll
-            for (int q = 0; q < PRE; ++q) {
-                const int idx = nxt + tid_o + q * THREADS;
-                if constexpr (PRE_LATE) pre[q] = idx < lim ? bsrc[idx] : make_uint4(0, 0, 0, 0);      // (assigned either way: pre[] is dead from the stage write above to here)
-                else if (idx < lim) pre[q] = bsrc[idx];
+                for (int q = 0; q < PRE; ++q) asm volatile("" : "=v"(pre[q].x), "=v"(pre[q].y), "=v"(pre[q].z), "=v"(pre[q].w));
             }
         };
         if constexpr (!PRE_LATE) request_next();

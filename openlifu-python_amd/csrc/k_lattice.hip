@@ -102,11 +102,28 @@ __global__ __launch_bounds__(LAT_THREADS, NT >= 4 ? 2 : 4) void field_lattice_k(
     static_assert(CHUNK_U4 % LAT_THREADS == 0, "chunk must split evenly over the block");
     uint4 pre[PRE];
     const uint4* const bsrc = bfrag + (size_t)tile * n_sb * (4 * NT * 128);
+    // A request is one chunk in PRE parts of LAT_THREADS uint4 (8 KiB); a super-block is NT whole parts, so a part lies inside the tile's n_sb super-blocks
+    // as a whole or not at all: ONE block-uniform test per part (scalar compare and branch) instead of a per-lane bounds test, and a lane's address is a
+    // scalar base per part + its 32-bit byte offset tid x 16 (kernel 2g's form, k_coset2.hip).  A part that does not exist leaves pre[q] as it was.
+    constexpr int REC_U4 = 4 * NT * 128;
+    static_assert(REC_U4 % LAT_THREADS == 0 && REC_U4 / LAT_THREADS == NT, "a super-block is NT whole parts of a request");
+    auto request = [&](const int sb_first, const int tid_r) __attribute__((always_inline)) {
+        const unsigned lane_b = (unsigned)tid_r << 4;
 #pragma unroll
-    for (int q = 0; q < PRE; ++q) {
-        const int idx = tid + q * LAT_THREADS;
-        pre[q] = idx < n_sb * 4 * NT * 128 ? bsrc[idx] : make_uint4(0, 0, 0, 0);
-    }
+        for (int q = 0; q < PRE; ++q) {
+            if (sb_first + q / NT >= n_sb) continue;                                  // (block-uniform)
+            unsigned first_q = (unsigned)(sb_first * REC_U4 + q * LAT_THREADS);      // the part's entry of lane 0 (opaque scalar: the part offset stays in the scalar base)
+            asm volatile("" : "+s"(first_q));
+            typedef unsigned uintx4_t __attribute__((ext_vector_type(4)));
+            uintx4_t v = {0u, 0u, 0u, 0u};
+            if (OLX_IN((long long)sb_first * REC_U4 + tid_r + q * LAT_THREADS, (long long)n_sb * REC_U4, 4))
+                v = *reinterpret_cast<const uintx4_t*>(reinterpret_cast<const unsigned char*>(bsrc + first_q) + lane_b);
+            pre[q].x = v.x; pre[q].y = v.y; pre[q].z = v.z; pre[q].w = v.w;
+        }
+    };
+#pragma unroll
+    for (int q = 0; q < PRE; ++q) pre[q] = make_uint4(0, 0, 0, 0);      // (parts beyond the last super-block are staged as zeros and never read)
+    request(0, tid);
     for (int sb0 = 0; sb0 < n_sb; sb0 += SB_PER_CHUNK) {
         const int sb_here = min(SB_PER_CHUNK, n_sb - sb0);
         __syncthreads();
@@ -114,12 +131,9 @@ __global__ __launch_bounds__(LAT_THREADS, NT >= 4 ? 2 : 4) void field_lattice_k(
         for (int q = 0; q < PRE; ++q) reinterpret_cast<uint4*>(smem)[tid + q * LAT_THREADS] = pre[q];
         __syncthreads();
         {
-            const int nxt = (sb0 + SB_PER_CHUNK) * 4 * NT * 128, lim = n_sb * 4 * NT * 128;
-#pragma unroll
-            for (int q = 0; q < PRE; ++q) {
-                const int idx = nxt + tid + q * LAT_THREADS;
-                if (idx < lim) pre[q] = bsrc[idx];
-            }
+            int tid_o = tid;
+            asm volatile("" : "+v"(tid_o));      // (opaque: base + lane offset is not hoisted and held as a 64-bit per-lane address across the chunks)
+            request(sb0 + SB_PER_CHUNK, tid_o);
         }
         if (!active) continue;
         if (sb0 == 0) OLX_STAMP(1);

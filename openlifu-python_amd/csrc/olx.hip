@@ -633,6 +633,17 @@ static int configure_variant(olx_ctx* c) {
         c->mp = p.mp; c->mfma_wscale = p.mfma_wscale;
         if (p.use_lattice && p.use_coset) {
             c->cp = p.cp; c->toep_nm = p.toep.nm;
+            if (p.use_cosetp) {
+                // kernel 2g requests its steering fragments a table pair (two super-blocks) at a time under ONE block-uniform test and without per-lane
+                // bounds: the super-block count of a launch tile is even, and each operand set (the second one, bfrag_half on, included) holds
+                // n_tiles x nsa x nsbp whole super-blocks of 4 K-step records x 2 column tiles x 128 uint4
+                const size_t n_sb = (size_t)p.cp.nsa * p.cp.nsbp;
+                if (p.cp.nsa < 1 || p.cp.nsbp < 2 || p.cp.nsbp % 2 != 0)
+                    return fail(c, OLX_ESTATE, "kernel 2g: %d x %d super-blocks: the steering requests need an even row count", p.cp.nsa, p.cp.nsbp);
+                if (c->nt != 2 || c->bfrag_half != (size_t)p.mp.n_tiles * n_sb * 4 * 2 * 128)
+                    return fail(c, OLX_ESTATE, "kernel 2g: the steering operands hold %zu uint4 per set, %d launch tiles x %zu super-blocks need %zu",
+                                c->bfrag_half, p.mp.n_tiles, n_sb, (size_t)p.mp.n_tiles * n_sb * 4 * 2 * 128);
+            }
             { int rc = upload_if_changed(c, c->d_jobs, c->up_jobs, p.jobs); if (rc) return rc; }
             {   // block records: they depend on the partition only, not on the steering table -- a call that changes nothing but the foci finds the
                 // records it uploaded last time still valid
