@@ -391,6 +391,20 @@ int olx_fullwave_run(olx_ctx *ctx, int first_step, int n_steps, int accumulate_p
 /* The records of the padded grid ([voxels] floats each) and the traces ([steps run * n_points] floats, step-major); any may be NULL.
  * OLX_ESTATE: nothing run, or p_sq asked of a run that did not accumulate it. */
 int olx_fullwave_fetch(olx_ctx *ctx, float *p_max, float *p_min, float *p_sq, float *traces);
+/* Single-frequency lock-in of the run that follows, over the steps n in [first_step, first_step + n_steps):
+ * with t_n = (n + 1) dt the time of the recorded p of step n and theta_n = 2 pi frac(freq t_n) formed in double,
+ *   volume != 0: per voxel of the padded grid C = sum_n p cosf_n, S = sum_n p sinf_n, one fused multiply-add per step in step order
+ *                from 0, with cosf_n / sinf_n the cosine / sine of theta_n rounded once to float;
+ *   receiver r < n_receivers: s_r(n) = sum_q weights[q] p(voxels[q]) over q in [row[r], row[r + 1]) in table order, then
+ *                C_r += s_r cos theta_n, S_r += s_r sin theta_n, all in double.  An empty row gives 0.
+ * Call it after olx_fullwave_sources and before olx_fullwave_run(first_step = 0); a continued run keeps accumulating, and
+ * olx_fullwave_sources clears the lock-in.  OLX_EINVAL: a window outside [0, n_steps of the sources), nothing to record, a voxel
+ * outside the grid, a row table that does not start at 0 or is not monotone.  OLX_ESTATE: no plan or no sources. */
+int olx_fullwave_lockin(olx_ctx *ctx, double freq, int first_step, int n_steps, int volume, int n_receivers, const int *row,
+                        const long long *voxels, const double *weights);
+/* The lock-in sums: [voxels] floats each, [n_receivers] doubles each; any may be NULL.  OLX_ESTATE: nothing run, something asked
+ * for that was not recorded, or the run has not reached the end of the window. */
+int olx_fullwave_fetch_lockin(olx_ctx *ctx, float *vol_cos, float *vol_sin, double *rec_cos, double *rec_sin);
 
 /* ---- kernel 4: steering map (DESIGN.md section 2 "Steering map") ---------------------------------------
  * Where can the array steer?  Every voxel of `grid` is a candidate target, in the frame of the element table (kernel 1 with

@@ -1,4 +1,4 @@
-// kernel 5 (fullwave_pack_k, fullwave_inject_k, fullwave_vel_k, fullwave_pres_k, fullwave_trace_k): full-wave FDTD field model --
+// kernel 5 (fullwave_pack_k, fullwave_inject_k, fullwave_vel_k, fullwave_pres_k, fullwave_trace_k, fullwave_receive_k): full-wave FDTD field model --
 // linear acoustics, first order in (p, v) on a staggered grid, second order in time, fourth order in space.
 // gfx950 (CDNA4, wave64) only.  Definition: DESIGN.md section 2 ("full-wave model") and section 5.14, fp64 oracle tests/fullwave_oracle.py.
 //
@@ -12,6 +12,10 @@
 //             ga = exp(-2 alpha c dt); then p_max = max(p_max, p~), p_min = max(p_min, -p~) and, opt-in, sum += p~^2 (one fmaf)
 //             (each lane reads v around it and reads / writes only its own p: in place)
 //   trace     opt-in: p~ at the trace voxels into row n
+//   lock-in   opt-in, for the steps n of a window only: theta_n = 2 pi frac(f0 (n + 1) dt) formed in fp64 on the host;
+//             volume: C += p~ cosf_n, S += p~ sinf_n (one fmaf each, cos / sin theta_n rounded once to float and passed as kernel arguments),
+//             the third template flag of the pressure launch; receivers: s_r = sum_q w_q p~(vox_q) in table order, C_r += s_r cos theta_n,
+//             S_r += s_r sin theta_n in fp64, ONE thread per receiver walking its CSR row (the form of inject: no atomics)
 // D = d_x[i] d_y[j] d_z[k] from three 1-D tables (1 in the interior, the absorbing layers' decay per step outside it).
 // A heterogeneous medium streams five coefficient volumes formed once by fullwave_pack_k (b_x, b_y, b_z for the velocity launch, kp, ga
 // for the pressure launch); the uniform instantiation (UNI) streams none of them.
@@ -110,11 +114,15 @@ __global__ __launch_bounds__(FW_BLOCK) void fullwave_vel_k(const float* __restri
     vz[v] = D * (vz[v] - cbz * dpz);
 }
 
-template <bool UNI, bool PII>
+// the lock-in arguments of the pressure launch; empty, and last, without LOCK: those instantiations keep their argument layout
+template <bool LOCK> struct FwLock { float *c, *s; float cosf_n, sinf_n; };
+template <> struct FwLock<false> {};
+
+template <bool UNI, bool PII, bool LOCK>
 __global__ __launch_bounds__(FW_BLOCK) void fullwave_pres_k(float* __restrict__ p, const float* __restrict__ vx, const float* __restrict__ vy,
                                                             const float* __restrict__ vz, const float* __restrict__ kp, const float* __restrict__ ga,
                                                             const float* __restrict__ dtab, float* __restrict__ pmax, float* __restrict__ pmin,
-                                                            float* __restrict__ psq, const FullwaveParams P) {
+                                                            float* __restrict__ psq, const FullwaveParams P, const FwLock<LOCK> L) {
     const long long v = (long long)blockIdx.x * FW_BLOCK + threadIdx.x;
     if (v >= P.vox || !OLX_IN(v, P.vox, 9)) return;
     int i, j, k;
@@ -131,12 +139,34 @@ __global__ __launch_bounds__(FW_BLOCK) void fullwave_pres_k(float* __restrict__ 
     pmax[v] = fmaxf(pmax[v], pn);
     pmin[v] = fmaxf(pmin[v], -pn);
     if (PII) psq[v] = fmaf(pn, pn, psq[v]);
+    if constexpr (LOCK) {
+        float* __restrict__ lc = L.c;
+        float* __restrict__ ls = L.s;
+        lc[v] = fmaf(pn, L.cosf_n, lc[v]);
+        ls[v] = fmaf(pn, L.sinf_n, ls[v]);
+    }
 }
 
 // row n of the traces: p~ of step n at the trace voxels
 __global__ void fullwave_trace_k(const float* __restrict__ p, const long long* __restrict__ pts, int npts, long long vox, float* __restrict__ row) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q < npts && OLX_IN(pts[q], vox, 13)) row[q] = p[pts[q]];
+}
+
+// the receivers of a step inside the lock-in window: row r of the CSR table is one receiver, its entries add in table order
+__global__ void fullwave_receive_k(const float* __restrict__ p, const int* __restrict__ row, const long long* __restrict__ rvox, const double* __restrict__ w,
+                                   int n_rec, int n_entries, long long vox, double cos_n, double sin_n, double* __restrict__ rc, double* __restrict__ rs) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rec || !OLX_IN(r + 1, n_rec + 1, 14)) return;
+    double s = 0.0;
+    for (int e = row[r]; e < row[r + 1]; ++e) {
+        if (!OLX_IN(e, n_entries, 15)) break;
+        const long long at = rvox[e];
+        if (!OLX_IN(at, vox, 16)) continue;
+        s = fma(w[e], (double)p[at], s);
+    }
+    rc[r] = fma(s, cos_n, rc[r]);
+    rs[r] = fma(s, sin_n, rs[r]);
 }
 
 OLX_BOUNDS_READER(fullwave)
@@ -153,6 +183,23 @@ void olx_fullwave_pack(olx_ctx* c, const float* cs, const float* rho, const floa
                        c->d_fw_coef[3], c->d_fw_coef[4]);
 }
 
+template <bool UNI>
+static void fw_launch_pres(olx_ctx* c, bool pii, bool lock, float cosf_n, float sinf_n, const float* kp, const float* ga) {
+    const FullwaveParams& P = c->fw;
+    const dim3 grid = fw_grid(P), block(FW_BLOCK);
+    float* p = c->d_fw_p;
+    const float *vx = c->d_fw_v[0], *vy = c->d_fw_v[1], *vz = c->d_fw_v[2], *dtab = c->d_fw_dtab;
+    float *pmax = c->d_fw_pmax, *pmin = c->d_fw_pmin, *psq = pii ? (float*)c->d_fw_psq : nullptr;
+    const FwLock<true> L{c->d_fw_lc, c->d_fw_ls, cosf_n, sinf_n};
+    if (lock) {
+        if (pii) hipLaunchKernelGGL((fullwave_pres_k<UNI, true, true>), grid, block, 0, c->stream, p, vx, vy, vz, kp, ga, dtab, pmax, pmin, psq, P, L);
+        else hipLaunchKernelGGL((fullwave_pres_k<UNI, false, true>), grid, block, 0, c->stream, p, vx, vy, vz, kp, ga, dtab, pmax, pmin, psq, P, L);
+    } else {
+        if (pii) hipLaunchKernelGGL((fullwave_pres_k<UNI, true, false>), grid, block, 0, c->stream, p, vx, vy, vz, kp, ga, dtab, pmax, pmin, psq, P, FwLock<false>{});
+        else hipLaunchKernelGGL((fullwave_pres_k<UNI, false, false>), grid, block, 0, c->stream, p, vx, vy, vz, kp, ga, dtab, pmax, pmin, psq, P, FwLock<false>{});
+    }
+}
+
 void olx_fullwave_step(olx_ctx* c, int step, bool pii) {
     const FullwaveParams& P = c->fw;
     const FullwaveSource& S = c->fw_src;
@@ -161,19 +208,29 @@ void olx_fullwave_step(olx_ctx* c, int step, bool pii) {
         hipLaunchKernelGGL(fullwave_inject_k, dim3((S.n_vox + 63) / 64), dim3(64), 0, c->stream, p, c->d_fw_svox, c->d_fw_srow, c->d_fw_samp, c->d_fw_stau, S,
                            c->fw_entries, P.vox, step);
     const dim3 grid = fw_grid(P), block(FW_BLOCK);
-    float *vx = c->d_fw_v[0], *vy = c->d_fw_v[1], *vz = c->d_fw_v[2], *pmax = c->d_fw_pmax, *pmin = c->d_fw_pmin, *psq = c->d_fw_psq;
+    float *vx = c->d_fw_v[0], *vy = c->d_fw_v[1], *vz = c->d_fw_v[2];
     const float* dtab = c->d_fw_dtab;
+    // the lock-in of a step inside the window: theta_n = 2 pi frac(f0 t_n), t_n = (n + 1) dt, in fp64
+    const bool lock = c->fw_lock && step >= c->fw_lock_w0 && step < c->fw_lock_w0 + c->fw_lock_nw;
+    double cos_n = 0.0, sin_n = 0.0;
+    if (lock) {
+        double ph = c->fw_lock_freq * ((double)(step + 1) * c->fw_dt);
+        ph -= std::floor(ph);
+        cos_n = std::cos(2.0 * M_PI * ph); sin_n = std::sin(2.0 * M_PI * ph);
+    }
+    const bool lock_vol = lock && c->fw_lock_vol;
     if (c->fw_uniform) {
         hipLaunchKernelGGL(fullwave_vel_k<true>, grid, block, 0, c->stream, p, vx, vy, vz, nullptr, nullptr, nullptr, dtab, P);
-        if (pii) hipLaunchKernelGGL((fullwave_pres_k<true, true>), grid, block, 0, c->stream, p, vx, vy, vz, nullptr, nullptr, dtab, pmax, pmin, psq, P);
-        else hipLaunchKernelGGL((fullwave_pres_k<true, false>), grid, block, 0, c->stream, p, vx, vy, vz, nullptr, nullptr, dtab, pmax, pmin, nullptr, P);
+        fw_launch_pres<true>(c, pii, lock_vol, (float)cos_n, (float)sin_n, nullptr, nullptr);
     } else {
         const float *bx = c->d_fw_coef[0], *by = c->d_fw_coef[1], *bz = c->d_fw_coef[2], *kp = c->d_fw_coef[3], *ga = c->d_fw_coef[4];
         hipLaunchKernelGGL(fullwave_vel_k<false>, grid, block, 0, c->stream, p, vx, vy, vz, bx, by, bz, dtab, P);
-        if (pii) hipLaunchKernelGGL((fullwave_pres_k<false, true>), grid, block, 0, c->stream, p, vx, vy, vz, kp, ga, dtab, pmax, pmin, psq, P);
-        else hipLaunchKernelGGL((fullwave_pres_k<false, false>), grid, block, 0, c->stream, p, vx, vy, vz, kp, ga, dtab, pmax, pmin, nullptr, P);
+        fw_launch_pres<false>(c, pii, lock_vol, (float)cos_n, (float)sin_n, kp, ga);
     }
     if (c->fw_npts > 0)
         hipLaunchKernelGGL(fullwave_trace_k, dim3((c->fw_npts + 255) / 256), dim3(256), 0, c->stream, p, c->d_fw_pts, c->fw_npts, P.vox,
                            c->d_fw_trace + (size_t)step * c->fw_npts);
+    if (lock && c->fw_lock_nrec > 0)
+        hipLaunchKernelGGL(fullwave_receive_k, dim3((c->fw_lock_nrec + 63) / 64), dim3(64), 0, c->stream, p, c->d_fw_lrow, c->d_fw_lvox, c->d_fw_lw,
+                           c->fw_lock_nrec, c->fw_lock_entries, P.vox, cos_n, sin_n, c->d_fw_lrc, c->d_fw_lrs);
 }

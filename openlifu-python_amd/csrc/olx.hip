@@ -3197,6 +3197,7 @@ int olx_fullwave_sources(olx_ctx* c, int n_entries, const long long* voxels, con
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->fw_sourced = false; c->fw_next = -1;
+    c->fw_lock = false; c->fw_lock_vol = false; c->fw_lock_nrec = 0; c->fw_lock_entries = 0;   // a new source table runs without a lock-in until olx_fullwave_lockin asks for one
     int rc = c->d_fw_svox.reserve(c, svox.size());
     if (!rc) rc = c->d_fw_srow.reserve(c, srow.size());
     if (!rc) rc = c->d_fw_samp.reserve(c, n_entries);
@@ -3234,11 +3235,87 @@ int olx_fullwave_run(olx_ctx* c, int first_step, int n_steps, int accumulate_psq
             HIPCHK(c, hipMemsetAsync(p, 0, sizeof(float) * vox, c->stream));
         if (pii) HIPCHK(c, hipMemsetAsync(c->d_fw_psq, 0, sizeof(float) * vox, c->stream));
         c->fw_pii = pii;
+        if (c->fw_lock && c->fw_lock_vol)
+            for (float* p : {(float*)c->d_fw_lc, (float*)c->d_fw_ls}) HIPCHK(c, hipMemsetAsync(p, 0, sizeof(float) * vox, c->stream));
+        if (c->fw_lock && c->fw_lock_nrec > 0)
+            for (double* p : {(double*)c->d_fw_lrc, (double*)c->d_fw_lrs}) HIPCHK(c, hipMemsetAsync(p, 0, sizeof(double) * c->fw_lock_nrec, c->stream));
     }
     for (int n = first_step; n < first_step + n_steps; ++n) olx_fullwave_step(c, n, pii);
     HIPCHK(c, hipGetLastError());
     c->fw_next = first_step + n_steps;
     return OLX_OK;
+}
+
+int olx_fullwave_lockin(olx_ctx* c, double freq, int first_step, int n_steps, int volume, int n_receivers, const int* row, const long long* voxels,
+                        const double* weights) {
+    if (!c) return OLX_EINVAL;
+    if (!c->fw_planned || !c->fw_sourced) return fail(c, OLX_ESTATE, "olx_fullwave_lockin: needs olx_fullwave_plan and olx_fullwave_sources first");
+    if (!(freq > 0) || !std::isfinite(freq)) return fail(c, OLX_EINVAL, "olx_fullwave_lockin: freq must be finite and > 0");
+    if (first_step < 0 || n_steps < 1 || (long long)first_step + n_steps > c->fw_steps)
+        return fail(c, OLX_EINVAL, "olx_fullwave_lockin: window [%d, %lld) outside the run of %d steps", first_step, (long long)first_step + n_steps, c->fw_steps);
+    if (n_receivers < 0 || (n_receivers > 0 && !row)) return fail(c, OLX_EINVAL, "olx_fullwave_lockin: n_receivers < 0 or null row table");
+    if (!volume && n_receivers == 0) return fail(c, OLX_EINVAL, "olx_fullwave_lockin: neither the volume nor a receiver to record");
+    int n_entries = 0;
+    if (n_receivers > 0) {
+        if (row[0] != 0) return fail(c, OLX_EINVAL, "olx_fullwave_lockin: row[0] must be 0");
+        for (int r = 0; r < n_receivers; ++r)
+            if (row[r + 1] < row[r]) return fail(c, OLX_EINVAL, "olx_fullwave_lockin: row table not monotone at receiver %d", r);
+        n_entries = row[n_receivers];
+        if (n_entries > 0 && (!voxels || !weights)) return fail(c, OLX_EINVAL, "olx_fullwave_lockin: null receiver table");
+        for (int e = 0; e < n_entries; ++e) {
+            if (voxels[e] < 0 || voxels[e] >= c->fw.vox) return fail(c, OLX_EINVAL, "olx_fullwave_lockin: entry %d: voxel %lld outside the grid of %lld voxels", e, voxels[e], c->fw.vox);
+            if (!std::isfinite(weights[e])) return fail(c, OLX_EINVAL, "olx_fullwave_lockin: entry %d: weight must be finite", e);
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->fw_lock = false; c->fw_next = -1;       // the records belong to the run that follows: olx_fullwave_run(first_step = 0)
+    int rc = OLX_OK;
+    if (volume) {
+        rc = c->d_fw_lc.reserve(c, (size_t)c->fw.vox);
+        if (!rc) rc = c->d_fw_ls.reserve(c, (size_t)c->fw.vox);
+    }
+    if (!rc && n_receivers > 0) {
+        rc = c->d_fw_lrow.reserve(c, (size_t)n_receivers + 1);
+        if (!rc) rc = c->d_fw_lvox.reserve(c, n_entries);
+        if (!rc) rc = c->d_fw_lw.reserve(c, n_entries);
+        if (!rc) rc = c->d_fw_lrc.reserve(c, n_receivers);
+        if (!rc) rc = c->d_fw_lrs.reserve(c, n_receivers);
+    }
+    if (rc) return rc;
+    if (n_receivers > 0) {
+        HIPCHK(c, hipMemcpy(c->d_fw_lrow, row, sizeof(int) * ((size_t)n_receivers + 1), hipMemcpyHostToDevice));
+        if (n_entries > 0) {
+            HIPCHK(c, hipMemcpy(c->d_fw_lvox, voxels, sizeof(long long) * n_entries, hipMemcpyHostToDevice));
+            HIPCHK(c, hipMemcpy(c->d_fw_lw, weights, sizeof(double) * n_entries, hipMemcpyHostToDevice));
+        }
+    }
+    c->fw_lock_freq = freq; c->fw_lock_w0 = first_step; c->fw_lock_nw = n_steps;
+    c->fw_lock_vol = volume != 0; c->fw_lock_nrec = n_receivers; c->fw_lock_entries = n_entries;
+    c->fw_lock = true;
+    return OLX_OK;
+}
+
+int olx_fullwave_fetch_lockin(olx_ctx* c, float* vol_cos, float* vol_sin, double* rec_cos, double* rec_sin) {
+    if (!c) return OLX_EINVAL;
+    if (!c->fw_planned || c->fw_next < 0) return fail(c, OLX_ESTATE, "olx_fullwave_fetch_lockin: nothing run");
+    if (!c->fw_lock) return fail(c, OLX_ESTATE, "olx_fullwave_fetch_lockin: the run recorded no lock-in");
+    if ((vol_cos || vol_sin) && !c->fw_lock_vol) return fail(c, OLX_ESTATE, "olx_fullwave_fetch_lockin: the run did not record the lock-in volume");
+    if ((rec_cos || rec_sin) && c->fw_lock_nrec == 0) return fail(c, OLX_ESTATE, "olx_fullwave_fetch_lockin: the run did not record receivers");
+    if (c->fw_next < c->fw_lock_w0 + c->fw_lock_nw)
+        return fail(c, OLX_ESTATE, "olx_fullwave_fetch_lockin: the run stands at step %d, before the end of the window [%d, %d)", c->fw_next, c->fw_lock_w0, c->fw_lock_w0 + c->fw_lock_nw);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+#ifdef OLX_DEBUG_BOUNDS
+    { int rc_ = report_bounds(c); if (rc_) return rc_; }
+#endif
+    const size_t vox = (size_t)c->fw.vox, nrec = (size_t)c->fw_lock_nrec;
+    int rc = OLX_OK;
+    if (vol_cos) rc = fetch_to_host(c, vol_cos, c->d_fw_lc, sizeof(float) * vox);
+    if (!rc && vol_sin) rc = fetch_to_host(c, vol_sin, c->d_fw_ls, sizeof(float) * vox);
+    if (!rc && rec_cos) rc = fetch_to_host(c, rec_cos, c->d_fw_lrc, sizeof(double) * nrec);
+    if (!rc && rec_sin) rc = fetch_to_host(c, rec_sin, c->d_fw_lrs, sizeof(double) * nrec);
+    return rc;
 }
 
 int olx_fullwave_fetch(olx_ctx* c, float* p_max, float* p_min, float* p_sq, float* traces) {

@@ -186,6 +186,10 @@ struct olx_ctx {
     bool fw_sourced = false; FullwaveSource fw_src{}; int fw_entries = 0, fw_steps = 0;
     DevBuf<long long> d_fw_svox; DevBuf<int> d_fw_srow; DevBuf<double> d_fw_samp, d_fw_stau;   // CSR source table: voxel per row, row offsets, entries in table order
     int fw_npts = 0; DevBuf<long long> d_fw_pts; DevBuf<float> d_fw_trace;   // trace voxels, [fw_steps][fw_npts] samples
+    // lock-in at one frequency over the steps [fw_lock_w0, fw_lock_w0 + fw_lock_nw) (olx_fullwave_lockin; cleared by olx_fullwave_sources)
+    bool fw_lock = false, fw_lock_vol = false; double fw_lock_freq = 0; int fw_lock_w0 = 0, fw_lock_nw = 0, fw_lock_nrec = 0, fw_lock_entries = 0;
+    DevBuf<float> d_fw_lc, d_fw_ls;           // [voxels] sum p~ cos theta_n, sum p~ sin theta_n (created by the first lock-in that asks for the volume)
+    DevBuf<int> d_fw_lrow; DevBuf<long long> d_fw_lvox; DevBuf<double> d_fw_lw, d_fw_lrc, d_fw_lrs;   // CSR receiver table: row offsets, voxels, weights; [receivers] sums
     int fw_next = -1; bool fw_pii = false;    // the step the next olx_fullwave_run continues with (-1: nothing run since the last plan / sources); the run accumulates sum p~^2
     // steering map (kernel 4, olx_steer_map): result volumes and element records of their own -- they never alias the field, aggregate or PII buffers
     DevBuf<float> d_sm_p; DevBuf<int> d_sm_n;          // [voxels] focal pressure [Pa], active elements; created by the first call, reused by later ones

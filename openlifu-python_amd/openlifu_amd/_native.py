@@ -45,7 +45,7 @@ SYMBOLS = [
     "olx_field_pulse", "olx_field_fetch_pmax", "olx_aggregate_fetch_pmax", "olx_field_fetch_pii", "olx_field_pulse_trace", "olx_field_pulse_medium",
     "olx_pii_post", "olx_pii_fetch_weighted", "olx_pii_fetch_max", "olx_pii_upload", "olx_thermal_source_pii",
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
-    "olx_fullwave_plan", "olx_fullwave_sources", "olx_fullwave_run", "olx_fullwave_fetch",
+    "olx_fullwave_plan", "olx_fullwave_sources", "olx_fullwave_run", "olx_fullwave_fetch", "olx_fullwave_lockin", "olx_fullwave_fetch_lockin",
     "olx_bf_set_medium", "olx_bf_solve_medium",
     "olx_bf_set_attenuation", "olx_bf_solve_compensated",
     "olx_steer_map", "olx_steer_time", "olx_steer_map_medium",
@@ -165,6 +165,8 @@ def load(require_gpu: bool = True):
                                              POINTER(ctypes.c_longlong)]
         lib.olx_fullwave_run.argtypes = [vp, c_int, c_int, c_int]
         lib.olx_fullwave_fetch.argtypes = [vp, fp, fp, fp, fp]
+        lib.olx_fullwave_lockin.argtypes = [vp, c_double, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(ctypes.c_longlong), dp]
+        lib.olx_fullwave_fetch_lockin.argtypes = [vp, fp, fp, dp, dp]
         lib.olx_set_element_apertures.argtypes = [vp, dp, dp]
         lib.olx_comm_export.argtypes = [vp, vp]
         lib.olx_comm_import.argtypes = [vp, vp]
@@ -756,6 +758,7 @@ class Context:
         self._chk(self._lib.olx_fullwave_sources(self._h, int(vx.size), vx.ctypes.data_as(lp), _dptr(am), _dptr(ta), float(freq), float(cycles),
                                                  float(ramp_cycles), int(n_steps), int(pts.size), pts.ctypes.data_as(lp)))
         self._fw_steps, self._fw_npts = int(n_steps), int(pts.size)
+        self._fw_lock_vol, self._fw_lock_nrec = False, 0
 
     def fullwave_run(self, first_step: int = 0, n_steps=None, psq: bool = False):
         n_steps = self._fw_steps - int(first_step) if n_steps is None else int(n_steps)
@@ -770,6 +773,30 @@ class Context:
         tr = np.empty((self._fw_ran, self._fw_npts), dtype=np.float32)
         self._chk(self._lib.olx_fullwave_fetch(self._h, _fptr(pmax), _fptr(pmin), _fptr(psq), _fptr(tr) if tr.size else None))
         return pmax, pmin, psq, tr
+
+    def fullwave_lockin(self, freq, first_step, n_steps, volume=True, row=None, voxels=None, weights=None):
+        """Lock-in at ``freq`` over the steps [first_step, first_step + n_steps) of the run that follows: the volume sums and / or the
+        receivers of the CSR table (``row`` [R + 1], ``voxels`` linear in the padded grid, ``weights``).  After ``fullwave_sources``."""
+        rw = np.ascontiguousarray([0] if row is None else row, dtype=np.int32)
+        vx = np.ascontiguousarray([] if voxels is None else voxels, dtype=np.int64)
+        wt = np.ascontiguousarray([] if weights is None else weights, dtype=np.float64)
+        if not (rw.ndim == 1 and rw.size >= 1 and vx.ndim == 1 and vx.shape == wt.shape):
+            raise ValueError(f"row must be 1-D with at least one offset, voxels and weights 1-D of one length, got {rw.shape}, {vx.shape}, {wt.shape}")
+        if int(rw[-1]) != vx.size:
+            raise ValueError(f"the last row offset {int(rw[-1])} is not the number of entries {vx.size}")
+        self._chk(self._lib.olx_fullwave_lockin(self._h, float(freq), int(first_step), int(n_steps), int(bool(volume)), int(rw.size - 1),
+                                                rw.ctypes.data_as(POINTER(c_int)), vx.ctypes.data_as(POINTER(ctypes.c_longlong)), _dptr(wt)))
+        self._fw_lock_vol, self._fw_lock_nrec = bool(volume), int(rw.size - 1)
+
+    def fullwave_fetch_lockin(self):
+        """(C, S) volumes of the padded grid (None when not recorded) and (C_r, S_r) float64[R] (None without receivers)."""
+        vc = np.empty(self._fw_shape, dtype=np.float32) if self._fw_lock_vol else None
+        vs = np.empty(self._fw_shape, dtype=np.float32) if self._fw_lock_vol else None
+        rc = np.empty(self._fw_lock_nrec, dtype=np.float64) if self._fw_lock_nrec else None
+        rs = np.empty(self._fw_lock_nrec, dtype=np.float64) if self._fw_lock_nrec else None
+        self._chk(self._lib.olx_fullwave_fetch_lockin(self._h, _fptr(vc), _fptr(vs), _dptr(rc) if rc is not None else None,
+                                                      _dptr(rs) if rs is not None else None))
+        return vc, vs, rc, rs
 
     def field_scale_aggregate(self, scale_per_focus):
         """``field_scale`` + ``field_aggregate_device`` in one pass (identical values)."""

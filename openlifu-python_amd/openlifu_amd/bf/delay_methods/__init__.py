@@ -2,16 +2,19 @@
 
 Namespace used for class-name lookup: ``DelayMethod.from_dict({"class": "Direct", ...})`` resolves
 ``"Direct"`` here, exactly like the reference's package of the same name.  ``StraightRay`` (aberration
-correction through the ``params`` medium) is this package's extension.
+correction through the ``params`` medium) and ``TimeReversal`` (delays from one full-wave
+run per focus, refraction and reflection included) are this package's extensions.
 """
 from __future__ import annotations
 
 from . import delaymethod as _base
 from . import direct as _direct
 from . import straightray as _straightray
+from . import timereversal as _timereversal
 
 DelayMethod = _base.DelayMethod
 Direct = _direct.Direct
 StraightRay = _straightray.StraightRay
+TimeReversal = _timereversal.TimeReversal
 
-__all__ = ("DelayMethod", "Direct", "StraightRay")
+__all__ = ("DelayMethod", "Direct", "StraightRay", "TimeReversal")

@@ -501,6 +501,18 @@ class Engine:
         self.ctx.fullwave_run(0, n_steps, psq=psq)
         return self.ctx.fullwave_fetch()
 
+    def fullwave_steady(self, spacing_m, n_padded, medium, c_ref, pml_size, pml_alpha, dt, n_steps, sources, freq, cycles, ramp_cycles, window,
+                        volume=True, receivers=None):
+        """A driven full-wave run with the lock-in at ``freq`` over the steps ``window = (w0, Nw)`` (sim/fullwave.py)
+        -> (C, S volumes of the padded grid | None, C_r, S_r float64 [R] | None).  ``receivers = (row, voxel, weight)``: the CSR table, voxels
+        linear in the padded grid.  The other arguments and what is left untouched are ``fullwave``'s."""
+        self.ctx.fullwave_plan(spacing_m, n_padded, *medium, c_ref=c_ref, pml_size=pml_size, pml_alpha=pml_alpha, dt=dt)
+        self.ctx.fullwave_sources(*sources, freq=freq, cycles=cycles, ramp_cycles=ramp_cycles, n_steps=n_steps)
+        row, vox, wt = (None, None, None) if receivers is None else receivers
+        self.ctx.fullwave_lockin(freq, window[0], window[1], volume=volume, row=row, voxels=vox, weights=wt)
+        self.ctx.fullwave_run(0, n_steps)
+        return self.ctx.fullwave_fetch_lockin()
+
     def upload_result(self, origin_m, spacing_m, n, pmag, intensity=None):
         """Bind host volumes [F,nx,ny,nz] as the resident result (analysis of a detached Solution)."""
         self.retire_results()

@@ -24,7 +24,7 @@ import numpy as np
 from .. import _native as nat
 from .. import bf, seg, sim
 from ..bf.apod_methods import ApodizationMethod, MediumCompensated
-from ..bf.delay_methods import Direct, StraightRay
+from ..bf.delay_methods import Direct, StraightRay, TimeReversal
 from ..engine import get_engine, gpu_available
 from ..geo import Point
 from ..sim.field import dataset_from_fields, lazy_stack, parse_field_model, parse_pii_option, parse_pulsed_medium_option, simulate_foci, _ATTRS
@@ -178,8 +178,11 @@ class Protocol:
         if self._fused():
             d, a = self._solve_fused(arr, target, params)
             return d[0], a[0]
-        return (self.delay_method.calc_delays(arr, target, params),
-                self.apod_method.calc_apodization(arr, target, params))
+        if type(self.delay_method) is TimeReversal:      # at the pulse's frequency unless the method has its own
+            delays = self.delay_method.calc_delays(arr, target, params, frequency=self.pulse.frequency)
+        else:
+            delays = self.delay_method.calc_delays(arr, target, params)
+        return delays, self.apod_method.calc_apodization(arr, target, params)
 
     def beamform_foci(self, arr, foci: List[Point], params):
         """(delays[F,N], apod[F,N]) for all foci in one launch; leaves the steering table on the device."""

@@ -11,5 +11,6 @@ run_simulation = field.run_simulation
 SimSetup = _sim_setup.SimSetup
 run_thermal_simulation = thermal.run_thermal_simulation
 run_fullwave_simulation = fullwave.run_fullwave_simulation
+run_fullwave_steady_state = fullwave.run_fullwave_steady_state
 
-__all__ = ("SimSetup", "run_simulation", "run_thermal_simulation", "run_fullwave_simulation", "field", "thermal", "fullwave")
+__all__ = ("SimSetup", "run_simulation", "run_thermal_simulation", "run_fullwave_simulation", "run_fullwave_steady_state", "field", "thermal", "fullwave")

@@ -18,6 +18,7 @@ import numpy as np
 
 from ..engine import Engine, get_engine, grid_from_coords
 from ..util import dataset as ds
+from ..util.units import getunitconversion
 from .field import _ATTRS, _medium, _np_per_m
 
 PPW_WARN = 8.0      # points per wavelength below which the fourth-order stencil's dispersion error is no longer small
@@ -89,21 +90,16 @@ def crop_volume(vol, pml_size: int):
     return np.ascontiguousarray(vol[q:vol.shape[0] - q, q:vol.shape[1] - q, q:vol.shape[2] - q]) if q else np.asarray(vol)
 
 
-def source_table(pos_m, area, apod, delays, origin_m, spacing_m, n, sound_speed, c_ref, freq, p0, dt, snap: float = 1e-9):
-    """Monopole source entries on the caller's (unpadded) grid -> (ijk [S, 3] int64, amplitude [S], tau [S], element [S]).
+def trilinear_entries(pos_m, origin_m, spacing_m, n, snap: float = 1e-9, what: str = "element"):
+    """The trilinear rule of the sources and of the receivers -> (ijk [S, 3] int64, weight [S], point [S]) on the caller's (unpadded) grid.
 
-    Element e contributes to the 8 voxels around its position with trilinear weights; weights of 0 are dropped, so an element
-    exactly on a voxel gives one entry (a position within ``snap`` voxels of a voxel centre counts as on it).  amplitude =
-    weight dt c(vox)^2 4 pi A_e / (2 pi freq h_x h_y h_z) with A_e = apod_e p0 area_e freq / c_ref: the monopole whose free-field
-    pressure is A_e / r cos(2 pi freq (t - tau_e - r / c)).  An element with a weighted voxel outside the grid raises ValueError."""
+    Point e spreads over the 8 voxels around its position; weights of 0 are dropped, so a point exactly on a voxel gives one entry (a
+    position within ``snap`` voxels of a voxel centre counts as on it).  A point with a weighted voxel outside the grid raises ValueError
+    naming it as ``what``."""
     pos = np.atleast_2d(np.asarray(pos_m, dtype=np.float64))
     h = np.broadcast_to(np.asarray(spacing_m, dtype=np.float64), (3,))
     n = tuple(int(v) for v in n)
-    cs = np.asarray(sound_speed, dtype=np.float64)
-    A = np.asarray(apod, dtype=np.float64) * np.asarray(area, dtype=np.float64) * float(p0) * float(freq) / float(c_ref)
-    tau = np.asarray(delays, dtype=np.float64)
-    scale = float(dt) * 4.0 * np.pi / (2.0 * np.pi * float(freq) * float(np.prod(h)))
-    ijk, amp, tt, el = [], [], [], []
+    ijk, wt, el = [], [], []
     for e in range(pos.shape[0]):
         q = (pos[e] - np.asarray(origin_m, dtype=np.float64)) / h
         near = np.rint(q)
@@ -118,16 +114,72 @@ def source_table(pos_m, area, apod, delays, origin_m, spacing_m, n, sound_speed,
                         continue
                     v = base + (di, dj, dk)
                     if np.any(v < 0) or np.any(v >= n):
-                        raise ValueError(f"full-wave simulation: element {e} at {tuple(pos[e])} m does not lie inside the grid "
-                                         f"(its source voxel {tuple(int(t) for t in v)} is outside {n})")
-                    c_v = float(cs) if cs.ndim == 0 else float(cs[tuple(v)])
-                    ijk.append(v); amp.append(w * scale * c_v * c_v * A[e]); tt.append(tau[e]); el.append(e)
-    return (np.asarray(ijk, dtype=np.int64).reshape(-1, 3), np.asarray(amp, dtype=np.float64), np.asarray(tt, dtype=np.float64),
-            np.asarray(el, dtype=np.int64))
+                        raise ValueError(f"full-wave simulation: {what} {e} at {tuple(pos[e])} m does not lie inside the grid "
+                                         f"(its {'source ' if what == 'element' else ''}voxel {tuple(int(t) for t in v)} is outside {n})")
+                    ijk.append(v); wt.append(w); el.append(e)
+    return np.asarray(ijk, dtype=np.int64).reshape(-1, 3), np.asarray(wt, dtype=np.float64), np.asarray(el, dtype=np.int64)
+
+
+def monopole_table(pos_m, A, delays, origin_m, spacing_m, n, sound_speed, freq, dt, snap: float = 1e-9, what: str = "element"):
+    """Monopole source entries of points with free-field pressure A_e / r cos(2 pi freq (t - tau_e - r / c)) -> (ijk, amplitude, tau, point):
+    amplitude = weight dt c(vox)^2 4 pi A_e / (2 pi freq h_x h_y h_z), in the order of ``trilinear_entries``."""
+    h = np.broadcast_to(np.asarray(spacing_m, dtype=np.float64), (3,))
+    cs = np.asarray(sound_speed, dtype=np.float64)
+    A, tau = np.asarray(A, dtype=np.float64), np.asarray(delays, dtype=np.float64)
+    scale = float(dt) * 4.0 * np.pi / (2.0 * np.pi * float(freq) * float(np.prod(h)))
+    ijk, wt, el = trilinear_entries(pos_m, origin_m, h, n, snap, what)
+    c_v = np.full(el.shape, float(cs)) if cs.ndim == 0 else cs[tuple(ijk.T)].astype(np.float64)
+    amp = np.asarray([w * scale * c * c * A[e] for w, c, e in zip(wt, c_v, el)], dtype=np.float64)
+    return ijk, amp, tau[el].astype(np.float64), el
+
+
+def source_table(pos_m, area, apod, delays, origin_m, spacing_m, n, sound_speed, c_ref, freq, p0, dt, snap: float = 1e-9):
+    """Monopole source entries on the caller's (unpadded) grid -> (ijk [S, 3] int64, amplitude [S], tau [S], element [S]).
+
+    Element e contributes to the 8 voxels around its position with trilinear weights; weights of 0 are dropped, so an element
+    exactly on a voxel gives one entry (a position within ``snap`` voxels of a voxel centre counts as on it).  amplitude =
+    weight dt c(vox)^2 4 pi A_e / (2 pi freq h_x h_y h_z) with A_e = apod_e p0 area_e freq / c_ref: the monopole whose free-field
+    pressure is A_e / r cos(2 pi freq (t - tau_e - r / c)).  An element with a weighted voxel outside the grid raises ValueError."""
+    A = np.asarray(apod, dtype=np.float64) * np.asarray(area, dtype=np.float64) * float(p0) * float(freq) / float(c_ref)
+    return monopole_table(pos_m, A, delays, origin_m, spacing_m, n, sound_speed, freq, dt, snap)
+
+
+def receiver_table(points_m, origin_m, spacing_m, n, snap: float = 1e-9):
+    """CSR receiver table on the caller's (unpadded) grid -> (row [R + 1] int32, ijk [S, 3] int64, weight [S]): receiver r reads
+    sum_q weight[q] p(ijk[q]) over q in [row[r], row[r + 1]), the trilinear rule of ``source_table``."""
+    pts = np.asarray(points_m, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError(f"receivers must have shape (P, 3), got {pts.shape}")
+    if not np.all(np.isfinite(pts)):
+        raise ValueError("full-wave simulation: receiver positions must be finite")
+    if pts.shape[0] == 0:
+        return np.zeros(1, dtype=np.int32), np.zeros((0, 3), dtype=np.int64), np.zeros(0)
+    ijk, wt, el = trilinear_entries(pts, origin_m, spacing_m, n, snap, "receiver")
+    row = np.concatenate([[0], np.cumsum(np.bincount(el, minlength=pts.shape[0]))]).astype(np.int32)
+    return row, ijk, wt
 
 
 def _broadcast(value, ref, shape):
     return np.full(shape, ref, dtype=np.float64) if value is None else np.asarray(value, dtype=np.float64)
+
+
+def _medium_of(params, freq, ref_values_only):
+    """(c_ref, rho_ref, sound speed, density, absorption [Np/m]), each of the last three a float or a volume of the caller's grid."""
+    c_ref, rho_ref, medium, absorption = _medium(params, freq, ref_values_only)
+    if medium is None:      # homogeneous: the uniform instantiation streams no coefficient volume
+        return c_ref, rho_ref, c_ref, rho_ref, float(absorption)
+    cs = c_ref if medium["sound_speed"] is None else np.asarray(medium["sound_speed"], dtype=np.float64)
+    rho = rho_ref if medium["density"] is None else np.asarray(medium["density"], dtype=np.float64)
+    alpha = 0.0 if medium["attenuation"] is None else np.asarray(medium["attenuation"], dtype=np.float64) * _np_per_m(1.0, freq)
+    return c_ref, rho_ref, cs, rho, alpha
+
+
+def _impedance(params, ref_values_only, c_ref, rho_ref, cs, rho):
+    """The impedance of the intensity: the volumes' own rho c (with ref_values_only too, as run_simulation forms it)."""
+    if ref_values_only:
+        uniform = all(getattr(params[k], "uniform_value", None) is not None for k in ("density", "sound_speed"))
+        return rho_ref * c_ref if uniform else np.asarray(params["density"].data, dtype=np.float64) * np.asarray(params["sound_speed"].data, dtype=np.float64)
+    return np.asarray(rho, dtype=np.float64) * np.asarray(cs, dtype=np.float64)
 
 
 def run_fullwave_simulation(arr, params, delays=None, apod=None, freq: float = 1e6, cycles: float = 20, amplitude: float = 1,
@@ -155,13 +207,7 @@ def run_fullwave_simulation(arr, params, delays=None, apod=None, freq: float = 1
     coords = params.coords
     origin, spacing, n = grid_from_coords(coords)
     n = tuple(int(v) for v in n)
-    c_ref, rho_ref, medium, absorption = _medium(params, freq, ref_values_only)
-    if medium is None:      # homogeneous: the uniform instantiation streams no coefficient volume
-        cs, rho, alpha = c_ref, rho_ref, float(absorption)
-    else:
-        cs = c_ref if medium["sound_speed"] is None else np.asarray(medium["sound_speed"], dtype=np.float64)
-        rho = rho_ref if medium["density"] is None else np.asarray(medium["density"], dtype=np.float64)
-        alpha = 0.0 if medium["attenuation"] is None else np.asarray(medium["attenuation"], dtype=np.float64) * _np_per_m(1.0, freq)
+    c_ref, rho_ref, cs, rho, alpha = _medium_of(params, freq, ref_values_only)
     dt, n_steps, dt_max, ppw = fullwave_time_axis(spacing, n, cs, freq, cycles, delays, dt, t_end, cfl)
     pos, _, area, _ = Engine._table_of(arr)
     p0 = float(amplitude) * (1.0 if arr.sensitivity is None else float(arr.sensitivity))
@@ -183,12 +229,7 @@ def run_fullwave_simulation(arr, params, delays=None, apod=None, freq: float = 1
                                           ramp_cycles, psq=bool(pulse_intensity_integral), points=None if tr_ijk is None else lin(tr_ijk))
     logging.info("Simulation Complete")
     pmax, pmin = crop_volume(pmax, pml_size), crop_volume(pmin, pml_size)
-    # the impedance of the intensity: the volumes' own rho c (with ref_values_only too, as run_simulation forms it)
-    if ref_values_only:
-        uniform = all(getattr(params[k], "uniform_value", None) is not None for k in ("density", "sound_speed"))
-        Z = rho_ref * c_ref if uniform else np.asarray(params["density"].data, dtype=np.float64) * np.asarray(params["sound_speed"].data, dtype=np.float64)
-    else:
-        Z = np.asarray(rho, dtype=np.float64) * np.asarray(cs, dtype=np.float64)
+    Z = _impedance(params, ref_values_only, c_ref, rho_ref, cs, rho)
     inten = (1e-4 * pmin.astype(np.float64) ** 2 / (2.0 * Z)).astype(np.float32)
     dims = list(coords.dims) if hasattr(coords, "dims") else list(coords.keys())
     out = {"p_max": ds.make_dataarray(pmax, coords=coords, dims=dims, name="p_max", attrs=_ATTRS["p_max"]),
@@ -205,3 +246,141 @@ def run_fullwave_simulation(arr, params, delays=None, apod=None, freq: float = 1
     if trace_voxels is not None:
         raw["p_trace"], raw["t"], raw["trace_voxels"] = np.ascontiguousarray(trace.T), (np.arange(n_steps) + 1) * dt, trace_voxels
     return dataset, raw
+
+
+# ---- steady state at the drive frequency: single-frequency lock-in over the last cycles of a driven run ----
+PHASE_ATTRS = {"units": "cycles", "long_name": "Phase lag behind sin(2 pi f0 t)"}
+
+
+def lockin_window(n_steps: int, dt: float, freq: float, lockin_cycles: float):
+    """(w0, Nw): the last Nw = rint(lockin_cycles / (freq dt)) steps of a run of ``n_steps``.  ValueError when Nw < 1 or the window does
+    not fit the run."""
+    x = float(lockin_cycles) / (float(freq) * float(dt))
+    if not (np.isfinite(x) and x > 0):
+        raise ValueError(f"full-wave steady state: lockin_cycles must be finite and > 0, got {lockin_cycles}")
+    nw = int(np.rint(x))
+    if nw < 1:
+        raise ValueError(f"full-wave steady state: a window of {lockin_cycles} cycles holds no step of dt = {dt:g} s")
+    if nw > int(n_steps):
+        raise ValueError(f"full-wave steady state: a window of {nw} steps ({lockin_cycles} cycles) does not fit the run of {n_steps} steps")
+    return int(n_steps) - nw, nw
+
+
+def lockin_angles(freq: float, dt: float, w0: int, nw: int):
+    """theta_n = 2 pi frac(freq t_n), t_n = (n + 1) dt, for the steps n of the window."""
+    ph = float(freq) * ((np.arange(int(w0), int(w0) + int(nw), dtype=np.float64) + 1.0) * float(dt))
+    return 2.0 * np.pi * (ph - np.floor(ph))
+
+
+def lockin_amplitude_phase(C, S, nw: int):
+    """Sums over a window of ``nw`` steps -> (amplitude A = 2 / nw hypot(C, S), lag psi = atan2(-C, S) / 2 pi [cycles] in (-1/2, 1/2]),
+    fp64: psi is the lag of p behind sin(2 pi f0 t), so a wave with travel time T has psi = f0 T (mod 1)."""
+    C, S = np.asarray(C, dtype=np.float64), np.asarray(S, dtype=np.float64)
+    psi = np.arctan2(-C, S) / (2.0 * np.pi)
+    return 2.0 / int(nw) * np.hypot(C, S), np.where(psi <= -0.5, 0.5, psi)
+
+
+def steady_state_run(params, pos_m, A, tau, freq, dt=0.0, t_end=0.0, cfl=0.3, ref_values_only=False, lockin_cycles=4, settle_cycles=3,
+                     ramp_cycles=2.0, pml_size=16, pml_alpha=2.0, receivers_m=None, volume=True, what="element"):
+    """One driven run of monopoles (``pos_m`` [E, 3] m, free-field amplitude ``A`` [Pa m], delay ``tau`` [s]) with the lock-in over its
+    last ``lockin_cycles`` cycles -> dict(C, S (cropped volumes or None), rec_C, rec_S (float64 [R] or None), dt, n_steps, window,
+    points_per_wavelength, cycles, t_end, medium = (c_ref, rho_ref, cs, rho)).  Every refusal is raised before any device call."""
+    pml_size = int(pml_size)
+    if pml_size < 0 or not (np.isfinite(pml_alpha) and pml_alpha >= 0):
+        raise ValueError(f"full-wave simulation: pml_size must be >= 0 and pml_alpha finite and >= 0, got {pml_size}, {pml_alpha}")
+    for name, v in (("lockin_cycles", lockin_cycles), ("settle_cycles", settle_cycles), ("ramp_cycles", ramp_cycles)):
+        if not (np.isfinite(v) and v >= 0):
+            raise ValueError(f"full-wave steady state: {name} must be finite and >= 0, got {v}")
+    if not lockin_cycles > 0:
+        raise ValueError(f"full-wave steady state: lockin_cycles must be > 0, got {lockin_cycles}")
+    coords = params.coords
+    origin, spacing, n = grid_from_coords(coords)
+    n = tuple(int(v) for v in n)
+    c_ref, rho_ref, cs, rho, alpha = _medium_of(params, freq, ref_values_only)
+    tau = np.asarray(tau, dtype=np.float64)
+    total = float(ramp_cycles) + float(settle_cycles) + float(lockin_cycles)
+    dt, n_steps, dt_max, ppw = fullwave_time_axis(spacing, n, cs, freq, total, tau, dt, t_end, cfl)
+    t_end = float(t_end)
+    if t_end == 0:      # (the default fullwave_time_axis has just taken: |n h| / c_min + max tau + total / freq)
+        h = np.broadcast_to(np.asarray(spacing, dtype=np.float64), (3,))
+        t_end = (float(np.sqrt(np.sum((np.asarray(n, dtype=np.float64) * h) ** 2))) / float(np.min(cs)) + (float(tau.max()) if tau.size else 0.0)
+                 + total / float(freq))
+    cycles = float(np.ceil(float(freq) * t_end) + 1.0)      # the drive lasts through the end of the run
+    w0, nw = lockin_window(n_steps, dt, freq, lockin_cycles)
+    ijk, amp, tt, _ = monopole_table(pos_m, A, tau, origin, spacing, n, cs, freq, dt, what=what)
+    row = r_ijk = r_w = None
+    if receivers_m is not None:
+        row, r_ijk, r_w = receiver_table(receivers_m, origin, spacing, n)
+    if not volume and row is None:
+        raise ValueError("full-wave steady state: neither the volume nor a receiver to record")
+    npad = tuple(v + 2 * pml_size for v in n)
+
+    def lin(v):
+        v = v + pml_size
+        return (v[:, 0] * npad[1] + v[:, 1]) * npad[2] + v[:, 2]
+
+    vols = [v if np.ndim(v) == 0 else pad_volume(v, pml_size) for v in (cs, rho, alpha)]
+    logging.info("Running full-wave steady-state simulation")
+    eng = get_engine()
+    vc, vs, rc, rs = eng.fullwave_steady(spacing, npad, vols, c_ref, pml_size, pml_alpha, dt, n_steps, (lin(ijk), amp, tt), freq, cycles, ramp_cycles,
+                                         window=(w0, nw), volume=bool(volume), receivers=None if row is None else (row, lin(r_ijk), r_w))
+    logging.info("Simulation Complete")
+    if row is not None and rc is None:      # an empty receiver table
+        rc = rs = np.zeros(0)
+    return {"C": None if vc is None else crop_volume(vc, pml_size), "S": None if vs is None else crop_volume(vs, pml_size), "rec_C": rc, "rec_S": rs,
+            "dt": dt, "n_steps": n_steps, "dt_max": dt_max, "window": (w0, nw), "points_per_wavelength": ppw, "cycles": cycles, "t_end": t_end,
+            "medium": (c_ref, rho_ref, cs, rho)}
+
+
+def run_fullwave_steady_state(arr, params, delays=None, apod=None, freq: float = 1e6, amplitude: float = 1, dt: float = 0, t_end: float = 0,
+                              cfl: float = 0.3, ref_values_only: bool = False, *, lockin_cycles: float = 4, settle_cycles: float = 3,
+                              ramp_cycles: float = 2.0, pml_size: int = 16, pml_alpha: float = 2.0, receivers=None):
+    """Steady state of one steering at the drive frequency -> (Dataset{p_max = p_min = A [Pa], intensity [W/cm^2], phase [cycles]} on
+    ``params.coords``, raw): the full-wave model driven through the end of the run, locked in at ``freq`` over its last ``lockin_cycles``
+    cycles (DESIGN.md section 2 "full-wave model", kernel section 5.15).
+
+    The drive ramps up over ``ramp_cycles`` and lasts ceil(freq t_end) + 1 cycles; t_end = 0 gives |n h| / c_min + max(delays) +
+    (ramp_cycles + settle_cycles + lockin_cycles) / freq.  The window is the last Nw = rint(lockin_cycles / (freq dt)) steps.  With the
+    sums C = sum p cos(theta_n), S = sum p sin(theta_n) over it, A = 2 / Nw hypot(C, S) and phase = atan2(-C, S) / 2 pi in (-1/2, 1/2],
+    the lag of p behind sin(2 pi freq t); Nw freq dt is not a whole number, so both carry a leakage of the order 1 / (2 Nw) that nothing
+    corrects.  intensity = 1e-4 A^2 / (2 rho c) with the impedance rules of ``run_fullwave_simulation``.  ``receivers`` [P, 3] in the
+    coordinates' units adds "receiver_amplitude", "receiver_phase" and "receiver_sums" (C_r + i S_r, trilinear weights) to ``raw``."""
+    n_el = arr.numelements()
+    delays = np.zeros(n_el) if delays is None else np.asarray(delays, dtype=np.float64)
+    apod = np.ones(n_el) if apod is None else np.asarray(apod, dtype=np.float64)
+    if delays.shape != (n_el,) or apod.shape != (n_el,):
+        raise ValueError(f"delays and apod must have shape ({n_el},), got {delays.shape} and {apod.shape}")
+    if not (np.all(np.isfinite(delays)) and np.all(np.isfinite(apod))):
+        raise ValueError("full-wave simulation: delays and apod must be finite")
+    coords = params.coords
+    rec_m = None
+    if receivers is not None:
+        dims = list(coords.dims) if hasattr(coords, "dims") else list(coords.keys())
+        rec = np.asarray(receivers, dtype=np.float64)
+        if rec.ndim != 2 or rec.shape[1] != 3:
+            raise ValueError(f"receivers must have shape (P, 3), got {rec.shape}")
+        rec_m = rec * getunitconversion(coords[dims[0]].attrs["units"], "m")
+    pos, _, area, _ = Engine._table_of(arr)
+    p0 = float(amplitude) * (1.0 if arr.sensitivity is None else float(arr.sensitivity))
+    c_ref = float(params["sound_speed"].attrs["ref_value"])
+    A0 = apod * np.asarray(area, dtype=np.float64) * p0 * float(freq) / c_ref
+    run = steady_state_run(params, pos, A0, delays, freq, dt, t_end, cfl, ref_values_only, lockin_cycles, settle_cycles, ramp_cycles, pml_size,
+                           pml_alpha, receivers_m=rec_m, volume=True)
+    w0, nw = run["window"]
+    A, psi = lockin_amplitude_phase(run["C"], run["S"], nw)
+    c_ref, rho_ref, cs, rho = run["medium"]
+    Z = _impedance(params, ref_values_only, c_ref, rho_ref, cs, rho)
+    inten = (1e-4 * A ** 2 / (2.0 * Z)).astype(np.float32)
+    A32, psi32 = A.astype(np.float32), psi.astype(np.float32)
+    dims = list(coords.dims) if hasattr(coords, "dims") else list(coords.keys())
+    out = {"p_max": ds.make_dataarray(A32, coords=coords, dims=dims, name="p_max", attrs=_ATTRS["p_max"]),
+           "p_min": ds.make_dataarray(A32.copy(), coords=coords, dims=dims, name="p_min", attrs=_ATTRS["p_min"]),
+           "intensity": ds.make_dataarray(inten, coords=coords, dims=dims, name="I", attrs=_ATTRS["intensity"]),
+           "phase": ds.make_dataarray(psi32, coords=coords, dims=dims, name="phase", attrs=PHASE_ATTRS)}
+    raw = {"dt": run["dt"], "n_steps": run["n_steps"], "dt_max": run["dt_max"], "window": (w0, nw), "points_per_wavelength": run["points_per_wavelength"],
+           "cycles": run["cycles"], "t_end": run["t_end"], "backend": "openlifu_amd/hip-gfx950"}
+    if rec_m is not None:
+        ra, rp = lockin_amplitude_phase(run["rec_C"], run["rec_S"], nw)
+        raw["receiver_amplitude"], raw["receiver_phase"] = ra, rp
+        raw["receiver_sums"] = np.asarray(run["rec_C"], dtype=np.float64) + 1j * np.asarray(run["rec_S"], dtype=np.float64)
+    return ds.make_dataset(out), raw

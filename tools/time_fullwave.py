@@ -2,12 +2,15 @@
 """Time kernel 5 (full-wave model, k_fullwave.hip): ms per step and achieved bytes/s at 256^3 plus absorbing layers, for the uniform
 instantiation and for a skull-slab medium (five coefficient volumes streamed).
 
-  python tools/time_fullwave.py [--n 256] [--pml 16] [--steps 300] [--out profiles/fullwave_time.json]
+  python tools/time_fullwave.py [--n 256] [--pml 16] [--steps 300] [--lockin] [--out profiles/fullwave_time.json]
 
 A run of --steps steps is bracketed by olx_sync (after one untimed warm-up run of 20 steps); the step is three launches (inject,
 velocity, pressure-and-record).  Bytes per voxel and step are the compulsory traffic of DESIGN.md section 5.14 -- every volume a launch
 reads or writes counted once, stencil neighbours served by the caches: 64 B uniform, 84 B with a medium, + 8 B with sum p^2.  The
-achieved bytes/s are set against the 6.29 TB/s a device-to-device copy reaches on this part."""
+achieved bytes/s are set against the 6.29 TB/s a device-to-device copy reaches on this part.
+
+--lockin adds, per medium, runs whose lock-in window is the whole run: the volume sums (+ 16 B per voxel and
+step: C and S read and written), and the volume sums with 64 receivers of 8 entries each (one more launch of one block per step)."""
 import argparse
 import json
 import os
@@ -31,6 +34,7 @@ def main():
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--pml", type=int, default=16)
     ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--lockin", action="store_true", help="also time the steps inside a lock-in window")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     n = a.n + 2 * a.pml
@@ -60,6 +64,23 @@ def main():
             tbps = b * vox / (ms * 1e-3) / 1e12
             rows.append({"medium": name, "sum_p2": psq, "grid": list(shape), "steps": a.steps, "ms_per_step": round(ms, 4), "bytes_per_voxel_step": b,
                          "achieved_TBps": round(tbps, 3), "fraction_of_copy": round(tbps / COPY_TBPS, 3)})
+            print(json.dumps(rows[-1]), flush=True)
+        if not a.lockin:
+            continue
+        rng = np.random.default_rng(0)
+        table = dict(row=np.arange(65) * 8, voxels=rng.integers(0, vox, 64 * 8), weights=np.full(64 * 8, 0.125))
+        for label, kw in (("volume", {}), ("volume + 64 receivers", table)):
+            ctx.fullwave_lockin(500e3, 0, a.steps, volume=True, **kw)
+            ctx.fullwave_run(0, 20)
+            ctx.sync()
+            t0 = time.perf_counter()
+            ctx.fullwave_run(0, a.steps)
+            ctx.sync()
+            ms = (time.perf_counter() - t0) * 1e3 / a.steps
+            b = BYTES[name] + 16
+            tbps = b * vox / (ms * 1e-3) / 1e12
+            rows.append({"medium": name, "sum_p2": False, "lockin": label, "grid": list(shape), "steps": a.steps, "ms_per_step": round(ms, 4),
+                         "bytes_per_voxel_step": b, "achieved_TBps": round(tbps, 3), "fraction_of_copy": round(tbps / COPY_TBPS, 3)})
             print(json.dumps(rows[-1]), flush=True)
     ctx.close()
     if a.out:
