@@ -91,6 +91,8 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
     if (npos <= 0) return;                              // block-uniform
     const int ibase = BK.ibase, jbase = BK.jbase;
     const int k0 = BK.k0;
+    // (Wave 0 always holds the extra tile of a 33-position block, but the dispatcher starts a block's waves on a different SIMD from block to block: over a
+    // launch every SIMD of a CU carries the same number of tiles as it is.  Rotating the ownership per record made the launch 1.4 % slower: DESIGN 5.6.)
     const int ntile = __builtin_amdgcn_readfirstlane((npos - wave + COS_NW - 1) / COS_NW);      // this wave's positions: wave, wave + 8, ... (wave-uniform, <= MT)
     // table generation role (planes 2 wave, 2 wave + 1): full form lane -> (wl = lane / 12 < 5, ui = lane % 12), round r: rows 5 r + wl; reuse form 8 x 8 (the fill lambda below).
     // (Its per-lane constants are formed inside the pair loop from an opaque copy of the lane index: hoisted, they would be live
@@ -259,7 +261,14 @@ __global__ __launch_bounds__(COS_NW * 64, 4) void field_cosetp_k(
         }
     };
     request(0, tid);        // the first pair: always there (n_sb >= PAIR)
+    OLX_CUTRACE(1, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) | ((unsigned long long)ntile << 8));      // XCC_ID | the wave's tiles << 8
     OLX_STAMP(0);
+#ifdef OLX_EXP_STAMPS   // developer build only (tools/stamps_cosetp.py splits the phases by it): the wave's tile count in the low 3 bits of stamp 0
+    if (lane == 0 && wave < 4 && blockIdx.y == 0 && blockIdx.x % 37 == 0 && blockIdx.x / 37 < 1024) {
+        unsigned long long& s0 = g_stamps[(blockIdx.x / 37) * 4 + wave][0];
+        s0 = (s0 & ~7ull) | (unsigned long long)ntile;
+    }
+#endif
     for (int sb0 = 0; sb0 < n_sb; sb0 += PAIR) {
         const int sa = sb0 / nsbp, sbb0 = sb0 - sa * nsbp;       // the pair (sa, sbb0), (sa, sbb0 + 1)
         // previous pair consumed: steering stage and tables are free.  (Not before the first pair: nothing to protect yet, and

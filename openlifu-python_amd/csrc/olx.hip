@@ -564,6 +564,7 @@ static olxplan::Pins read_pins() {
     if (const char* e = getenv("OLX_EXP_KGRP")) pins.kgrp = std::max(1, atoi(e));
     { const char* e = getenv("OLX_EXP_CP_NOREUSE"); pins.cp_noreuse = e && atoi(e) != 0; }
     { const char* e = getenv("OLX_EXP_CP_NOFILLAHEAD"); pins.cp_nofillahead = e && atoi(e) != 0; }
+    { const char* e = getenv("OLX_EXP_CP_NOSORT"); pins.cp_nosort = e && atoi(e) != 0; }
 #endif
     return pins;
 }
@@ -833,7 +834,7 @@ int olx_field_plan(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n_fo
         // derived below is still valid -- an interactive caller re-plans per target while only the steering changes.  The steering-
         // dependent part (configure_variant + packing) is redone at the next launch anyway when the table changed.
         std::string env;   // the developer switches the plan below reads
-        for (const char* name : {"OLX_FIELD_VARIANT", "OLX_FP8_CORRECTION", "OLX_EXP_TOEP_SAW", "OLX_EXP_TOEP_NM", "OLX_EXP_KGRP", "OLX_INTENSITY_STORED", "OLX_EXP_CP_NOREUSE", "OLX_EXP_CP_NOFILLAHEAD"}) { const char* e = getenv(name); env += e ? e : ""; env += '|'; }
+        for (const char* name : {"OLX_FIELD_VARIANT", "OLX_FP8_CORRECTION", "OLX_EXP_TOEP_SAW", "OLX_EXP_TOEP_NM", "OLX_EXP_KGRP", "OLX_INTENSITY_STORED", "OLX_EXP_CP_NOREUSE", "OLX_EXP_CP_NOFILLAHEAD", "OLX_EXP_CP_NOSORT"}) { const char* e = getenv(name); env += e ? e : ""; env += '|'; }
         const bool same = c->planned && !c->uploaded && !c->hetero && !c->pulsed && memcmp(&c->grid, g, sizeof *g) == 0 && c->slab.x_begin == s.x_begin &&
                           c->slab.x_count == s.x_count && c->plan_foci == n_foci && c->freq == freq && c->c == cs && c->rho == rho &&
                           c->p0_pa == p0_pa && c->flags == flags && c->plan_absorb == c->absorb_np_m && c->nbuf == (c->comm_active() ? olx_ctx::NBUF : 1) && c->plan_env == env;

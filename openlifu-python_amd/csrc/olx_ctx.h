@@ -105,7 +105,7 @@ struct olx_ctx {
     bool use_coset = false; bool fp8corr = false; CosetParams cp{}; DevBuf<int> d_jobs;   // kernel 2e (whole cosets per wave) instead of 2d's row tiles
     // kernel 2f (one steering column: Toeplitz weights stationary, 16 planes per MFMA tile)
     DevBuf<CosetBlock> d_cpblocks; unsigned cp_nblocks = 0;   // kernel 2g block records
-    int up_blocks_key[16] = {0};               // the partition up_blocks was derived from
+    int up_blocks_key[17] = {0};              // the partition up_blocks was derived from
     std::vector<CosetBlock> up_blocks; std::vector<int> up_jobs, up_slot;   // host copies of what d_cpblocks / d_jobs / d_slot hold (re-uploaded only when they change)
     std::vector<int> up_perm, up_colinfo;                                  // ... and of d_perm / d_colinfo (a new target of the same pattern changes none of them)
     bool use_cosetp = false;   // kernel 2g: 2e's NT = 2 shape with the planes in the MFMA rows (no output staging)

@@ -172,11 +172,31 @@ void coset_partition(CosetParams& Q, int kxw, int zb, int kyw) {
 // blockIdx.x -> (coset, part, plane block), in the kernels' former decode order (the two blocks that write the two 64-byte halves of the
 // same 128-byte lines get ids 8 apart = same XCD under round-robin dispatch)
 bool build_coset_blocks(const CosetParams& Q, int zb, unsigned grp, int max_pos,
-                        std::vector<CosetBlock>& blk, std::string& msg) {
+                        std::vector<CosetBlock>& blk, std::string& msg, bool heavy_first) {
     const int px = Q.xs * Q.mx;
     const unsigned nblk = (unsigned)(px * Q.my * Q.nsx * Q.nsy * Q.kblocks);
     blk.assign(nblk, CosetBlock{});
     const int wx = Q.nx - Q.x_lo, wy = Q.ny - Q.y_lo;
+    // heavy_first (kernel 2g): the position sets are issued in the order of falling position count (stable) instead of the coset order, so that a CU's two
+    // resident blocks are of one size for most of the launch and its last round is made of the lightest blocks (headline: 33-, 30-, 22-, then 20-position
+    // blocks; measured in DESIGN 5.5).  The plane blocks of a set stay in a row on one XCD as before.  set_order: slot in the issue order -> position set.
+    std::vector<unsigned> set_order;
+    if (heavy_first) {
+        const unsigned nsets = (unsigned)(px * Q.my * Q.nsx * Q.nsy);
+        std::vector<int> npos_of(nsets);
+        for (unsigned u = 0; u < nsets; ++u) {
+            unsigned b = u;
+            const int sy_part = (int)(b % (unsigned)Q.nsy); b /= (unsigned)Q.nsy;
+            const int sx_part = (int)(b % (unsigned)Q.nsx); b /= (unsigned)Q.nsx;
+            const int ry = (int)(b % (unsigned)Q.my), rx = (int)(b / (unsigned)Q.my);
+            const int kx_all = rx < wx ? (wx - 1 - rx) / px + 1 : 0, ky_all = ry < wy ? (wy - 1 - ry) / Q.my + 1 : 0;
+            const int KX = (sx_part + 1) * kx_all / Q.nsx - sx_part * kx_all / Q.nsx, KY = (sy_part + 1) * ky_all / Q.nsy - sy_part * ky_all / Q.nsy;
+            npos_of[u] = (KX > 0 && KY > 0) ? KX * KY : 0;
+        }
+        set_order.resize(nsets);
+        for (unsigned u = 0; u < nsets; ++u) set_order[u] = u;
+        std::stable_sort(set_order.begin(), set_order.end(), [&](unsigned a, unsigned c) { return npos_of[a] > npos_of[c]; });
+    }
     for (unsigned id = 0; id < nblk; ++id) {
         unsigned b = id;
         int kblock, ry_lo = 0;
@@ -190,6 +210,7 @@ bool build_coset_blocks(const CosetParams& Q, int zb, unsigned grp, int max_pos,
             const unsigned xcd = b % 8, sft = b / 8, kb_lo = sft % grp, u = (sft / grp) * 8 + xcd, part = (unsigned)Q.kblocks / grp;
             kblock = (int)(grp * (u % part) + kb_lo); b = u / part;
         } else { kblock = (int)(b % (unsigned)Q.kblocks); b /= (unsigned)Q.kblocks; }
+        if (gy == 1 && !set_order.empty()) b = set_order[b];      // (y cosets grouped on an XCD keep their order: a slot there is a group of sets)
         const int sy_part = (int)(b % (unsigned)Q.nsy); b /= (unsigned)Q.nsy;
         const int sx_part = (int)(b % (unsigned)Q.nsx); b /= (unsigned)Q.nsx;
         const unsigned myh = (unsigned)Q.my / gy;
@@ -622,6 +643,7 @@ static VariantPlan decide_pass(const VariantIn& in, std::vector<double>& nf_s2, 
                 Q.cp_noreuse = pins.cp_noreuse ? 1 : 0;             // (A/B) kernel 2g fills every table pair in full; the variant name says "noreuse"
                 Q.cp_nofillahead = pins.cp_nofillahead ? 1 : 0;     // (A/B) kernel 2g keeps the reuse fill a phase of its own; the variant name says "nofillahead"
 #endif
+                p.heavy_first = p.use_cosetp && !pins.cp_nosort;    // kernel 2g's position sets heaviest first ((A/B) OLX_EXP_CP_NOSORT=1: the coset order; the variant name says "nosort")
                 Q.dir_wx = (p.dir_lattice && in.directivity) ? (float)(0.5 * in.size0 / lambda) : 0.f;      // element width / length over 2 lambda (DIR instantiations)
                 Q.dir_wy = (p.dir_lattice && in.directivity) ? (float)(0.5 * in.size1 / lambda) : 0.f;
                 Q.absorb_l2 = p.dir_lattice ? (float)(in.absorb_np_m * lambda * 1.4426950408889634) : 0.f;   // exp(-a d) = exp2(-a lambda log2(e) d'), d' [wavelengths]
@@ -645,7 +667,8 @@ static VariantPlan decide_pass(const VariantIn& in, std::vector<double>& nf_s2, 
                     const int kb_near = kcut / zb, kb_far = Q.kblocks - kb_near;
                     p.kgrp = pick_grp(kb_far); p.kgrp_near = kb_near > 0 ? pick_grp(kb_near) : 0u;
                     if (pins.kgrp > 0) { p.kgrp = (unsigned)pins.kgrp; if (kb_near > 0) p.kgrp_near = p.kgrp; }
-                    const int rec_key[16] = {Q.nx, Q.ny, Q.nz, Q.x_lo, Q.y_lo, Q.mx, Q.my, Q.nsx, Q.nsy, Q.kblocks, zb, (int)p.kgrp, p.use_cosetp ? 40 : 0, Q.xs, kcut, (int)p.kgrp_near};
+                    const int rec_key[17] = {Q.nx, Q.ny, Q.nz, Q.x_lo, Q.y_lo, Q.mx, Q.my, Q.nsx, Q.nsy, Q.kblocks, zb, (int)p.kgrp, p.use_cosetp ? 40 : 0, Q.xs, kcut, (int)p.kgrp_near,
+                                             p.heavy_first ? 1 : 0};
                     memcpy(p.rec_key, rec_key, sizeof rec_key);
                     p.blocks_near = (unsigned)((unsigned long long)Q.xs * Q.mx * Q.my * Q.nsx * Q.nsy * kb_near);
                 }
@@ -688,7 +711,8 @@ static VariantPlan decide_pass(const VariantIn& in, std::vector<double>& nf_s2, 
                         p.n_mfma = (long long)((double)npos_all * Q.kblocks * A.nsa * A.nsb * 4 * p.nt * corr_units * ntiles);
                     }
 #ifdef OLX_DEV_PINS
-                    const std::string pin_tags = std::string((p.use_cosetp && pins.cp_noreuse) ? ",noreuse" : "") + ((p.use_cosetp && pins.cp_nofillahead) ? ",nofillahead" : "");
+                    const std::string pin_tags = std::string((p.use_cosetp && pins.cp_noreuse) ? ",noreuse" : "") + ((p.use_cosetp && pins.cp_nofillahead) ? ",nofillahead" : "") +
+                                                 ((p.use_cosetp && pins.cp_nosort) ? ",nosort" : "");
 #else
                     const std::string pin_tags;      // (the product cannot name the tags: tests/test_gpu_cosetp_fill_ahead.py)
 #endif
@@ -734,12 +758,12 @@ bool build_variant_blocks(const VariantPlan& p, std::vector<CosetBlock>& blk, st
     const int zb = COS_ZB, kcut = p.fp8corr ? p.fp8_kcut : 0, kb_near = kcut / zb, max_pos = p.use_cosetp ? 40 : 0;
     // each side of the cut gets its own record list (plane blocks of a position set in a row per XCD within the side)
     CosetParams Qf = p.cp; Qf.kblocks = p.cp.kblocks - kb_near;
-    if (!build_coset_blocks(Qf, zb, p.kgrp, max_pos, blk, msg)) return false;
+    if (!build_coset_blocks(Qf, zb, p.kgrp, max_pos, blk, msg, p.heavy_first)) return false;
     for (CosetBlock& b : blk) b.k0 += kcut;
     if (kb_near > 0) {
         std::vector<CosetBlock> near;
         CosetParams Qn = p.cp; Qn.kblocks = kb_near;
-        if (!build_coset_blocks(Qn, zb, p.kgrp_near, max_pos, near, msg)) return false;
+        if (!build_coset_blocks(Qn, zb, p.kgrp_near, max_pos, near, msg, p.heavy_first)) return false;
         blk.insert(blk.end(), near.begin(), near.end());
     }
     return true;

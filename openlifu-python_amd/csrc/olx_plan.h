@@ -68,7 +68,8 @@ void coset_partition(CosetParams& Q, int kxw, int zb, int kyw = olx::COS_KYW);
 
 // Block records of kernels 2e / 2f / 2g: blockIdx.x -> (coset, part, plane block).  zb = planes per block, grp = blocks that share
 // 128-byte output lines (ids 8 apart = one XCD).  Returns false (msg) when a part exceeds max_pos positions (0 = no limit).
-bool build_coset_blocks(const CosetParams& Q, int zb, unsigned grp, int max_pos, std::vector<CosetBlock>& blk, std::string& msg);
+// heavy_first (kernel 2g): the position sets in the order of falling position count (stable) instead of the coset order.
+bool build_coset_blocks(const CosetParams& Q, int zb, unsigned grp, int max_pos, std::vector<CosetBlock>& blk, std::string& msg, bool heavy_first = false);
 
 // dense store-job lists of kernel 2e per (launch tile, column tile): job = c16 | image << 4 | focus << 6; entry [jobs_per_tile] = log2 ceil
 std::vector<int> build_store_jobs(const Tiles& tiles, int max_nt, int cols_per_nt, int jobs_per_tile, bool want_p, bool want_i);
@@ -131,6 +132,7 @@ struct Pins {
     int toep_saw = 0, toep_nm = 0;             // OLX_EXP_TOEP_SAW (8 .. 24), OLX_EXP_TOEP_NM (1 | 3); 0 = none
     int kgrp = 0;                              // OLX_EXP_KGRP (>= 1); 0 = none
     bool cp_noreuse = false, cp_nofillahead = false;      // OLX_EXP_CP_NOREUSE, OLX_EXP_CP_NOFILLAHEAD
+    bool cp_nosort = false;                    // OLX_EXP_CP_NOSORT: kernel 2g's position sets in the coset order, not heaviest first
 };
 
 // What olx_field_plan established and what the steering provides: values and read-only arrays
@@ -176,7 +178,8 @@ struct VariantPlan {
     olx::MfmaParams mp{}; olx::LatParams lp{}; olx::CosetParams cp{};
     unsigned kgrp = 1, kgrp_near = 0;          // plane blocks of one position set in a row per XCD, above / below the cut
     unsigned blocks_near = 0;                  // block records of the plane blocks below the cut (they follow the others)
-    int rec_key[16] = {0};                     // everything build_coset_blocks reads: the caller rebuilds its block records only when this changes
+    bool heavy_first = false;                  // kernel 2g: the position sets of the block records in the order of falling position count
+    int rec_key[17] = {0};                     // everything build_variant_blocks reads: the caller rebuilds its block records only when this changes
     long long n_mfma = 0, n_dense = 0;
     std::string variant;
 };

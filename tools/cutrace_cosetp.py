@@ -66,7 +66,48 @@ for k in np.unique(key):
 gaps = np.array(gaps)
 print(f"per CU: span {np.median(spans):.0f} cycles, blocks {nb / len(np.unique(key)):.1f}, slot occupancy (2 slots) {np.median(busy):.3f}")
 print("  slot freed (last ack of the leaving block) -> next block's first wave in:", q(gaps), f" mean {gaps.mean():.0f}")
+print(f"  span over the CUs (first wave in -> last ack; the launch ends with the slowest CU): median {np.median(spans):.0f}, p90 {np.percentile(spans, 90):.0f}, max {np.max(spans):.0f} cycles"
+      f" = {np.max(spans) / np.median(spans):.4f} of the median")
+# the tail: how long a CU's last block runs alone (the other slot already empty for good)
+alone = []
+for k in np.unique(key):
+    m = key == k
+    e = np.sort(t_ack[m])
+    alone.append(e[-1] - e[-2])
+print(f"  a CU's last block outlives its second-last by (cycles, median / p10 / p90): {q(np.array(alone))}; size of the last block started per CU (tiles of wave 0):",
+      np.bincount([int(((b[np.where(key == k)[0][np.argmax(t_in[key == k])], 0, 1]) >> 8) & 0xFF) for k in np.unique(key)], minlength=6).tolist())
 print(f"  sum of gaps per slot {gaps.sum() / (2 * len(np.unique(key))):.0f} cycles = {gaps.sum() / (2 * len(np.unique(key))) / np.median(spans):.3f} of the span")
+# ---- where the waves of a block sit: HW_ID's SIMD field per (block, wave), and the tiles each SIMD of a CU carries over the launch
+simd = (b[:, :, 0] >> 4) & 3
+ntile = (b[:, :, 1] >> 8) & 0xFF
+print("wave -> SIMD (HW_ID bits 5:4):")
+print("  SIMD of wave 0 over the blocks:", np.bincount(simd[:, 0], minlength=4).tolist())
+rel = (simd - simd[:, :1]) & 3
+pats, cnts = np.unique(rel, axis=0, return_counts=True)
+for pat, cnt in sorted(zip(pats.tolist(), cnts.tolist()), key=lambda t: -t[1])[:6]:
+    print(f"  SIMD of waves 0 .. 7 relative to wave 0's: {pat} on {cnt} blocks")
+print("  blocks per SIMD count of a block (4 = two waves on each):", np.bincount([len(set(r)) for r in simd.tolist()], minlength=5).tolist())
+per = np.zeros((len(np.unique(key)), 4))
+for ci, k in enumerate(np.unique(key)):
+    m = key == k
+    per[ci] = np.bincount(simd[m].ravel(), weights=ntile[m].ravel().astype(float), minlength=4)
+tot = per.sum(axis=0)
+print("  tiles per SIMD over the launch (all CUs):", tot.astype(int).tolist(), " vs mean:", np.round(tot / tot.mean() - 1, 4).tolist())
+srt = np.sort(per, axis=1)[:, ::-1]
+print("  per CU, SIMDs sorted by load: mean tiles", np.round(srt.mean(axis=0), 1).tolist(), " busiest / mean of the CU:", f"{(srt[:, 0] / per.mean(axis=1)).mean():.4f}",
+      f"(p10 {np.percentile(srt[:, 0] / per.mean(axis=1), 10):.4f}, p90 {np.percentile(srt[:, 0] / per.mean(axis=1), 90):.4f})")
+five = (ntile == 5)
+if five.any():
+    print("  SIMD of the five-tile waves:", np.bincount(simd[five], minlength=4).tolist())
+# the two blocks resident on a CU at a time: for each block the block of the same CU that started last before it -- do their most loaded SIMDs coincide?
+heavy = np.array([np.bincount(simd[i], weights=ntile[i].astype(float), minlength=4).argmax() for i in range(nb)])
+uneven = np.array([np.ptp(np.bincount(simd[i], weights=ntile[i].astype(float), minlength=4)) > 0 for i in range(nb)])
+same = tot_pairs = 0
+for k in np.unique(key):
+    m = np.where((key == k) & uneven)[0]
+    o = m[np.argsort(t_in[m])]
+    same += int((heavy[o[1:]] == heavy[o[:-1]]).sum()); tot_pairs += len(o) - 1
+print(f"  blocks that follow each other on a CU (uneven ones): most loaded SIMD the same in {same} of {tot_pairs} pairs ({same / max(tot_pairs, 1):.3f}; 0.25 = by chance)")
 if "--dump" in sys.argv[1:]:
     k = np.unique(key)[3]
     m = np.where(key == k)[0]

@@ -6,7 +6,8 @@
 //   columns      every (focus, image) is a store target of exactly one column, all targets of a column carry the same steering vector,
 //                tiles hold at most maxc columns, at most 4 (2 after balancing, where slots were free) targets per column
 //   blocks       the positions of all records x their plane blocks cover every voxel of the computed region exactly once, lie inside it,
-//                respect the per-part limit, and the kernels' magic division pos / KY is exact for every position
+//                respect the per-part limit, and the kernels' magic division pos / KY is exact for every position; kernel 2g's order (the position
+//                sets heaviest first) covers the same voxels, keeps the plane blocks of a set 8 ids apart, and its position counts never rise along an XCD
 //   store jobs   the dense job lists name exactly the targets of their columns
 //   foci         geometric delays are recognised and reproduce the foci; scrambled delays are refused
 //   mirrors      every row of mirror_perms is a permutation and an involution, row 0 and the rows past the image count are the identity, the row of
@@ -236,8 +237,9 @@ static void check_shape(const Shape& S, std::mt19937_64& rng, int nt_force) {
         coset_partition(Q, fm.kxw, fm.zb);
         std::vector<CosetBlock> blk;
         std::string why;
-        {
-            const bool ok = build_coset_blocks(Q, fm.zb, fm.grp, fm.max_pos, blk, why);
+        for (const bool heavy : {false, true}) {      // kernel 2g's records also with the position sets in the order of falling position count
+            if (heavy && fm.max_pos == 0) continue;
+            const bool ok = build_coset_blocks(Q, fm.zb, fm.grp, fm.max_pos, blk, why, heavy);
             CHECK(ok, "%s: %s", fm.name, why.c_str());
             if (!ok) continue;
             CHECK(blk.size() == (size_t)(Q.xs * Q.mx * Q.my * Q.nsx * Q.nsy * Q.kblocks), "record count");
@@ -260,6 +262,15 @@ static void check_shape(const Shape& S, std::mt19937_64& rng, int nt_force) {
             for (unsigned char v : cover) bad += v != 1;
             CHECK(bad == 0, "%s: %zu (voxel column, plane block) cells not covered exactly once (grid %dx%dx%d pitch %dx%d fold %d%d slab %d+%d)", fm.name, bad, S.n[0], S.n[1], S.n[2],
                   S.mxv, S.myv, mxf, myf, S.x_begin, S.x_count);
+            // heaviest sets first: along every XCD's records (where a set's plane blocks stand in a row there, or every record is a set of its own) the position count never rises
+            if (heavy && (fm.grp <= (unsigned)Q.kblocks || blk.size() % (8 * fm.grp) != 0)) {
+                const bool rows = fm.grp <= (unsigned)Q.kblocks && (Q.kblocks % fm.grp) == 0 && blk.size() % (8 * fm.grp) == 0;
+                if (rows && (unsigned)Q.kblocks == fm.grp) {
+                    for (size_t id = 8; id < blk.size(); ++id) CHECK(blk[id].npos <= blk[id - 8].npos, "heaviest first: record %zu has %d positions behind %d", id, blk[id].npos, blk[id - 8].npos);
+                } else if (!rows) {
+                    for (size_t id = (size_t)Q.kblocks; id < blk.size(); ++id) CHECK(blk[id].npos <= blk[id - Q.kblocks].npos, "heaviest first: record %zu has %d positions behind %d", id, blk[id].npos, blk[id - Q.kblocks].npos);
+                }
+            }
             // the records that share z lines (plane blocks j, j + 1, ... of one part) sit 8 ids apart = one XCD (when the id space allows it)
             if (fm.grp >= 2 && fm.grp <= (unsigned)Q.kblocks && (Q.kblocks % fm.grp) == 0 && blk.size() % (8 * fm.grp) == 0)
                 for (size_t id = 0; id + 8 < blk.size(); ++id)
@@ -346,8 +357,9 @@ static void check_decision(const Geometry& G, int F, bool cplx, bool absorb) {
     CHECK(!p.use_toep || (p.total_cols == 1 && p.toep.nm >= 1 && p.toep.nm <= TOEP_MAX_NM), "decision: kernel 2f with %d columns, %d row tiles", p.total_cols, p.toep.nm);
     // the record key: it names every quantity build_coset_blocks reads, and plans with one key have the same records (what the caller's cache relies on)
     const int kcut = p.fp8corr ? p.fp8_kcut : 0;
-    const int key[16] = {Q.nx, Q.ny, Q.nz, Q.x_lo, Q.y_lo, Q.mx, Q.my, Q.nsx, Q.nsy, Q.kblocks, COS_ZB, (int)p.kgrp, p.use_cosetp ? 40 : 0, Q.xs, kcut, (int)p.kgrp_near};
-    CHECK(std::equal(key, key + 16, p.rec_key), "decision: the record key misses a quantity the block records depend on (%s)", v);
+    const int key[17] = {Q.nx, Q.ny, Q.nz, Q.x_lo, Q.y_lo, Q.mx, Q.my, Q.nsx, Q.nsy, Q.kblocks, COS_ZB, (int)p.kgrp, p.use_cosetp ? 40 : 0, Q.xs, kcut, (int)p.kgrp_near, p.use_cosetp ? 1 : 0};      // (kernel 2g: its position sets heaviest first)
+    CHECK(std::equal(key, key + 17, p.rec_key), "decision: the record key misses a quantity the block records depend on (%s)", v);
+    CHECK(p.heavy_first == p.use_cosetp, "decision: heaviest sets first is kernel 2g's order and no other kernel's (%s)", v);
     std::vector<CosetBlock> blk;
     std::string why;
     const bool ok = build_variant_blocks(p, blk, why);
@@ -355,7 +367,7 @@ static void check_decision(const Geometry& G, int F, bool cplx, bool absorb) {
     if (!ok) return;
     CHECK(blk.size() == (size_t)Q.xs * Q.mx * Q.my * Q.nsx * Q.nsy * Q.kblocks && p.blocks_near <= blk.size() && p.blocks_near == (size_t)Q.xs * Q.mx * Q.my * Q.nsx * Q.nsy * (kcut / COS_ZB),
           "decision: %zu block records, %u below the cut", blk.size(), p.blocks_near);
-    const auto hit = g_records_of_key.emplace(std::vector<int>(p.rec_key, p.rec_key + 16), blk);
+    const auto hit = g_records_of_key.emplace(std::vector<int>(p.rec_key, p.rec_key + 17), blk);
     if (!hit.second) CHECK(hit.first->second.size() == blk.size() && !memcmp(hit.first->second.data(), blk.data(), blk.size() * sizeof(CosetBlock)), "decision: two plans with one record key, different block records (%s)", v);
 }
 

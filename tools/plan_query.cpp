@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../openlifu-python_amd/csrc/olx_plan.h"
@@ -67,16 +68,16 @@ int olq_fp8_first_plane(int n, const double* pos, const double* area, const doub
 
 int olq_fp8_split_pays(int x_count, int ny, int nz, int F, int cut) { return fp8_split_pays(x_count, ny, nz, F, cut) ? 1 : 0; }
 
-// The variant string of the real decision (decide_variant) for a plan described by plain values; returns its length, the string itself in out (cap bytes).
+// The real decision (decide_variant) for a plan described by plain values; olq_variant returns the length of its variant string, the string itself in out (cap bytes).
 //   pos = [3][n] (SoA) [m], area = [n], delays / apod = [F][n], foci = [F][3] [m] or null (not known), flags = the plan flags of include/olx.h
 //   mods = {the elements are flat, axis-aligned and of equal size (what lets the per-term factors into the lattice tables), intensity stored (OLX_INTENSITY_STORED)},
 //   elem = {width, length of element 0 [m], uniform absorption [Np/m]}, family_pin / fp8_pin = OLX_FIELD_VARIANT / OLX_FP8_CORRECTION or null,
 //   medium = null (homogeneous) or {marched, one-sum, non-trivial planes, layers, planes per layer} as olx_field_set_medium established them.
 // What olx_field_plan derives from these before it asks for the decision -- flatness, the clamp and near classes, the lattice, the mirror folds, the family
 // pin's kind -- is derived here in the same way; a build with -DOLX_DEV_PINS honours the forcing value of fp8_pin as the developer library does.
-int olq_variant(int n, const double* pos, const double* area, int F, const double* delays, const double* apod, const double* foci, const double* origin,
-                const double* spacing, const int* gn, int x_begin, int x_count, double freq, double c, double rho, double p0_pa, unsigned flags, const int* mods,
-                const double* elem, const char* family_pin, const char* fp8_pin, const int* medium, char* out, int cap) {
+static VariantPlan plan_of(int n, const double* pos, const double* area, int F, const double* delays, const double* apod, const double* foci, const double* origin,
+                           const double* spacing, const int* gn, int x_begin, int x_count, double freq, double c, double rho, double p0_pa, unsigned flags, const int* mods,
+                           const double* elem, const char* family_pin, const char* fp8_pin, const int* medium) {
     constexpr unsigned DIRECTIVITY = 16u;      // OLX_FIELD_DIRECTIVITY
     VariantIn in;
     in.n = n; in.F = F; in.pos = pos; in.area = area; in.delays = delays; in.apod = apod; in.foci = foci;
@@ -151,9 +152,33 @@ int olq_variant(int n, const double* pos, const double* area, int F, const doubl
     if (!in.foci && !in.hetero && variant_reads_foci(in) && infer_foci(in.flat, n, F, pos, delays, c, origin[2] + 0.5 * (gn[2] - 1) * spacing[2], inferred)) in.foci = inferred.data();
     std::vector<double> nf_s2;
     int slot_rows = L.nsbp;
-    const VariantPlan p = decide_variant(in, nf_s2, slot_rows);
+    return decide_variant(in, nf_s2, slot_rows);
+}
+
+int olq_variant(int n, const double* pos, const double* area, int F, const double* delays, const double* apod, const double* foci, const double* origin,
+                const double* spacing, const int* gn, int x_begin, int x_count, double freq, double c, double rho, double p0_pa, unsigned flags, const int* mods,
+                const double* elem, const char* family_pin, const char* fp8_pin, const int* medium, char* out, int cap) {
+    const VariantPlan p = plan_of(n, pos, area, F, delays, apod, foci, origin, spacing, gn, x_begin, x_count, freq, c, rho, p0_pa, flags, mods, elem, family_pin, fp8_pin, medium);
     snprintf(out, (size_t)cap, "%s", p.variant.c_str());
     return (int)p.variant.size();
+}
+
+// The block records of the same plan as the launches read them (build_variant_blocks: kernel 2g's position sets heaviest first): 8 ints per record
+// {ibase, jbase, k0, npos, KY, ky_magic, KX, 0} into rec (cap records), *n_near = the records of the launch below the e4m3 cut (they come last; each
+// side is a launch of its own, ids from 0), *is_2g = the plan launches kernel 2g.  Returns the record count, 0 for a plan without coset records, -1 when
+// the records are refused.
+int olq_blocks(int n, const double* pos, const double* area, int F, const double* delays, const double* apod, const double* foci, const double* origin,
+               const double* spacing, const int* gn, int x_begin, int x_count, double freq, double c, double rho, double p0_pa, unsigned flags, const int* mods,
+               const double* elem, const char* family_pin, const char* fp8_pin, const int* medium, int* rec, int cap, int* n_near, int* is_2g) {
+    const VariantPlan p = plan_of(n, pos, area, F, delays, apod, foci, origin, spacing, gn, x_begin, x_count, freq, c, rho, p0_pa, flags, mods, elem, family_pin, fp8_pin, medium);
+    *n_near = (int)p.blocks_near; *is_2g = p.use_cosetp ? 1 : 0;
+    if (!p.use_coset) return 0;
+    std::vector<olx::CosetBlock> blk;
+    std::string why;
+    if (!build_variant_blocks(p, blk, why)) return -1;
+    static_assert(sizeof(olx::CosetBlock) == 8 * sizeof(int), "eight ints per record");
+    if ((int)blk.size() <= cap) memcpy(rec, blk.data(), blk.size() * sizeof(olx::CosetBlock));
+    return (int)blk.size();
 }
 
 }  // extern "C"

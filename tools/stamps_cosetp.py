@@ -42,5 +42,22 @@ if (buf[ok][:, 7] > 0).all():      # second pair in detail: wait at its barrier 
     w2 = s[:, 7] - s[:, 4]; r2 = s[:, 5] - s[:, 7]
     print(f"  {'  pair 1: barrier on entry (vmcnt drain)':45s} {np.median(w2):10.0f} {np.percentile(w2, 10):10.0f} {np.percentile(w2, 90):10.0f}")
     print(f"  {'  pair 1: tables + barrier + K-steps':45s} {np.median(r2):10.0f} {np.percentile(r2, 10):10.0f} {np.percentile(r2, 90):10.0f}")
+# split by the tile count of the wave (low 3 bits of stamp 0) and by its index (the sampled waves are waves 0 .. 3 of their blocks)
+nti = s[:, 0] & 7
+wave_ix = np.where(ok)[0] % 4
+if (buf[ok][:, 7] > 0).all():
+    print("  by tile count of the wave: waves | K-steps pair 0 | pair 1 entry barrier | pair 1 tables + barrier + K-steps | |p| + stores issued | lifetime (medians)")
+    for nt_ in sorted(set(nti.tolist())):
+        m = nti == nt_
+        print(f"    {nt_} tiles {m.sum():6d} {np.median(d[m, 3]):10.0f} {np.median(s[m, 7] - s[m, 4]):10.0f} {np.median(s[m, 5] - s[m, 7]):10.0f} {np.median(d[m, 5]):10.0f} {np.median(s[m, 6] - s[m, 0]):10.0f}")
+    print("  by wave index:")
+    for w_ in range(4):
+        m = wave_ix == w_
+        print(f"    wave {w_}  {m.sum():6d} {np.median(d[m, 3]):10.0f} {np.median(s[m, 7] - s[m, 4]):10.0f} {np.median(s[m, 5] - s[m, 7]):10.0f} {np.median(d[m, 5]):10.0f} {np.median(s[m, 6] - s[m, 0]):10.0f}")
+    # a block's sampled waves (0 .. 3): spread of the times they leave the K-steps of pair 0 and of the times their stores are issued
+    full = ok.reshape(-1, 4).all(axis=1)
+    sb = buf.reshape(-1, 4, 8)[full].astype(np.int64)
+    print(f"  per block ({full.sum()} blocks, waves 0 .. 3): spread of the end of pair 0's K-steps {np.median(np.ptp(sb[:, :, 4], axis=1)):8.0f}, of pair 1's entry {np.median(np.ptp(sb[:, :, 7], axis=1)):8.0f},"
+          f" of the last stamp {np.median(np.ptp(sb[:, :, 6], axis=1)):8.0f}")
 tot = s[:, 6] - s[:, 0]
 print(f"  {'wave lifetime':45s} {np.median(tot):10.0f} {np.percentile(tot, 10):10.0f} {np.percentile(tot, 90):10.0f}")
