@@ -319,6 +319,23 @@ int olx_pii_upload(olx_ctx *ctx, int n_foci, const float *pii);
  * samples (F * n_points * n_t) in one call give OLX_EINVAL.  Synchronous. */
 #define OLX_PULSE_TRACE_MAX_SAMPLES (1ll << 26) /* 256 MiB of float32 */
 int olx_field_pulse_trace(olx_ctx *ctx, int n_points, const long long *voxels, float *trace_out);
+/* Drive impulse responses for the pulsed plans that follow, like olx_field_pulse (DESIGN.md section 2 "drive taps", kernel 2p's RESP
+ * instantiations): the reference's Transducer.calc_output drives element e with the tone burst convolved with the array's and the element's
+ * impulse responses resampled to dt.  With the drive taps g_e[m], m = 0 .. M_e - 1, on the dt grid the field is
+ *   p(v, t_k) = sum_e w_e exp(-a d_e) / d_e sum_m g_e[m] cos(2 pi f0 (t_k - t_e - m dt)) 1[0 <= t_k - t_e - m dt < T]
+ * and p_max, p_min, the intensity, OLX_OUT_PII and olx_field_pulse_trace are formed from it as from the bare burst; n_t is unchanged (ring-down
+ * past it is cut).  Elements with identical taps share a class: class_of_element[N] in 0 .. n_classes - 1, the taps of class r are
+ * taps[row[r] .. row[r + 1]) (fp64; the kernel takes them as float2 with the carrier's phase e^{-j 2 pi f0 dt m} folded in on the host).
+ * A trace is exactly 0 before the first arrival and from the last burst end + M_max - 1 on.  One class with the single tap 1.0 gives
+ * the plain plan's volumes bit for bit.  n_classes = 0 clears the response: the plans that follow launch exactly what they launch today.
+ * Needs the element table (OLX_ESTATE); olx_set_elements clears it, as it clears the apertures.  OLX_EINVAL, before anything is kept: a
+ * class id out of range, a row table that does not start at 0 or is not strictly increasing, more than OLX_PULSE_RESPONSE_MAX_TAPS taps in
+ * a class, more than OLX_PULSE_RESPONSE_MAX_CLASSES classes, a tap that is not finite.  Continuous-wave plans ignore it;
+ * olx_field_pulse_medium refuses a plan that carries one (kernel 2ph has no response).  olx_field_variant then ends in
+ * "; response: R classes, M taps" (M = the longest class). */
+#define OLX_PULSE_RESPONSE_MAX_TAPS 256
+#define OLX_PULSE_RESPONSE_MAX_CLASSES 4
+int olx_field_pulse_response(olx_ctx *ctx, int n_classes, const int32_t *class_of_element, const int32_t *row, const double *taps);
 /* Heterogeneous medium for the CURRENT pulsed plan, opt-in (DESIGN.md section 2 "Pulsed model through a medium", kernel 2ph): valid only
  * after olx_field_plan of a pulsed plan (OLX_ESTATE otherwise), until the next olx_field_plan.  Volumes as olx_field_set_medium's: float32
  * [nx*ny*nz] of the whole planned grid, C order, NULL = the plan's constant; attenuation in dB/cm/MHz^alpha_power.  olx_field_launch and

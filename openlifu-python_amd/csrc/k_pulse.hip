@@ -27,6 +27,13 @@
 //   TRACE  one wave per (point, focus) instead of per voxel, v from a voxel-index list: the lanes store p at their valid samples between
 //          the first arrival and the last burst end (both fp64) to trace[(f n_points + i) n_t + k] and no volume; the launcher zeroes the
 //          trace first, so every other sample is an exact 0.
+//   RESP   drive impulse responses (olx_field_pulse_response; DESIGN.md section 2 "drive taps", section 5.16; fp64 oracle
+//          tests/pulsed_response_oracle.py): the elements are split into classes of identical taps; per pass and per class in turn, on the
+//          same two LDS arrays, the class's elements are scattered and scanned as above, the envelope C is written back to LDS and every
+//          lane applies the class's taps gamma[m] = g[m] e^{-j 2 pi frac(f0 dt m)} to its 21 samples, C'_k += gamma[m] C_{k-m} in ascending
+//          m with fused multiply-adds (a window of 21 registers slides back one sample per tap, one LDS read each); C' adds up over the
+//          classes from 0 and p = Re(e^{j theta_k} C'_k) is evaluated once.  Consecutive passes overlap by H = M_max - 1 samples (the
+//          history of the first outputs of a pass); the window's upper end and the trace's last burst end grow by H.
 // Single-pass capacity: PULSE_L = 64 x 21 = 1344 samples per voxel window (20 cycles at 400 kHz on a 0.25 mm grid with the default
 // dt = 0.5 x 0.25 mm / 1500 m/s: T / dt = 600 samples + the arrival spread of a 256-element array, ~1100 in all).  Longer windows take
 // ceil(window / 1344) passes, each re-walking the elements (the time axis is split, nothing else changes).
@@ -74,11 +81,33 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// RESP: p and the rotation's real part with their roundings written out (products rounded, then the difference / one fused multiply-add):
+// the forms the plain instantiations compile to.  Left to the compiler, the RESP instantiations contract them differently from one
+// another, and a trace would not carry the bits of the volumes.
+__device__ __forceinline__ float pulse_resp_p(float er, float ei, float xr, float xi) {
+#pragma clang fp contract(off)
+    return er * xr - ei * xi;
+}
+__device__ __forceinline__ float pulse_resp_rot(float er, float ei, float c, float s) {
+#pragma clang fp contract(off)
+    const float t = ei * s;
+    return fmaf(er, c, -t);
+}
+
+// RESP: what olx_field_pulse_response adds to the arguments; empty without it (the plain instantiations take nothing more)
+template <bool RESP> struct PulseRespArgs {
+    const int* tab;       // [n_el] class of each element, then [n_classes + 1] first tap of each class in gam
+    const float* gam;     // [n_taps][2] gamma (re, im)
+    int n_classes, n_taps, hist;      // hist = M_max - 1
+};
+template <> struct PulseRespArgs<false> {};
+
 // TRACE: pmin_out is the trace buffer [n_foci][n_points][n_t], points the voxel indices, pmax_out / inten_out / pii_out unused
-template <bool PII, bool TRACE>
+template <bool PII, bool TRACE, bool RESP>
 __global__ __launch_bounds__(64 * PULSE_WAVES) void field_pulse_k(const double4* __restrict__ tab, const float* __restrict__ wtab, const PulseParams P,
                                                                   float* __restrict__ pmin_out, float* __restrict__ pmax_out, float* __restrict__ inten_out,
-                                                                  float* __restrict__ pii_out, const long long* __restrict__ points, int n_points) {
+                                                                  float* __restrict__ pii_out, const long long* __restrict__ points, int n_points,
+                                                                  const PulseRespArgs<RESP> R) {
     __shared__ float lds[PULSE_WAVES][2][PULSE_L];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long w = (long long)blockIdx.x * PULSE_WAVES + wave;      // the wave's voxel, or its entry of the point list
@@ -119,7 +148,12 @@ __global__ __launch_bounds__(64 * PULSE_WAVES) void field_pulse_k(const double4*
         return;
     }
     const double lo = fmax(floor((double)umin) - 2.0, 0.0);
-    const double hi = fmin(ceil((double)umax + P.tdt) + 2.0, (double)P.n_t);          // exclusive
+    double hi = fmin(ceil((double)umax + P.tdt) + 2.0, (double)P.n_t);          // exclusive
+    int H = 0, n_cls = 1;                         // RESP: samples of history a pass carries in front of its outputs, classes
+    if constexpr (RESP) {
+        H = R.hist; n_cls = R.n_classes;
+        hi = fmin(ceil((double)umax + P.tdt) + 2.0 + H, (double)P.n_t);
+    }
 
     float pmax = 0.f, pmin = 0.f;                 // (samples outside the window are 0: they bound both from the zero side)
     float e2 = 0.f;                               // PII: the lane's sum of p^2 over its samples of all passes
@@ -127,13 +161,26 @@ __global__ __launch_bounds__(64 * PULSE_WAVES) void field_pulse_k(const double4*
     const int s0 = lane * PULSE_SEG;
 #pragma unroll
     for (int s = 0; s < PULSE_SEG; ++s) { re[s0 + s] = 0.f; im[s0 + s] = 0.f; }
-    for (double base = lo; base < hi; base += PULSE_L) {
+    // RESP: a pass starts H samples before its first output (before `lo` every C is 0) and advances by PULSE_L - H
+    for (double base = RESP ? lo - H : lo; RESP ? base + H < hi : base < hi; base += RESP ? PULSE_L - H : PULSE_L) {
         double kbeg = 1.0e300, kend = -1.0e300;   // TRACE: first arrival, last burst end (the fp64 integers; the same in every pass)
+        float sr[PULSE_SEG], si[PULSE_SEG];
+        float cr, ci;
+        float ar[RESP ? PULSE_SEG : 1], ai[RESP ? PULSE_SEG : 1];      // RESP: C' of the lane's samples, summed over the classes
+        if constexpr (RESP) {
+#pragma unroll
+            for (int s = 0; s < PULSE_SEG; ++s) { ar[s] = 0.f; ai[s] = 0.f; }
+        }
+        int r = 0;                                // RESP: the class whose turn it is (without RESP: one turn, no loop)
+        do {                                      // (2a, 2b and 2b' are its body, kept at the pass's indentation: without RESP they are the pass)
         wave_lds_sync();
         // 2a. scatter the element terms into the difference array of this pass
         for (int e = lane; e < P.n_el; e += 64) {
             const float we = W[e];
             if (we == 0.f) continue;
+            if constexpr (RESP) {
+                if (!OLX_IN(e, P.n_el, 7) || R.tab[e] != r) continue;      // another class's turn
+            }
             const double4 el = T[e];
             const double dx = px - el.x, dy = py - el.y, dz = pz - el.z;
             const double d = fmax(sqrt(fma(dx, dx, fma(dy, dy, dz * dz))), P.dmin);
@@ -157,7 +204,6 @@ __global__ __launch_bounds__(64 * PULSE_WAVES) void field_pulse_k(const double4*
         }
         wave_lds_sync();
         // 2b. prefix scan: the lane's own segment, then the exclusive scan of the segment totals across the wave
-        float sr[PULSE_SEG], si[PULSE_SEG];
         float tr = 0.f, ti = 0.f;
 #pragma unroll
         for (int s = 0; s < PULSE_SEG; ++s) {
@@ -165,7 +211,7 @@ __global__ __launch_bounds__(64 * PULSE_WAVES) void field_pulse_k(const double4*
             tr += sr[s]; ti += si[s];
             sr[s] = tr; si[s] = ti;
         }
-        float cr = tr, ci = ti;                  // inclusive scan of the totals
+        cr = tr; ci = ti;                        // inclusive scan of the totals
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const float ur = __shfl_up(cr, o), ui = __shfl_up(ci, o);
@@ -173,8 +219,36 @@ __global__ __launch_bounds__(64 * PULSE_WAVES) void field_pulse_k(const double4*
         }
         cr -= tr; ci -= ti;                      // ... exclusive: the carry into this lane's segment
         wave_lds_sync();
+        if constexpr (RESP) {
+            // 2b'. C back to LDS (the lanes read each other's), then the class's taps over the lane's samples: wr / wi hold C_{k-m}
+            float wr[PULSE_SEG], wi[PULSE_SEG];
+#pragma unroll
+            for (int s = 0; s < PULSE_SEG; ++s) {
+                wr[s] = cr + sr[s]; wi[s] = ci + si[s];
+                if (OLX_IN(s0 + s, PULSE_L, 9)) { re[s0 + s] = wr[s]; im[s0 + s] = wi[s]; }
+            }
+            wave_lds_sync();
+            int g0 = 0, g1 = 0;
+            if (OLX_IN(P.n_el + r + 1, P.n_el + R.n_classes + 1, 7)) { g0 = R.tab[P.n_el + r]; g1 = R.tab[P.n_el + r + 1]; }
+            for (int g = g0; g < g1; ++g) {       // tap m = g - g0, ascending
+                if (!OLX_IN(g, R.n_taps, 8)) break;
+                const float gr = R.gam[2 * g], gi = R.gam[2 * g + 1];
+#pragma unroll
+                for (int s = 0; s < PULSE_SEG; ++s) {
+                    ar[s] = fmaf(gr, wr[s], ar[s]); ar[s] = fmaf(-gi, wi[s], ar[s]);
+                    ai[s] = fmaf(gr, wi[s], ai[s]); ai[s] = fmaf(gi, wr[s], ai[s]);
+                }
+#pragma unroll
+                for (int s = PULSE_SEG - 1; s > 0; --s) { wr[s] = wr[s - 1]; wi[s] = wi[s - 1]; }
+                const int h = s0 - 1 - (g - g0);      // the sample before the window (before the pass: history nobody reads, or 0)
+                const bool in = h >= 0 && OLX_IN(h, PULSE_L, 10);
+                wr[0] = in ? re[h] : 0.f; wi[0] = in ? im[h] : 0.f;
+            }
+            wave_lds_sync();
+        }
 #pragma unroll
         for (int s = 0; s < PULSE_SEG; ++s) { re[s0 + s] = 0.f; im[s0 + s] = 0.f; }     // (cleared for the next pass)
+        } while (RESP && ++r < n_cls);
         // 2c. p at the pass's samples: theta_k = 2 pi f0 dt (k - lo), exact at the segment's first sample, rotated by 2 pi f0 dt after it
         const double kfirst = base + s0;
         double cyc = P.f0dt * (kfirst - lo);
@@ -185,22 +259,29 @@ __global__ __launch_bounds__(64 * PULSE_WAVES) void field_pulse_k(const double4*
         if constexpr (TRACE) {
 #pragma unroll
             for (int o = 32; o >= 1; o >>= 1) { kbeg = fmin(kbeg, __shfl_xor(kbeg, o)); kend = fmax(kend, __shfl_xor(kend, o)); }
+            if constexpr (RESP) kend += H;        // (the last tap of the last burst)
             sbeg = (int)fmin(fmax(kbeg - kfirst, 0.0), (double)PULSE_SEG);
             send = min(nvalid, (int)fmin(fmax(kend - kfirst, 0.0), (double)PULSE_SEG));
         }
+        int vbeg = 0;                             // RESP: the lane's first sample past the pass's history
+        if constexpr (RESP) { vbeg = min(max(H - s0, 0), PULSE_SEG); sbeg = max(sbeg, vbeg); }
 #pragma unroll
         for (int s = 0; s < PULSE_SEG; ++s) {
-            const float p = er * (cr + sr[s]) - ei * (ci + si[s]);
+            float p;
+            if constexpr (RESP) p = pulse_resp_p(er, ei, ar[s], ai[s]);
+            else p = er * (cr + sr[s]) - ei * (ci + si[s]);
             if constexpr (TRACE) {
                 if (s >= sbeg && s < send) {
                     const long long kk = (long long)kfirst + s;
                     if (OLX_IN(kk, P.n_t, 4)) trace[kk] = p;
                 }
-            } else if (s < nvalid) {
+            } else if (RESP ? s >= vbeg && s < nvalid : s < nvalid) {
                 pmax = fmaxf(pmax, p); pmin = fminf(pmin, p);
                 if constexpr (PII) e2 = fmaf(p, p, e2);
             }
-            const float nr = er * P.rot_c - ei * P.rot_s;
+            float nr;
+            if constexpr (RESP) nr = pulse_resp_rot(er, ei, P.rot_c, P.rot_s);
+            else nr = er * P.rot_c - ei * P.rot_s;
             ei = fmaf(er, P.rot_s, ei * P.rot_c);
             er = nr;
         }
@@ -231,23 +312,42 @@ static void launch_pulse_table(olx_ctx* c) {
                        c->plan_foci, c->pulse_plan_dt, c->p0_pa * c->freq / c->c, c->d_ptab, c->d_pw);      // (the dt of the plan, not of a later olx_field_pulse)
 }
 
+// the plan's response (olx_field_pulse_response) as the RESP instantiations take it
+static PulseRespArgs<true> resp_args(const olx_ctx* c) {
+    PulseRespArgs<true> R;
+    R.tab = c->d_presp_tab; R.gam = c->d_presp_gam;
+    R.n_classes = c->presp_classes; R.n_taps = c->presp_taps; R.hist = c->presp_hist;
+    return R;
+}
+
 void olx_launch_pulse(olx_ctx* c, float* pm) {
     const PulseParams& P = c->pulse;
     launch_pulse_table(c);
     const dim3 grid((unsigned)((P.vox + PULSE_WAVES - 1) / PULSE_WAVES), c->plan_foci);
     float* const px = (c->flags & OLX_OUT_PMAX) ? (float*)c->d_pmax : nullptr;
     float* const it = (c->flags & OLX_OUT_INTENSITY) ? (float*)c->d_inten : nullptr;
-    if (c->flags & OLX_OUT_PII)
-        hipLaunchKernelGGL((field_pulse_k<true, false>), grid, dim3(64 * PULSE_WAVES), 0, c->stream, c->d_ptab, c->d_pw, P, pm, px, it, (float*)c->d_pii,
-                           (const long long*)nullptr, 0);
+    if (c->presp_classes > 0) {
+        if (c->flags & OLX_OUT_PII)
+            hipLaunchKernelGGL((field_pulse_k<true, false, true>), grid, dim3(64 * PULSE_WAVES), 0, c->stream, c->d_ptab, c->d_pw, P, pm, px, it,
+                               (float*)c->d_pii, (const long long*)nullptr, 0, resp_args(c));
+        else
+            hipLaunchKernelGGL((field_pulse_k<false, false, true>), grid, dim3(64 * PULSE_WAVES), 0, c->stream, c->d_ptab, c->d_pw, P, pm, px, it,
+                               (float*)nullptr, (const long long*)nullptr, 0, resp_args(c));
+    } else if (c->flags & OLX_OUT_PII)
+        hipLaunchKernelGGL((field_pulse_k<true, false, false>), grid, dim3(64 * PULSE_WAVES), 0, c->stream, c->d_ptab, c->d_pw, P, pm, px, it, (float*)c->d_pii,
+                           (const long long*)nullptr, 0, PulseRespArgs<false>{});
     else
-        hipLaunchKernelGGL((field_pulse_k<false, false>), grid, dim3(64 * PULSE_WAVES), 0, c->stream, c->d_ptab, c->d_pw, P, pm, px, it, (float*)nullptr,
-                           (const long long*)nullptr, 0);
+        hipLaunchKernelGGL((field_pulse_k<false, false, false>), grid, dim3(64 * PULSE_WAVES), 0, c->stream, c->d_ptab, c->d_pw, P, pm, px, it, (float*)nullptr,
+                           (const long long*)nullptr, 0, PulseRespArgs<false>{});
 }
 
 void olx_launch_pulse_trace(olx_ctx* c, int n_points) {
     launch_pulse_table(c);      // (the caller has zeroed c->d_ptrace on the stream)
-    hipLaunchKernelGGL((field_pulse_k<false, true>), dim3((unsigned)((n_points + PULSE_WAVES - 1) / PULSE_WAVES), c->plan_foci), dim3(64 * PULSE_WAVES), 0,
-                       c->stream, c->d_ptab, c->d_pw, c->pulse, (float*)c->d_ptrace, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                       (const long long*)c->d_ptrace_vox, n_points);
+    const dim3 grid((unsigned)((n_points + PULSE_WAVES - 1) / PULSE_WAVES), c->plan_foci);
+    if (c->presp_classes > 0)
+        hipLaunchKernelGGL((field_pulse_k<false, true, true>), grid, dim3(64 * PULSE_WAVES), 0, c->stream, c->d_ptab, c->d_pw, c->pulse, (float*)c->d_ptrace,
+                           (float*)nullptr, (float*)nullptr, (float*)nullptr, (const long long*)c->d_ptrace_vox, n_points, resp_args(c));
+    else
+        hipLaunchKernelGGL((field_pulse_k<false, true, false>), grid, dim3(64 * PULSE_WAVES), 0, c->stream, c->d_ptab, c->d_pw, c->pulse, (float*)c->d_ptrace,
+                           (float*)nullptr, (float*)nullptr, (float*)nullptr, (const long long*)c->d_ptrace_vox, n_points, PulseRespArgs<false>{});
 }

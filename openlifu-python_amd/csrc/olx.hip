@@ -208,6 +208,7 @@ int olx_set_elements(olx_ctx* c, const double* pos_m, const double* normal, cons
     c->h_area.assign(area_m2, area_m2 + n);
     c->h_nrm.assign(normal, normal + 3 * (size_t)n);
     c->h_xaxis.clear(); c->h_size.clear();     // apertures belong to an element table
+    c->resp_cls.clear(); c->resp_row.clear(); c->resp_taps.clear();      // ... and so do the drive impulse responses
     c->n_el = n;
     c->sm_valid = false;
     c->n_foci = 0;      // steering shape depends on N
@@ -777,6 +778,32 @@ static int plan_pulse(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n
     if (!rc) rc = c->d_ptab.reserve(c, fn);
     if (!rc) rc = c->d_pw.reserve(c, fn);
     if (rc) return rc;
+    // drive impulse responses (olx_field_pulse_response): class table and row table as one int buffer, gamma in fp64 -> float2, of THIS plan's f0 dt
+    const int n_resp = c->resp_row.empty() ? 0 : (int)c->resp_row.size() - 1;
+    if (n_resp > 0) {
+        if ((int)c->resp_cls.size() != c->n_el) return fail(c, OLX_ESTATE, "olx_field_plan: the impulse responses belong to another element table");
+        std::vector<int> tab(c->resp_cls);
+        tab.insert(tab.end(), c->resp_row.begin(), c->resp_row.end());
+        const int n_taps = c->resp_row[n_resp];
+        std::vector<float> gam(2 * (size_t)n_taps);
+        int m_max = 1;
+        for (int r = 0; r < n_resp; ++r) {
+            m_max = std::max(m_max, c->resp_row[r + 1] - c->resp_row[r]);
+            for (int g = c->resp_row[r]; g < c->resp_row[r + 1]; ++g) {
+                double cyc = freq * c->pulse_dt * (double)(g - c->resp_row[r]);
+                cyc -= std::floor(cyc);
+                gam[2 * (size_t)g] = (float)(c->resp_taps[g] * std::cos(2.0 * M_PI * cyc));
+                gam[2 * (size_t)g + 1] = (float)(-c->resp_taps[g] * std::sin(2.0 * M_PI * cyc));
+            }
+        }
+        rc = c->d_presp_tab.reserve(c, tab.size());
+        if (!rc) rc = c->d_presp_gam.reserve(c, gam.size());
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpy(c->d_presp_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_presp_gam, gam.data(), sizeof(float) * gam.size(), hipMemcpyHostToDevice));
+        c->presp_taps = n_taps; c->presp_hist = m_max - 1;
+    }
+    c->presp_classes = n_resp;
     // (the scans -- aggregate, scale, analysis -- read the volume shape from fp)
     FieldParams& F = c->fp;
     F.nx = g->n[0]; F.ny = g->n[1]; F.nz = g->n[2]; F.n_el = c->n_el; F.x_begin = 0; F.vox = vox;
@@ -802,6 +829,10 @@ static int plan_pulse(olx_ctx* c, const olx_grid* g, const olx_slab* slab, int n
     char nm[128];
     snprintf(nm, sizeof nm, "field_pulse_k (pulsed: %d samples, %.4g samples per burst)", c->pulse_nt, P.tdt);
     c->variant = nm;
+    if (c->presp_classes > 0) {
+        snprintf(nm, sizeof nm, "; response: %d classes, %d taps", c->presp_classes, c->presp_hist + 1);
+        c->variant += nm;
+    }
     c->packed_version = ~0ull;
     c->planned = true; c->uploaded = false;
     return OLX_OK;
@@ -1694,6 +1725,34 @@ int olx_field_pulse(olx_ctx* c, double cycles, double dt, int n_t) {
     return OLX_OK;
 }
 
+// Drive impulse responses of the pulsed model for the plans that follow: checked and kept on the host; olx_field_plan forms gamma from them
+// with its own f0 dt (plan_pulse).  Nothing here touches the device.
+int olx_field_pulse_response(olx_ctx* c, int n_classes, const int32_t* class_of_element, const int32_t* row, const double* taps) {
+    if (!c) return OLX_EINVAL;
+    if (n_classes == 0) { c->resp_cls.clear(); c->resp_row.clear(); c->resp_taps.clear(); return OLX_OK; }
+    if (c->n_el <= 0) return fail(c, OLX_ESTATE, "olx_field_pulse_response: call olx_set_elements first");
+    if (n_classes < 0 || n_classes > OLX_PULSE_RESPONSE_MAX_CLASSES)
+        return fail(c, OLX_EINVAL, "olx_field_pulse_response: %d classes, at most OLX_PULSE_RESPONSE_MAX_CLASSES = %d (0 clears the response)", n_classes,
+                    OLX_PULSE_RESPONSE_MAX_CLASSES);
+    if (!class_of_element || !row || !taps) return fail(c, OLX_EINVAL, "olx_field_pulse_response: null pointer");
+    if (row[0] != 0) return fail(c, OLX_EINVAL, "olx_field_pulse_response: the row table must start at 0, got %d", (int)row[0]);
+    for (int r = 0; r < n_classes; ++r) {
+        if (row[r + 1] <= row[r]) return fail(c, OLX_EINVAL, "olx_field_pulse_response: the row table must be strictly increasing (class %d has no taps)", r);
+        if (row[r + 1] - row[r] > OLX_PULSE_RESPONSE_MAX_TAPS)
+            return fail(c, OLX_EINVAL, "olx_field_pulse_response: class %d has %d taps, at most OLX_PULSE_RESPONSE_MAX_TAPS = %d", r, (int)(row[r + 1] - row[r]),
+                        OLX_PULSE_RESPONSE_MAX_TAPS);
+    }
+    for (int e = 0; e < c->n_el; ++e)
+        if (class_of_element[e] < 0 || class_of_element[e] >= n_classes)
+            return fail(c, OLX_EINVAL, "olx_field_pulse_response: element %d: class %d outside 0 .. %d", e, (int)class_of_element[e], n_classes - 1);
+    for (int g = 0; g < row[n_classes]; ++g)
+        if (!std::isfinite(taps[g])) return fail(c, OLX_EINVAL, "olx_field_pulse_response: tap %d is not finite", g);
+    c->resp_cls.assign(class_of_element, class_of_element + c->n_el);
+    c->resp_row.assign(row, row + n_classes + 1);
+    c->resp_taps.assign(taps, taps + row[n_classes]);
+    return OLX_OK;
+}
+
 // Kernel 2ph: the medium of the CURRENT pulsed plan (DESIGN.md section 2 "Pulsed model through a medium").  Buffers and a flag of its own
 // (pulse_med, d_pm_*): `hetero` selects the CW machinery -- the 2h / 2m launch, the d_inv2z readers -- and stays false.  A pulsed plan stores
 // its intensity, so every scan reads this result as it reads kernel 2p's.
@@ -1701,6 +1760,8 @@ int olx_field_pulse_medium(olx_ctx* c, const float* sound_speed, const float* at
     if (!c) return OLX_EINVAL;
     if (!c->planned || c->uploaded || !c->pulsed)
         return fail(c, OLX_ESTATE, "olx_field_pulse_medium: needs a pulsed plan (olx_field_pulse, then olx_field_plan)");
+    if (c->presp_classes > 0)
+        return fail(c, OLX_EINVAL, "olx_field_pulse_medium: the plan carries a drive impulse response (olx_field_pulse_response); kernel 2ph has none");
     if (c->plan_absorb > 0 || c->absorb_np_m > 0)
         return fail(c, OLX_EINVAL, "olx_field_pulse_medium: a uniform absorption (olx_field_absorption) and a heterogeneous medium exclude each other: put the absorption into the medium volumes");
     if (c->n_el != c->pulse.n_el) return fail(c, OLX_ESTATE, "olx_field_pulse_medium: the element table changed since the plan");

@@ -158,6 +158,12 @@ struct olx_ctx {
     DevBuf<double> d_pii_A;                    // [PII_MAXF * 12] ... its focal frames
     DevBuf<unsigned> d_pii_peak;               // [4 * PII_MAXF + 1] ... its peaks (bit patterns)
     DevBuf<long long> d_ptrace_vox; DevBuf<float> d_ptrace;   // olx_field_pulse_trace: the voxel list and [F][n_points][n_t] samples
+    // drive impulse responses of the pulsed model (olx_field_pulse_response, field_pulse_k<.., RESP>): the setting for the plans that follow
+    // (host, fp64 taps as given) and what the current pulsed plan holds (presp_classes = 0: the plain kernel)
+    std::vector<int> resp_cls, resp_row; std::vector<double> resp_taps;      // empty: no response
+    int presp_classes = 0, presp_taps = 0, presp_hist = 0;                  // classes, taps in all, M_max - 1
+    DevBuf<int> d_presp_tab;                   // [N] class of each element, then [classes + 1] first tap of each class
+    DevBuf<float> d_presp_gam;                 // [taps][2] gamma_r[m] = g_r[m] e^{-j 2 pi frac(f0 dt m)} of the plan's f0 dt
     // pulsed model through a medium (kernel 2ph, olx_field_pulse_medium): buffers of their own, apart from the CW medium (`hetero`, d_med, d_inv2z ...)
     bool pulse_med = false;                    // the current pulsed plan launches kernel 2ph (until the next plan or upload)
     int pulse_med_R = 0;                       // its cache slots per lane: 4 (N <= 256) or 16 (N <= 1024)

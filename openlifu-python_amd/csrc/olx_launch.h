@@ -18,8 +18,8 @@ void olx_pack_toep(olx_ctx* c, const LatticePart& q);                  //     it
 void olx_launch_hetero(olx_ctx* c, float* pm);       // 2h  field_hetero_k
 void olx_launch_hmarch(olx_ctx* c, float* pm);       // 2m  field_hmarch_k (marched ray sums: one launch per plane segment)
 void olx_pack_hetero(olx_ctx* c);                    //     its steering table (c->nf foci per launch tile)
-void olx_launch_pulse(olx_ctx* c, float* pm);       // 2p  field_pulse_k (pulsed model, olx_field_pulse; writes p_min to pm)
-void olx_launch_pulse_trace(olx_ctx* c, int n_points);   // 2p  field_pulse_k<false, true>: p(t_k) at the n_points voxels of c->d_ptrace_vox into c->d_ptrace (zeroed on the stream by the caller)
+void olx_launch_pulse(olx_ctx* c, float* pm);       // 2p  field_pulse_k (pulsed model, olx_field_pulse; writes p_min to pm; the RESP instantiations when the plan carries olx_field_pulse_response)
+void olx_launch_pulse_trace(olx_ctx* c, int n_points);   // 2p  field_pulse_k<false, true, RESP>: p(t_k) at the n_points voxels of c->d_ptrace_vox into c->d_ptrace (zeroed on the stream by the caller)
 void olx_launch_pulse_med(olx_ctx* c, float* pm);   // 2ph field_pulse_med_k (pulsed model through a medium, olx_field_pulse_medium; all foci in one wave per voxel)
 void olx_launch_pulse_med_trace(olx_ctx* c, int n_points);   // 2ph field_pulse_med_k<R, false, true>: as olx_launch_pulse_trace
 void olx_launch_bfmed(olx_ctx* c, int n_foci);      // 1m  bf_med_k (StraightRay delays into the steering table; after bf_solve_k)

@@ -42,7 +42,7 @@ SYMBOLS = [
     "olx_aggregate_fetch", "olx_field_aggregate_device", "olx_field_analysis_peaks", "olx_field_aggregate_counts", "olx_rccl_path", "olx_bf_time", "olx_field_fetch_all", "olx_field_medium_layering", "olx_field_medium_model", "olx_set_element_apertures",
     "olx_solution_analyze", "olx_scan_time", "olx_comm_export", "olx_comm_import", "olx_comm_transport",
     "olx_field_scale_aggregate", "olx_field_absorption", "olx_comm_ranks_seen",
-    "olx_field_pulse", "olx_field_fetch_pmax", "olx_aggregate_fetch_pmax", "olx_field_fetch_pii", "olx_field_pulse_trace", "olx_field_pulse_medium",
+    "olx_field_pulse", "olx_field_fetch_pmax", "olx_aggregate_fetch_pmax", "olx_field_fetch_pii", "olx_field_pulse_trace", "olx_field_pulse_medium", "olx_field_pulse_response",
     "olx_pii_post", "olx_pii_fetch_weighted", "olx_pii_fetch_max", "olx_pii_upload", "olx_thermal_source_pii",
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
     "olx_fullwave_plan", "olx_fullwave_sources", "olx_fullwave_run", "olx_fullwave_fetch", "olx_fullwave_lockin", "olx_fullwave_fetch_lockin",
@@ -146,6 +146,7 @@ def load(require_gpu: bool = True):
         lib.olx_field_fetch_pii.argtypes = [vp, fp]
         lib.olx_field_pulse_trace.argtypes = [vp, c_int, POINTER(ctypes.c_longlong), fp]
         lib.olx_field_pulse_medium.argtypes = [vp, fp, fp, fp, c_double]
+        lib.olx_field_pulse_response.argtypes = [vp, c_int, POINTER(c_int32), POINTER(c_int32), dp]
         lib.olx_pii_post.argtypes = [vp, dp, dp, c_int, dp, dp, c_double, c_double, c_double, fp]
         lib.olx_pii_fetch_weighted.argtypes = [vp, fp]
         lib.olx_pii_fetch_max.argtypes = [vp, fp]
@@ -616,6 +617,25 @@ class Context:
             if arrs[-1] is not None and arrs[-1].shape != self._grid_shape:
                 raise ValueError(f"medium volumes must have the grid shape {self._grid_shape}, got {arrs[-1].shape}")
         self._chk(self._lib.olx_field_pulse_medium(self._h, _fptr(arrs[0]), _fptr(arrs[1]), _fptr(arrs[2]), float(alpha_power)))
+
+    PULSE_RESPONSE_MAX_TAPS = 256
+    PULSE_RESPONSE_MAX_CLASSES = 4
+
+    def field_pulse_response(self, class_of_element=None, taps=()):
+        """Drive impulse responses for the pulsed plans that follow (olx_field_pulse_response): ``class_of_element`` [N] ints and ``taps``, one
+        1-D fp64 array of drive taps on the dt grid per class.  No classes (the default) clears the response.  The limits, the class ids
+        and the taps are checked by the library (ValueError)."""
+        taps = [np.ascontiguousarray(t, dtype=np.float64).ravel() for t in taps]
+        if not taps:
+            self._chk(self._lib.olx_field_pulse_response(self._h, 0, None, None, None))
+            return
+        cls = np.ascontiguousarray(class_of_element, dtype=np.int32).ravel()
+        if cls.size != self.n_el:
+            raise ValueError(f"class_of_element must have one entry per element ({self.n_el}), got {cls.size}")
+        row = np.concatenate([[0], np.cumsum([t.size for t in taps])]).astype(np.int32)
+        flat = np.concatenate(taps) if row[-1] else np.zeros(1)
+        self._chk(self._lib.olx_field_pulse_response(self._h, len(taps), cls.ctypes.data_as(POINTER(c_int32)), row.ctypes.data_as(POINTER(c_int32)),
+                                                     _dptr(flat)))
 
     # ---- pulse intensity integrals (pii_post_k) ------------------------------------------------------------------------------
     PII_MAX_FOCI = 8

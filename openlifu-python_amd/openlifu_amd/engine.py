@@ -354,7 +354,8 @@ class Engine:
     # ---- kernel 2 -----------------------------------------------------------------------------
     def field(self, arr, delays, apod, origin_m, spacing_m, n, freq, c, rho, p0_pa,
               want=("pmag", "intensity"), slab=None, steering_resident=False, medium=None, fp8_correction=None,
-              lazy=False, directivity=False, absorption=0.0, pulse=None, trace_voxels=None, pulsed_medium_model=None):
+              lazy=False, directivity=False, absorption=0.0, pulse=None, trace_voxels=None, pulsed_medium_model=None,
+              pulsed_drive_model=None):
         """Pressure field for F foci -> dict of float32 arrays [F, nx, ny, nz] (fresh, writable,
         caller-owned).  ``steering_resident`` reuses the table the last ``beamform`` left on the
         device instead of uploading ``delays`` / ``apod``.  ``fp8_correction=False`` opts OUT of the e4m3
@@ -367,7 +368,13 @@ class Engine:
         ``pulse_time_axis``): "pmag" then holds p_min and the result carries p_max under "pmax"; "pii" in ``want`` adds the pulse
         intensity integral [J/cm^2] (OLX_OUT_PII; a lazy result carries it like p_max, under "pii"), ``trace_voxels`` (linear voxel indices) adds the waveforms
         p(t_k) there under "trace" [F, P, n_t] (olx_field_pulse_trace).  ``pulsed_medium_model="straight_ray"`` lets the pulsed model take a
-        ``medium`` (olx_field_pulse_medium, kernel 2ph); without it a pulsed request with a medium is refused."""
+        ``medium`` (olx_field_pulse_medium, kernel 2ph); without it a pulsed request with a medium is refused.
+        ``pulsed_drive_model="impulse_response"`` drives the pulsed model through ``arr``'s impulse responses (sim/field.py ``drive_taps`` at the
+        plan's dt, olx_field_pulse_response; no medium); an array without any response runs the plain kernel."""
+        if pulsed_drive_model not in (None, "impulse_response"):
+            raise ValueError(f'pulsed_drive_model must be None or "impulse_response", got {pulsed_drive_model!r}')
+        if pulsed_drive_model is not None and pulse is None:
+            raise ValueError("pulsed_drive_model needs the pulsed field model (the continuous-wave model has no drive waveform)")
         if pulsed_medium_model not in (None, "straight_ray"):
             raise ValueError(f'pulsed_medium_model must be None or "straight_ray", got {pulsed_medium_model!r}')
         if pulsed_medium_model is not None and pulse is None:
@@ -375,6 +382,8 @@ class Engine:
         if pulse is None and ("pii" in want or trace_voxels is not None):
             raise ValueError('the pulse intensity integral ("pii") and the waveform traces need the pulsed field model')
         if pulse is not None:
+            if medium is not None and pulsed_drive_model is not None:
+                raise NotImplementedError("pulsed field model: impulse_response drives through a heterogeneous medium are not implemented")
             if medium is not None and pulsed_medium_model is None:
                 raise NotImplementedError("pulsed field model: heterogeneous media are not implemented (homogeneous media, with or without uniform absorption, only)")
             if directivity:
@@ -388,6 +397,10 @@ class Engine:
             cycles, dt, t_end, cfl = pulse
             dt, n_t = pulse_time_axis(spacing_m, n, dt, t_end, cfl)
             want = tuple(want) + ("pmax",)
+            response = None
+            if pulsed_drive_model is not None:     # (the limits raise here, before anything is retired or uploaded)
+                from .sim.field import drive_taps
+                response = drive_taps(arr, dt)
         self.retire_results()
         if steering_resident:
             # the resident steering table belongs to the resident element table: another transducer (or the same one with edited
@@ -408,6 +421,12 @@ class Engine:
         if pulse is not None:
             self.ctx.field_pulse(cycles, dt, n_t)
             self._pulsed = True
+            if response is not None and response[1]:
+                self.ctx.field_pulse_response(*response)
+                self._pulse_response = True
+            elif getattr(self, "_pulse_response", False):
+                self.ctx.field_pulse_response()       # back to the bare burst
+                self._pulse_response = False
             flags |= nat.OUT_PMAX
             if "pii" in want:
                 flags |= nat.OUT_PII

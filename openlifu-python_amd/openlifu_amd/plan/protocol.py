@@ -27,7 +27,7 @@ from ..bf.apod_methods import ApodizationMethod, MediumCompensated
 from ..bf.delay_methods import Direct, StraightRay, TimeReversal
 from ..engine import get_engine, gpu_available
 from ..geo import Point
-from ..sim.field import dataset_from_fields, lazy_stack, parse_field_model, parse_pii_option, parse_pulsed_medium_option, simulate_foci, _ATTRS
+from ..sim.field import dataset_from_fields, lazy_stack, parse_field_model, parse_pii_option, parse_pulsed_drive_option, parse_pulsed_medium_option, simulate_foci, _ATTRS
 from ..util import dataset as ds
 from .param_constraint import ParameterConstraint
 from .solution import Solution
@@ -78,6 +78,13 @@ def pulsed_medium_from_options(sim_setup):
     """``SimSetup.options["pulsed_medium_model"]`` (default None; "straight_ray" opts in): the pulsed model runs through a heterogeneous
     medium along straight rays (kernel 2ph).  ValueError for any other value, and unless ``options["field_model"]`` is "pulsed"."""
     return parse_pulsed_medium_option(getattr(sim_setup, "options", {}))
+
+
+def pulsed_drive_from_options(sim_setup):
+    """``SimSetup.options["pulsed_drive_model"]`` (default None; "impulse_response" opts in): the pulsed model is driven through the
+    transducer's and the elements' impulse responses (kernel 2p's RESP instantiations).  ValueError for any other value, and unless
+    ``options["field_model"]`` is "pulsed"."""
+    return parse_pulsed_drive_option(getattr(sim_setup, "options", {}))
 
 
 # module-level seam, as in the reference (plan/protocol.py:24; its tests patch this name)
@@ -245,6 +252,7 @@ class Protocol:
         self.check_target(target)
         want_pii = pii_from_options(sim_options)      # (raises when the field model has no time axis)
         pulsed_medium = pulsed_medium_from_options(sim_options)      # (likewise)
+        pulsed_drive = pulsed_drive_from_options(sim_options)        # (likewise)
         custom_seam = run_simulation is not sim.run_simulation  # patched seam (reference tests mock it)
         # `params` never leaves this call on the built-in path.  With xarray installed the Dataset factories hand out real xarray objects, which
         # cannot defer: the uniform reference medium would cost five full volumes (0.3 s at 256^3) nobody reads -- the call then works on the
@@ -283,7 +291,8 @@ class Protocol:
                                    self.pulse.amplitude * voltage, steering_resident=resident, fp8_correction=fp8, lazy=True,
                                    hetero_planes_per_layer=int(getattr(sim_options, "options", {}).get("hetero_planes_per_layer", 1)),
                                    directivity=str(getattr(sim_options, "options", {}).get("directivity", "0")).lower() in ("1", "true", "yes"),
-                                   pulse=pulse, want=("pmag", "intensity") + (("pii",) if want_pii else ()), pulsed_medium_model=pulsed_medium)
+                                   pulse=pulse, want=("pmag", "intensity") + (("pii",) if want_pii else ()), pulsed_medium_model=pulsed_medium,
+                                   pulsed_drive_model=pulsed_drive)
             coords = params.coords
             stacked = lazy_stack(fields, _standin_coords(coords) if ds.HAVE_XARRAY else coords, internal=ds.HAVE_XARRAY)
         elif simulate:

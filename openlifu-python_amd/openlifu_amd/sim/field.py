@@ -13,7 +13,10 @@ like ``directivity``):
     (HIP kernel 2p; definition DESIGN.md section 2, time axis ``pulse_time_axis``).  Homogeneous media
     by default; ``medium_model="straight_ray"`` opts in to a heterogeneous ``params``: the same model with the straight-ray sums of
     the medium on every (voxel, element) ray, intensity and PII with the voxel's own impedance (HIP kernel 2ph; sampled quadrature,
-    one plane per layer, whole grid on one GPU).  Directivity, impulse responses and the multi-GPU paths raise NotImplementedError.  Two opt-in outputs of its time axis:
+    one plane per layer, whole grid on one GPU).  ``drive_model="impulse_response"`` opts in to the transducer's and the elements'
+    ``impulse_response``: the drive of ``Transducer.calc_output`` -- the burst convolved with both, resampled to ``dt`` -- instead of the bare
+    burst (``drive_taps``; kernel 2p's RESP instantiations, homogeneous media only).  Directivity, impulse responses without that opt-in and
+    the multi-GPU paths raise NotImplementedError.  Two opt-in outputs of its time axis:
     ``pulse_intensity_integral=True`` adds PII = 1e-4 dt / (rho c) sum_k p(t_k)^2 [J/cm^2] (PII / (cycles / freq) is the pulse-average
     intensity; ``run_thermal_simulation(pulse_energy=...)`` heats with it), ``record_points`` [P, 3] in the units of ``params.coords``
     adds the waveforms p(t_k) at the nearest voxels to the raw dict ("p_trace" [P, n_t], "t" = k dt, "trace_voxels").
@@ -38,6 +41,8 @@ _ATTRS = {"p_max": {"units": "Pa", "long_name": "PPP"}, "p_min": {"units": "Pa",
 ALPHA_POWER = 0.9      # the reference's kWaveMedium(alpha_power=0.9), sim/kwave_if.py:57
 FIELD_MODELS = ("cw", "pulsed")
 PULSED_MEDIUM_MODELS = ("straight_ray",)      # how the pulsed model crosses a heterogeneous medium, opt-in (kernel 2ph)
+PULSED_DRIVE_MODELS = ("impulse_response",)   # what drives the elements of the pulsed model besides the bare burst, opt-in (kernel 2p, RESP)
+PULSE_RESPONSE_MAX_TAPS, PULSE_RESPONSE_MAX_CLASSES = 256, 4      # include/olx.h OLX_PULSE_RESPONSE_MAX_*
 
 
 def parse_field_model(value) -> str:
@@ -58,15 +63,67 @@ def parse_pulsed_medium_model(value):
     return model
 
 
+def parse_pulsed_drive_model(value):
+    """``drive_model`` of run_simulation / ``SimSetup.options["pulsed_drive_model"]``: None (default, also for ""), or "impulse_response"."""
+    if value is None or str(value).strip() == "":
+        return None
+    model = str(value).strip().lower()
+    if model not in PULSED_DRIVE_MODELS:
+        raise ValueError(f"the pulsed model's drive_model must be None or one of {PULSED_DRIVE_MODELS}, got {value!r}")
+    return model
+
+
+def drive_taps(arr, dt):
+    """(class_of_element int32 [N], [taps_r fp64]): the drive taps g_e = H_arr * H_el,e of every element on the ``dt`` grid (DESIGN.md
+    section 2), the drive of ``Transducer.calc_output`` being sum_m g_e[m] burst((k - m) dt).  H_arr = the array's response resampled to
+    ``dt`` ([1] without one); H_el,e = [1] without a response, [h0] for a length-1 response, else the element's resampled to ``dt``.
+    Elements whose taps are exactly equal share a class, numbered by first appearance.  A transducer without any response gives no classes
+    (the plain kernel runs).  ValueError for a class longer than PULSE_RESPONSE_MAX_TAPS or more than PULSE_RESPONSE_MAX_CLASSES classes."""
+    dt = float(dt)
+    n = arr.numelements()
+    cls = np.zeros(n, dtype=np.int32)
+    has_arr = getattr(arr, "impulse_response", None) is not None
+    if not has_arr and all(getattr(el, "impulse_response", None) is None for el in arr.elements):
+        return cls, []
+    h_arr = np.asarray(arr.interp_impulse_response(dt)[0], dtype=np.float64) if has_arr else np.ones(1)
+    one = np.ones(1)
+    h_of, index, taps = {}, {}, []      # element response (as given) -> H_el on the dt grid; taps -> class
+    for e, el in enumerate(arr.elements):
+        ir = getattr(el, "impulse_response", None)
+        if ir is None:
+            h_el = one
+        else:
+            key = (np.asarray(ir).tobytes(), el.impulse_dt)
+            if key not in h_of:
+                h_of[key] = np.asarray(ir, dtype=np.float64) if len(ir) == 1 else np.asarray(el.interp_impulse_response(dt)[0], dtype=np.float64)
+            h_el = h_of[key]
+        g = np.convolve(h_arr, h_el, mode="full")
+        key = g.tobytes()
+        if key not in index:
+            if len(g) > PULSE_RESPONSE_MAX_TAPS:
+                raise ValueError(f"pulsed field model: element {e}'s impulse response has {len(g)} taps at dt = {dt:g} s, "
+                                 f"at most {PULSE_RESPONSE_MAX_TAPS} are supported")
+            if len(taps) == PULSE_RESPONSE_MAX_CLASSES:
+                raise ValueError(f"pulsed field model: the elements carry more than {PULSE_RESPONSE_MAX_CLASSES} different impulse responses "
+                                 f"(at most {PULSE_RESPONSE_MAX_CLASSES} classes of identical drive taps are supported)")
+            index[key] = len(taps)
+            taps.append(g)
+        cls[e] = index[key]
+    return cls, taps
+
+
 def truncate_delays(delays, dt):
     """The reference's whole-step delays (sim/kwave_if.py: zeros(int(delay / dt)) in front of the drive): floor(tau / dt) dt."""
     return np.floor(np.asarray(delays, dtype=np.float64) / float(dt)) * float(dt)
 
 
-def check_pulsed_supported(arr, directivity=False):
-    """NotImplementedError, naming the reason, for what the pulsed model does not cover on the transducer side."""
+def check_pulsed_supported(arr, directivity=False, drive_model=None):
+    """NotImplementedError, naming the reason, for what the pulsed model does not cover on the transducer side.  ``drive_model=
+    "impulse_response"`` (the opt-in) lets the impulse responses through."""
     if directivity:
         raise NotImplementedError("pulsed field model: element directivity is not implemented")
+    if drive_model is not None:
+        return
     if getattr(arr, "impulse_response", None) is not None:
         raise NotImplementedError("pulsed field model: the transducer's impulse_response is not implemented (the drive is the bare tone burst)")
     if any(getattr(el, "impulse_response", None) is not None for el in arr.elements):
@@ -113,21 +170,29 @@ def _medium(params, freq, ref_values_only=False):
 
 def simulate_foci(arr, params, delays, apod, freq, amplitude, want=("pmag", "intensity"),
                   steering_resident=False, slab=None, fp8_correction=None, lazy=False, hetero_planes_per_layer=1,
-                  hetero_model="auto", directivity=False, ref_values_only=False, pulse=None, trace_voxels=None, pulsed_medium_model=None):
+                  hetero_model="auto", directivity=False, ref_values_only=False, pulse=None, trace_voxels=None, pulsed_medium_model=None,
+                  pulsed_drive_model=None):
     """Batched core: F foci in one launch -> dict of float32 arrays [F, nx, ny, nz], or with ``lazy`` a
     ``DeviceResult`` whose volumes stay in HBM until read (``lazy_stack`` wraps it in the reference's schema).
     ``pulse = (cycles, dt, t_end, cfl)``: the pulsed model -- "pmag" holds p_min, "pmax" p_max, "pii" in ``want`` adds the pulse intensity
     integral and ``trace_voxels`` (linear voxel indices) the waveforms there under "trace" [F, P, n_t] (not with ``lazy``).
     ``pulsed_medium_model="straight_ray"`` opts the pulsed model in to a heterogeneous ``params`` (kernel 2ph: sampled quadrature, one plane
-    per layer); without it such a ``params`` is refused, and a homogeneous one runs kernel 2p either way."""
+    per layer); without it such a ``params`` is refused, and a homogeneous one runs kernel 2p either way.
+    ``pulsed_drive_model="impulse_response"`` opts in to the impulse responses of ``arr`` (``drive_taps``; homogeneous media only)."""
     pulsed_medium_model = parse_pulsed_medium_model(pulsed_medium_model)
+    pulsed_drive_model = parse_pulsed_drive_model(pulsed_drive_model)
     if pulsed_medium_model is not None and pulse is None:
         raise ValueError("pulsed_medium_model needs the pulsed field model (the continuous-wave model picks its medium kernels by itself)")
+    if pulsed_drive_model is not None and pulse is None:
+        raise ValueError("pulsed_drive_model needs the pulsed field model (the continuous-wave model has no drive waveform)")
     if pulse is not None:
-        check_pulsed_supported(arr, directivity)
+        check_pulsed_supported(arr, directivity, pulsed_drive_model)
     coords = params.coords
     origin, spacing, n = grid_from_coords(coords)
     c, rho, medium, absorption = _medium(params, freq, ref_values_only)
+    if pulse is not None and medium is not None and pulsed_drive_model is not None:
+        raise NotImplementedError("pulsed field model: impulse_response drives (drive_model) through a heterogeneous medium are not implemented "
+                                  "(kernel 2ph has no response)")
     if pulse is not None and medium is not None and pulsed_medium_model is None:
         raise NotImplementedError("pulsed field model: heterogeneous media are not implemented (homogeneous media, with or without uniform absorption, only)")
     if pulse is not None and medium is not None and int(hetero_planes_per_layer) > 1:
@@ -140,7 +205,7 @@ def simulate_foci(arr, params, delays, apod, freq, amplitude, want=("pmag", "int
     return get_engine().field(arr, delays, apod, origin, spacing, n, float(freq), c, rho, p0, want=want,
                               slab=slab, steering_resident=steering_resident, medium=medium,
                               fp8_correction=fp8_correction, lazy=lazy, directivity=directivity, absorption=absorption, pulse=pulse,
-                              trace_voxels=trace_voxels, pulsed_medium_model=pulsed_medium_model)
+                              trace_voxels=trace_voxels, pulsed_medium_model=pulsed_medium_model, pulsed_drive_model=pulsed_drive_model)
 
 
 def parse_pii_option(options) -> bool:
@@ -169,6 +234,17 @@ def parse_pulsed_medium_option(options):
     if model is not None and parse_field_model(options.get("field_model", "cw")) != "pulsed":
         raise ValueError('options["pulsed_medium_model"] needs options["field_model"] = "pulsed" '
                          f'(got field_model = {options.get("field_model", "cw")!r}: the continuous-wave model picks its medium kernels by itself)')
+    return model
+
+
+def parse_pulsed_drive_option(options):
+    """``SimSetup.options["pulsed_drive_model"]``: None / "" (default) or "impulse_response" -- the pulsed model driven through the
+    transducer's and the elements' impulse responses; ValueError for anything else.  It needs ``options["field_model"] = "pulsed"``."""
+    options = options or {}
+    model = parse_pulsed_drive_model(options.get("pulsed_drive_model"))
+    if model is not None and parse_field_model(options.get("field_model", "cw")) != "pulsed":
+        raise ValueError('options["pulsed_drive_model"] needs options["field_model"] = "pulsed" '
+                         f'(got field_model = {options.get("field_model", "cw")!r}: the continuous-wave model has no drive waveform)')
     return model
 
 
@@ -210,12 +286,15 @@ def run_simulation(arr, params, delays=None, apod=None, freq: float = 1e6, cycle
                    amplitude: float = 1, dt: float = 0, t_end: float = 0, cfl: float = 0.5,
                    bli_tolerance: float = 0.05, upsampling_rate: int = 5, gpu: bool = True,
                    ref_values_only: bool = False, directivity: bool = False, field_model: str = "cw",
-                   pulse_intensity_integral: bool = False, record_points=None, medium_model=None):
+                   pulse_intensity_integral: bool = False, record_points=None, medium_model=None, drive_model=None):
     n = arr.numelements()
     pulse = (float(cycles), float(dt), float(t_end), float(cfl)) if parse_field_model(field_model) == "pulsed" else None
     medium_model = parse_pulsed_medium_model(medium_model)
     if medium_model is not None and pulse is None:
         raise ValueError('medium_model needs field_model="pulsed" (the continuous-wave model picks its medium kernels by itself)')
+    drive_model = parse_pulsed_drive_model(drive_model)
+    if drive_model is not None and pulse is None:
+        raise ValueError('drive_model needs field_model="pulsed" (the continuous-wave model has no drive waveform)')
     if pulse is None and (pulse_intensity_integral or record_points is not None):
         raise ValueError('pulse_intensity_integral and record_points need field_model="pulsed" (the continuous-wave model has no time axis)')
     want, trace_voxels = ("pmag", "intensity"), None
@@ -232,7 +311,8 @@ def run_simulation(arr, params, delays=None, apod=None, freq: float = 1e6, cycle
     logging.info("Running simulation")
     # (directivity: this path's extension -- the far-field pattern of the rectangular elements k-Wave models as finite sources)
     fields = simulate_foci(arr, params, delays[None, :], apod[None, :], freq, amplitude, want=want, directivity=directivity,
-                           ref_values_only=ref_values_only, pulse=pulse, trace_voxels=trace_voxels, pulsed_medium_model=medium_model)
+                           ref_values_only=ref_values_only, pulse=pulse, trace_voxels=trace_voxels, pulsed_medium_model=medium_model,
+                           pulsed_drive_model=drive_model)
     logging.info("Simulation Complete")
     if ref_values_only:
         # The reference then SIMULATES the reference medium (get_medium, sim/kwave_if.py:49-56) but still forms the intensity with

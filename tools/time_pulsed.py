@@ -5,7 +5,9 @@ of one shard.  Prints the per-launch time of each shape from HIP events (median 
 <PII> instantiation), `--trace N` also times one olx_field_pulse_trace of N points per shape (host clock around the synchronous call:
 table, memset, kernel and the copy out).  `--medium` puts the skull slab of BASELINE configs[4] into the timed grid (skull_slab_volumes; the
 water's own 0.0022 dB/cm/MHz dropped, so that only the slab's planes are non-trivial) and times, per shape, kernel 2p (no medium), kernel 2h
-(the sampled continuous-wave kernel through the same medium: 2h + 2p per focus is the yardstick) and kernel 2ph (olx_field_pulse_medium)."""
+(the sampled continuous-wave kernel through the same medium: 2h + 2p per focus is the yardstick) and kernel 2ph (olx_field_pulse_medium).
+`--response M` also times each shape with one class of M Hann-windowed taps at the drive frequency (olx_field_pulse_response, the RESP
+instantiations) after the plain plan."""
 from __future__ import annotations
 
 import argparse
@@ -35,6 +37,7 @@ def main():
     ap.add_argument("--pii", action="store_true", help="plan with OUT_PII: the pulse intensity integral volume")
     ap.add_argument("--trace", type=int, default=0, help="also time olx_field_pulse_trace of this many points")
     ap.add_argument("--medium", action="store_true", help="skull slab in the grid: time kernels 2p, 2h (sampled) and 2ph per shape")
+    ap.add_argument("--response", type=int, default=0, help="also time the plan with a Hann-windowed impulse response of this many taps")
     args = ap.parse_args()
     pos, size, _ = bo.gen_matrix_array(16, 16, 3.0, 0.3)
     pos_m = pos * 1e-3
@@ -61,6 +64,16 @@ def main():
         ms = ctx.field_time(args.iters)
         print(f"{n}^3 x {nfoci} foci{' + PII' if args.pii else ''}: {np.median(ms):.2f} ms per launch ({np.median(ms) / nfoci:.2f} ms per focus), "
               f"n_t = {n_t}, {ctx.field_variant()}", flush=True)
+        if args.response:
+            m = np.arange(args.response)
+            taps = (0.5 - 0.5 * np.cos(2 * np.pi * (m + 0.5) / args.response)) * np.sin(2 * np.pi * F0 * dt * m + 0.3)
+            ctx.field_pulse_response(np.zeros(256, dtype=np.int32), [taps])
+            ctx.field_plan(origin, (h, h, h), (n, n, n), F0, C, RHO, P0, flags=flags)
+            ms_r = ctx.field_time(args.iters)
+            print(f"{n}^3 x {nfoci} foci{' + PII' if args.pii else ''}, {args.response}-tap response: {np.median(ms_r):.2f} ms per launch "
+                  f"({np.median(ms_r) / np.median(ms):.2f} x the plain plan), {ctx.field_variant()}", flush=True)
+            ctx.field_pulse_response()
+            ctx.field_plan(origin, (h, h, h), (n, n, n), F0, C, RHO, P0, flags=flags)      # (what follows times the plain plan)
         if args.medium:
             ctx.field_pulse_medium(vol["sound_speed"], vol["attenuation"], vol["density"])
             ms = ctx.field_time(args.iters)
