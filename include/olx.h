@@ -36,6 +36,7 @@ extern "C" {
 #define OLX_EHIP (-3)    /* HIP runtime error (message has hipGetErrorString) */
 #define OLX_ENOMEM (-4)  /* device or host allocation failed */
 #define OLX_ECOMM (-5)   /* RCCL error or RCCL unavailable */
+#define OLX_ENOCONV (-6) /* an iteration did not converge within its cap (olx_eikonal_solve); nothing partial is kept */
 
 /* apodization kinds: bf/apod_methods/{uniform,maxangle,piecewiselinear}.py */
 #define OLX_APOD_UNIFORM 0   /* p0 = value                              (uniform.py:21-22) */
@@ -422,6 +423,23 @@ int olx_fullwave_lockin(olx_ctx *ctx, double freq, int first_step, int n_steps, 
 /* The lock-in sums: [voxels] floats each, [n_receivers] doubles each; any may be NULL.  OLX_ESTATE: nothing run, something asked
  * for that was not recorded, or the run has not reached the end of the window. */
 int olx_fullwave_fetch_lockin(olx_ctx *ctx, float *vol_cos, float *vol_sin, double *rec_cos, double *rec_sin);
+
+/* Eikonal travel times (DESIGN.md section 2 "Eikonal", kernel 6): first-arrival times T [s] from the point source_m through the sound
+ * speed of `grid` ([nx * ny * nz] floats, C order; NULL = c_uniform everywhere, and no volume is streamed), refraction included.
+ * Voxels within init_radius voxels of the source (index space) start at |x_v - x_t| / c(v) and stay; the others are lowered by Jacobi
+ * sweeps of the first-order upwind update (fp32 state) until a sweep changes no voxel.  *sweeps_out (may be NULL) = the number of
+ * sweeps, that last one included.  Synchronous.  Buffers of its own: the plan, the resident result, the thermal and the full-wave
+ * buffers stay as they are.  OLX_EINVAL before the device is touched: a speed that is not finite and > 0, a source outside
+ * [0, n_a - 1] index coordinates on an axis, init_radius < 1, max_sweeps < 1, 2^31 voxels or more.  OLX_ENOCONV when max_sweeps
+ * sweeps did not converge: no field is kept (olx_eikonal_sample / _fetch then return OLX_ESTATE), the context stays usable. */
+int olx_eikonal_solve(olx_ctx *ctx, const olx_grid *grid, const float *sound_speed, double c_uniform, const double *source_m,
+                      double init_radius, int max_sweeps, int *sweeps_out);
+/* T of the last solve at n_points points: t_out[r] = sum_q weights[q] (double) T(voxels[q]) over q in [row[r], row[r + 1]) in table
+ * order, in double.  OLX_ESTATE before a converged solve.  OLX_EINVAL: n_points < 1, a voxel outside the grid, a weight that is not
+ * finite, a row table that does not start at 0 or is not monotone.  Synchronous. */
+int olx_eikonal_sample(olx_ctx *ctx, int n_points, const int *row, const long long *voxels, const double *weights, double *t_out);
+/* The whole volume of the last solve ([voxels] floats, +inf where nothing arrived).  OLX_ESTATE before a converged solve. */
+int olx_eikonal_fetch(olx_ctx *ctx, float *t_out);
 
 /* ---- kernel 4: steering map (DESIGN.md section 2 "Steering map") ---------------------------------------
  * Where can the array steer?  Every voxel of `grid` is a candidate target, in the frame of the element table (kernel 1 with

@@ -10,6 +10,7 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <thread>
 
 #include "k_small.hip.h"
@@ -82,13 +83,14 @@ int olx_ctx_destroy(olx_ctx* c) {
 const char* olx_last_error(const olx_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 #ifdef OLX_DEBUG_BOUNDS   // debug build (k_types.hip.h): the kernels' index checks report here
-extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); int olx_dbg_bounds_bfmed(unsigned*); int olx_dbg_bounds_small(unsigned*); int olx_dbg_bounds_steer(unsigned*); int olx_dbg_bounds_steermed(unsigned*); int olx_dbg_bounds_pulsemed(unsigned*); int olx_dbg_bounds_fullwave(unsigned*); }
+extern "C" { int olx_dbg_bounds_cosetp(unsigned*); int olx_dbg_bounds_coset(unsigned*); int olx_dbg_bounds_toep(unsigned*); int olx_dbg_bounds_hmarch(unsigned*); int olx_dbg_bounds_pulse(unsigned*); int olx_dbg_bounds_thermal(unsigned*); int olx_dbg_bounds_bfmed(unsigned*); int olx_dbg_bounds_small(unsigned*); int olx_dbg_bounds_steer(unsigned*); int olx_dbg_bounds_steermed(unsigned*); int olx_dbg_bounds_pulsemed(unsigned*); int olx_dbg_bounds_fullwave(unsigned*); int olx_dbg_bounds_eikonal(unsigned*); }
 static int report_bounds(olx_ctx* c) {
     struct { const char* name; int (*read)(unsigned*); } units[] = {{"2g (k_coset2.hip)", olx_dbg_bounds_cosetp}, {"2e (k_coset.hip)", olx_dbg_bounds_coset},
                                                                      {"2f (k_toep.hip)", olx_dbg_bounds_toep}, {"2m (k_hmarch.hip)", olx_dbg_bounds_hmarch},
                                                                      {"2p (k_pulse.hip)", olx_dbg_bounds_pulse}, {"3 (k_thermal.hip)", olx_dbg_bounds_thermal},
                                                                      {"1m / 1a (k_bfmed.hip)", olx_dbg_bounds_bfmed}, {"pii_post_k (k_small.hip.h)", olx_dbg_bounds_small}, {"4 (k_steer.hip)", olx_dbg_bounds_steer},
-                                                                     {"4h (k_steer_med.hip)", olx_dbg_bounds_steermed}, {"2ph (k_pulse_med.hip)", olx_dbg_bounds_pulsemed}, {"5 (k_fullwave.hip)", olx_dbg_bounds_fullwave}};
+                                                                     {"4h (k_steer_med.hip)", olx_dbg_bounds_steermed}, {"2ph (k_pulse_med.hip)", olx_dbg_bounds_pulsemed}, {"5 (k_fullwave.hip)", olx_dbg_bounds_fullwave},
+                                                                     {"6 (k_eikonal.hip)", olx_dbg_bounds_eikonal}};
     int rc = OLX_OK;
     for (auto& u : units) {
         unsigned w[4] = {0, 0, 0, 0};
@@ -3396,6 +3398,130 @@ int olx_fullwave_fetch(olx_ctx* c, float* p_max, float* p_min, float* p_sq, floa
     if (!rc && p_sq) rc = fetch_to_host(c, p_sq, c->d_fw_psq, sizeof(float) * vox);
     if (!rc && traces && c->fw_npts > 0 && c->fw_next > 0) rc = fetch_to_host(c, traces, c->d_fw_trace, sizeof(float) * (size_t)c->fw_next * c->fw_npts);
     return rc;
+}
+
+}  // extern "C"
+
+// ---- eikonal travel times (kernel 6, k_eikonal.hip) ---------------------------------------------------------------------------------
+extern "C" {
+
+static constexpr int EK_CHECK = 8;     // the host reads the sweeps' flags after every EK_CHECK sweeps (once the launch box covers the grid)
+
+int olx_eikonal_solve(olx_ctx* c, const olx_grid* g, const float* sound_speed, double c_uniform, const double* source_m, double init_radius,
+                      int max_sweeps, int* sweeps_out) {
+    if (!c) return OLX_EINVAL;
+    if (!g || !source_m) return fail(c, OLX_EINVAL, "olx_eikonal_solve: null grid or source");
+    for (int a = 0; a < 3; ++a)
+        if (g->n[a] < 1 || !(g->spacing[a] > 0) || !std::isfinite(g->spacing[a]) || !std::isfinite(g->origin[a])) return fail(c, OLX_EINVAL, "olx_eikonal_solve: bad grid axis %d", a);
+    const long long voxll = (long long)g->n[0] * g->n[1] * g->n[2];
+    if (voxll >= (1ll << 31)) return fail(c, OLX_EINVAL, "olx_eikonal_solve: grid of %lld voxels is too large (< 2^31)", voxll);
+    if (!(init_radius >= 1) || !std::isfinite(init_radius)) return fail(c, OLX_EINVAL, "olx_eikonal_solve: init_radius must be finite and >= 1");
+    if (max_sweeps < 1) return fail(c, OLX_EINVAL, "olx_eikonal_solve: max_sweeps must be >= 1");
+    EikonalParams P{};
+    P.nx = g->n[0]; P.ny = g->n[1]; P.nz = g->n[2]; P.vox = voxll; P.radius = init_radius;
+    for (int a = 0; a < 3; ++a) {
+        const double q = (source_m[a] - g->origin[a]) / g->spacing[a];
+        if (!(q >= 0 && q <= g->n[a] - 1))
+            return fail(c, OLX_EINVAL, "olx_eikonal_solve: the source (%g, %g, %g) m lies outside the grid (axis %d: index %g not in [0, %d])", source_m[0], source_m[1], source_m[2], a, q, g->n[a] - 1);
+        P.q[a] = q; P.h[a] = g->spacing[a];
+        P.hf[a] = (float)g->spacing[a]; P.wf[a] = (float)(1.0 / (g->spacing[a] * g->spacing[a]));
+        P.ilo[a] = (int)std::max(std::ceil(q - init_radius), 0.0);
+        P.ihi[a] = (int)std::min(std::floor(q + init_radius), (double)(g->n[a] - 1));
+    }
+    const size_t vox = (size_t)voxll;
+    if (sound_speed) {
+        bool bad = false;       // (no early exit: the scan of 16.7 M voxels vectorises, and it is part of every solve with a volume)
+        for (size_t o = 0; o < vox; ++o) bad |= !(sound_speed[o] > 0.f && sound_speed[o] <= std::numeric_limits<float>::max());
+        if (bad) return fail(c, OLX_EINVAL, "olx_eikonal_solve: sound speed must be finite and > 0");
+    } else {
+        P.c0 = (float)c_uniform;
+        if (!(c_uniform > 0) || !std::isfinite(c_uniform) || !(P.c0 > 0.f) || !std::isfinite(P.c0)) return fail(c, OLX_EINVAL, "olx_eikonal_solve: the uniform sound speed must be finite and > 0");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ek_solved = false;
+    c->ek = P;
+    int rc = c->d_ek_T[0].reserve(c, vox);
+    if (!rc) rc = c->d_ek_T[1].reserve(c, vox);
+    if (!rc) rc = c->d_ek_flag.reserve(c, (size_t)max_sweeps);
+    if (!rc && sound_speed) rc = c->d_ek_c.reserve(c, vox);
+    if (rc) return rc;
+    const float* cs = nullptr;
+    if (sound_speed) {
+        HIPCHK(c, hipMemcpy(c->d_ek_c, sound_speed, sizeof(float) * vox, hipMemcpyHostToDevice));
+        cs = c->d_ek_c;
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_ek_flag, 0, sizeof(int) * (size_t)max_sweeps, c->stream));
+    olx_eikonal_init(c, cs);
+    HIPCHK(c, hipGetLastError());
+    // no sweep before this one can be the last: until the launch box covers the grid, every sweep reaches new voxels
+    int cover = 1;
+    for (int a = 0; a < 3; ++a) cover = std::max(cover, std::max(P.ilo[a], g->n[a] - 1 - P.ihi[a]));
+    std::vector<int> flags;
+    int done = 0, converged = 0;
+    while (!converged && done < max_sweeps) {
+        const int upto = std::min(max_sweeps, std::max(done + EK_CHECK, cover));
+        for (int s = done + 1; s <= upto; ++s) olx_eikonal_sweep(c, cs, s);
+        HIPCHK(c, hipGetLastError());
+        flags.resize((size_t)(upto - done));
+        HIPCHK(c, hipMemcpyAsync(flags.data(), c->d_ek_flag + done, sizeof(int) * flags.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int s = done + 1; s <= upto && !converged; ++s)
+            if (flags[(size_t)(s - done - 1)] == 0) converged = s;
+        done = upto;
+    }
+    if (sweeps_out) *sweeps_out = converged ? converged : done;
+    if (!converged) return fail(c, OLX_ENOCONV, "olx_eikonal_solve: no convergence within max_sweeps = %d sweeps", max_sweeps);
+    // the sweeps after the first one that changed nothing changed nothing either: both buffers hold the field
+    c->ek_cur = done & 1;
+    c->ek_solved = true;
+    return OLX_OK;
+}
+
+int olx_eikonal_sample(olx_ctx* c, int n_points, const int* row, const long long* voxels, const double* weights, double* t_out) {
+    if (!c) return OLX_EINVAL;
+    if (!c->ek_solved) return fail(c, OLX_ESTATE, "olx_eikonal_sample: no converged olx_eikonal_solve");
+    if (n_points < 1 || !row || !t_out) return fail(c, OLX_EINVAL, "olx_eikonal_sample: n_points < 1, or null row table or output");
+    if (row[0] != 0) return fail(c, OLX_EINVAL, "olx_eikonal_sample: row[0] must be 0");
+    for (int r = 0; r < n_points; ++r)
+        if (row[r + 1] < row[r]) return fail(c, OLX_EINVAL, "olx_eikonal_sample: row table not monotone at point %d", r);
+    const int n_entries = row[n_points];
+    if (n_entries > 0 && (!voxels || !weights)) return fail(c, OLX_EINVAL, "olx_eikonal_sample: null sample table");
+    for (int e = 0; e < n_entries; ++e) {
+        if (voxels[e] < 0 || voxels[e] >= c->ek.vox) return fail(c, OLX_EINVAL, "olx_eikonal_sample: entry %d: voxel %lld outside the grid of %lld voxels", e, voxels[e], c->ek.vox);
+        if (!std::isfinite(weights[e])) return fail(c, OLX_EINVAL, "olx_eikonal_sample: entry %d: weight must be finite", e);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int rc = c->d_ek_row.reserve(c, (size_t)n_points + 1);
+    if (!rc) rc = c->d_ek_vox.reserve(c, n_entries);
+    if (!rc) rc = c->d_ek_w.reserve(c, n_entries);
+    if (!rc) rc = c->d_ek_out.reserve(c, n_points);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpy(c->d_ek_row, row, sizeof(int) * ((size_t)n_points + 1), hipMemcpyHostToDevice));
+    if (n_entries > 0) {
+        HIPCHK(c, hipMemcpy(c->d_ek_vox, voxels, sizeof(long long) * n_entries, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_ek_w, weights, sizeof(double) * n_entries, hipMemcpyHostToDevice));
+    }
+    olx_eikonal_sample_launch(c, n_points, n_entries);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+#ifdef OLX_DEBUG_BOUNDS
+    { int rc_ = report_bounds(c); if (rc_) return rc_; }
+#endif
+    return fetch_to_host(c, t_out, c->d_ek_out, sizeof(double) * (size_t)n_points);
+}
+
+int olx_eikonal_fetch(olx_ctx* c, float* t_out) {
+    if (!c) return OLX_EINVAL;
+    if (!c->ek_solved) return fail(c, OLX_ESTATE, "olx_eikonal_fetch: no converged olx_eikonal_solve");
+    if (!t_out) return fail(c, OLX_EINVAL, "olx_eikonal_fetch: null output");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+#ifdef OLX_DEBUG_BOUNDS
+    { int rc_ = report_bounds(c); if (rc_) return rc_; }
+#endif
+    return fetch_to_host(c, t_out, c->d_ek_T[c->ek_cur], sizeof(float) * (size_t)c->ek.vox);
 }
 
 }  // extern "C"

@@ -197,6 +197,12 @@ struct olx_ctx {
     DevBuf<float> d_fw_lc, d_fw_ls;           // [voxels] sum p~ cos theta_n, sum p~ sin theta_n (created by the first lock-in that asks for the volume)
     DevBuf<int> d_fw_lrow; DevBuf<long long> d_fw_lvox; DevBuf<double> d_fw_lw, d_fw_lrc, d_fw_lrs;   // CSR receiver table: row offsets, voxels, weights; [receivers] sums
     int fw_next = -1; bool fw_pii = false;    // the step the next olx_fullwave_run continues with (-1: nothing run since the last plan / sources); the run accumulates sum p~^2
+    // eikonal travel times (kernel 6, olx_eikonal_*): buffers of their own, apart from the plan, the resident result, the thermal and the full-wave buffers
+    bool ek_solved = false; EikonalParams ek{}; int ek_cur = 0;   // a converged field stands in d_ek_T[ek_cur]
+    DevBuf<float> d_ek_T[2];                  // [voxels] the ping-pong travel times [s], +inf = nothing arrived
+    DevBuf<float> d_ek_c;                     // [voxels] the sound-speed volume of the running solve (not created for a uniform one)
+    DevBuf<int> d_ek_flag;                    // [max_sweeps] sweep n + 1 lowered a voxel
+    DevBuf<int> d_ek_row; DevBuf<long long> d_ek_vox; DevBuf<double> d_ek_w, d_ek_out;   // CSR sample table: row offsets, voxels, weights; [points] T
     // steering map (kernel 4, olx_steer_map): result volumes and element records of their own -- they never alias the field, aggregate or PII buffers
     DevBuf<float> d_sm_p; DevBuf<int> d_sm_n;          // [voxels] focal pressure [Pa], active elements; created by the first call, reused by later ones
     DevBuf<double> d_sm_tabd; DevBuf<float> d_sm_tabf; // [N * STEER_TD], [N * STEER_TF] element records (olx_params.h)

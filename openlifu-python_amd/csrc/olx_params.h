@@ -204,6 +204,23 @@ struct FullwaveSource {
     int n_vox;                       // distinct source voxels (CSR rows)
 };
 
+// kernel 6 (eikonal_*_k, k_eikonal.hip): first-arrival travel times from a point, upwind Godunov update swept Jacobi-wise (olx_eikonal_*)
+struct EikonalParams {
+    int nx, ny, nz;
+    long long vox;
+    double q[3];                     // the source in index coordinates, 0 <= q_a <= n_a - 1
+    double h[3];                     // spacing [m]
+    double radius;                   // init_radius [voxels]
+    int ilo[3], ihi[3];              // the init box: ceil(q - radius) .. floor(q + radius), clipped by the grid
+    float hf[3], wf[3];              // h_a and 1 / h_a^2 rounded once to float
+    float c0;                        // the uniform sound speed (no volume) [m/s]
+};
+struct EikonalBox {                  // the voxels one sweep is launched over
+    int lo[3], n[3];
+    unsigned mul[3]; int sh[3];      // l / n[a] == (l * mul[a]) >> sh[a] for l < 2^31
+    long long count;
+};
+
 // kernel 1m (bf_med_k, k_bfmed.hip): straight-ray delays through the medium of olx_bf_set_medium (DESIGN.md section 2 "StraightRay")
 struct BfMedParams {
     double ox, oy, oz, hx, hy, hz;  // grid origin and spacing [m]

@@ -16,7 +16,7 @@ import numpy as np
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OLX_LIB_PATH") or os.path.join(os.path.dirname(_PKG_DIR), "lib", "libolx.so")  # env: kernel A/B builds
 
-OLX_OK, OLX_EINVAL, OLX_ESTATE, OLX_EHIP, OLX_ENOMEM, OLX_ECOMM = 0, -1, -2, -3, -4, -5
+OLX_OK, OLX_EINVAL, OLX_ESTATE, OLX_EHIP, OLX_ENOMEM, OLX_ECOMM, OLX_ENOCONV = 0, -1, -2, -3, -4, -5, -6
 APOD_UNIFORM, APOD_MAXANGLE, APOD_PIECEWISE = 0, 1, 2
 COMP_MODES = {"equalize": 0, "matched": 1}   # OLX_COMP_*
 STEER_COMP_NONE = -1                         # OLX_STEER_COMP_NONE
@@ -46,6 +46,7 @@ SYMBOLS = [
     "olx_pii_post", "olx_pii_fetch_weighted", "olx_pii_fetch_max", "olx_pii_upload", "olx_thermal_source_pii",
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
     "olx_fullwave_plan", "olx_fullwave_sources", "olx_fullwave_run", "olx_fullwave_fetch", "olx_fullwave_lockin", "olx_fullwave_fetch_lockin",
+    "olx_eikonal_solve", "olx_eikonal_sample", "olx_eikonal_fetch",
     "olx_bf_set_medium", "olx_bf_solve_medium",
     "olx_bf_set_attenuation", "olx_bf_solve_compensated",
     "olx_steer_map", "olx_steer_time", "olx_steer_map_medium",
@@ -54,6 +55,10 @@ SYMBOLS = [
 
 class NativeError(RuntimeError):
     """A C-ABI call returned a negative OLX_E* code."""
+
+
+class ConvergenceError(NativeError):
+    """OLX_ENOCONV: an iteration did not converge within its cap; no partial result is kept."""
 
 
 class OlxGrid(ctypes.Structure):
@@ -168,6 +173,9 @@ def load(require_gpu: bool = True):
         lib.olx_fullwave_fetch.argtypes = [vp, fp, fp, fp, fp]
         lib.olx_fullwave_lockin.argtypes = [vp, c_double, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(ctypes.c_longlong), dp]
         lib.olx_fullwave_fetch_lockin.argtypes = [vp, fp, fp, dp, dp]
+        lib.olx_eikonal_solve.argtypes = [vp, POINTER(OlxGrid), fp, c_double, dp, c_double, c_int, POINTER(c_int)]
+        lib.olx_eikonal_sample.argtypes = [vp, c_int, POINTER(c_int), POINTER(ctypes.c_longlong), dp, dp]
+        lib.olx_eikonal_fetch.argtypes = [vp, fp]
         lib.olx_set_element_apertures.argtypes = [vp, dp, dp]
         lib.olx_comm_export.argtypes = [vp, vp]
         lib.olx_comm_import.argtypes = [vp, vp]
@@ -231,6 +239,8 @@ class Context:
             msg = msg.decode() if msg else ""
             if rc == OLX_EINVAL:
                 raise ValueError(msg)
+            if rc == OLX_ENOCONV:
+                raise ConvergenceError(f"[olx {rc}] {msg}")
             raise NativeError(f"[olx {rc}] {msg}")
 
     def close(self):
@@ -817,6 +827,53 @@ class Context:
         self._chk(self._lib.olx_fullwave_fetch_lockin(self._h, _fptr(vc), _fptr(vs), _dptr(rc) if rc is not None else None,
                                                       _dptr(rs) if rs is not None else None))
         return vc, vs, rc, rs
+
+    # ---- eikonal travel times (kernel 6) -----------------------------------------------------------------------------------
+    def eikonal_solve(self, origin_m, spacing_m, n, sound_speed, source_m, init_radius: float = 3.0, max_sweeps=None) -> int:
+        """First-arrival travel times from ``source_m`` through ``sound_speed`` -- a float (uniform: no volume is streamed) or a
+        [nx, ny, nz] volume -- on the grid; returns the number of sweeps.  ``max_sweeps`` None = 4 (nx + ny + nz).  ValueError for a bad
+        argument, ``ConvergenceError`` when the cap passes (no field is kept)."""
+        shape = tuple(int(v) for v in n)
+        g = OlxGrid()
+        for a in range(3):
+            g.origin[a] = float(origin_m[a]); g.spacing[a] = float(spacing_m[a]); g.n[a] = shape[a]
+        vol, c_uni = None, 0.0
+        if np.ndim(sound_speed) == 0:
+            c_uni = float(sound_speed)
+        else:
+            vol = np.ascontiguousarray(sound_speed, dtype=np.float32)
+            if vol.shape != shape:
+                raise ValueError(f"eikonal sound-speed volume must be {shape}, got {vol.shape}")
+        src = _f64(source_m, (3,))
+        max_sweeps = 4 * sum(shape) if max_sweeps is None else int(max_sweeps)
+        sweeps = c_int(0)
+        self._ek_shape = None
+        self._chk(self._lib.olx_eikonal_solve(self._h, ctypes.byref(g), _fptr(vol), c_uni, _dptr(src), float(init_radius), max_sweeps,
+                                              ctypes.byref(sweeps)))
+        self._ek_shape = shape
+        return int(sweeps.value)
+
+    def eikonal_sample(self, row, voxels, weights):
+        """T [s] of the last solve at the points of the CSR table (``row`` [P + 1], ``voxels`` linear, ``weights``) -> float64 [P]."""
+        rw = np.ascontiguousarray(row, dtype=np.int32)
+        vx = np.ascontiguousarray(voxels, dtype=np.int64)
+        wt = np.ascontiguousarray(weights, dtype=np.float64)
+        if not (rw.ndim == 1 and rw.size >= 2 and vx.ndim == 1 and vx.shape == wt.shape):
+            raise ValueError(f"row must be 1-D with at least two offsets, voxels and weights 1-D of one length, got {rw.shape}, {vx.shape}, {wt.shape}")
+        if int(rw[-1]) != vx.size:
+            raise ValueError(f"the last row offset {int(rw[-1])} is not the number of entries {vx.size}")
+        out = np.empty(rw.size - 1, dtype=np.float64)
+        self._chk(self._lib.olx_eikonal_sample(self._h, int(rw.size - 1), rw.ctypes.data_as(POINTER(c_int)), vx.ctypes.data_as(POINTER(ctypes.c_longlong)),
+                                               _dptr(wt), _dptr(out)))
+        return out
+
+    def eikonal_fetch(self):
+        """The travel-time volume of the last solve, float32 [nx, ny, nz], +inf where nothing arrived."""
+        if getattr(self, "_ek_shape", None) is None:
+            raise NativeError("eikonal_fetch: no converged eikonal_solve")
+        out = np.empty(self._ek_shape, dtype=np.float32)
+        self._chk(self._lib.olx_eikonal_fetch(self._h, _fptr(out)))
+        return out
 
     def field_scale_aggregate(self, scale_per_focus):
         """``field_scale`` + ``field_aggregate_device`` in one pass (identical values)."""

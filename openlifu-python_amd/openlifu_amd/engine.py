@@ -532,6 +532,15 @@ class Engine:
         self.ctx.fullwave_run(0, n_steps)
         return self.ctx.fullwave_fetch_lockin()
 
+    # ---- kernel 6 -----------------------------------------------------------------------------
+    def eikonal(self, origin_m, spacing_m, n, sound_speed, source_m, points=None, init_radius=3.0, max_sweeps=None, volume=False):
+        """First-arrival travel times from ``source_m`` through ``sound_speed`` (a float, or a [nx, ny, nz] volume) on the grid
+        (bf/delay_methods/eikonal.py, kernel 6) -> (T [P] float64 at the ``points = (row, voxel, weight)`` CSR table | None, sweeps,
+        T volume float32 | None).  The field / aggregate / thermal / full-wave volumes and every lazy array over them are left as they are."""
+        sweeps = self.ctx.eikonal_solve(origin_m, spacing_m, n, sound_speed, source_m, init_radius=init_radius, max_sweeps=max_sweeps)
+        at = None if points is None else self.ctx.eikonal_sample(*points)
+        return at, sweeps, (self.ctx.eikonal_fetch() if volume else None)
+
     def upload_result(self, origin_m, spacing_m, n, pmag, intensity=None):
         """Bind host volumes [F,nx,ny,nz] as the resident result (analysis of a detached Solution)."""
         self.retire_results()
