@@ -423,6 +423,37 @@ int olx_fullwave_lockin(olx_ctx *ctx, double freq, int first_step, int n_steps, 
 /* The lock-in sums: [voxels] floats each, [n_receivers] doubles each; any may be NULL.  OLX_ESTATE: nothing run, something asked
  * for that was not recorded, or the run has not reached the end of the window. */
 int olx_fullwave_fetch_lockin(olx_ctx *ctx, float *vol_cos, float *vol_sin, double *rec_cos, double *rec_sin);
+/* Finite rectangular element apertures (DESIGN.md section 2 "full-wave model: apertures", section 5.18).  Element e is the rectangle
+ * with centre centre[3 e ..] [m, in the frame of the planned grid], in-plane unit axes u_axis[3 e ..] (width) and v_axis[3 e ..]
+ * (length) and size size[2 e ..] = (w, l) [m], sampled at the n_w[e] x n_l[e] points
+ *   x_ab = c + ((a + 1/2) / n_w - 1/2) w u + ((b + 1/2) / n_l - 1/2) l v,
+ * q_ab = (x_ab - origin) / h per axis, a coordinate within 1e-9 of a whole number counting as that number.  The weight of voxel m is
+ *   W_e(m) = 1 / (n_w n_l) sum_a sum_b prod_axis max(0, 1 - |q_ab,axis - m_axis|)      (a outer, b inner, double),
+ * the trilinear spread of n_w n_l equal monopoles merged per voxel; sum_m W_e(m) = 1.  fullwave_aperture_k evaluates it with one lane
+ * per (element, voxel of the element's index box).  Returns a per-element CSR of the weights that are not 0: row[n_el + 1],
+ * voxels (linear C-order index of the planned grid, ascending inside a row) and weights.  *n_needed (may be NULL) receives the number
+ * of entries; when it is above `capacity` only row is written and the call still returns OLX_OK: call again with room for n_needed.
+ * OLX_ESTATE without olx_fullwave_plan.  OLX_EINVAL, naming the element, before any launch: a centre, axis or size that is not finite,
+ * a size < 0, n_w or n_l < 1, more than 65536 points, a weighted voxel outside the grid.  Synchronous; changes no source table, run
+ * or record. */
+int olx_fullwave_apertures(olx_ctx *ctx, int n_el, const double *centre, const double *u_axis, const double *v_axis, const double *size,
+                           const int *n_w, const int *n_l, long long capacity, int *row, long long *voxels, double *weights,
+                           long long *n_needed);
+/* The source table in element-factored form: entry q adds (float)(amplitude[q] s_e(n)), e = elements[q] < n_el, to p at voxels[q] at
+ * the start of step n, with the drive s_e(n) = A[e] env(u) sin(2 pi frac(freq u)), u = (n - 1/2) dt - tau[e], exactly 0 outside
+ * 0 <= u < cycles / freq (double, as olx_fullwave_sources forms it).  The entries are sorted by voxel, stably, so those of one voxel
+ * add in table order; one launch (fullwave_drive_k) fills the drive table s[n_steps][n_el], and each step of olx_fullwave_run then
+ * launches fullwave_inject_elem_k in place of fullwave_inject_k.  The other arguments, the reset of the run and of the lock-in are
+ * olx_fullwave_sources's, and whichever of the two was called last decides the inject kernel.  OLX_EINVAL before the device is
+ * touched: an element outside [0, n_el), a voxel outside the grid, an amplitude, A or tau that is not finite, a drive table above
+ * 2^28 bytes (n_steps n_el doubles). */
+int olx_fullwave_sources_elements(olx_ctx *ctx, int n_entries, const long long *voxels, const int *elements, const double *amplitude,
+                                  int n_el, const double *A, const double *tau, double freq, double cycles, double ramp_cycles,
+                                  int n_steps, int n_points, const long long *points);
+/* New A[n_el], tau[n_el] for the table of olx_fullwave_sources_elements: re-fills the drive table and resets the run (the next
+ * olx_fullwave_run starts at step 0; a lock-in is cleared as by a source call); the entry table stays on the device.  OLX_ESTATE
+ * when the last source call was not olx_fullwave_sources_elements. */
+int olx_fullwave_drive(olx_ctx *ctx, const double *A, const double *tau);
 
 /* Eikonal travel times (DESIGN.md section 2 "Eikonal", kernel 6): first-arrival times T [s] from the point source_m through the sound
  * speed of `grid` ([nx * ny * nz] floats, C order; NULL = c_uniform everywhere, and no volume is streamed), refraction included.

@@ -1,4 +1,5 @@
-// kernel 5 (fullwave_pack_k, fullwave_inject_k, fullwave_vel_k, fullwave_pres_k, fullwave_trace_k, fullwave_receive_k): full-wave FDTD field model --
+// kernel 5 (fullwave_pack_k, fullwave_inject_k, fullwave_vel_k, fullwave_pres_k, fullwave_trace_k, fullwave_receive_k; element apertures:
+// fullwave_aperture_k, fullwave_drive_k, fullwave_inject_elem_k): full-wave FDTD field model --
 // linear acoustics, first order in (p, v) on a staggered grid, second order in time, fourth order in space.
 // gfx950 (CDNA4, wave64) only.  Definition: DESIGN.md section 2 ("full-wave model") and section 5.14, fp64 oracle tests/fullwave_oracle.py.
 //
@@ -16,6 +17,9 @@
 //             volume: C += p~ cosf_n, S += p~ sinf_n (one fmaf each, cos / sin theta_n rounded once to float and passed as kernel arguments),
 //             the third template flag of the pressure launch; receivers: s_r = sum_q w_q p~(vox_q) in table order, C_r += s_r cos theta_n,
 //             S_r += s_r sin theta_n in fp64, ONE thread per receiver walking its CSR row (the form of inject: no atomics)
+//   apertures opt-in: fullwave_aperture_k spreads each element's rectangle over the voxels (weights W_e(m), fp64, once per
+//             geometry); the sources then stand in element-factored form -- entries (voxel, element, amp_{e,m}) and a drive table s_e(n) filled
+//             by ONE launch of fullwave_drive_k -- and fullwave_inject_elem_k takes the place of inject: p[vox] += (float)(amp_{e,m} s_e(n))
 // D = d_x[i] d_y[j] d_z[k] from three 1-D tables (1 in the interior, the absorbing layers' decay per step outside it).
 // A heterogeneous medium streams five coefficient volumes formed once by fullwave_pack_k (b_x, b_y, b_z for the velocity launch, kp, ga
 // for the pressure launch); the uniform instantiation (UNI) streams none of them.
@@ -92,6 +96,85 @@ __global__ void fullwave_inject_k(float* __restrict__ p, const long long* __rest
         any = true;
     }
     if (any) p[at] = acc;
+}
+
+// element-factored sources: the drive s_e(n) of every (step, element), one lane each, formed as fullwave_inject_k forms
+// it and exactly 0.0 outside the burst; the step loop then holds no trigonometry
+__global__ __launch_bounds__(FW_BLOCK) void fullwave_drive_k(const double* __restrict__ A, const double* __restrict__ tau, const FullwaveSource S, int n_el,
+                                                             long long total, double* __restrict__ drive) {
+    const long long g = (long long)blockIdx.x * FW_BLOCK + threadIdx.x;
+    if (g >= total || !OLX_IN(g, total, 21)) return;
+    const long long n = g / n_el;
+    const int e = (int)(g - n * n_el);
+    if (!OLX_IN(e, n_el, 22)) return;
+    const double u = ((double)n - 0.5) * S.dt - tau[e];
+    double s = 0.0;
+    if (u >= 0.0 && u < S.T) {
+        double ph = S.freq * u;
+        ph -= floor(ph);
+        double env = 1.0;
+        if (S.Tr > 0.0) {
+            if (u < S.Tr) env *= 0.5 * (1.0 - cos(M_PI * u / S.Tr));
+            if (S.T - u < S.Tr) env *= 0.5 * (1.0 - cos(M_PI * (S.T - u) / S.Tr));
+        }
+        s = A[e] * env * sin(2.0 * M_PI * ph);
+    }
+    drive[g] = s;
+}
+
+// the sources of step n in element-factored form: row r of the CSR table is one voxel, its entries (amp_{e,m}, e) add in table order
+__global__ void fullwave_inject_elem_k(float* __restrict__ p, const long long* __restrict__ svox, const int* __restrict__ srow, const double* __restrict__ samp,
+                                       const int* __restrict__ sel, const double* __restrict__ drive, int n_vox, int n_entries, int n_el, long long n_drive,
+                                       long long vox, int step) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_vox || !OLX_IN(r + 1, n_vox + 1, 23)) return;
+    const long long at = svox[r];
+    if (!OLX_IN(at, vox, 24)) return;
+    float acc = p[at];
+    bool any = false;
+    for (int q = srow[r]; q < srow[r + 1]; ++q) {
+        if (!OLX_IN(q, n_entries, 25)) break;
+        const int e = sel[q];
+        const long long d = (long long)step * n_el + e;
+        if (!OLX_IN(e, n_el, 26) || !OLX_IN(d, n_drive, 27)) continue;
+        const double s = drive[d];
+        if (s == 0.0) continue;
+        acc += (float)(samp[q] * s);
+        any = true;
+    }
+    if (any) p[at] = acc;
+}
+
+// aperture weights in gather form: one lane per (element, voxel of the element's index box) walks the element's quadrature points in the
+// order of the definition (a outer, b inner) and writes W_e(m) in fp64.  Every operation is rounded on its own (no contraction), so the
+// coordinates are the bits that the host's refusals and the fp64 oracle see.
+__global__ __launch_bounds__(FW_BLOCK) void fullwave_aperture_k(const FullwaveAperture* __restrict__ ap, int n_el, double ox, double oy, double oz, double hx,
+                                                                double hy, double hz, double* __restrict__ W, long long total) {
+#pragma clang fp contract(off)
+    const int e = blockIdx.x;
+    if (!OLX_IN(e, n_el, 28)) return;
+    const FullwaveAperture E = ap[e];
+    const long long t = (long long)blockIdx.y * FW_BLOCK + threadIdx.x;
+    if (t >= (long long)E.dim[0] * E.dim[1] * E.dim[2]) return;
+    const long long row = t / E.dim[2];
+    const double mk = (double)(E.lo[2] + (int)(t - row * E.dim[2]));
+    const double mj = (double)(E.lo[1] + (int)(row % E.dim[1]));
+    const double mi = (double)(E.lo[0] + (int)(row / E.dim[1]));
+    double acc = 0.0;
+    for (int a = 0; a < E.nw; ++a) {
+        const double sa = fw_aperture_s(a, E.nw);
+        for (int b = 0; b < E.nl; ++b) {
+            const double sb = fw_aperture_s(b, E.nl);
+            const double dx = 1.0 - fabs(fw_aperture_q(E, sa, sb, 0, ox, hx) - mi);
+            if (!(dx > 0.0)) continue;
+            const double dy = 1.0 - fabs(fw_aperture_q(E, sa, sb, 1, oy, hy) - mj);
+            if (!(dy > 0.0)) continue;
+            const double dz = 1.0 - fabs(fw_aperture_q(E, sa, sb, 2, oz, hz) - mk);
+            if (!(dz > 0.0)) continue;
+            acc += (dx * dy) * dz;
+        }
+    }
+    if (OLX_IN(E.off + t, total, 29)) W[E.off + t] = acc / (double)(E.nw * E.nl);
 }
 
 template <bool UNI>
@@ -204,7 +287,10 @@ void olx_fullwave_step(olx_ctx* c, int step, bool pii) {
     const FullwaveParams& P = c->fw;
     const FullwaveSource& S = c->fw_src;
     float* p = c->d_fw_p;
-    if (S.n_vox > 0)
+    if (S.n_vox > 0 && c->fw_elem)
+        hipLaunchKernelGGL(fullwave_inject_elem_k, dim3((S.n_vox + 63) / 64), dim3(64), 0, c->stream, p, c->d_fw_svox, c->d_fw_srow, c->d_fw_samp, c->d_fw_sel,
+                           c->d_fw_drive, S.n_vox, c->fw_entries, c->fw_nel, (long long)c->fw_steps * c->fw_nel, P.vox, step);
+    else if (S.n_vox > 0)
         hipLaunchKernelGGL(fullwave_inject_k, dim3((S.n_vox + 63) / 64), dim3(64), 0, c->stream, p, c->d_fw_svox, c->d_fw_srow, c->d_fw_samp, c->d_fw_stau, S,
                            c->fw_entries, P.vox, step);
     const dim3 grid = fw_grid(P), block(FW_BLOCK);
@@ -233,4 +319,15 @@ void olx_fullwave_step(olx_ctx* c, int step, bool pii) {
     if (lock && c->fw_lock_nrec > 0)
         hipLaunchKernelGGL(fullwave_receive_k, dim3((c->fw_lock_nrec + 63) / 64), dim3(64), 0, c->stream, p, c->d_fw_lrow, c->d_fw_lvox, c->d_fw_lw,
                            c->fw_lock_nrec, c->fw_lock_entries, P.vox, cos_n, sin_n, c->d_fw_lrc, c->d_fw_lrs);
+}
+
+void olx_fullwave_aperture_weights(olx_ctx* c, int n_el, long long max_box, long long total) {
+    hipLaunchKernelGGL(fullwave_aperture_k, dim3((unsigned)n_el, (unsigned)((max_box + FW_BLOCK - 1) / FW_BLOCK)), dim3(FW_BLOCK), 0, c->stream, c->d_fw_ap, n_el,
+                       c->fw_origin[0], c->fw_origin[1], c->fw_origin[2], c->fw_h[0], c->fw_h[1], c->fw_h[2], c->d_fw_apw, total);
+}
+
+void olx_fullwave_drive_fill(olx_ctx* c) {
+    const long long total = (long long)c->fw_steps * c->fw_nel;
+    hipLaunchKernelGGL(fullwave_drive_k, dim3((unsigned)((total + FW_BLOCK - 1) / FW_BLOCK)), dim3(FW_BLOCK), 0, c->stream, c->d_fw_dA, c->d_fw_dtau, c->fw_src,
+                       c->fw_nel, total, c->d_fw_drive);
 }

@@ -3190,7 +3190,8 @@ int olx_fullwave_plan(olx_ctx* c, const olx_grid* g, const float* sound_speed, c
     P.dt = (float)dt;
     P.c0 = (float)sound_speed0; P.rho0 = (float)density0; P.alpha0 = (float)absorption0;
     c->fw_uniform = !sound_speed && !density && !absorption;
-    c->fw_dt = dt; c->fw_dt_max = dt_max;
+    c->fw_dt = dt; c->fw_dt_max = dt_max; c->fw_elem = false;
+    for (int a = 0; a < 3; ++a) { c->fw_h[a] = g->spacing[a]; c->fw_origin[a] = g->origin[a]; }
     for (DevBuf<float>* b : {&c->d_fw_p, &c->d_fw_v[0], &c->d_fw_v[1], &c->d_fw_v[2], &c->d_fw_pmax, &c->d_fw_pmin}) { int rc = b->reserve(c, vox); if (rc) return rc; }
     // the layers' decay per step: d_a[i] = exp(-pml_alpha (c_ref / h_a) (depth / pml_size)^4 dt), depth = voxels into the layer (0 inside)
     const int ntab = P.nx + P.ny + P.nz;
@@ -3279,8 +3280,164 @@ int olx_fullwave_sources(olx_ctx* c, int n_entries, const long long* voxels, con
     FullwaveSource& S = c->fw_src;
     S = FullwaveSource{};
     S.freq = freq; S.T = cycles / freq; S.Tr = ramp_cycles / freq; S.dt = c->fw_dt; S.n_vox = (int)svox.size();
-    c->fw_entries = n_entries; c->fw_steps = n_steps; c->fw_npts = n_points;
+    c->fw_entries = n_entries; c->fw_steps = n_steps; c->fw_npts = n_points; c->fw_elem = false;
     c->fw_sourced = true;
+    return OLX_OK;
+}
+
+int olx_fullwave_sources_elements(olx_ctx* c, int n_entries, const long long* voxels, const int* elements, const double* amplitude, int n_el, const double* A,
+                                  const double* tau_s, double freq, double cycles, double ramp_cycles, int n_steps, int n_points, const long long* points) {
+    if (!c) return OLX_EINVAL;
+    if (!c->fw_planned) return fail(c, OLX_ESTATE, "olx_fullwave_sources_elements: no full-wave plan");
+    if (n_entries < 0 || (n_entries > 0 && (!voxels || !elements || !amplitude))) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: n_entries < 0 or null table");
+    if (n_el < 1 || !A || !tau_s) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: n_el < 1 or null A / tau");
+    if (!(freq > 0) || !std::isfinite(freq) || !(cycles > 0) || !std::isfinite(cycles) || !(ramp_cycles >= 0) || !std::isfinite(ramp_cycles))
+        return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: freq and cycles must be finite and > 0, ramp_cycles finite and >= 0");
+    if (n_steps < 1 || n_points < 0 || (n_points > 0 && !points)) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: n_steps < 1 or bad points");
+    for (int e = 0; e < n_el; ++e)
+        if (!std::isfinite(A[e]) || !std::isfinite(tau_s[e])) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: element %d: A and delay must be finite", e);
+    for (int q = 0; q < n_entries; ++q) {
+        if (voxels[q] < 0 || voxels[q] >= c->fw.vox) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: entry %d: voxel %lld outside the grid of %lld voxels", q, voxels[q], c->fw.vox);
+        if (elements[q] < 0 || elements[q] >= n_el) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: entry %d: element %d outside [0, %d)", q, elements[q], n_el);
+        if (!std::isfinite(amplitude[q])) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: entry %d: amplitude must be finite", q);
+    }
+    for (int p = 0; p < n_points; ++p)
+        if (points[p] < 0 || points[p] >= c->fw.vox) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: trace point %d outside the grid", p);
+    if ((double)n_steps * n_points > 268435456.0) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: %g trace samples are too many (trace fewer points)", (double)n_steps * n_points);
+    if ((double)n_steps * n_el * sizeof(double) > 268435456.0)
+        return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: a drive table of %d steps x %d elements (%g bytes) is too large (2^28 bytes)", n_steps, n_el, (double)n_steps * n_el * sizeof(double));
+    // CSR by voxel: a stable sort keeps the entries of one voxel in table order (ascending element for a table built element by element)
+    std::vector<int> order(n_entries);
+    for (int q = 0; q < n_entries; ++q) order[q] = q;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return voxels[a] < voxels[b]; });
+    std::vector<long long> svox; std::vector<int> srow, sel(n_entries); std::vector<double> samp(n_entries);
+    for (int q = 0; q < n_entries; ++q) {
+        const int e = order[q];
+        if (q == 0 || voxels[e] != svox.back()) { svox.push_back(voxels[e]); srow.push_back(q); }
+        samp[q] = amplitude[e]; sel[q] = elements[e];
+    }
+    srow.push_back(n_entries);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->fw_sourced = false; c->fw_next = -1;
+    c->fw_lock = false; c->fw_lock_vol = false; c->fw_lock_nrec = 0; c->fw_lock_entries = 0;
+    int rc = c->d_fw_svox.reserve(c, svox.size());
+    if (!rc) rc = c->d_fw_srow.reserve(c, srow.size());
+    if (!rc) rc = c->d_fw_samp.reserve(c, n_entries);
+    if (!rc) rc = c->d_fw_sel.reserve(c, n_entries);
+    if (!rc) rc = c->d_fw_dA.reserve(c, n_el);
+    if (!rc) rc = c->d_fw_dtau.reserve(c, n_el);
+    if (!rc) rc = c->d_fw_drive.reserve(c, (size_t)n_steps * n_el);
+    if (!rc) rc = c->d_fw_pts.reserve(c, n_points);
+    if (!rc) rc = c->d_fw_trace.reserve(c, (size_t)n_steps * n_points);
+    if (rc) return rc;
+    if (n_entries > 0) {
+        HIPCHK(c, hipMemcpy(c->d_fw_svox, svox.data(), sizeof(long long) * svox.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_fw_samp, samp.data(), sizeof(double) * n_entries, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_fw_sel, sel.data(), sizeof(int) * n_entries, hipMemcpyHostToDevice));
+    }
+    HIPCHK(c, hipMemcpy(c->d_fw_srow, srow.data(), sizeof(int) * srow.size(), hipMemcpyHostToDevice));
+    if (n_points > 0) HIPCHK(c, hipMemcpy(c->d_fw_pts, points, sizeof(long long) * n_points, hipMemcpyHostToDevice));
+    FullwaveSource& S = c->fw_src;
+    S = FullwaveSource{};
+    S.freq = freq; S.T = cycles / freq; S.Tr = ramp_cycles / freq; S.dt = c->fw_dt; S.n_vox = (int)svox.size();
+    c->fw_entries = n_entries; c->fw_steps = n_steps; c->fw_npts = n_points; c->fw_elem = true; c->fw_nel = n_el;
+    c->fw_sourced = true;
+    return olx_fullwave_drive(c, A, tau_s);
+}
+
+int olx_fullwave_drive(olx_ctx* c, const double* A, const double* tau_s) {
+    if (!c) return OLX_EINVAL;
+    if (!c->fw_planned || !c->fw_sourced || !c->fw_elem) return fail(c, OLX_ESTATE, "olx_fullwave_drive: needs olx_fullwave_sources_elements as the last source call");
+    if (!A || !tau_s) return fail(c, OLX_EINVAL, "olx_fullwave_drive: null A / tau");
+    for (int e = 0; e < c->fw_nel; ++e)
+        if (!std::isfinite(A[e]) || !std::isfinite(tau_s[e])) return fail(c, OLX_EINVAL, "olx_fullwave_drive: element %d: A and delay must be finite", e);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->fw_next = -1;                            // the run starts again, without a lock-in until olx_fullwave_lockin asks for one
+    c->fw_lock = false; c->fw_lock_vol = false; c->fw_lock_nrec = 0; c->fw_lock_entries = 0;
+    HIPCHK(c, hipMemcpy(c->d_fw_dA, A, sizeof(double) * c->fw_nel, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_fw_dtau, tau_s, sizeof(double) * c->fw_nel, hipMemcpyHostToDevice));
+    olx_fullwave_drive_fill(c);
+    HIPCHK(c, hipGetLastError());
+    return OLX_OK;
+}
+
+int olx_fullwave_apertures(olx_ctx* c, int n_el, const double* centre, const double* u_axis, const double* v_axis, const double* size, const int* n_w,
+                           const int* n_l, long long capacity, int* row, long long* voxels, double* weights, long long* n_needed) {
+    if (!c) return OLX_EINVAL;
+    if (!c->fw_planned) return fail(c, OLX_ESTATE, "olx_fullwave_apertures: no full-wave plan");
+    if (n_el < 1 || !centre || !u_axis || !v_axis || !size || !n_w || !n_l || !row) return fail(c, OLX_EINVAL, "olx_fullwave_apertures: n_el < 1 or null argument");
+    if (capacity < 0 || (capacity > 0 && (!voxels || !weights))) return fail(c, OLX_EINVAL, "olx_fullwave_apertures: capacity < 0 or null output");
+    const FullwaveParams& P = c->fw;
+    const int ng[3] = {P.nx, P.ny, P.nz};
+    std::vector<FullwaveAperture> ap(n_el);
+    long long total = 0, max_box = 0;
+    for (int e = 0; e < n_el; ++e) {
+        FullwaveAperture& E = ap[e];
+        for (int a = 0; a < 3; ++a) { E.c[a] = centre[3 * e + a]; E.u[a] = u_axis[3 * e + a]; E.v[a] = v_axis[3 * e + a]; }
+        E.w = size[2 * e]; E.l = size[2 * e + 1]; E.nw = n_w[e]; E.nl = n_l[e];
+        bool finite = std::isfinite(E.w) && std::isfinite(E.l);
+        for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(E.c[a]) && std::isfinite(E.u[a]) && std::isfinite(E.v[a]);
+        if (!finite) return fail(c, OLX_EINVAL, "olx_fullwave_apertures: element %d: centre, axes and size must be finite", e);
+        if (E.w < 0 || E.l < 0) return fail(c, OLX_EINVAL, "olx_fullwave_apertures: element %d: size (%g, %g) m must be >= 0", e, E.w, E.l);
+        if (E.nw < 1 || E.nl < 1) return fail(c, OLX_EINVAL, "olx_fullwave_apertures: element %d: n_w = %d, n_l = %d must be >= 1", e, E.nw, E.nl);
+        if ((long long)E.nw * E.nl > 65536) return fail(c, OLX_EINVAL, "olx_fullwave_apertures: element %d: %lld points are too many (65536)", e, (long long)E.nw * E.nl);
+        // the extreme points bound every point's coordinates (each operation is monotone): their weighted voxels decide the refusal; the
+        // index box is that of the rectangle's four corners, floor(min) .. floor(max) + 1, clipped to the grid
+        long long box = 1;
+        for (int a = 0; a < 3; ++a) {
+            double qlo = 0, qhi = 0, blo = 0, bhi = 0;
+            for (int t = 0; t < 4; ++t) {
+                const double q = fw_aperture_q(E, fw_aperture_s(t & 1 ? E.nw - 1 : 0, E.nw), fw_aperture_s(t & 2 ? E.nl - 1 : 0, E.nl), a, c->fw_origin[a], c->fw_h[a]);
+                const double b = fw_aperture_q(E, t & 1 ? 0.5 : -0.5, t & 2 ? 0.5 : -0.5, a, c->fw_origin[a], c->fw_h[a]);
+                if (t == 0 || q < qlo) qlo = q;
+                if (t == 0 || q > qhi) qhi = q;
+                if (t == 0 || b < blo) blo = b;
+                if (t == 0 || b > bhi) bhi = b;
+            }
+            if (qlo < 0 || std::ceil(qhi) > ng[a] - 1)
+                return fail(c, OLX_EINVAL, "olx_fullwave_apertures: element %d does not lie inside the grid (axis %d: its points span voxels %g .. %g of %d)", e, a, qlo, qhi, ng[a]);
+            const int lo = (int)std::max(0.0, std::floor(std::min(blo, qlo))), hi = (int)std::min((double)(ng[a] - 1), std::floor(std::max(bhi, qhi)) + 1.0);
+            E.lo[a] = lo; E.dim[a] = hi - lo + 1;
+            box *= E.dim[a];
+        }
+        E.off = total;
+        total += box; max_box = std::max(max_box, box);
+    }
+    if (max_box > 65535ll * 256 || (double)total * sizeof(double) > 268435456.0)
+        return fail(c, OLX_EINVAL, "olx_fullwave_apertures: index boxes of %lld voxels (largest %lld) are too large", total, max_box);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = c->d_fw_ap.reserve(c, n_el);
+    if (!rc) rc = c->d_fw_apw.reserve(c, (size_t)total);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_fw_ap, ap.data(), sizeof(FullwaveAperture) * n_el, hipMemcpyHostToDevice, c->stream));
+    olx_fullwave_aperture_weights(c, n_el, max_box, total);
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> dense((size_t)total);
+    HIPCHK(c, hipMemcpyAsync(dense.data(), c->d_fw_apw, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+#ifdef OLX_DEBUG_BOUNDS
+    { int rc_ = report_bounds(c); if (rc_) return rc_; }
+#endif
+    // per-element CSR of the weights that are not 0, in the box's C order: ascending linear voxel inside a row
+    long long n = 0;
+    for (int e = 0; e < n_el; ++e) {
+        if (n > 2147483647ll) break;
+        row[e] = (int)n;
+        const FullwaveAperture& E = ap[e];
+        long long t = E.off;
+        for (int i = 0; i < E.dim[0]; ++i)
+            for (int j = 0; j < E.dim[1]; ++j)
+                for (int k = 0; k < E.dim[2]; ++k, ++t) {
+                    if (dense[(size_t)t] == 0.0) continue;
+                    if (n < capacity) { voxels[n] = ((long long)(E.lo[0] + i) * P.ny + (E.lo[1] + j)) * P.nz + (E.lo[2] + k); weights[n] = dense[(size_t)t]; }
+                    ++n;
+                }
+    }
+    if (n > 2147483647ll) return fail(c, OLX_EINVAL, "olx_fullwave_apertures: more than 2^31 - 1 entries");
+    row[n_el] = (int)n;
+    if (n_needed) *n_needed = n;
     return OLX_OK;
 }
 

@@ -191,6 +191,13 @@ struct olx_ctx {
     DevBuf<float> d_fw_dtab;                  // [nx + ny + nz] the layers' per-step decay d_x | d_y | d_z
     bool fw_sourced = false; FullwaveSource fw_src{}; int fw_entries = 0, fw_steps = 0;
     DevBuf<long long> d_fw_svox; DevBuf<int> d_fw_srow; DevBuf<double> d_fw_samp, d_fw_stau;   // CSR source table: voxel per row, row offsets, entries in table order
+    // element-factored sources (olx_fullwave_sources_elements): the CSR table above holds amp_{e,m}, d_fw_sel the element of each entry, and the drive
+    // s_e(n) of every (step, element) stands in a table that olx_fullwave_drive re-fills; fw_elem says which inject kernel olx_fullwave_run launches
+    bool fw_elem = false; int fw_nel = 0;
+    DevBuf<int> d_fw_sel; DevBuf<double> d_fw_drive, d_fw_dA, d_fw_dtau;   // [entries] element; [fw_steps][fw_nel] drive; [fw_nel] A_e, tau_e
+    // aperture weights (olx_fullwave_apertures): the planned grid in fp64, per-element geometry and index box, the dense weights of every box
+    double fw_h[3] = {0, 0, 0}, fw_origin[3] = {0, 0, 0};
+    DevBuf<FullwaveAperture> d_fw_ap; DevBuf<double> d_fw_apw;   // [elements]; [sum of the boxes' voxels]
     int fw_npts = 0; DevBuf<long long> d_fw_pts; DevBuf<float> d_fw_trace;   // trace voxels, [fw_steps][fw_npts] samples
     // lock-in at one frequency over the steps [fw_lock_w0, fw_lock_w0 + fw_lock_nw) (olx_fullwave_lockin; cleared by olx_fullwave_sources)
     bool fw_lock = false, fw_lock_vol = false; double fw_lock_freq = 0; int fw_lock_w0 = 0, fw_lock_nw = 0, fw_lock_nrec = 0, fw_lock_entries = 0;
@@ -308,3 +315,17 @@ struct DevScratch {
     template <class T> T* at(size_t byte_off) const { return reinterpret_cast<T*>(static_cast<unsigned char*>(p) + byte_off); }
 };
 
+// Quadrature points of an aperture (olx_fullwave_apertures, fullwave_aperture_k): the offset (i + 1/2) / n - 1/2 of point i of n along an
+// in-plane axis, and coordinate `axis` of the point with offsets (sa, sb) in voxel units, within 1e-9 of a whole number = that number.
+// Every operation is rounded on its own (no fused multiply-add), so the host's refusals, the kernel and the fp64 oracle see the same bits.
+__host__ __device__ inline double fw_aperture_s(int i, int n) {
+#pragma clang fp contract(off)
+    return ((double)i + 0.5) / (double)n - 0.5;
+}
+__host__ __device__ inline double fw_aperture_q(const FullwaveAperture& E, double sa, double sb, int axis, double origin, double h) {
+#pragma clang fp contract(off)
+    const double ta = (sa * E.w) * E.u[axis], tb = (sb * E.l) * E.v[axis];
+    const double q = (((E.c[axis] + ta) + tb) - origin) / h;
+    const double near = rint(q);
+    return fabs(q - near) <= 1e-9 ? near : q;
+}

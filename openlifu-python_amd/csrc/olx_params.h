@@ -203,6 +203,14 @@ struct FullwaveSource {
     double dt;                       // [s]
     int n_vox;                       // distinct source voxels (CSR rows)
 };
+// one element of fullwave_aperture_k: a rectangle of n_w x n_l quadrature points and the index box its weights are written for
+struct FullwaveAperture {
+    double c[3], u[3], v[3];         // centre [m] in the planned grid's frame, in-plane unit axes (width, length)
+    double w, l;                     // size [m]
+    int nw, nl;                      // quadrature points along u, v
+    int lo[3], dim[3];               // the index box (clipped to the grid): first voxel and voxels per axis
+    long long off;                   // where the box's dense weights start
+};
 
 // kernel 6 (eikonal_*_k, k_eikonal.hip): first-arrival travel times from a point, upwind Godunov update swept Jacobi-wise (olx_eikonal_*)
 struct EikonalParams {

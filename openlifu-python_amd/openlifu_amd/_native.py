@@ -46,6 +46,7 @@ SYMBOLS = [
     "olx_pii_post", "olx_pii_fetch_weighted", "olx_pii_fetch_max", "olx_pii_upload", "olx_thermal_source_pii",
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
     "olx_fullwave_plan", "olx_fullwave_sources", "olx_fullwave_run", "olx_fullwave_fetch", "olx_fullwave_lockin", "olx_fullwave_fetch_lockin",
+    "olx_fullwave_apertures", "olx_fullwave_sources_elements", "olx_fullwave_drive",
     "olx_eikonal_solve", "olx_eikonal_sample", "olx_eikonal_fetch",
     "olx_bf_set_medium", "olx_bf_solve_medium",
     "olx_bf_set_attenuation", "olx_bf_solve_compensated",
@@ -173,6 +174,11 @@ def load(require_gpu: bool = True):
         lib.olx_fullwave_fetch.argtypes = [vp, fp, fp, fp, fp]
         lib.olx_fullwave_lockin.argtypes = [vp, c_double, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(ctypes.c_longlong), dp]
         lib.olx_fullwave_fetch_lockin.argtypes = [vp, fp, fp, dp, dp]
+        lib.olx_fullwave_apertures.argtypes = [vp, c_int, dp, dp, dp, dp, POINTER(c_int), POINTER(c_int), ctypes.c_longlong, POINTER(c_int),
+                                               POINTER(ctypes.c_longlong), dp, POINTER(ctypes.c_longlong)]
+        lib.olx_fullwave_sources_elements.argtypes = [vp, c_int, POINTER(ctypes.c_longlong), POINTER(c_int), dp, c_int, dp, dp, c_double, c_double, c_double,
+                                                      c_int, c_int, POINTER(ctypes.c_longlong)]
+        lib.olx_fullwave_drive.argtypes = [vp, dp, dp]
         lib.olx_eikonal_solve.argtypes = [vp, POINTER(OlxGrid), fp, c_double, dp, c_double, c_int, POINTER(c_int)]
         lib.olx_eikonal_sample.argtypes = [vp, c_int, POINTER(c_int), POINTER(ctypes.c_longlong), dp, dp]
         lib.olx_eikonal_fetch.argtypes = [vp, fp]
@@ -788,6 +794,62 @@ class Context:
         self._chk(self._lib.olx_fullwave_sources(self._h, int(vx.size), vx.ctypes.data_as(lp), _dptr(am), _dptr(ta), float(freq), float(cycles),
                                                  float(ramp_cycles), int(n_steps), int(pts.size), pts.ctypes.data_as(lp)))
         self._fw_steps, self._fw_npts = int(n_steps), int(pts.size)
+        self._fw_lock_vol, self._fw_lock_nrec = False, 0
+
+    def fullwave_apertures(self, centre, u_axis, v_axis, size, n_w, n_l, capacity=None):
+        """Aperture weights of rectangular elements on the planned (padded) grid -> per-element CSR (row [E + 1] int32, voxels int64 linear
+        in that grid, weights float64): ``centre`` [E, 3] m in the grid's frame (voxel 0 at 0), unit axes ``u_axis`` / ``v_axis`` [E, 3],
+        ``size`` [E, 2] m, ``n_w`` / ``n_l`` [E] quadrature points.  ``capacity`` None: eight corners per point; a call whose capacity is too
+        small is repeated with what it reports.  After ``fullwave_plan``."""
+        ce, ua, va = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3) for a in (centre, u_axis, v_axis))
+        sz = np.ascontiguousarray(size, dtype=np.float64).reshape(-1, 2)
+        nw, nl = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (n_w, n_l))
+        n_el = ce.shape[0]
+        if not (ua.shape[0] == va.shape[0] == sz.shape[0] == nw.size == nl.size == n_el):
+            raise ValueError("centre, u_axis, v_axis, size, n_w and n_l must describe one number of elements")
+        cap = int(min(8 * int(np.sum(nw.astype(np.int64) * nl)), 1 << 22)) if capacity is None else int(capacity)
+        ip, lp = POINTER(c_int), POINTER(ctypes.c_longlong)
+        while True:
+            row = np.zeros(n_el + 1, dtype=np.int32)
+            vox = np.zeros(max(cap, 1), dtype=np.int64)
+            wt = np.zeros(max(cap, 1), dtype=np.float64)
+            need = ctypes.c_longlong(0)
+            self._chk(self._lib.olx_fullwave_apertures(self._h, n_el, _dptr(ce), _dptr(ua), _dptr(va), _dptr(sz), nw.ctypes.data_as(ip), nl.ctypes.data_as(ip),
+                                                       cap, row.ctypes.data_as(ip), vox.ctypes.data_as(lp), _dptr(wt), ctypes.byref(need)))
+            if need.value <= cap:
+                return row, vox[:need.value].copy(), wt[:need.value].copy()
+            if capacity is not None:
+                raise ValueError(f"fullwave_apertures: {need.value} entries do not fit the capacity {cap}")
+            cap = int(need.value)
+
+    def fullwave_sources_elements(self, voxels, elements, amplitude, A, tau, freq, cycles, ramp_cycles, n_steps, points=None):
+        """Element-factored source table: entry q adds amplitude[q] s_e(n), e = elements[q], at voxels[q] (linear in the padded grid), with
+        the drive s_e(n) = A[e] env sin of element e's delay tau[e]; ``fullwave_drive`` replaces (A, tau) without a new table."""
+        vx = np.ascontiguousarray(voxels, dtype=np.int64)
+        el = np.ascontiguousarray(elements, dtype=np.int32)
+        am = np.ascontiguousarray(amplitude, dtype=np.float64)
+        AA = np.ascontiguousarray(A, dtype=np.float64)
+        ta = np.ascontiguousarray(tau, dtype=np.float64)
+        if not (vx.ndim == 1 and vx.shape == am.shape == el.shape):
+            raise ValueError(f"voxels, elements and amplitude must be 1-D of one length, got {vx.shape}, {el.shape}, {am.shape}")
+        if not (AA.ndim == 1 and AA.shape == ta.shape):
+            raise ValueError(f"A and tau must be 1-D of one length, got {AA.shape}, {ta.shape}")
+        pts = np.ascontiguousarray([] if points is None else points, dtype=np.int64)
+        lp = POINTER(ctypes.c_longlong)
+        self._chk(self._lib.olx_fullwave_sources_elements(self._h, int(vx.size), vx.ctypes.data_as(lp), el.ctypes.data_as(POINTER(c_int)), _dptr(am),
+                                                          int(AA.size), _dptr(AA), _dptr(ta), float(freq), float(cycles), float(ramp_cycles), int(n_steps),
+                                                          int(pts.size), pts.ctypes.data_as(lp)))
+        self._fw_steps, self._fw_npts, self._fw_nel = int(n_steps), int(pts.size), int(AA.size)
+        self._fw_lock_vol, self._fw_lock_nrec = False, 0
+
+    def fullwave_drive(self, A, tau):
+        """New (A, tau) per element for the table of ``fullwave_sources_elements``; the run starts again and a lock-in is cleared."""
+        AA = np.ascontiguousarray(A, dtype=np.float64)
+        ta = np.ascontiguousarray(tau, dtype=np.float64)
+        n_el = getattr(self, "_fw_nel", None)
+        if n_el is not None and not (AA.shape == ta.shape == (n_el,)):
+            raise ValueError(f"A and tau must have shape ({n_el},), got {AA.shape}, {ta.shape}")
+        self._chk(self._lib.olx_fullwave_drive(self._h, _dptr(AA), _dptr(ta)))
         self._fw_lock_vol, self._fw_lock_nrec = False, 0
 
     def fullwave_run(self, first_step: int = 0, n_steps=None, psq: bool = False):

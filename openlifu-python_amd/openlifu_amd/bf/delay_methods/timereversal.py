@@ -8,7 +8,11 @@ microseconds).  The run gives each element the steady-state sum Z_e = C_e + i S_
 (the ``anchor``: ``StraightRay``, or ``Direct``) is good to well within half a cycle, so it fixes m_e: with the anchor's relative
 delays d_e, x_e = -f0 d_e - psi_e, off = the |Z_e|-weighted circular mean of x_e (the common travel time that relative delays do not
 know), m_e = rint(x_e - off), T_e = (psi_e + m_e) / f0 and delays_e = max T - T_e.  The tie margin 1/2 - max |x_e - off - m_e| says how
-far the rounding was from a wrap; below ``TIE_WARN`` a warning is logged.  Without ``params`` it is ``Direct(c0)``."""
+far the rounding was from a wrap; below ``TIE_WARN`` a warning is logged.  Without ``params`` it is ``Direct(c0)``.
+
+``element_model="point"`` (the default) samples p trilinearly at each element's centre; ``"aperture"`` makes Z_e the average of p over
+the element's rectangle (``upsampling_rate`` quadrature points per smallest voxel edge, DESIGN.md section 2 "full-wave model:
+apertures"), so an element a wavelength wide hears an oblique wave with its directivity, in amplitude and in phase."""
 from __future__ import annotations
 
 import logging
@@ -48,6 +52,8 @@ class TimeReversal(DelayMethod):
     cfl: float = 0.3
     pml_size: int = 16
     anchor: str = "straight_ray"
+    element_model: str = "point"     # "aperture": the elements listen with the averages over their rectangles (sim/fullwave.py)
+    upsampling_rate: int = 5         # quadrature points per smallest voxel edge of the "aperture" model
 
     def __post_init__(self):
         if isinstance(self.c0, bool) or not isinstance(self.c0, (int, float)):
@@ -68,6 +74,16 @@ class TimeReversal(DelayMethod):
         self.pml_size = int(self.pml_size)
         if self.anchor not in ANCHORS:
             raise ValueError(f"TimeReversal: anchor must be one of {ANCHORS}, got {self.anchor!r}")
+        from ...sim.fullwave import checked_element_model      # (sim imports bf through plan: resolve at call time)
+        self.element_model, self.upsampling_rate = checked_element_model(self.element_model, self.upsampling_rate)
+
+    def to_dict(self):
+        """The tagged dict; the element model is written only when it is not the default, so the stored form of a method that does not use it
+        is what it was before the option existed (``from_dict`` fills the defaults in)."""
+        d = super().to_dict()
+        if self.element_model == "point":
+            del d["element_model"], d["upsampling_rate"]
+        return d
 
     @staticmethod
     def checked_frequency(frequency) -> float:
@@ -90,7 +106,8 @@ class TimeReversal(DelayMethod):
         if frequency is None:
             raise ValueError("TimeReversal: a frequency is needed to drive the full-wave run (set `frequency`, or solve through a Protocol)")
         frequency = self.checked_frequency(frequency)
-        from ...sim.fullwave import lockin_amplitude_phase, steady_state_run      # (sim imports bf through plan: resolve at call time)
+        from ...sim.fullwave import aperture_geometry, lockin_amplitude_phase, steady_state_run      # (sim imports bf through plan: resolve at call time)
+        from ...engine import grid_from_coords
         foci = focus_positions_m(targets)
         pos = np.asarray(arr.element_table()[0], dtype=np.float64)
         if transform is not None:
@@ -98,11 +115,14 @@ class TimeReversal(DelayMethod):
             if M.shape != (4, 4):
                 raise ValueError(f"transform must be a 4 x 4 matrix, got {M.shape}")
             pos = pos @ M[:3, :3].T + M[:3, 3]
+        listen = {"receivers_m": pos}
+        if self.element_model == "aperture":      # Z_e is the average of p over the element's rectangle: sum_m W_e(m) p(m)
+            listen = {"receiver_apertures": aperture_geometry(arr, grid_from_coords(params.coords)[1], self.upsampling_rate, transform=transform)}
         runs = []
         for f in range(foci.shape[0]):
             runs.append(steady_state_run(params, foci[f][None], [1.0], [0.0], frequency, cfl=self.cfl, lockin_cycles=self.lockin_cycles,
-                                         settle_cycles=self.settle_cycles, ramp_cycles=self.ramp_cycles, pml_size=self.pml_size, receivers_m=pos,
-                                         volume=False, what="target"))
+                                         settle_cycles=self.settle_cycles, ramp_cycles=self.ramp_cycles, pml_size=self.pml_size, volume=False,
+                                         what="target", **listen))
         if self.anchor == "straight_ray":
             anchor = StraightRay(c0=self.c0).solve(arr, foci, params, transform=transform)[0]
         else:

@@ -513,20 +513,45 @@ class Engine:
                  psq=False, points=None):
         """Full-wave model (sim/fullwave.py, kernel 5) on the padded grid -> (p_max, p_min, sum p^2 | None, traces [n_steps, P]), float32.
         ``medium = (sound_speed, density, absorption [Np/m])``, each a float or a padded [nx, ny, nz] volume; ``sources = (voxel, amplitude,
-        tau)`` per entry, voxels and ``points`` as linear indices of the padded grid.  The field / aggregate / thermal volumes and every lazy
+        tau)`` per entry, or the element-factored dict of ``_fullwave_sources``; voxels and ``points`` as linear indices of the padded grid.  The field / aggregate / thermal volumes and every lazy
         array over them are left as they are."""
         self.ctx.fullwave_plan(spacing_m, n_padded, *medium, c_ref=c_ref, pml_size=pml_size, pml_alpha=pml_alpha, dt=dt)
-        self.ctx.fullwave_sources(*sources, freq=freq, cycles=cycles, ramp_cycles=ramp_cycles, n_steps=n_steps, points=points)
+        self._fullwave_sources(sources, spacing_m, medium, dt, freq=freq, cycles=cycles, ramp_cycles=ramp_cycles, n_steps=n_steps, points=points)
         self.ctx.fullwave_run(0, n_steps, psq=psq)
         return self.ctx.fullwave_fetch()
+
+    fullwave_aperture_entries = None     # (element, voxel) entries of the last full-wave source table in element-factored form (None: per-entry form)
+
+    def _fullwave_sources(self, sources, spacing_m, medium, dt, freq, **kw):
+        """The source call of a planned full-wave run.  ``sources`` is (voxel, amplitude, tau) per entry -- olx_fullwave_sources -- or a dict,
+        the element-factored form of olx_fullwave_sources_elements: {"A" [E], "tau" [E]} plus either "voxels", "elements", "amplitude" per
+        entry, or "geometry" = (centre [E, 3] m in the padded grid's frame, u, v, size, n_w, n_l): the rectangles whose weights
+        olx_fullwave_apertures forms on the plan, amplitude = W dt c(voxel)^2 4 pi / (2 pi freq h_x h_y h_z)."""
+        if not isinstance(sources, dict):
+            self.fullwave_aperture_entries = None
+            return self.ctx.fullwave_sources(*sources, freq=freq, **kw)
+        if "geometry" in sources:
+            row, vox, wt = self.ctx.fullwave_apertures(*sources["geometry"])
+            el = np.repeat(np.arange(row.size - 1, dtype=np.int32), np.diff(row))
+            c = medium[0]
+            c_v = float(c) if np.ndim(c) == 0 else np.asarray(c, dtype=np.float64).reshape(-1)[vox]
+            h = np.broadcast_to(np.asarray(spacing_m, dtype=np.float64), (3,))
+            amp = wt * float(dt) * c_v ** 2 * 4.0 * np.pi / (2.0 * np.pi * float(freq) * float(np.prod(h)))
+        else:
+            vox, el, amp = sources["voxels"], sources["elements"], sources["amplitude"]
+        self.fullwave_aperture_entries = int(np.size(vox))
+        return self.ctx.fullwave_sources_elements(vox, el, amp, sources["A"], sources["tau"], freq=freq, **kw)
 
     def fullwave_steady(self, spacing_m, n_padded, medium, c_ref, pml_size, pml_alpha, dt, n_steps, sources, freq, cycles, ramp_cycles, window,
                         volume=True, receivers=None):
         """A driven full-wave run with the lock-in at ``freq`` over the steps ``window = (w0, Nw)`` (sim/fullwave.py)
         -> (C, S volumes of the padded grid | None, C_r, S_r float64 [R] | None).  ``receivers = (row, voxel, weight)``: the CSR table, voxels
-        linear in the padded grid.  The other arguments and what is left untouched are ``fullwave``'s."""
+        linear in the padded grid, or {"geometry": ...} (``_fullwave_sources``): the elements' aperture averages.  The other arguments and what
+        is left untouched are ``fullwave``'s."""
         self.ctx.fullwave_plan(spacing_m, n_padded, *medium, c_ref=c_ref, pml_size=pml_size, pml_alpha=pml_alpha, dt=dt)
-        self.ctx.fullwave_sources(*sources, freq=freq, cycles=cycles, ramp_cycles=ramp_cycles, n_steps=n_steps)
+        if isinstance(receivers, dict):      # the aperture averages sum_m W_e(m) p(m): the weights' CSR is the receiver table
+            receivers = self.ctx.fullwave_apertures(*receivers["geometry"])
+        self._fullwave_sources(sources, spacing_m, medium, dt, freq=freq, cycles=cycles, ramp_cycles=ramp_cycles, n_steps=n_steps)
         row, vox, wt = (None, None, None) if receivers is None else receivers
         self.ctx.fullwave_lockin(freq, window[0], window[1], volume=volume, row=row, voxels=vox, weights=wt)
         self.ctx.fullwave_run(0, n_steps)

@@ -2,7 +2,7 @@
 """Time kernel 5 (full-wave model, k_fullwave.hip): ms per step and achieved bytes/s at 256^3 plus absorbing layers, for the uniform
 instantiation and for a skull-slab medium (five coefficient volumes streamed).
 
-  python tools/time_fullwave.py [--n 256] [--pml 16] [--steps 300] [--lockin] [--out profiles/fullwave_time.json]
+  python tools/time_fullwave.py [--n 256] [--pml 16] [--steps 300] [--lockin | --aperture [--rounds 3]] [--out profiles/fullwave_time.json]
 
 A run of --steps steps is bracketed by olx_sync (after one untimed warm-up run of 20 steps); the step is three launches (inject,
 velocity, pressure-and-record).  Bytes per voxel and step are the compulsory traffic of DESIGN.md section 5.14 -- every volume a launch
@@ -10,7 +10,13 @@ reads or writes counted once, stencil neighbours served by the caches: 64 B unif
 achieved bytes/s are set against the 6.29 TB/s a device-to-device copy reaches on this part.
 
 --lockin adds, per medium, runs whose lock-in window is the whole run: the volume sums (+ 16 B per voxel and
-step: C and S read and written), and the volume sums with 64 receivers of 8 entries each (one more launch of one block per step)."""
+step: C and S read and written), and the volume sums with 64 receivers of 8 entries each (one more launch of one block per step).
+
+--aperture times the element-factored sources of DESIGN.md section 5.18 instead: a 16 x 16 array of 2.9 mm elements (pitch 3 mm) at
+upsampling rate 5 on the uniform medium, against the same array as 256 point sources -- the two alternate in ONE process on ONE box
+(--rounds times each, the median is reported) -- with the number of (element, voxel) entries, and the build of the weight table on the
+device (olx_fullwave_apertures, wall time of the call) against a NumPy scatter build of the same table (np.add.at over the 8 corners
+of every point)."""
 import argparse
 import json
 import os
@@ -29,6 +35,89 @@ COPY_TBPS = 6.29
 BYTES = {"uniform": 64, "medium": 84}
 
 
+def numpy_scatter_table(centre, size, nw, nl, h, n):
+    """The aperture weights of axis-aligned elements by a NumPy scatter: every point on its 8 corners, merged per (element, voxel)"""
+    row, vox, wt = [0], [], []
+    for e in range(len(centre)):
+        sa = np.repeat((np.arange(nw[e]) + 0.5) / nw[e] - 0.5, nl[e])
+        sb = np.tile((np.arange(nl[e]) + 0.5) / nl[e] - 0.5, nw[e])
+        q = (centre[e] + np.stack([sa * size[e, 0], sb * size[e, 1], np.zeros_like(sa)], axis=1)) / h
+        near = np.rint(q)
+        q = np.where(np.abs(q - near) <= 1e-9, near, q)
+        lo = np.floor(q).astype(np.int64)
+        f = q - lo
+        keys, vals = [], []
+        for di in (0, 1):
+            for dj in (0, 1):
+                for dk in (0, 1):
+                    w = (f[:, 0] if di else 1 - f[:, 0]) * (f[:, 1] if dj else 1 - f[:, 1]) * (f[:, 2] if dk else 1 - f[:, 2])
+                    keys.append(((lo[:, 0] + di) * n + lo[:, 1] + dj) * n + lo[:, 2] + dk); vals.append(w)
+        keys, vals = np.concatenate(keys), np.concatenate(vals)
+        uniq, inv = np.unique(keys, return_inverse=True)
+        sums = np.zeros(uniq.size)
+        np.add.at(sums, inv, vals)
+        keep = sums != 0
+        vox.append(uniq[keep]); wt.append(sums[keep] / (nw[e] * nl[e])); row.append(row[-1] + int(keep.sum()))
+    return np.asarray(row), np.concatenate(vox), np.concatenate(wt)
+
+
+def aperture_main(a):
+    n = a.n + 2 * a.pml
+    h = 0.25e-3
+    shape = (n, n, n)
+    dt = 0.9 * 6.0 / (7.0 * 1500.0 * np.sqrt(3.0) / h)
+    g = (np.arange(16) - 7.5) * 3.0e-3 + (n // 2 + 0.3) * h
+    centre = np.array([[x, y, (a.pml + 2.3) * h] for x in g for y in g])
+    E = len(centre)
+    size = np.full((E, 2), 2.9e-3)
+    nw = nl = np.full(E, int(np.ceil(5 * 2.9e-3 / h - 1e-9)), dtype=np.int32)
+    u, v = np.tile([1.0, 0.0, 0.0], (E, 1)), np.tile([0.0, 1.0, 0.0], (E, 1))
+    A, tau = np.ones(E), (np.arange(E) % 7) * 0.37 * dt
+    ctx = nat.Context(0)
+    ctx.fullwave_plan((h,) * 3, shape, 1500.0, 1000.0, 0.0, 1500.0, a.pml, 2.0, dt)
+    ctx.fullwave_apertures(centre, u, v, size, nw, nl)          # (untimed: the first call creates the buffers)
+    t0 = time.perf_counter()
+    row, vox, wt = ctx.fullwave_apertures(centre, u, v, size, nw, nl)
+    t_dev = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    r2, v2, w2 = numpy_scatter_table(centre, size, nw, nl, h, n)
+    t_np = time.perf_counter() - t0
+    assert np.array_equal(row, r2) and np.array_equal(vox, v2) and np.abs(wt - w2).max() <= 1e-12
+    el = np.repeat(np.arange(E, dtype=np.int32), np.diff(row))
+    scale = dt * 1500.0 ** 2 * 4 * np.pi / (2 * np.pi * 500e3 * h ** 3)
+    # the same array as point sources: one trilinear monopole per element (8 entries each)
+    pr, pv, pw = numpy_scatter_table(centre, np.zeros((E, 2)), np.ones(E, dtype=np.int32), np.ones(E, dtype=np.int32), h, n)
+    pe = np.repeat(np.arange(E), np.diff(pr))
+
+    def point():
+        ctx.fullwave_sources(pv, pw * scale * A[pe], tau[pe], 500e3, 1e6, 0.0, a.steps)
+
+    def aperture():
+        ctx.fullwave_sources_elements(vox, el, wt * scale, A, tau, 500e3, 1e6, 0.0, a.steps)
+
+    times = {"point": [], "aperture": []}
+    for _ in range(a.rounds):
+        for name, set_sources in (("point", point), ("aperture", aperture)):
+            set_sources()
+            ctx.fullwave_run(0, 20)
+            ctx.sync()
+            t0 = time.perf_counter()
+            ctx.fullwave_run(0, a.steps)
+            ctx.sync()
+            times[name].append((time.perf_counter() - t0) * 1e3 / a.steps)
+    ctx.close()
+    out = {"tool": "tools/time_fullwave.py --aperture", "grid": list(shape), "steps": a.steps, "rounds": a.rounds, "elements": E,
+           "points_per_element": int(nw[0]) * int(nl[0]), "entries": {"point": int(pv.size), "aperture": int(vox.size)},
+           "ms_per_step": {k: round(float(np.median(t)), 4) for k, t in times.items()}, "ms_per_step_all": {k: [round(x, 4) for x in t] for k, t in times.items()},
+           "aperture_over_point": round(float(np.median(times["aperture"]) / np.median(times["point"])), 4),
+           "table_build_ms": {"device": round(t_dev * 1e3, 3), "numpy_scatter": round(t_np * 1e3, 3)}}
+    print(json.dumps(out), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=256)
@@ -36,7 +125,11 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--lockin", action="store_true", help="also time the steps inside a lock-in window")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--aperture", action="store_true", help="time 256 aperture elements against 256 point sources (section 5.18)")
+    ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
+    if a.aperture:
+        return aperture_main(a)
     n = a.n + 2 * a.pml
     h = 0.25e-3
     shape = (n, n, n)
