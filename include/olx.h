@@ -269,8 +269,9 @@ int olx_field_medium_model(olx_ctx *ctx, int model);
  * constants and every term carries exp(-a d), a = np_per_m (the caller converts the reference's dB/cm/MHz^y: alpha f_MHz^0.9 *
  * 100 / 8.686, alpha_power 0.9 as sim/kwave_if.py:57).  A medium that is the same everywhere is homogeneous: this runs on the
  * homogeneous kernels (the lattice kernels' "modified table" instantiations, else the per-pair kernel 2a-d), not on the
- * layered-ray kernels of olx_field_set_medium -- which it excludes.  Example: the reference's example_protocol.json (water with
- * 0.0022 dB/cm/MHz). */
+ * layered-ray kernels of olx_field_set_medium -- which the absorption a PLAN was made under excludes.  A plan keeps the value it was made under: a later call changes no
+ * launch of a plan that stands, whatever steering table that launch runs with.  Example: the reference's example_protocol.json (water
+ * with 0.0022 dB/cm/MHz). */
 int olx_field_absorption(olx_ctx *ctx, double np_per_m);
 
 /* Pulsed (tone-burst) field model for the plans that follow, the reference's time-domain run (sim/kwave_if.py:100-139 drives every

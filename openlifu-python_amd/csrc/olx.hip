@@ -590,11 +590,11 @@ static int configure_variant(olx_ctx* c) {
     for (int a = 0; a < 3; ++a) { in.origin[a] = c->grid.origin[a]; in.spacing[a] = c->grid.spacing[a]; in.gn[a] = c->grid.n[a]; }
     in.x_begin = c->slab.x_begin; in.x_count = c->slab.x_count; in.flags = c->flags; in.fp = c->fp;
     in.flat = c->flat; in.clamp = c->clamp; in.near = c->near; in.min_dist = c->min_dist; in.mx = c->mx; in.my = c->my;
-    in.allow_shared = c->allow_shared; in.dir_lattice = c->dir_lattice; in.directivity = c->directivity; in.absorb_np_m = c->absorb_np_m;
+    in.allow_shared = c->allow_shared; in.dir_lattice = c->dir_lattice; in.directivity = c->directivity; in.absorb_np_m = c->plan_absorb;      // (the plan's absorption, not a later olx_field_absorption)
     in.force_kind = c->force_kind;
     if (c->h_size.size() >= 2) { in.size0 = c->h_size[0]; in.size1 = c->h_size[1]; }
     in.hetero = c->hetero; in.marched = c->marched; in.march_one = c->march_one;
-    in.n_planes = c->hp.n_planes; in.n_layers = c->hp.n_layers; in.planes_per_layer = c->planes_per_layer;
+    in.n_planes = c->hp.n_planes; in.n_layers = c->hp.n_layers; in.planes_per_layer = c->plan_ppl;
     in.lat = &c->lat;
     in.pins = read_pins();
     if (olxplan::variant_reads_foci(in)) {      // the e4m3 rule wants the foci: known from olx_bf_solve in the element frame, or external delays that are geometric
@@ -1540,7 +1540,7 @@ int olx_field_set_medium(olx_ctx* c, const float* sound_speed, const float* atte
     if (!c->planned || c->uploaded) return fail(c, OLX_ESTATE, "olx_field_set_medium: call olx_field_plan first");
     if (c->directivity) return fail(c, OLX_EINVAL, "olx_field_set_medium: OLX_FIELD_DIRECTIVITY is not available with a heterogeneous medium");
     if (c->pulsed) return fail(c, OLX_EINVAL, "olx_field_set_medium: the pulsed model (olx_field_pulse) has no heterogeneous-medium kernel");
-    if (c->absorb_np_m > 0) return fail(c, OLX_EINVAL, "olx_field_set_medium: a uniform absorption (olx_field_absorption) and a heterogeneous medium exclude each other: put the absorption into the medium volumes");
+    if (c->plan_absorb > 0) return fail(c, OLX_EINVAL, "olx_field_set_medium: a uniform absorption (olx_field_absorption) and a heterogeneous medium exclude each other: put the absorption into the medium volumes");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const olx_grid& g = c->grid;
@@ -1705,6 +1705,7 @@ int olx_field_set_medium(olx_ctx* c, const float* sound_speed, const float* atte
     H.inv_hx = (float)(1.0 / (g.spacing[0] * rev)); H.inv_hy = (float)(1.0 / (g.spacing[1] * rev));
     H.u0 = 0.f; H.v0 = 0.f;  // table origin == grid origin for kernel 2h
     c->hetero = true;
+    c->plan_ppl = c->planes_per_layer;      // (the layering this medium was built with: what the variant names, whatever olx_field_medium_layering says later)
     c->packed_version = ~0ull;
     return configure_variant(c);
 }

@@ -69,7 +69,9 @@ struct olx_ctx {
     std::vector<double> h_area, h_delays, h_apod;  // host mirrors for variant decisions
     std::vector<double> h_foci; unsigned long long foci_version = ~0ull;  // foci of the last olx_bf_solve in the element frame (M == identity)
     // optional piston directivity: local x axes [N][3] and sizes [N][2] on the host, packed frame table on the device
-    std::vector<double> h_xaxis, h_size, h_nrm; DevBuf<float> d_tab2; bool directivity = false; double absorb_np_m = 0; bool modifier() const { return directivity || absorb_np_m > 0; }   // per-term factors beyond w / d: piston directivity, uniform absorption
+    std::vector<double> h_xaxis, h_size, h_nrm; DevBuf<float> d_tab2; bool directivity = false; double absorb_np_m = 0;   // per-term factors beyond w / d: piston directivity, uniform absorption (the live setting, "for the plans that follow")
+    double plan_absorb = 0;     // olx_field_absorption as seen by the last olx_field_plan: what that plan's launches carry, whatever the setting became since
+    bool modifier() const { return directivity || plan_absorb > 0; }      // of the PLAN (olx_field_plan sets both before it asks)
     bool dir_lattice = false;   // dir_lattice: flat, axis-aligned, equal-size elements -> D_e folds into the lattice kernels' tables
     bool allow_shared = true;
     // steering
@@ -78,7 +80,6 @@ struct olx_ctx {
     unsigned long long steer_version = 0, packed_version = ~0ull, configured_version = ~0ull;   // steering table / what the operands were packed from / what configure_variant decided for
     // field plan
     bool planned = false;
-    double plan_absorb = 0;     // olx_field_absorption as seen by the last olx_field_plan
     std::string plan_env;   // OLX_FIELD_VARIANT | OLX_FP8_CORRECTION as seen by the last olx_field_plan (a changed pin forces a full re-plan)
     bool uploaded = false;  // volumes came from olx_field_upload: not launchable
     olx_grid grid{};
@@ -129,6 +130,7 @@ struct olx_ctx {
     bool hetero = false; HeteroParams hp{}; DevBuf<float4> d_med; DevBuf<int> d_plane_k, d_plane_of_k;
     DevBuf<float> d_inv2z; DevBuf<int> d_kfirst, d_klast;
     int planes_per_layer = 1;                  // olx_field_medium_layering: 1 = one sample per plane (default)
+    int plan_ppl = 1;                          // ... as seen by the last olx_field_set_medium: the layering its plan was built with
     DevBuf<float4> d_med_layer; DevBuf<int> d_layer_lo, d_layer_hi;
     // marched ray sums (kernel 2m): model requested for the next olx_field_set_medium, decision, double-buffered U[element][i][j]
     int medium_model = 0;                      // OLX_MEDIUM_AUTO / _SAMPLED / _MARCHED
