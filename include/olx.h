@@ -361,7 +361,10 @@ int olx_field_pulse_medium(olx_ctx *ctx, const float *sound_speed, const float *
  * Plan the grid and the medium: per-voxel density [kg/m^3], specific heat [J/kg/K], thermal conductivity [W/m/K] and absorption [Np/m]
  * ([nx * ny * nz] floats each, C order), each may be NULL for the uniform value that follows it; perfusion W [W/m^3/K] is uniform.
  * With all four volumes NULL no coefficient volume is formed or streamed.  dt_max_out (may be NULL) receives the FTCS bound
- * 1 / max_v (sum_faces K_face / h^2 + W) / (rho Cp)_v [s] (fp32 coefficients). */
+ * 1 / max_v (sum_faces K_face / h^2 + W) / (rho Cp)_v [s] (fp32 coefficients).
+ * OLX_EINVAL, before any device call and with a standing thermal plan left as it was: a density, specific heat or conductivity volume
+ * holding a value that is not finite and > 0, an absorption volume holding one that is not finite and >= 0 (the message names the
+ * volume and the first such voxel); a scalar of a NULL volume that is not > 0 (absorption: not >= 0); perfusion not finite or < 0. */
 int olx_thermal_plan(olx_ctx *ctx, const olx_grid *grid, const float *density, const float *specific_heat, const float *conductivity,
                      const float *absorption, double density0, double specific_heat0, double conductivity0, double absorption0,
                      double perfusion, double *dt_max_out);

@@ -2965,6 +2965,17 @@ int olx_thermal_plan(olx_ctx* c, const olx_grid* g, const float* density, const 
     if ((!density && !(density0 > 0)) || (!specific_heat && !(specific_heat0 > 0)) || (!conductivity && !(conductivity0 > 0)) ||
         (!absorption && !(absorption0 >= 0)) || !(perfusion >= 0) || !std::isfinite(perfusion))
         return fail(c, OLX_EINVAL, "olx_thermal_plan: the scalars of NULL volumes must be > 0 (absorption >= 0) and perfusion finite and >= 0");
+    {   // the volumes that are given: the pack kernel's maximum drops a NaN rate and a negative one loses to any sane lane of its wave
+        const float* vol[4] = {density, specific_heat, conductivity, absorption};
+        const char* what[4] = {"density", "specific heat", "conductivity", "absorption"};
+        const size_t nvox = (size_t)g->n[0] * g->n[1] * g->n[2];
+        for (int q = 0; q < 4; ++q) {
+            if (!vol[q]) continue;
+            for (size_t o = 0; o < nvox; ++o)
+                if (!std::isfinite(vol[q][o]) || !(q == 3 ? vol[q][o] >= 0.f : vol[q][o] > 0.f))
+                    return fail(c, OLX_EINVAL, "olx_thermal_plan: %s must be finite and %s (voxel %zu)", what[q], q == 3 ? ">= 0" : "> 0", o);
+        }
+    }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     ThermalParams& P = c->th;
