@@ -15,6 +15,7 @@
 
 #include "k_small.hip.h"
 #include "olx_launch.h"
+#include "olx_medium.h"
 #include "olx_plan.h"
 #include "k_toep.hip.h"
 
@@ -30,6 +31,11 @@ template <class T> static int upload_if_changed(olx_ctx* c, DevBuf<T>& d, std::v
     HIPCHK(c, hipStreamSynchronize(c->stream));
     held = v;
     return OLX_OK;
+}
+
+// olxmed::check_grid's verdict in the words of every entry point that takes a grid
+static int grid_fail(olx_ctx* c, const char* who, olxmed::GridFault f) {
+    return fail(c, OLX_EINVAL, f == olxmed::GRID_SIZE ? "%s: grid sizes must be >= 1" : "%s: grid spacing must be finite and > 0, origin finite", who);
 }
 
 extern "C" {
@@ -299,31 +305,27 @@ int olx_bf_time(olx_ctx* c, int iters, float* us_each) {
 }
 
 // ---- kernel 1m: StraightRay delays through a medium ------------------------------------------------------------------
+// the grid part of kernel 1m's / 1a's parameters; `value` = the reference sound speed (1m) or the frequency (1a)
+static void bfmed_params(BfMedParams& P, const olx_grid& g, double value, int n_planes) {
+    P.ox = g.origin[0]; P.oy = g.origin[1]; P.oz = g.origin[2];
+    P.hx = g.spacing[0]; P.hy = g.spacing[1]; P.hz = g.spacing[2];
+    P.dmin = 0.5 * std::min(P.hx, std::min(P.hy, P.hz));
+    P.ztol = 1e-6 * P.hz;
+    P.c = value;
+    P.nx = g.n[0]; P.ny = g.n[1]; P.nz = g.n[2]; P.n_planes = n_planes;
+}
 int olx_bf_set_medium(olx_ctx* c, const float* sound_speed, const olx_grid* grid, double c_ref) {
     if (!c) return OLX_EINVAL;
     if (!grid) return fail(c, OLX_EINVAL, "olx_bf_set_medium: null grid");
     if (!(c_ref > 0) || !std::isfinite(c_ref)) return fail(c, OLX_EINVAL, "olx_bf_set_medium: c_ref must be finite and > 0");
-    for (int a = 0; a < 3; ++a) {
-        if (grid->n[a] < 1) return fail(c, OLX_EINVAL, "olx_bf_set_medium: grid sizes must be >= 1");
-        if (!(grid->spacing[a] > 0) || !std::isfinite(grid->spacing[a]) || !std::isfinite(grid->origin[a]))
-            return fail(c, OLX_EINVAL, "olx_bf_set_medium: grid spacing must be finite and > 0, origin finite");
-    }
+    if (auto f = olxmed::check_grid(*grid)) return grid_fail(c, "olx_bf_set_medium", f);
     const int nx = grid->n[0], ny = grid->n[1], nz = grid->n[2];
     const size_t nxy = (size_t)nx * ny;
-    if (sound_speed)
-        for (size_t o = 0; o < nxy * nz; ++o)
-            if (!(sound_speed[o] > 0.f) || !std::isfinite(sound_speed[o])) return fail(c, OLX_EINVAL, "olx_bf_set_medium: sound speed must be finite and > 0");
-    // the held planes: olx_field_set_medium's rule for the sound speed (a plane with any voxel != c_ref), sigma = c_ref / c - 1 in fp64
-    std::vector<int> pk(nz, -1);
+    if (olxmed::first_bad(sound_speed, nxy * nz, olxmed::POSITIVE) < nxy * nz) return fail(c, OLX_EINVAL, "olx_bf_set_medium: sound speed must be finite and > 0");
+    // the held planes: olxmed::scan_planes_columns, scan_planes' rule for the sound speed (a plane with any voxel != c_ref), sigma = c_ref / c - 1 in fp64
     std::vector<double> zp, sig;
-    for (int k = 0; k < nz && sound_speed; ++k) {
-        bool any = false;
-        for (size_t ij = 0; ij < nxy && !any; ++ij) any = (double)sound_speed[ij * nz + k] != c_ref;
-        if (!any) continue;
-        pk[k] = (int)zp.size();
-        zp.push_back(grid->origin[2] + k * grid->spacing[2]);
-        for (size_t ij = 0; ij < nxy; ++ij) sig.push_back(c_ref / (double)sound_speed[ij * nz + k] - 1.0);
-    }
+    olxmed::Planes pl = olxmed::scan_planes_columns(sound_speed, c_ref, nullptr, 0.0, nx, ny, nz, sig);
+    for (int k : pl.plane_k) zp.push_back(grid->origin[2] + k * grid->spacing[2]);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));      // (a solve of the previous medium may still read the buffers)
     c->bm_set = false; c->bc_valid = false;
@@ -333,15 +335,9 @@ int olx_bf_set_medium(olx_ctx* c, const float* sound_speed, const olx_grid* grid
     if (rc) return rc;
     if (!sig.empty()) HIPCHK(c, hipMemcpy(c->d_bm_sig, sig.data(), sizeof(double) * sig.size(), hipMemcpyHostToDevice));
     if (!zp.empty()) HIPCHK(c, hipMemcpy(c->d_bm_zp, zp.data(), sizeof(double) * zp.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_bm_pk, pk.data(), sizeof(int) * nz, hipMemcpyHostToDevice));
-    BfMedParams& P = c->bm;
-    P.ox = grid->origin[0]; P.oy = grid->origin[1]; P.oz = grid->origin[2];
-    P.hx = grid->spacing[0]; P.hy = grid->spacing[1]; P.hz = grid->spacing[2];
-    P.dmin = 0.5 * std::min(P.hx, std::min(P.hy, P.hz));
-    P.ztol = 1e-6 * P.hz;
-    P.c = c_ref;
-    P.nx = nx; P.ny = ny; P.nz = nz; P.n_planes = (int)zp.size();
-    c->h_bm_pk.swap(pk);
+    HIPCHK(c, hipMemcpy(c->d_bm_pk, pl.plane_of_k.data(), sizeof(int) * nz, hipMemcpyHostToDevice));
+    bfmed_params(c->bm, *grid, c_ref, (int)zp.size());
+    c->h_bm_pk.swap(pl.plane_of_k);
     c->bm_set = true;
     return OLX_OK;
 }
@@ -377,28 +373,14 @@ int olx_bf_set_attenuation(olx_ctx* c, const float* att, const olx_grid* grid, d
     if (!c) return OLX_EINVAL;
     if (!grid) return fail(c, OLX_EINVAL, "olx_bf_set_attenuation: null grid");
     if (!(freq_hz > 0) || !std::isfinite(freq_hz)) return fail(c, OLX_EINVAL, "olx_bf_set_attenuation: freq_hz must be finite and > 0");
-    for (int a = 0; a < 3; ++a) {
-        if (grid->n[a] < 1) return fail(c, OLX_EINVAL, "olx_bf_set_attenuation: grid sizes must be >= 1");
-        if (!(grid->spacing[a] > 0) || !std::isfinite(grid->spacing[a]) || !std::isfinite(grid->origin[a]))
-            return fail(c, OLX_EINVAL, "olx_bf_set_attenuation: grid spacing must be finite and > 0, origin finite");
-    }
+    if (auto f = olxmed::check_grid(*grid)) return grid_fail(c, "olx_bf_set_attenuation", f);
     const int nx = grid->n[0], ny = grid->n[1], nz = grid->n[2];
     const size_t nxy = (size_t)nx * ny;
-    if (att)
-        for (size_t o = 0; o < nxy * nz; ++o)
-            if (!(att[o] >= 0.f) || !std::isfinite(att[o])) return fail(c, OLX_EINVAL, "olx_bf_set_attenuation: attenuation must be finite and >= 0");
-    // the held planes: olx_bf_set_medium's rule for the attenuation (a plane with any voxel != 0), a [Np/m] in fp64 (sim/field.py _np_per_m)
-    const double fpow = std::pow(freq_hz * 1e-6, 0.9);
-    std::vector<int> pk(nz, -1);
+    if (olxmed::first_bad(att, nxy * nz, olxmed::NON_NEGATIVE) < nxy * nz) return fail(c, OLX_EINVAL, "olx_bf_set_attenuation: attenuation must be finite and >= 0");
+    // the held planes: olxmed::scan_planes_columns, scan_planes' rule for the attenuation (a plane with any voxel != 0), a [Np/m] in fp64 (sim/field.py _np_per_m)
     std::vector<double> zp, av;
-    for (int k = 0; k < nz && att; ++k) {
-        bool any = false;
-        for (size_t ij = 0; ij < nxy && !any; ++ij) any = att[ij * nz + k] != 0.f;
-        if (!any) continue;
-        pk[k] = (int)zp.size();
-        zp.push_back(grid->origin[2] + k * grid->spacing[2]);
-        for (size_t ij = 0; ij < nxy; ++ij) av.push_back((double)att[ij * nz + k] * fpow * 100.0 / 8.685889638065035);
-    }
+    olxmed::Planes pl = olxmed::scan_planes_columns(nullptr, 0.0, att, std::pow(freq_hz * 1e-6, 0.9), nx, ny, nz, av);
+    for (int k : pl.plane_k) zp.push_back(grid->origin[2] + k * grid->spacing[2]);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));      // (a solve of the previous attenuation may still read the buffers)
     c->ba_set = false; c->bc_valid = false;
@@ -408,15 +390,9 @@ int olx_bf_set_attenuation(olx_ctx* c, const float* att, const olx_grid* grid, d
     if (rc) return rc;
     if (!av.empty()) HIPCHK(c, hipMemcpy(c->d_ba_att, av.data(), sizeof(double) * av.size(), hipMemcpyHostToDevice));
     if (!zp.empty()) HIPCHK(c, hipMemcpy(c->d_ba_zp, zp.data(), sizeof(double) * zp.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_ba_pk, pk.data(), sizeof(int) * nz, hipMemcpyHostToDevice));
-    BfMedParams& P = c->ba;
-    P.ox = grid->origin[0]; P.oy = grid->origin[1]; P.oz = grid->origin[2];
-    P.hx = grid->spacing[0]; P.hy = grid->spacing[1]; P.hz = grid->spacing[2];
-    P.dmin = 0.5 * std::min(P.hx, std::min(P.hy, P.hz));
-    P.ztol = 1e-6 * P.hz;
-    P.c = freq_hz;
-    P.nx = nx; P.ny = ny; P.nz = nz; P.n_planes = (int)zp.size();
-    c->h_ba_pk.swap(pk);
+    HIPCHK(c, hipMemcpy(c->d_ba_pk, pl.plane_of_k.data(), sizeof(int) * nz, hipMemcpyHostToDevice));
+    bfmed_params(c->ba, *grid, freq_hz, (int)zp.size());
+    c->h_ba_pk.swap(pl.plane_of_k);
     c->ba_set = true;
     return OLX_OK;
 }
@@ -1299,6 +1275,32 @@ int olx_field_pulse_trace(olx_ctx* c, int n_points, const long long* voxels, flo
 
 // ---- kernel 4: steering map (DESIGN.md section 2 "Steering map") ---------------------------------------------------
 // Reads the element table (and the apertures), writes buffers of its own: the plan, the steering table and every resident result stay as they are.
+// What kernels 4 and 4h check and fill alike: the grid, the apodization rule and its part of SteerParams (`who` words the messages).
+static int steer_params(olx_ctx* c, const char* who, const olx_grid* g, int apod_kind, double p0, double p1, SteerParams& P, int& kind) {
+    if (auto f = olxmed::check_grid(*g)) return grid_fail(c, who, f);
+    double hmin = 1e300;
+    for (int a = 0; a < 3; ++a) hmin = std::min(hmin, g->spacing[a]);
+    const double to_rad = (apod_kind & OLX_APOD_RADIANS) ? 1.0 : (3.14159265358979323846 / 180.0);
+    kind = apod_kind & ~OLX_APOD_RADIANS;
+    if (kind < 0 || kind > 2) return fail(c, OLX_EINVAL, "%s: unknown apod_kind %d", who, apod_kind);
+    if (!std::isfinite(p0) || (kind != OLX_APOD_UNIFORM && !(p0 >= 0))) return fail(c, OLX_EINVAL, "%s: apodization parameter must be finite (angles >= 0)", who);
+    if (kind == OLX_APOD_PIECEWISE && !(p1 < p0 && p1 >= 0)) return fail(c, OLX_EINVAL, "%s: rolloff must be >= 0 and < zero angle", who);
+    P.n_el = c->n_el;
+    P.nx = g->n[0]; P.ny = g->n[1]; P.nz = g->n[2];
+    P.vox = (long long)P.nx * P.ny * P.nz;
+    P.ox = g->origin[0]; P.oy = g->origin[1]; P.oz = g->origin[2];
+    P.hx = g->spacing[0]; P.hy = g->spacing[1]; P.hz = g->spacing[2];
+    P.dmin2 = (float)(0.25 * hmin * hmin);
+    P.value = kind == OLX_APOD_UNIFORM ? (float)p0 : 1.0f;
+    P.lim2 = 2.0;      // every angle passes
+    if (kind != OLX_APOD_UNIFORM) {
+        const double lim = p0 * to_rad, half_pi = 1.5707963267948966;
+        if (kind == OLX_APOD_MAXANGLE ? lim < half_pi : lim <= half_pi) { const double s = std::sin(lim); P.lim2 = s * s; }
+        if (kind == OLX_APOD_PIECEWISE) { const double span = (p0 - p1) * to_rad; P.pw_scale = (float)(1.0 / span); P.pw_off = (float)(lim / span); }
+    }
+    return OLX_OK;
+}
+
 int olx_steer_map(olx_ctx* c, const olx_grid* g, double freq, double cs, double p0_pa, int apod_kind, double p0, double p1,
                   double absorption_np_m, unsigned flags, float* pfocal_out, int* n_active_out) {
     if (!c) return OLX_EINVAL;
@@ -1310,33 +1312,9 @@ int olx_steer_map(olx_ctx* c, const olx_grid* g, double freq, double cs, double 
     if (!(freq > 0) || !(cs > 0) || !std::isfinite(freq) || !std::isfinite(cs) || !std::isfinite(p0_pa))
         return fail(c, OLX_EINVAL, "olx_steer_map: freq and c must be finite and > 0, p0_pa finite");
     if (!(absorption_np_m >= 0) || !std::isfinite(absorption_np_m)) return fail(c, OLX_EINVAL, "olx_steer_map: absorption must be finite and >= 0");
-    double hmin = 1e300;
-    for (int a = 0; a < 3; ++a) {
-        if (g->n[a] < 1) return fail(c, OLX_EINVAL, "olx_steer_map: grid sizes must be >= 1");
-        if (!(g->spacing[a] > 0) || !std::isfinite(g->spacing[a]) || !std::isfinite(g->origin[a]))
-            return fail(c, OLX_EINVAL, "olx_steer_map: grid spacing must be finite and > 0, origin finite");
-        hmin = std::min(hmin, g->spacing[a]);
-    }
-    const double to_rad = (apod_kind & OLX_APOD_RADIANS) ? 1.0 : (3.14159265358979323846 / 180.0);
-    const int kind = apod_kind & ~OLX_APOD_RADIANS;
-    if (kind < 0 || kind > 2) return fail(c, OLX_EINVAL, "olx_steer_map: unknown apod_kind %d", apod_kind);
-    if (!std::isfinite(p0) || (kind != OLX_APOD_UNIFORM && !(p0 >= 0))) return fail(c, OLX_EINVAL, "olx_steer_map: apodization parameter must be finite (angles >= 0)");
-    if (kind == OLX_APOD_PIECEWISE && !(p1 < p0 && p1 >= 0)) return fail(c, OLX_EINVAL, "olx_steer_map: rolloff must be >= 0 and < zero angle");
-    SteerParams P{};
-    P.n_el = c->n_el;
-    P.nx = g->n[0]; P.ny = g->n[1]; P.nz = g->n[2];
-    P.vox = (long long)P.nx * P.ny * P.nz;
+    SteerParams P{}; int kind;
+    { int rc = steer_params(c, "olx_steer_map", g, apod_kind, p0, p1, P, kind); if (rc) return rc; }
     if ((long long)P.nx * P.ny * ((P.nz + 3) / 4) > (long long)INT_MAX * 128) return fail(c, OLX_EINVAL, "olx_steer_map: grid too large");
-    P.ox = g->origin[0]; P.oy = g->origin[1]; P.oz = g->origin[2];
-    P.hx = g->spacing[0]; P.hy = g->spacing[1]; P.hz = g->spacing[2];
-    P.dmin2 = (float)(0.25 * hmin * hmin);
-    P.value = kind == OLX_APOD_UNIFORM ? (float)p0 : 1.0f;
-    P.lim2 = 2.0;      // every angle passes
-    if (kind != OLX_APOD_UNIFORM) {
-        const double lim = p0 * to_rad, half_pi = 1.5707963267948966;
-        if (kind == OLX_APOD_MAXANGLE ? lim < half_pi : lim <= half_pi) { const double s = std::sin(lim); P.lim2 = s * s; }
-        if (kind == OLX_APOD_PIECEWISE) { const double span = (p0 - p1) * to_rad; P.pw_scale = (float)(1.0 / span); P.pw_off = (float)(lim / span); }
-    }
     P.absorb_l2 = (float)(absorption_np_m * 1.4426950408889634);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->n_el;
@@ -1379,90 +1357,36 @@ int olx_steer_map_medium(olx_ctx* c, const olx_grid* g, double freq, double cs, 
         return fail(c, OLX_EINVAL, "olx_steer_map_medium: unknown comp %d", comp);
     if (delays != OLX_STEER_DELAYS_STRAIGHTRAY && delays != OLX_STEER_DELAYS_DIRECT)
         return fail(c, OLX_EINVAL, "olx_steer_map_medium: unknown delays %d", delays);
-    double hmin = 1e300;
-    for (int a = 0; a < 3; ++a) {
-        if (g->n[a] < 1) return fail(c, OLX_EINVAL, "olx_steer_map_medium: grid sizes must be >= 1");
-        if (!(g->spacing[a] > 0) || !std::isfinite(g->spacing[a]) || !std::isfinite(g->origin[a]))
-            return fail(c, OLX_EINVAL, "olx_steer_map_medium: grid spacing must be finite and > 0, origin finite");
-        hmin = std::min(hmin, g->spacing[a]);
-    }
-    const double to_rad = (apod_kind & OLX_APOD_RADIANS) ? 1.0 : (3.14159265358979323846 / 180.0);
-    const int kind = apod_kind & ~OLX_APOD_RADIANS;
-    if (kind < 0 || kind > 2) return fail(c, OLX_EINVAL, "olx_steer_map_medium: unknown apod_kind %d", apod_kind);
-    if (!std::isfinite(p0) || (kind != OLX_APOD_UNIFORM && !(p0 >= 0))) return fail(c, OLX_EINVAL, "olx_steer_map_medium: apodization parameter must be finite (angles >= 0)");
-    if (kind == OLX_APOD_PIECEWISE && !(p1 < p0 && p1 >= 0)) return fail(c, OLX_EINVAL, "olx_steer_map_medium: rolloff must be >= 0 and < zero angle");
+    SteerMedParams M{};
+    SteerParams& P = M.S; int kind;
+    { int rc = steer_params(c, "olx_steer_map_medium", g, apod_kind, p0, p1, P, kind); if (rc) return rc; }
     const int nx = g->n[0], ny = g->n[1], nz = g->n[2];
     const size_t nvox = (size_t)nx * ny * nz;
     // (32-bit byte offsets into a stencil plane of 32 bytes per cell, 24-bit factors; one block per 8 x 8 x 16 voxels)
     if ((long long)nx * ny > (1ll << 26) || nx >= (1 << 24) || ny >= (1 << 24) ||
         (long long)((nx + 7) / 8) * ((ny + 7) / 8) * ((nz + 15) / 16) > (long long)INT_MAX)
         return fail(c, OLX_EINVAL, "olx_steer_map_medium: grid too large");
-    if (sound_speed)
-        for (size_t o = 0; o < nvox; ++o)
-            if (!(sound_speed[o] > 0.f) || !std::isfinite(sound_speed[o])) return fail(c, OLX_EINVAL, "olx_steer_map_medium: sound speed must be finite and > 0");
-    if (attenuation)
-        for (size_t o = 0; o < nvox; ++o)
-            if (!(attenuation[o] >= 0.f) || !std::isfinite(attenuation[o])) return fail(c, OLX_EINVAL, "olx_steer_map_medium: attenuation must be finite and >= 0");
+    if (olxmed::first_bad(sound_speed, nvox, olxmed::POSITIVE) < nvox) return fail(c, OLX_EINVAL, "olx_steer_map_medium: sound speed must be finite and > 0");
+    if (olxmed::first_bad(attenuation, nvox, olxmed::NON_NEGATIVE) < nvox) return fail(c, OLX_EINVAL, "olx_steer_map_medium: attenuation must be finite and >= 0");
     const bool phase = delays == OLX_STEER_DELAYS_DIRECT;
     const float* ssv = phase ? sound_speed : nullptr;      // StraightRay delays put every term in phase: the sound speed does not enter
-    SteerMedParams M{};
-    SteerParams& P = M.S;
-    P.n_el = c->n_el;
-    P.nx = nx; P.ny = ny; P.nz = nz;
-    P.vox = (long long)nvox;
-    P.ox = g->origin[0]; P.oy = g->origin[1]; P.oz = g->origin[2];
-    P.hx = g->spacing[0]; P.hy = g->spacing[1]; P.hz = g->spacing[2];
-    P.dmin2 = (float)(0.25 * hmin * hmin);
-    P.value = kind == OLX_APOD_UNIFORM ? (float)p0 : 1.0f;
-    P.lim2 = 2.0;      // every angle passes
-    if (kind != OLX_APOD_UNIFORM) {
-        const double lim = p0 * to_rad, half_pi = 1.5707963267948966;
-        if (kind == OLX_APOD_MAXANGLE ? lim < half_pi : lim <= half_pi) { const double s = std::sin(lim); P.lim2 = s * s; }
-        if (kind == OLX_APOD_PIECEWISE) { const double span = (p0 - p1) * to_rad; P.pw_scale = (float)(1.0 / span); P.pw_off = (float)(lim / span); }
-    }
     const double lambda = cs / freq;
     M.inv_hx = 1.0 / P.hx; M.inv_hy = 1.0 / P.hy;
     M.hz_w = (float)(P.hz / lambda);
     M.abs_value = std::fabs(P.value);
     M.spreading = spreading ? 1 : 0;
     // non-trivial planes and their pre-gathered stencil (kernel 2h's layout and conversions, power 0.9 as kernel 1a)
-    const double afac = std::pow(freq * 1e-6, 0.9) * 100.0 / 8.685889638065035 * lambda;      // dB/cm/MHz^0.9 -> Np per wavelength
-    std::vector<int> plane_of_k(nz, -1), plane_k;
-    for (int k = 0; k < nz; ++k) {
-        bool any = false;
-        for (size_t ij = 0; ij < (size_t)nx * ny && !any; ++ij) {
-            const size_t o = ij * nz + k;
-            if (ssv && (double)ssv[o] != cs) any = true;
-            if (attenuation && attenuation[o] != 0.f) any = true;
-        }
-        if (any) { plane_of_k[k] = (int)plane_k.size(); plane_k.push_back(k); }
-    }
-    const int np = (int)plane_k.size();
-    M.n_planes = np;
-    std::vector<float> med((size_t)std::max(np, 1) * nx * ny * 8, 0.f);
-    auto term = [&](int i, int j, int k, float* out) {
-        const size_t o = ((size_t)i * ny + j) * nz + k;
-        out[0] = ssv ? (float)(cs / (double)ssv[o] - 1.0) : 0.f;
-        out[1] = attenuation ? (float)((double)attenuation[o] * afac) : 0.f;
-    };
-    for (int p = 0; p < np; ++p)
-        for (int i = 0; i < nx; ++i)
-            for (int j = 0; j < ny; ++j) {
-                float* tx = &med[(((size_t)p * nx + i) * ny + j) * 8];
-                const int i1 = std::min(i + 1, nx - 1), j1 = std::min(j + 1, ny - 1), k = plane_k[p];
-                term(i, j, k, tx); term(i, j1, k, tx + 2); term(i1, j, k, tx + 4); term(i1, j1, k, tx + 6);
-            }
-    // per element: first plane strictly above, last plane strictly below (fp64, z_k = oz + k hz: kernel 2h's table entries), and S_e
+    const double afac = olxmed::np_per_m_factor(freq, 0.9) * lambda;      // dB/cm/MHz^0.9 -> Np per wavelength
+    const auto [plane_of_k, plane_k] = olxmed::scan_planes(ssv, cs, attenuation, nx, ny, nz);
+    const int np = M.n_planes = (int)plane_k.size();
+    const std::vector<float> med = olxmed::gather_stencil(olxmed::plane_cells(ssv, cs, attenuation, afac, (size_t)nx * ny, nz, plane_k), np, nx, ny);
+    // per element: first plane strictly above, last plane strictly below (olxmed::element_plane_bounds: kernel 2h's table entries), and S_e
     const size_t n = (size_t)c->n_el;
+    const auto [kfirst, klast] = olxmed::element_plane_bounds(c->h_pos.data() + 2 * n, c->n_el, P.oz, P.hz, nz);
     std::vector<float> tabm(n * STEER_TM);
     for (size_t e = 0; e < n; ++e) {
-        const double ez = c->h_pos[2 * n + e];
-        int kf = 0;
-        while (kf < nz && !(P.oz + kf * P.hz > ez)) ++kf;
-        int kl = nz - 1;
-        while (kl >= 0 && !(P.oz + kl * P.hz < ez)) --kl;
         float* t = &tabm[e * STEER_TM];
-        memcpy(&t[0], &kf, 4); memcpy(&t[1], &kl, 4);
+        memcpy(&t[0], &kfirst[e], 4); memcpy(&t[1], &klast[e], 4);
         t[2] = (float)c->h_area[e]; t[3] = (float)(1.0 / c->h_area[e]);
     }
     HIPCHK(c, hipSetDevice(c->device));
@@ -1547,47 +1471,14 @@ int olx_field_set_medium(olx_ctx* c, const float* sound_speed, const float* atte
     const int nx = g.n[0], ny = g.n[1], nz = g.n[2], n = c->n_el;
     const size_t nvox = (size_t)nx * ny * nz;
     const double c0 = c->c, lambda = c->c / c->freq, rev = c->freq / c->c;
-    const double np_per_db = 1.0 / 8.685889638065035;
-    const double afac = std::pow(c->freq * 1e-6, alpha_power) * 100.0 * np_per_db * lambda;  // dB/cm/MHz^y -> Np per wavelength
-    // non-trivial planes
-    std::vector<int> plane_of_k(nz, -1), plane_k;
-    for (int k = 0; k < nz; ++k) {
-        bool any = false;
-        for (size_t ij = 0; ij < (size_t)nx * ny && !any; ++ij) {
-            const size_t o = ij * nz + k;
-            if (sound_speed && (double)sound_speed[o] != c0) any = true;
-            if (attenuation && attenuation[o] != 0.f) any = true;
-        }
-        if (any) { plane_of_k[k] = (int)plane_k.size(); plane_k.push_back(k); }
-    }
+    const double afac = olxmed::np_per_wavelength_factor(c->freq, alpha_power, lambda);
+    const auto [plane_of_k, plane_k] = olxmed::scan_planes(sound_speed, c0, attenuation, nx, ny, nz);      // the non-trivial planes
     const int np = (int)plane_k.size();
-    // pre-gathered bilinear stencil: texel (p,i,j) = { sig, a' } of (i,j), (i,j+1), (i+1,j), (i+1,j+1), edge-clamped
-    std::vector<float> med((size_t)std::max(np, 1) * nx * ny * 8, 0.f);
-    auto term = [&](int i, int j, int k, float* out) {
-        const size_t o = ((size_t)i * ny + j) * nz + k;
-        out[0] = sound_speed ? (float)(c0 / (double)sound_speed[o] - 1.0) : 0.f;
-        out[1] = attenuation ? (float)((double)attenuation[o] * afac) : 0.f;
-    };
-    if (sound_speed)
-        for (size_t o = 0; o < nvox; ++o)
-            if (!(sound_speed[o] > 0.f)) return fail(c, OLX_EINVAL, "olx_field_set_medium: sound speed must be > 0");
-    for (int p = 0; p < np; ++p)
-        for (int i = 0; i < nx; ++i)
-            for (int j = 0; j < ny; ++j) {
-                float* tx = &med[(((size_t)p * nx + i) * ny + j) * 8];
-                const int i1 = std::min(i + 1, nx - 1), j1 = std::min(j + 1, ny - 1), k = plane_k[p];
-                term(i, j, k, tx); term(i, j1, k, tx + 2); term(i1, j, k, tx + 4); term(i1, j1, k, tx + 6);
-            }
+    // (known difference: +inf passes here, the other four entry points ask for finite values; unifying it would change behaviour)
+    if (olxmed::first_bad(sound_speed, nvox, olxmed::POSITIVE, false) < nvox) return fail(c, OLX_EINVAL, "olx_field_set_medium: sound speed must be > 0");
+    const std::vector<float> med = olxmed::gather_stencil(olxmed::plane_cells(sound_speed, c0, attenuation, afac, (size_t)nx * ny, nz, plane_k), np, nx, ny);
     // per element: first plane strictly above, last plane strictly below (fp64, same predicate as the oracle)
-    std::vector<int> kfirst(n), klast(n);
-    for (int e = 0; e < n; ++e) {
-        const double ez = c->h_pos[2 * (size_t)n + e];
-        int kf = 0;
-        while (kf < nz && !(g.origin[2] + kf * g.spacing[2] > ez)) ++kf;
-        int kl = nz - 1;
-        while (kl >= 0 && !(g.origin[2] + kl * g.spacing[2] < ez)) --kl;
-        kfirst[e] = kf; klast[e] = kl;
-    }
+    const auto [kfirst, klast] = olxmed::element_plane_bounds(c->h_pos.data() + 2 * (size_t)n, n, g.origin[2], g.spacing[2], nz);
     // marched ray sums (kernel 2m) need rays that cross the non-trivial planes upwards only, and a 2 x 2 stencil
     bool march_ok = c->planes_per_layer == 1 && nx >= 2 && ny >= 2 && (size_t)n * nx * ny * sizeof(float2) < ((size_t)1 << 32);   // (32-bit lane offsets into U)
     if (np > 0)
@@ -1597,21 +1488,12 @@ int olx_field_set_medium(olx_ctx* c, const float* sound_speed, const float* atte
         return fail(c, OLX_EINVAL, "olx_field_set_medium: OLX_MEDIUM_MARCHED needs every element strictly below the first non-trivial "
                                     "plane, >= 2 voxels along x and y and planes_per_layer = 1");
     c->marched = march_ok && c->medium_model != OLX_MEDIUM_SAMPLED;
-    // kernel 2m's one-sum form: every voxel's stencil values {sig, a'} lie on ONE line through the origin (a two-material medium over a lossless
-    // reference: water + skull).  Compared as products of the stored floats in fp64 -- exact for the handful of distinct pairs a segmentation has.
+    // kernel 2m's one-sum form (olxmed::detect_one_line): a two-material medium over a lossless reference, water + skull
     c->march_one = false; c->hp.kappa = 0.f;
     if (c->marched && np > 0) {
-        double s_ref = 0, a_ref = 0;
-        bool one = true;
-        for (int p = 0; p < np && one; ++p)
-            for (size_t ij = 0; ij < (size_t)nx * ny && one; ++ij) {
-                const double sg = med[((size_t)p * nx * ny + ij) * 8], ab = med[((size_t)p * nx * ny + ij) * 8 + 1];
-                if (sg == 0.0 && ab == 0.0) continue;
-                if (s_ref == 0.0 && a_ref == 0.0) { s_ref = sg; a_ref = ab; if (s_ref == 0.0) one = false; continue; }
-                if (sg * a_ref != ab * s_ref) one = false;
-            }
+        const olxmed::OneLine L = olxmed::detect_one_line(med, (size_t)np * nx * ny);
         const char* pin = getenv("OLX_MARCH_SUMS");
-        if (one && s_ref != 0.0 && !(pin && !strcmp(pin, "2"))) { c->march_one = true; c->hp.kappa = (float)(a_ref / s_ref); }
+        if (L.one && L.s_ref != 0.0 && !(pin && !strcmp(pin, "2"))) { c->march_one = true; c->hp.kappa = (float)(L.a_ref / L.s_ref); }
     }
     if (c->march_one) {     // row-pair form of the last running sums (k_hmarch.hip TEX): 8 bytes per cell + one cell of padding, 32-bit byte offsets like U
         { int rc = c->d_Utex.reserve(c, (size_t)n * nx * ny + 1); if (rc) return rc; }
@@ -1629,39 +1511,12 @@ int olx_field_set_medium(olx_ctx* c, const float* sound_speed, const float* atte
     }
     if (c->marched)
         for (DevBuf<float2>& u : c->d_U) { int rc = u.reserve(c, (size_t)n * nx * ny); if (rc) return rc; }
-    // two-level quadrature (opt-in, olx_field_medium_layering): every maximal run of consecutive non-trivial planes is cut
-    // into layers of <= G planes; a layer's stencil holds the column sums of its planes (fp64 sums, rounded once)
+    // two-level quadrature (opt-in, olx_field_medium_layering): olxmed::layer_runs, a layer's stencil holds the column sums of its planes
     std::vector<int> layer_lo, layer_hi;
     if (c->planes_per_layer > 1) {
-        int run = 0;
-        for (int q = 0; q < np; ++q) {
-            const bool contiguous = q > 0 && plane_k[q] == plane_k[q - 1] + 1;
-            if (!contiguous || run == c->planes_per_layer) { layer_lo.push_back(plane_k[q]); layer_hi.push_back(plane_k[q]); run = 1; }
-            else { layer_hi.back() = plane_k[q]; ++run; }
-        }
+        olxmed::layer_runs(plane_k, c->planes_per_layer, layer_lo, layer_hi);
         const int nl = (int)layer_lo.size();
-        std::vector<float> lay((size_t)std::max(nl, 1) * nx * ny * 8, 0.f);
-        std::vector<double> acc((size_t)nx * ny * 2);
-        for (int g = 0; g < nl; ++g) {
-            std::fill(acc.begin(), acc.end(), 0.0);
-            for (int k = layer_lo[g]; k <= layer_hi[g]; ++k)
-                for (int i = 0; i < nx; ++i)
-                    for (int j = 0; j < ny; ++j) {
-                        const size_t o = ((size_t)i * ny + j) * nz + k;
-                        if (sound_speed) acc[((size_t)i * ny + j) * 2] += c0 / (double)sound_speed[o] - 1.0;
-                        if (attenuation) acc[((size_t)i * ny + j) * 2 + 1] += (double)attenuation[o] * afac;
-                    }
-            for (int i = 0; i < nx; ++i)
-                for (int j = 0; j < ny; ++j) {
-                    float* tx = &lay[(((size_t)g * nx + i) * ny + j) * 8];
-                    const int i1 = std::min(i + 1, nx - 1), j1 = std::min(j + 1, ny - 1);
-                    const int cs[4][2] = {{i, j}, {i, j1}, {i1, j}, {i1, j1}};
-                    for (int q = 0; q < 4; ++q) {
-                        tx[2 * q] = (float)acc[((size_t)cs[q][0] * ny + cs[q][1]) * 2];
-                        tx[2 * q + 1] = (float)acc[((size_t)cs[q][0] * ny + cs[q][1]) * 2 + 1];
-                    }
-                }
-        }
+        const std::vector<float> lay = olxmed::gather_stencil(olxmed::layer_cells(sound_speed, c0, attenuation, afac, (size_t)nx * ny, nz, layer_lo, layer_hi), nl, nx, ny);
         int rc = c->d_med_layer.reserve(c, lay.size() / 4);
         if (!rc) rc = c->d_layer_lo.reserve(c, nl);
         if (!rc) rc = c->d_layer_hi.reserve(c, nl);
@@ -1687,11 +1542,7 @@ int olx_field_set_medium(olx_ctx* c, const float* sound_speed, const float* atte
     HIPCHK(c, hipMemcpy(c->d_klast, klast.data(), sizeof(int) * n, hipMemcpyHostToDevice));
     if (density || sound_speed) {  // per-voxel 1e-4 / (2 rho c) for the intensity (sim/kwave_if.py:140-141), slab part
         const size_t sv = (size_t)c->fp.vox, off = (size_t)c->slab.x_begin * ny * nz;
-        std::vector<float> iz(sv);
-        for (size_t o = 0; o < sv; ++o) {
-            const double rho = density ? (double)density[off + o] : c->rho, cs = sound_speed ? (double)sound_speed[off + o] : c0;
-            iz[o] = (float)(1e-4 / (2.0 * rho * cs));
-        }
+        const std::vector<float> iz = olxmed::impedance_volume(density, c->rho, sound_speed, c0, off, sv);
         { int rc = c->d_inv2z.reserve(c, sv); if (rc) return rc; }
         HIPCHK(c, hipMemcpy(c->d_inv2z, iz.data(), sizeof(float) * sv, hipMemcpyHostToDevice));
     }
@@ -1774,47 +1625,27 @@ int olx_field_pulse_medium(olx_ctx* c, const float* sound_speed, const float* at
     const olx_grid& g = c->grid;
     const int nx = g.n[0], ny = g.n[1], nz = g.n[2], n = c->n_el;
     const size_t nvox = (size_t)nx * ny * nz;
-    for (size_t o = 0; o < nvox; ++o) {
-        if (sound_speed && (!(sound_speed[o] > 0.f) || !std::isfinite(sound_speed[o]))) return fail(c, OLX_EINVAL, "olx_field_pulse_medium: sound speed must be finite and > 0");
-        if (attenuation && (!(attenuation[o] >= 0.f) || !std::isfinite(attenuation[o]))) return fail(c, OLX_EINVAL, "olx_field_pulse_medium: attenuation must be finite and >= 0");
-        if (density && (!(density[o] > 0.f) || !std::isfinite(density[o]))) return fail(c, OLX_EINVAL, "olx_field_pulse_medium: density must be finite and > 0");
+    // the three volumes voxel by voxel: the lowest bad index wins, ties go sound speed, attenuation, density
+    const size_t bad[3] = {olxmed::first_bad(sound_speed, nvox, olxmed::POSITIVE), olxmed::first_bad(attenuation, nvox, olxmed::NON_NEGATIVE), olxmed::first_bad(density, nvox, olxmed::POSITIVE)};
+    switch (olxmed::first_bad_volume(bad, 3, nvox)) {
+        case 0: return fail(c, OLX_EINVAL, "olx_field_pulse_medium: sound speed must be finite and > 0");
+        case 1: return fail(c, OLX_EINVAL, "olx_field_pulse_medium: attenuation must be finite and >= 0");
+        case 2: return fail(c, OLX_EINVAL, "olx_field_pulse_medium: density must be finite and > 0");
     }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const double c0 = c->c;
-    const double afac = std::pow(c->freq * 1e-6, alpha_power) * 100.0 / 8.685889638065035;      // dB/cm/MHz^y -> Np/m
-    // non-trivial planes: olx_field_set_medium's rule
-    std::vector<int> plane_of_k(nz, -1), plane_k;
-    for (int k = 0; k < nz; ++k) {
-        bool any = false;
-        for (size_t ij = 0; ij < (size_t)nx * ny && !any; ++ij) {
-            const size_t o = ij * nz + k;
-            if (sound_speed && (double)sound_speed[o] != c0) any = true;
-            if (attenuation && attenuation[o] != 0.f) any = true;
-        }
-        if (any) { plane_of_k[k] = (int)plane_k.size(); plane_k.push_back(k); }
-    }
+    const double afac = olxmed::np_per_m_factor(c->freq, alpha_power);
+    const auto [plane_of_k, plane_k] = olxmed::scan_planes(sound_speed, c0, attenuation, nx, ny, nz);      // the non-trivial planes
     const int np = (int)plane_k.size();
     const size_t nxy = (size_t)nx * ny;
-    // compact [plane][i][j] arrays: sig = c_ref / c - 1 in fp64 from the float32 volume, a in Np/m rounded once
-    std::vector<double> sig(sound_speed ? std::max<size_t>(np * nxy, 1) : 0);
-    std::vector<float> att(attenuation ? std::max<size_t>(np * nxy, 1) : 0);
-    for (int p = 0; p < np; ++p)
-        for (size_t ij = 0; ij < nxy; ++ij) {
-            const size_t o = ij * nz + plane_k[p];
-            if (sound_speed) sig[p * nxy + ij] = c0 / (double)sound_speed[o] - 1.0;
-            if (attenuation) att[p * nxy + ij] = (float)((double)attenuation[o] * afac);
-        }
-    // per element: first plane strictly above, last plane strictly below (fp64: olx_field_set_medium's loop)
-    std::vector<int2> kb(n);
-    for (int e = 0; e < n; ++e) {
-        const double ez = c->h_pos[2 * (size_t)n + e];
-        int kf = 0;
-        while (kf < nz && !(g.origin[2] + kf * g.spacing[2] > ez)) ++kf;
-        int kl = nz - 1;
-        while (kl >= 0 && !(g.origin[2] + kl * g.spacing[2] < ez)) --kl;
-        kb[e] = make_int2(kf, kl);
-    }
+    // compact [plane][i][j] arrays: sig = c_ref / c - 1 in fp64 from the float32 volume, a in Np/m rounded once; one zero where no plane is held
+    std::vector<double> sig; std::vector<float> att;
+    if (sound_speed) { sig = olxmed::plane_sigma(sound_speed, c0, nxy, nz, plane_k); sig.resize(std::max<size_t>(sig.size(), 1)); }
+    if (attenuation) { att = olxmed::plane_att(attenuation, afac, nxy, nz, plane_k); att.resize(std::max<size_t>(att.size(), 1)); }
+    const auto [kfirst, klast] = olxmed::element_plane_bounds(c->h_pos.data() + 2 * (size_t)n, n, g.origin[2], g.spacing[2], nz);
+    std::vector<int2> kb(n);      // per element: first plane strictly above, last plane strictly below
+    for (int e = 0; e < n; ++e) kb[e] = make_int2(kfirst[e], klast[e]);
     c->pulse_med = false;      // (until everything below is in place)
     int rc = c->d_pm_plane_k.reserve(c, np);
     if (!rc) rc = c->d_pm_plane_of_k.reserve(c, nz);
@@ -1829,11 +1660,7 @@ int olx_field_pulse_medium(olx_ctx* c, const float* sound_speed, const float* at
     if (attenuation) HIPCHK(c, hipMemcpy(c->d_pm_att, att.data(), sizeof(float) * att.size(), hipMemcpyHostToDevice));
     c->pm_has_sig = sound_speed != nullptr; c->pm_has_att = attenuation != nullptr; c->pm_has_z = density || sound_speed;
     if (c->pm_has_z) {      // per-voxel 1e-4 / (2 rho c) of the intensity and the PII (sim/kwave_if.py:140-141)
-        std::vector<float> iz(nvox);
-        for (size_t o = 0; o < nvox; ++o) {
-            const double rho = density ? (double)density[o] : c->rho, cs = sound_speed ? (double)sound_speed[o] : c0;
-            iz[o] = (float)(1e-4 / (2.0 * rho * cs));
-        }
+        const std::vector<float> iz = olxmed::impedance_volume(density, c->rho, sound_speed, c0, 0, nvox);
         rc = c->d_pm_inv2z.reserve(c, nvox);
         if (rc) return rc;
         HIPCHK(c, hipMemcpy(c->d_pm_inv2z, iz.data(), sizeof(float) * nvox, hipMemcpyHostToDevice));
@@ -2971,9 +2798,8 @@ int olx_thermal_plan(olx_ctx* c, const olx_grid* g, const float* density, const 
         const size_t nvox = (size_t)g->n[0] * g->n[1] * g->n[2];
         for (int q = 0; q < 4; ++q) {
             if (!vol[q]) continue;
-            for (size_t o = 0; o < nvox; ++o)
-                if (!std::isfinite(vol[q][o]) || !(q == 3 ? vol[q][o] >= 0.f : vol[q][o] > 0.f))
-                    return fail(c, OLX_EINVAL, "olx_thermal_plan: %s must be finite and %s (voxel %zu)", what[q], q == 3 ? ">= 0" : "> 0", o);
+            const size_t o = olxmed::first_bad(vol[q], nvox, q == 3 ? olxmed::NON_NEGATIVE : olxmed::POSITIVE);
+            if (o < nvox) return fail(c, OLX_EINVAL, "olx_thermal_plan: %s must be finite and %s (voxel %zu)", what[q], q == 3 ? ">= 0" : "> 0", o);
         }
     }
     HIPCHK(c, hipSetDevice(c->device));

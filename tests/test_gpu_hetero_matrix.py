@@ -145,7 +145,7 @@ def medium(case):
 
 
 def nontrivial_planes(cvol, avol):
-    """olx_field_set_medium's rule: a plane with any voxel whose float32 sound speed != c_ref or float32 attenuation != 0."""
+    """olxmed::scan_planes' rule: a plane with any voxel whose float32 sound speed != c_ref or float32 attenuation != 0."""
     return [k for k in range(cvol.shape[2]) if (np.float32(cvol[:, :, k]).astype(np.float64) != C).any() or (np.float32(avol[:, :, k]) != 0).any()]
 
 
