@@ -458,6 +458,16 @@ int olx_fullwave_sources_elements(olx_ctx *ctx, int n_entries, const long long *
  * olx_fullwave_run starts at step 0; a lock-in is cleared as by a source call); the entry table stays on the device.  OLX_ESTATE
  * when the last source call was not olx_fullwave_sources_elements. */
 int olx_fullwave_drive(olx_ctx *ctx, const double *A, const double *tau);
+/* The layer model of the plan (DESIGN.md section 2 "full-wave model: split layers", section 5.19): 0 = the multiplicative sponge of
+ * olx_fullwave_plan, 1 = split perfectly matched layers.  With sigma_a(d) = pml_alpha (c_ref / h_a) (d / pml_size)^4 of the plan, d_c the
+ * depth of a voxel's centre and d_f that of its + face [voxels], r_a = exp(-sigma_a(d_c) dt / 2) and s_a = exp(-sigma_a(d_f) dt / 2)
+ * (double, rounded once to float), the split model steps v_a <- s_a (s_a v_a - b_a d+_a p) in every voxel and, in a layer voxel
+ * (d_c > 0 on any axis), three components p_a <- ga (r_a (r_a p_a - (kp d-_a v_a) / h_a)) with p = (p_x + p_y) + p_z; interior voxels
+ * and every record are the sponge's with D = 1.  Sources must then lie on interior voxels: the source calls answer OLX_EINVAL for an
+ * entry on a layer voxel.  Call it after olx_fullwave_plan; it clears the sources, the lock-in and the run as a source call does, and
+ * every olx_fullwave_plan returns to the sponge.  The first split model creates three more [voxels] float volumes.  OLX_ESTATE without
+ * a plan, OLX_EINVAL for any other model. */
+int olx_fullwave_layers(olx_ctx *ctx, int model);
 
 /* Eikonal travel times (DESIGN.md section 2 "Eikonal", kernel 6): first-arrival times T [s] from the point source_m through the sound
  * speed of `grid` ([nx * ny * nz] floats, C order; NULL = c_uniform everywhere, and no volume is streamed), refraction included.

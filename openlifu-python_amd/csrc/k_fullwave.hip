@@ -21,6 +21,10 @@
 //             geometry); the sources then stand in element-factored form -- entries (voxel, element, amp_{e,m}) and a drive table s_e(n) filled
 //             by ONE launch of fullwave_drive_k -- and fullwave_inject_elem_k takes the place of inject: p[vox] += (float)(amp_{e,m} s_e(n))
 // D = d_x[i] d_y[j] d_z[k] from three 1-D tables (1 in the interior, the absorbing layers' decay per step outside it).
+// Split layers (opt-in, olx_fullwave_layers; DESIGN.md section 2 "full-wave model: split layers", section 5.19): two 1-D tables per axis take the place
+// of d -- s_a (face depth) for the velocity launch fullwave_vel_k<UNI, SPLIT>, v_a <- s_a (s_a v_a - b_a d+_a p), and r_a (centre depth) for the
+// pressure launch, a kernel of its own (fullwave_pres_split_k; fullwave_pres_k is untouched), which in a layer voxel advances three components p_a <- ga (r_a (r_a p_a - (kp d-_a v_a) / h_a)) and stores p~ = (p_x + p_y) + p_z;
+// an interior voxel takes the update above with D = 1 and touches no component.
 // A heterogeneous medium streams five coefficient volumes formed once by fullwave_pack_k (b_x, b_y, b_z for the velocity launch, kp, ga
 // for the pressure launch); the uniform instantiation (UNI) streams none of them.
 #include "k_types.hip.h"
@@ -177,7 +181,7 @@ __global__ __launch_bounds__(FW_BLOCK) void fullwave_aperture_k(const FullwaveAp
     if (OLX_IN(E.off + t, total, 29)) W[E.off + t] = acc / (double)(E.nw * E.nl);
 }
 
-template <bool UNI>
+template <bool UNI, bool SPLIT = false>
 __global__ __launch_bounds__(FW_BLOCK) void fullwave_vel_k(const float* __restrict__ p, float* __restrict__ vx, float* __restrict__ vy, float* __restrict__ vz,
                                                            const float* __restrict__ bx, const float* __restrict__ by, const float* __restrict__ bz,
                                                            const float* __restrict__ dtab, const FullwaveParams P) {
@@ -186,15 +190,29 @@ __global__ __launch_bounds__(FW_BLOCK) void fullwave_vel_k(const float* __restri
     int i, j, k;
     fw_ijk((unsigned)v, P, i, j, k);
     const long long pl = (long long)P.ny * P.nz, nz = P.nz;
-    const float D = fw_layer(dtab, P, i, j, k);
+    float D = 1.f, sx = 1.f, sy = 1.f, sz = 1.f;
+    if constexpr (SPLIT) {      // dtab is s_x | s_y | s_z: each component is damped by its own axis only
+        const int n = P.nx + P.ny + P.nz;
+        if (OLX_IN(i, n, 30) && OLX_IN(P.nx + j, n, 30) && OLX_IN(P.nx + P.ny + k, n, 30)) { sx = dtab[i]; sy = dtab[P.nx + j]; sz = dtab[P.nx + P.ny + k]; }
+    } else {
+        D = fw_layer(dtab, P, i, j, k);
+    }
     const float pc = p[v];
     const float dpx = FW_C1 * (fw_ld(p, i + 1 < P.nx, v + pl, P.vox, 6) - pc) - FW_C2 * (fw_ld(p, i + 2 < P.nx, v + 2 * pl, P.vox, 6) - fw_ld(p, i > 0, v - pl, P.vox, 6));
     const float dpy = FW_C1 * (fw_ld(p, j + 1 < P.ny, v + nz, P.vox, 7) - pc) - FW_C2 * (fw_ld(p, j + 2 < P.ny, v + 2 * nz, P.vox, 7) - fw_ld(p, j > 0, v - nz, P.vox, 7));
     const float dpz = FW_C1 * (fw_ld(p, k + 1 < P.nz, v + 1, P.vox, 8) - pc) - FW_C2 * (fw_ld(p, k + 2 < P.nz, v + 2, P.vox, 8) - fw_ld(p, k > 0, v - 1, P.vox, 8));
     const float cbx = UNI ? P.bx0 : bx[v], cby = UNI ? P.by0 : by[v], cbz = UNI ? P.bz0 : bz[v];
-    vx[v] = D * (vx[v] - cbx * dpx);
-    vy[v] = D * (vy[v] - cby * dpy);
-    vz[v] = D * (vz[v] - cbz * dpz);
+    if constexpr (SPLIT) {
+        // the fused multiply-add is spelled out: s_a v_a is rounded first and b_a d+ p enters unrounded, so that s_a = 1 gives the bits of the
+        // update below (left to the compiler, s v - b dp may contract around the other product)
+        vx[v] = sx * fmaf(-cbx, dpx, sx * vx[v]);
+        vy[v] = sy * fmaf(-cby, dpy, sy * vy[v]);
+        vz[v] = sz * fmaf(-cbz, dpz, sz * vz[v]);
+    } else {
+        vx[v] = D * (vx[v] - cbx * dpx);
+        vy[v] = D * (vy[v] - cby * dpy);
+        vz[v] = D * (vz[v] - cbz * dpz);
+    }
 }
 
 // the lock-in arguments of the pressure launch; empty, and last, without LOCK: those instantiations keep their argument layout
@@ -218,6 +236,65 @@ __global__ __launch_bounds__(FW_BLOCK) void fullwave_pres_k(float* __restrict__ 
     const float div = dvx * P.ihx + dvy * P.ihy + dvz * P.ihz;
     const float ckp = UNI ? P.kp0 : kp[v], g = D * (UNI ? P.ga0 : ga[v]);
     const float pn = g * (p[v] - ckp * div);
+    p[v] = pn;
+    pmax[v] = fmaxf(pmax[v], pn);
+    pmin[v] = fmaxf(pmin[v], -pn);
+    if (PII) psq[v] = fmaf(pn, pn, psq[v]);
+    if constexpr (LOCK) {
+        float* __restrict__ lc = L.c;
+        float* __restrict__ ls = L.s;
+        lc[v] = fmaf(pn, L.cosf_n, lc[v]);
+        ls[v] = fmaf(pn, L.sinf_n, ls[v]);
+    }
+}
+
+// the split layers' arguments of the pressure launch: the component volumes, their extent and the layers' thickness
+struct FwSplit { float *px, *py, *pz; long long ext; int pml; };
+
+// d- of one axis as the gfx950 code of fullwave_pres_k rounds it: C2 (c - d) on its own, then one fused multiply-add
+__device__ __forceinline__ float fw_dminus(float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+    return fmaf(a - b, FW_C1, -(FW_C2 * (c - d)));
+}
+
+// the pressure launch of the split layers, a kernel of its own beside fullwave_pres_k (which stays as it is).  rtab is r_x | r_y | r_z.  Every rounding is
+// spelled out (no contraction is left to the compiler): an interior voxel takes the roundings that the gfx950 code of fullwave_pres_k takes with D = 1 --
+// div = fma(dvx, 1/h_x, dvy 1/h_y) + dvz 1/h_z, p~ = ga (p - kp div) with kp div and the difference rounded on their own -- so a run that never
+// reaches a layer has the sponge's bits in the interior; a layer voxel advances its three components and does not read p.
+template <bool UNI, bool PII, bool LOCK>
+__global__ __launch_bounds__(FW_BLOCK) void fullwave_pres_split_k(float* __restrict__ p, const float* __restrict__ vx, const float* __restrict__ vy,
+                                                                  const float* __restrict__ vz, const float* __restrict__ kp, const float* __restrict__ ga,
+                                                                  const float* __restrict__ rtab, float* __restrict__ pmax, float* __restrict__ pmin,
+                                                                  float* __restrict__ psq, const FullwaveParams P, const FwLock<LOCK> L, const FwSplit Q) {
+#pragma clang fp contract(off)
+    const long long v = (long long)blockIdx.x * FW_BLOCK + threadIdx.x;
+    if (v >= P.vox || !OLX_IN(v, P.vox, 9)) return;
+    int i, j, k;
+    fw_ijk((unsigned)v, P, i, j, k);
+    const long long pl = (long long)P.ny * P.nz, nz = P.nz;
+    const float dvx = fw_dminus(vx[v], fw_ld(vx, i > 0, v - pl, P.vox, 10), fw_ld(vx, i + 1 < P.nx, v + pl, P.vox, 10), fw_ld(vx, i > 1, v - 2 * pl, P.vox, 10));
+    const float dvy = fw_dminus(vy[v], fw_ld(vy, j > 0, v - nz, P.vox, 11), fw_ld(vy, j + 1 < P.ny, v + nz, P.vox, 11), fw_ld(vy, j > 1, v - 2 * nz, P.vox, 11));
+    const float dvz = fw_dminus(vz[v], fw_ld(vz, k > 0, v - 1, P.vox, 12), fw_ld(vz, k + 1 < P.nz, v + 1, P.vox, 12), fw_ld(vz, k > 1, v - 2, P.vox, 12));
+    const float ckp = UNI ? P.kp0 : kp[v], g = UNI ? P.ga0 : ga[v];
+    float pn;
+    if (i < Q.pml || i >= P.nx - Q.pml || j < Q.pml || j >= P.ny - Q.pml || k < Q.pml || k >= P.nz - Q.pml) {
+        // the components live in the layer voxels only: an interior voxel never reads or writes them
+        const int n = P.nx + P.ny + P.nz;
+        float rx = 1.f, ry = 1.f, rz = 1.f;
+        if (OLX_IN(i, n, 30) && OLX_IN(P.nx + j, n, 30) && OLX_IN(P.nx + P.ny + k, n, 30)) { rx = rtab[i]; ry = rtab[P.nx + j]; rz = rtab[P.nx + P.ny + k]; }
+        float* __restrict__ qx = Q.px;
+        float* __restrict__ qy = Q.py;
+        float* __restrict__ qz = Q.pz;
+        if (!OLX_IN(v, Q.ext, 31)) return;
+        const float ax = g * (rx * (rx * qx[v] - (ckp * dvx) * P.ihx));
+        const float ay = g * (ry * (ry * qy[v] - (ckp * dvy) * P.ihy));
+        const float az = g * (rz * (rz * qz[v] - (ckp * dvz) * P.ihz));
+        qx[v] = ax; qy[v] = ay; qz[v] = az;
+        pn = (ax + ay) + az;
+    } else {
+        const float div = fmaf(dvx, P.ihx, dvy * P.ihy) + dvz * P.ihz;
+        pn = g * (p[v] - ckp * div);
+    }
     p[v] = pn;
     pmax[v] = fmaxf(pmax[v], pn);
     pmin[v] = fmaxf(pmin[v], -pn);
@@ -283,6 +360,26 @@ static void fw_launch_pres(olx_ctx* c, bool pii, bool lock, float cosf_n, float 
     }
 }
 
+template <bool UNI>
+static void fw_launch_pres_split(olx_ctx* c, bool pii, bool lock, float cosf_n, float sinf_n, const float* kp, const float* ga) {
+    const FullwaveParams& P = c->fw;
+    const dim3 grid = fw_grid(P), block(FW_BLOCK);
+    float* p = c->d_fw_p;
+    const float *vx = c->d_fw_v[0], *vy = c->d_fw_v[1], *vz = c->d_fw_v[2], *rtab = c->d_fw_rtab;
+    float *pmax = c->d_fw_pmax, *pmin = c->d_fw_pmin, *psq = pii ? (float*)c->d_fw_psq : nullptr;
+    const FwLock<true> L{c->d_fw_lc, c->d_fw_ls, cosf_n, sinf_n};
+    long long ext = (long long)c->d_fw_pc[0].capacity();
+    for (const DevBuf<float>& b : c->d_fw_pc) ext = std::min(ext, (long long)b.capacity());
+    const FwSplit Q{c->d_fw_pc[0], c->d_fw_pc[1], c->d_fw_pc[2], ext, c->fw_pml};
+    if (lock) {
+        if (pii) hipLaunchKernelGGL((fullwave_pres_split_k<UNI, true, true>), grid, block, 0, c->stream, p, vx, vy, vz, kp, ga, rtab, pmax, pmin, psq, P, L, Q);
+        else hipLaunchKernelGGL((fullwave_pres_split_k<UNI, false, true>), grid, block, 0, c->stream, p, vx, vy, vz, kp, ga, rtab, pmax, pmin, psq, P, L, Q);
+    } else {
+        if (pii) hipLaunchKernelGGL((fullwave_pres_split_k<UNI, true, false>), grid, block, 0, c->stream, p, vx, vy, vz, kp, ga, rtab, pmax, pmin, psq, P, FwLock<false>{}, Q);
+        else hipLaunchKernelGGL((fullwave_pres_split_k<UNI, false, false>), grid, block, 0, c->stream, p, vx, vy, vz, kp, ga, rtab, pmax, pmin, psq, P, FwLock<false>{}, Q);
+    }
+}
+
 void olx_fullwave_step(olx_ctx* c, int step, bool pii) {
     const FullwaveParams& P = c->fw;
     const FullwaveSource& S = c->fw_src;
@@ -295,7 +392,8 @@ void olx_fullwave_step(olx_ctx* c, int step, bool pii) {
                            c->fw_entries, P.vox, step);
     const dim3 grid = fw_grid(P), block(FW_BLOCK);
     float *vx = c->d_fw_v[0], *vy = c->d_fw_v[1], *vz = c->d_fw_v[2];
-    const float* dtab = c->d_fw_dtab;
+    const bool split = c->fw_layers == 1;
+    const float* dtab = split ? c->d_fw_stab : c->d_fw_dtab;
     // the lock-in of a step inside the window: theta_n = 2 pi frac(f0 t_n), t_n = (n + 1) dt, in fp64
     const bool lock = c->fw_lock && step >= c->fw_lock_w0 && step < c->fw_lock_w0 + c->fw_lock_nw;
     double cos_n = 0.0, sin_n = 0.0;
@@ -306,12 +404,22 @@ void olx_fullwave_step(olx_ctx* c, int step, bool pii) {
     }
     const bool lock_vol = lock && c->fw_lock_vol;
     if (c->fw_uniform) {
-        hipLaunchKernelGGL(fullwave_vel_k<true>, grid, block, 0, c->stream, p, vx, vy, vz, nullptr, nullptr, nullptr, dtab, P);
-        fw_launch_pres<true>(c, pii, lock_vol, (float)cos_n, (float)sin_n, nullptr, nullptr);
+        if (split) {
+            hipLaunchKernelGGL((fullwave_vel_k<true, true>), grid, block, 0, c->stream, p, vx, vy, vz, nullptr, nullptr, nullptr, dtab, P);
+            fw_launch_pres_split<true>(c, pii, lock_vol, (float)cos_n, (float)sin_n, nullptr, nullptr);
+        } else {
+            hipLaunchKernelGGL(fullwave_vel_k<true>, grid, block, 0, c->stream, p, vx, vy, vz, nullptr, nullptr, nullptr, dtab, P);
+            fw_launch_pres<true>(c, pii, lock_vol, (float)cos_n, (float)sin_n, nullptr, nullptr);
+        }
     } else {
         const float *bx = c->d_fw_coef[0], *by = c->d_fw_coef[1], *bz = c->d_fw_coef[2], *kp = c->d_fw_coef[3], *ga = c->d_fw_coef[4];
-        hipLaunchKernelGGL(fullwave_vel_k<false>, grid, block, 0, c->stream, p, vx, vy, vz, bx, by, bz, dtab, P);
-        fw_launch_pres<false>(c, pii, lock_vol, (float)cos_n, (float)sin_n, kp, ga);
+        if (split) {
+            hipLaunchKernelGGL((fullwave_vel_k<false, true>), grid, block, 0, c->stream, p, vx, vy, vz, bx, by, bz, dtab, P);
+            fw_launch_pres_split<false>(c, pii, lock_vol, (float)cos_n, (float)sin_n, kp, ga);
+        } else {
+            hipLaunchKernelGGL(fullwave_vel_k<false>, grid, block, 0, c->stream, p, vx, vy, vz, bx, by, bz, dtab, P);
+            fw_launch_pres<false>(c, pii, lock_vol, (float)cos_n, (float)sin_n, kp, ga);
+        }
     }
     if (c->fw_npts > 0)
         hipLaunchKernelGGL(fullwave_trace_k, dim3((c->fw_npts + 255) / 256), dim3(256), 0, c->stream, p, c->d_fw_pts, c->fw_npts, P.vox,

@@ -3029,6 +3029,7 @@ int olx_fullwave_plan(olx_ctx* c, const olx_grid* g, const float* sound_speed, c
     P.c0 = (float)sound_speed0; P.rho0 = (float)density0; P.alpha0 = (float)absorption0;
     c->fw_uniform = !sound_speed && !density && !absorption;
     c->fw_dt = dt; c->fw_dt_max = dt_max; c->fw_elem = false;
+    c->fw_layers = 0; c->fw_pml = pml_size; c->fw_pml_alpha = pml_alpha; c->fw_c_ref = c_ref;   // every plan returns to the sponge (olx_fullwave_layers)
     for (int a = 0; a < 3; ++a) { c->fw_h[a] = g->spacing[a]; c->fw_origin[a] = g->origin[a]; }
     for (DevBuf<float>* b : {&c->d_fw_p, &c->d_fw_v[0], &c->d_fw_v[1], &c->d_fw_v[2], &c->d_fw_pmax, &c->d_fw_pmin}) { int rc = b->reserve(c, vox); if (rc) return rc; }
     // the layers' decay per step: d_a[i] = exp(-pml_alpha (c_ref / h_a) (depth / pml_size)^4 dt), depth = voxels into the layer (0 inside)
@@ -3071,6 +3072,49 @@ int olx_fullwave_plan(olx_ctx* c, const olx_grid* g, const float* sound_speed, c
     return OLX_OK;
 }
 
+int olx_fullwave_layers(olx_ctx* c, int model) {
+    if (!c) return OLX_EINVAL;
+    if (!c->fw_planned) return fail(c, OLX_ESTATE, "olx_fullwave_layers: no full-wave plan");
+    if (model != 0 && model != 1) return fail(c, OLX_EINVAL, "olx_fullwave_layers: model must be 0 (sponge) or 1 (split layers), got %d", model);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // as a source call: the sources, the lock-in and the run state go
+    c->fw_sourced = false; c->fw_next = -1; c->fw_elem = false;
+    c->fw_lock = false; c->fw_lock_vol = false; c->fw_lock_nrec = 0; c->fw_lock_entries = 0;
+    c->fw_steps = 0; c->fw_npts = 0; c->fw_entries = 0;
+    c->fw_layers = 0;
+    if (model == 0) return OLX_OK;
+    // r_a[i] = exp(-sigma_a(d_c(i)) dt / 2), s_a[i] = exp(-sigma_a(d_f(i)) dt / 2), sigma_a(d) = pml_alpha (c_ref / h_a) (d / pml_size)^4: the depth of the
+    // voxel's centre and of its + face, in voxels; formed in fp64 and rounded once
+    const FullwaveParams& P = c->fw;
+    const int ng[3] = {P.nx, P.ny, P.nz}, ntab = P.nx + P.ny + P.nz, pml = c->fw_pml;
+    std::vector<float> rt(ntab), st(ntab);
+    for (int a = 0, at = 0; a < 3; at += ng[a], ++a)
+        for (int i = 0; i < ng[a]; ++i) {
+            const double last = (double)(ng[a] - 1 - pml);
+            const double dc = std::max(std::max((double)pml - i, i - last), 0.0), df = std::max(std::max((double)pml - (i + 0.5), (i + 0.5) - last), 0.0);
+            const double xc = pml > 0 ? dc / pml : 0.0, xf = pml > 0 ? df / pml : 0.0;
+            const double k = c->fw_pml_alpha * (c->fw_c_ref / c->fw_h[a]);
+            rt[at + i] = (float)std::exp(-(k * (xc * xc * xc * xc)) * c->fw_dt / 2);
+            st[at + i] = (float)std::exp(-(k * (xf * xf * xf * xf)) * c->fw_dt / 2);
+        }
+    int rc = c->d_fw_rtab.reserve(c, ntab);
+    if (!rc) rc = c->d_fw_stab.reserve(c, ntab);
+    for (DevBuf<float>& b : c->d_fw_pc) if (!rc) rc = b.reserve(c, (size_t)P.vox);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpy(c->d_fw_rtab, rt.data(), sizeof(float) * ntab, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_fw_stab, st.data(), sizeof(float) * ntab, hipMemcpyHostToDevice));
+    c->fw_layers = 1;
+    return OLX_OK;
+}
+
+// the split model takes sources on interior voxels only: true when linear voxel `at` lies in a layer
+static bool fw_in_layer(const olx_ctx* c, long long at) {
+    const FullwaveParams& P = c->fw;
+    const int pml = c->fw_pml, k = (int)(at % P.nz), j = (int)((at / P.nz) % P.ny), i = (int)(at / ((long long)P.nz * P.ny));
+    return i < pml || i >= P.nx - pml || j < pml || j >= P.ny - pml || k < pml || k >= P.nz - pml;
+}
+
 int olx_fullwave_sources(olx_ctx* c, int n_entries, const long long* voxels, const double* amplitude, const double* tau_s, double freq, double cycles,
                          double ramp_cycles, int n_steps, int n_points, const long long* points) {
     if (!c) return OLX_EINVAL;
@@ -3081,6 +3125,7 @@ int olx_fullwave_sources(olx_ctx* c, int n_entries, const long long* voxels, con
     if (n_steps < 1 || n_points < 0 || (n_points > 0 && !points)) return fail(c, OLX_EINVAL, "olx_fullwave_sources: n_steps < 1 or bad points");
     for (int e = 0; e < n_entries; ++e) {
         if (voxels[e] < 0 || voxels[e] >= c->fw.vox) return fail(c, OLX_EINVAL, "olx_fullwave_sources: entry %d: voxel %lld outside the grid of %lld voxels", e, voxels[e], c->fw.vox);
+        if (c->fw_layers == 1 && fw_in_layer(c, voxels[e])) return fail(c, OLX_EINVAL, "olx_fullwave_sources: entry %d: voxel %lld lies in a layer (the split layers take sources on interior voxels only)", e, voxels[e]);
         if (!std::isfinite(amplitude[e]) || !std::isfinite(tau_s[e])) return fail(c, OLX_EINVAL, "olx_fullwave_sources: entry %d: amplitude and delay must be finite", e);
     }
     for (int p = 0; p < n_points; ++p)
@@ -3136,6 +3181,7 @@ int olx_fullwave_sources_elements(olx_ctx* c, int n_entries, const long long* vo
         if (!std::isfinite(A[e]) || !std::isfinite(tau_s[e])) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: element %d: A and delay must be finite", e);
     for (int q = 0; q < n_entries; ++q) {
         if (voxels[q] < 0 || voxels[q] >= c->fw.vox) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: entry %d: voxel %lld outside the grid of %lld voxels", q, voxels[q], c->fw.vox);
+        if (c->fw_layers == 1 && fw_in_layer(c, voxels[q])) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: entry %d: voxel %lld lies in a layer (the split layers take sources on interior voxels only)", q, voxels[q]);
         if (elements[q] < 0 || elements[q] >= n_el) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: entry %d: element %d outside [0, %d)", q, elements[q], n_el);
         if (!std::isfinite(amplitude[q])) return fail(c, OLX_EINVAL, "olx_fullwave_sources_elements: entry %d: amplitude must be finite", q);
     }
@@ -3293,6 +3339,8 @@ int olx_fullwave_run(olx_ctx* c, int first_step, int n_steps, int accumulate_psq
         for (float* p : {(float*)c->d_fw_p, (float*)c->d_fw_v[0], (float*)c->d_fw_v[1], (float*)c->d_fw_v[2], (float*)c->d_fw_pmax, (float*)c->d_fw_pmin})
             HIPCHK(c, hipMemsetAsync(p, 0, sizeof(float) * vox, c->stream));
         if (pii) HIPCHK(c, hipMemsetAsync(c->d_fw_psq, 0, sizeof(float) * vox, c->stream));
+        if (c->fw_layers == 1)
+            for (DevBuf<float>& b : c->d_fw_pc) HIPCHK(c, hipMemsetAsync(b, 0, sizeof(float) * vox, c->stream));
         c->fw_pii = pii;
         if (c->fw_lock && c->fw_lock_vol)
             for (float* p : {(float*)c->d_fw_lc, (float*)c->d_fw_ls}) HIPCHK(c, hipMemsetAsync(p, 0, sizeof(float) * vox, c->stream));

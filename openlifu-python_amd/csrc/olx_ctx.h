@@ -191,6 +191,11 @@ struct olx_ctx {
     DevBuf<float> d_fw_p, d_fw_v[3], d_fw_pmax, d_fw_pmin, d_fw_psq;   // [voxels] state p, v_x / v_y / v_z; p_max, p_min; sum p~^2 (created by the first run that asks for it)
     DevBuf<float> d_fw_coef[5];               // [voxels] b_x, b_y, b_z, kp, ga of a heterogeneous medium (not created for a uniform one)
     DevBuf<float> d_fw_dtab;                  // [nx + ny + nz] the layers' per-step decay d_x | d_y | d_z
+    // split layers (olx_fullwave_layers; every olx_fullwave_plan returns to the sponge): the plan's layer arguments, the two tables per axis, and the
+    // pressure components of the layer voxels, stored for the whole padded grid (an interior voxel's entries are never read or written)
+    int fw_layers = 0, fw_pml = 0; double fw_pml_alpha = 0, fw_c_ref = 0;
+    DevBuf<float> d_fw_rtab, d_fw_stab;       // [nx + ny + nz] r_x | r_y | r_z (centre depth), s_x | s_y | s_z (+ face depth); created by the first split model
+    DevBuf<float> d_fw_pc[3];                 // [voxels] p_x, p_y, p_z; created by the first split model
     bool fw_sourced = false; FullwaveSource fw_src{}; int fw_entries = 0, fw_steps = 0;
     DevBuf<long long> d_fw_svox; DevBuf<int> d_fw_srow; DevBuf<double> d_fw_samp, d_fw_stau;   // CSR source table: voxel per row, row offsets, entries in table order
     // element-factored sources (olx_fullwave_sources_elements): the CSR table above holds amp_{e,m}, d_fw_sel the element of each entry, and the drive

@@ -46,7 +46,7 @@ SYMBOLS = [
     "olx_pii_post", "olx_pii_fetch_weighted", "olx_pii_fetch_max", "olx_pii_upload", "olx_thermal_source_pii",
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
     "olx_fullwave_plan", "olx_fullwave_sources", "olx_fullwave_run", "olx_fullwave_fetch", "olx_fullwave_lockin", "olx_fullwave_fetch_lockin",
-    "olx_fullwave_apertures", "olx_fullwave_sources_elements", "olx_fullwave_drive",
+    "olx_fullwave_apertures", "olx_fullwave_sources_elements", "olx_fullwave_drive", "olx_fullwave_layers",
     "olx_eikonal_solve", "olx_eikonal_sample", "olx_eikonal_fetch",
     "olx_bf_set_medium", "olx_bf_solve_medium",
     "olx_bf_set_attenuation", "olx_bf_solve_compensated",
@@ -179,6 +179,7 @@ def load(require_gpu: bool = True):
         lib.olx_fullwave_sources_elements.argtypes = [vp, c_int, POINTER(ctypes.c_longlong), POINTER(c_int), dp, c_int, dp, dp, c_double, c_double, c_double,
                                                       c_int, c_int, POINTER(ctypes.c_longlong)]
         lib.olx_fullwave_drive.argtypes = [vp, dp, dp]
+        lib.olx_fullwave_layers.argtypes = [vp, c_int]
         lib.olx_eikonal_solve.argtypes = [vp, POINTER(OlxGrid), fp, c_double, dp, c_double, c_int, POINTER(c_int)]
         lib.olx_eikonal_sample.argtypes = [vp, c_int, POINTER(c_int), POINTER(ctypes.c_longlong), dp, dp]
         lib.olx_eikonal_fetch.argtypes = [vp, fp]
@@ -760,9 +761,14 @@ class Context:
         return rise, cem, tr
 
     # ---- full-wave model (kernel 5) ----------------------------------------------------------------------------------------
-    def fullwave_plan(self, spacing_m, n, sound_speed, density, absorption, c_ref, pml_size, pml_alpha, dt) -> float:
+    FULLWAVE_LAYER_MODELS = ("sponge", "pml")
+
+    def fullwave_plan(self, spacing_m, n, sound_speed, density, absorption, c_ref, pml_size, pml_alpha, dt, layer_model="sponge") -> float:
         """Padded grid and medium of the full-wave model; each medium argument is a float (uniform) or a [nx, ny, nz] volume
-        (absorption in Np/m).  Returns the stability bound dt_max [s]."""
+        (absorption in Np/m).  ``layer_model`` "pml" selects the split layers (``fullwave_layers``) on the new plan.  Returns the
+        stability bound dt_max [s]."""
+        if layer_model not in self.FULLWAVE_LAYER_MODELS:
+            raise ValueError(f"layer_model must be one of {self.FULLWAVE_LAYER_MODELS}, got {layer_model!r}")
         shape = tuple(int(v) for v in n)
         g = OlxGrid()
         for a in range(3):
@@ -780,7 +786,15 @@ class Context:
         self._chk(self._lib.olx_fullwave_plan(self._h, ctypes.byref(g), *[_fptr(a) for a in vols], *scal, float(c_ref), int(pml_size),
                                               float(pml_alpha), float(dt), ctypes.byref(dt_max)))
         self._fw_shape = shape
+        if layer_model == "pml":
+            self.fullwave_layers(1)
         return float(dt_max.value)
+
+    def fullwave_layers(self, model: int):
+        """The layer model of the plan: 0 = sponge, 1 = split layers.  Clears the sources, the lock-in and the run."""
+        self._chk(self._lib.olx_fullwave_layers(self._h, int(model)))
+        self._fw_steps = self._fw_npts = 0
+        self._fw_lock_vol, self._fw_lock_nrec = False, 0
 
     def fullwave_sources(self, voxels, amplitude, tau, freq, cycles, ramp_cycles, n_steps, points=None):
         """Source table (linear voxel of the padded grid, amplitude, delay per entry) and trace voxels."""

@@ -12,7 +12,9 @@ far the rounding was from a wrap; below ``TIE_WARN`` a warning is logged.  Witho
 
 ``element_model="point"`` (the default) samples p trilinearly at each element's centre; ``"aperture"`` makes Z_e the average of p over
 the element's rectangle (``upsampling_rate`` quadrature points per smallest voxel edge, DESIGN.md section 2 "full-wave model:
-apertures"), so an element a wavelength wide hears an oblique wave with its directivity, in amplitude and in phase."""
+apertures"), so an element a wavelength wide hears an oblique wave with its directivity, in amplitude and in phase.
+``layer_model="pml"`` runs the listening run with split perfectly matched layers in place of the sponge (DESIGN.md section 2 "full-wave
+model: split layers"): the choice for a grid cropped narrowly around the beam."""
 from __future__ import annotations
 
 import logging
@@ -54,6 +56,7 @@ class TimeReversal(DelayMethod):
     anchor: str = "straight_ray"
     element_model: str = "point"     # "aperture": the elements listen with the averages over their rectangles (sim/fullwave.py)
     upsampling_rate: int = 5         # quadrature points per smallest voxel edge of the "aperture" model
+    layer_model: str = "sponge"      # "pml": the run's absorbing layers are split perfectly matched layers (sim/fullwave.py)
 
     def __post_init__(self):
         if isinstance(self.c0, bool) or not isinstance(self.c0, (int, float)):
@@ -74,15 +77,18 @@ class TimeReversal(DelayMethod):
         self.pml_size = int(self.pml_size)
         if self.anchor not in ANCHORS:
             raise ValueError(f"TimeReversal: anchor must be one of {ANCHORS}, got {self.anchor!r}")
-        from ...sim.fullwave import checked_element_model      # (sim imports bf through plan: resolve at call time)
+        from ...sim.fullwave import checked_element_model, checked_layer_model      # (sim imports bf through plan: resolve at call time)
         self.element_model, self.upsampling_rate = checked_element_model(self.element_model, self.upsampling_rate)
+        self.layer_model = checked_layer_model(self.layer_model)
 
     def to_dict(self):
-        """The tagged dict; the element model is written only when it is not the default, so the stored form of a method that does not use it
-        is what it was before the option existed (``from_dict`` fills the defaults in)."""
+        """The tagged dict; the element model and the layer model are written only when they are not the defaults, so the stored form of a
+        method that does not use them is what it was before the options existed (``from_dict`` fills the defaults in)."""
         d = super().to_dict()
         if self.element_model == "point":
             del d["element_model"], d["upsampling_rate"]
+        if self.layer_model == "sponge":
+            del d["layer_model"]
         return d
 
     @staticmethod
@@ -118,6 +124,8 @@ class TimeReversal(DelayMethod):
         listen = {"receivers_m": pos}
         if self.element_model == "aperture":      # Z_e is the average of p over the element's rectangle: sum_m W_e(m) p(m)
             listen = {"receiver_apertures": aperture_geometry(arr, grid_from_coords(params.coords)[1], self.upsampling_rate, transform=transform)}
+        if self.layer_model != "sponge":
+            listen["layer_model"] = self.layer_model
         runs = []
         for f in range(foci.shape[0]):
             runs.append(steady_state_run(params, foci[f][None], [1.0], [0.0], frequency, cfl=self.cfl, lockin_cycles=self.lockin_cycles,

@@ -510,12 +510,13 @@ class Engine:
 
     # ---- kernel 5 -----------------------------------------------------------------------------
     def fullwave(self, spacing_m, n_padded, medium, c_ref, pml_size, pml_alpha, dt, n_steps, sources, freq, cycles, ramp_cycles=0.0,
-                 psq=False, points=None):
+                 psq=False, points=None, layer_model="sponge"):
         """Full-wave model (sim/fullwave.py, kernel 5) on the padded grid -> (p_max, p_min, sum p^2 | None, traces [n_steps, P]), float32.
+        ``layer_model`` "pml" runs the split layers (olx_fullwave_layers; sources on interior voxels only).
         ``medium = (sound_speed, density, absorption [Np/m])``, each a float or a padded [nx, ny, nz] volume; ``sources = (voxel, amplitude,
         tau)`` per entry, or the element-factored dict of ``_fullwave_sources``; voxels and ``points`` as linear indices of the padded grid.  The field / aggregate / thermal volumes and every lazy
         array over them are left as they are."""
-        self.ctx.fullwave_plan(spacing_m, n_padded, *medium, c_ref=c_ref, pml_size=pml_size, pml_alpha=pml_alpha, dt=dt)
+        self.ctx.fullwave_plan(spacing_m, n_padded, *medium, c_ref=c_ref, pml_size=pml_size, pml_alpha=pml_alpha, dt=dt, layer_model=layer_model)
         self._fullwave_sources(sources, spacing_m, medium, dt, freq=freq, cycles=cycles, ramp_cycles=ramp_cycles, n_steps=n_steps, points=points)
         self.ctx.fullwave_run(0, n_steps, psq=psq)
         return self.ctx.fullwave_fetch()
@@ -543,12 +544,12 @@ class Engine:
         return self.ctx.fullwave_sources_elements(vox, el, amp, sources["A"], sources["tau"], freq=freq, **kw)
 
     def fullwave_steady(self, spacing_m, n_padded, medium, c_ref, pml_size, pml_alpha, dt, n_steps, sources, freq, cycles, ramp_cycles, window,
-                        volume=True, receivers=None):
+                        volume=True, receivers=None, layer_model="sponge"):
         """A driven full-wave run with the lock-in at ``freq`` over the steps ``window = (w0, Nw)`` (sim/fullwave.py)
         -> (C, S volumes of the padded grid | None, C_r, S_r float64 [R] | None).  ``receivers = (row, voxel, weight)``: the CSR table, voxels
         linear in the padded grid, or {"geometry": ...} (``_fullwave_sources``): the elements' aperture averages.  The other arguments and what
         is left untouched are ``fullwave``'s."""
-        self.ctx.fullwave_plan(spacing_m, n_padded, *medium, c_ref=c_ref, pml_size=pml_size, pml_alpha=pml_alpha, dt=dt)
+        self.ctx.fullwave_plan(spacing_m, n_padded, *medium, c_ref=c_ref, pml_size=pml_size, pml_alpha=pml_alpha, dt=dt, layer_model=layer_model)
         if isinstance(receivers, dict):      # the aperture averages sum_m W_e(m) p(m): the weights' CSR is the receiver table
             receivers = self.ctx.fullwave_apertures(*receivers["geometry"])
         self._fullwave_sources(sources, spacing_m, medium, dt, freq=freq, cycles=cycles, ramp_cycles=ramp_cycles, n_steps=n_steps)

@@ -83,6 +83,35 @@ def layer_profile(n_padded: int, spacing_m: float, pml_size: int, pml_alpha: flo
     return np.exp(-float(pml_alpha) * (float(c_ref) / float(spacing_m)) * x ** 4 * float(dt))
 
 
+LAYER_MODELS = ("sponge", "pml")
+
+
+def checked_layer_model(layer_model):
+    """The model or ValueError: "sponge" (the multiplicative layers of ``layer_profile``) or "pml" (split perfectly matched layers,
+    ``split_layer_tables``)."""
+    if layer_model not in LAYER_MODELS:
+        raise ValueError(f"full-wave simulation: layer_model must be one of {LAYER_MODELS}, got {layer_model!r}")
+    return layer_model
+
+
+def split_layer_tables(n_padded: int, spacing_m: float, pml_size: int, pml_alpha: float, c_ref: float, dt: float):
+    """(r [n_padded], s [n_padded]) of one axis of the split layers (DESIGN.md section 2 "full-wave model: split layers"), fp64:
+    r[i] = exp(-sigma(d_c(i)) dt / 2) with d_c = max(pml_size - i, i - (n - 1 - pml_size), 0) the depth of voxel i's centre, s[i] the same
+    of the depth of its + face, d_f = max(pml_size - (i + 1/2), (i + 1/2) - (n - 1 - pml_size), 0); sigma(d) = pml_alpha (c_ref / h)
+    (d / pml_size)^4.  Both are 1 in the interior, and everywhere with pml_size = 0."""
+    n_padded, pml_size = int(n_padded), int(pml_size)
+    if pml_size == 0:
+        return np.ones(n_padded), np.ones(n_padded)
+    i = np.arange(n_padded, dtype=np.float64)
+    last = n_padded - 1 - pml_size
+    k = float(pml_alpha) * (float(c_ref) / float(spacing_m))
+    out = []
+    for pos in (i, i + 0.5):
+        x = np.maximum(np.maximum(pml_size - pos, pos - last), 0.0) / pml_size
+        out.append(np.exp(-(k * x ** 4) * float(dt) / 2))
+    return out[0], out[1]
+
+
 def pad_volume(vol, pml_size: int):
     """[nx, ny, nz] -> the volume extended by ``pml_size`` voxels per side by edge replication."""
     return np.pad(np.asarray(vol), int(pml_size), mode="edge")
@@ -270,6 +299,11 @@ def _padded_geometry(geom, origin_m, spacing_m, pml_size):
     return (geom["centre"] - (np.asarray(origin_m, dtype=np.float64) - int(pml_size) * h), geom["u"], geom["v"], geom["size"], geom["n_w"], geom["n_l"])
 
 
+def _layer_kw(layer_model):
+    """The engine's keyword for a layer model that is not the default (the default call stays the one it was)."""
+    return {} if layer_model == "sponge" else {"layer_model": layer_model}
+
+
 def _broadcast(value, ref, shape):
     return np.full(shape, ref, dtype=np.float64) if value is None else np.asarray(value, dtype=np.float64)
 
@@ -296,7 +330,8 @@ def _impedance(params, ref_values_only, c_ref, rho_ref, cs, rho):
 def run_fullwave_simulation(arr, params, delays=None, apod=None, freq: float = 1e6, cycles: float = 20, amplitude: float = 1,
                             dt: float = 0, t_end: float = 0, cfl: float = 0.3, bli_tolerance: float = 0.05, upsampling_rate: int = 5,
                             gpu: bool = True, ref_values_only: bool = False, *, pml_size: int = 16, pml_alpha: float = 2.0,
-                            ramp_cycles: float = 0.0, pulse_intensity_integral: bool = False, record_points=None, element_model: str = "point"):
+                            ramp_cycles: float = 0.0, pulse_intensity_integral: bool = False, record_points=None, element_model: str = "point",
+                            layer_model: str = "sponge"):
     """Full-wave simulation of one steering -> (Dataset{p_max [Pa], p_min [Pa], intensity [W/cm^2]} on ``params.coords``, raw).
 
     The leading arguments are ``run_simulation``'s; ``gpu`` is accepted and ignored (there is no CPU path).  ``element_model`` "point"
@@ -305,8 +340,12 @@ def run_fullwave_simulation(arr, params, delays=None, apod=None, freq: float = 1
     the spread is trilinear, not band-limited.  ``raw`` names the model and, for "aperture", its number of (element, voxel) entries.
     ``delays`` are used as given (no truncation to whole steps).  intensity = 1e-4 p_min^2 / (2 rho c) and, with
     ``pulse_intensity_integral``, PII = 1e-4 dt sum p^2 / (rho c) [J/cm^2], both with the voxel's own rho c.  ``record_points`` [P, 3] in
-    the coordinates' units adds "p_trace" [P, n_steps] (p after each step), "t" and "trace_voxels" to ``raw``."""
+    the coordinates' units adds "p_trace" [P, n_steps] (p after each step), "t" and "trace_voxels" to ``raw``.  ``layer_model`` "sponge"
+    (the default) damps every field of a layer voxel each step; "pml" runs split perfectly matched layers (``split_layer_tables``), which
+    leave a wave travelling along a layer alone, so a grid cropped narrowly around the beam keeps its on-axis amplitude;
+    ``raw["layer_model"]`` reports it."""
     element_model, upsampling_rate = checked_element_model(element_model, upsampling_rate if element_model == "aperture" else 1)
+    layer_model = checked_layer_model(layer_model)
     n_el = arr.numelements()
     delays = np.zeros(n_el) if delays is None else np.asarray(delays, dtype=np.float64)
     apod = np.ones(n_el) if apod is None else np.asarray(apod, dtype=np.float64)
@@ -347,7 +386,8 @@ def run_fullwave_simulation(arr, params, delays=None, apod=None, freq: float = 1
     eng = get_engine()
     sources = (lin(ijk), amp, tau) if element_model == "point" else {"geometry": _padded_geometry(geom, origin, spacing, pml_size), "A": A, "tau": delays}
     pmax, pmin, psq, trace = eng.fullwave(spacing, npad, vols, c_ref, pml_size, pml_alpha, dt, n_steps, sources, freq, cycles,
-                                          ramp_cycles, psq=bool(pulse_intensity_integral), points=None if tr_ijk is None else lin(tr_ijk))
+                                          ramp_cycles, psq=bool(pulse_intensity_integral), points=None if tr_ijk is None else lin(tr_ijk),
+                                          **_layer_kw(layer_model))
     logging.info("Simulation Complete")
     pmax, pmin = crop_volume(pmax, pml_size), crop_volume(pmin, pml_size)
     Z = _impedance(params, ref_values_only, c_ref, rho_ref, cs, rho)
@@ -358,7 +398,7 @@ def run_fullwave_simulation(arr, params, delays=None, apod=None, freq: float = 1
            "intensity": ds.make_dataarray(inten, coords=coords, dims=dims, name="I", attrs=_ATTRS["intensity"])}
     dataset = ds.make_dataset(out)
     raw = {"p_max": pmax, "p_min": -pmin, "dt": dt, "n_steps": n_steps, "dt_max": dt_max, "points_per_wavelength": ppw,
-           "backend": "openlifu_amd/hip-gfx950", "element_model": element_model,
+           "backend": "openlifu_amd/hip-gfx950", "element_model": element_model, "layer_model": layer_model,
            "aperture_entries": eng.fullwave_aperture_entries if element_model == "aperture" else None}
     if pulse_intensity_integral:
         pii = (1e-4 * dt * crop_volume(psq, pml_size).astype(np.float64) / Z).astype(np.float32)
@@ -404,12 +444,14 @@ def lockin_amplitude_phase(C, S, nw: int):
 
 def steady_state_run(params, pos_m, A, tau, freq, dt=0.0, t_end=0.0, cfl=0.3, ref_values_only=False, lockin_cycles=4, settle_cycles=3,
                      ramp_cycles=2.0, pml_size=16, pml_alpha=2.0, receivers_m=None, volume=True, what="element", apertures=None,
-                     receiver_apertures=None):
+                     receiver_apertures=None, *, layer_model="sponge"):
     """One driven run of monopoles (``pos_m`` [E, 3] m, free-field amplitude ``A`` [Pa m], delay ``tau`` [s]) with the lock-in over its
     last ``lockin_cycles`` cycles -> dict(C, S (cropped volumes or None), rec_C, rec_S (float64 [R] or None), dt, n_steps, window,
     points_per_wavelength, cycles, t_end, medium = (c_ref, rho_ref, cs, rho), aperture_entries).  ``apertures`` (``aperture_geometry``)
     makes the sources the elements' rectangles, ``pos_m`` being ignored; ``receiver_apertures`` makes the receivers the aperture averages
-    sum_m W_e(m) p(m) of those rectangles in place of ``receivers_m``.  Every refusal is raised before any device call."""
+    sum_m W_e(m) p(m) of those rectangles in place of ``receivers_m``.  ``layer_model`` is ``run_fullwave_simulation``'s.  Every refusal is
+    raised before any device call."""
+    layer_model = checked_layer_model(layer_model)
     pml_size = int(pml_size)
     if pml_size < 0 or not (np.isfinite(pml_alpha) and pml_alpha >= 0):
         raise ValueError(f"full-wave simulation: pml_size must be >= 0 and pml_alpha finite and >= 0, got {pml_size}, {pml_alpha}")
@@ -460,7 +502,7 @@ def steady_state_run(params, pos_m, A, tau, freq, dt=0.0, t_end=0.0, cfl=0.3, re
     else:
         receivers = None if row is None else (row, lin(r_ijk), r_w)
     vc, vs, rc, rs = eng.fullwave_steady(spacing, npad, vols, c_ref, pml_size, pml_alpha, dt, n_steps, sources, freq, cycles, ramp_cycles,
-                                         window=(w0, nw), volume=bool(volume), receivers=receivers)
+                                         window=(w0, nw), volume=bool(volume), receivers=receivers, **_layer_kw(layer_model))
     logging.info("Simulation Complete")
     if receivers is not None and rc is None:      # an empty receiver table
         rc = rs = np.zeros(0)
@@ -472,7 +514,7 @@ def steady_state_run(params, pos_m, A, tau, freq, dt=0.0, t_end=0.0, cfl=0.3, re
 def run_fullwave_steady_state(arr, params, delays=None, apod=None, freq: float = 1e6, amplitude: float = 1, dt: float = 0, t_end: float = 0,
                               cfl: float = 0.3, ref_values_only: bool = False, *, lockin_cycles: float = 4, settle_cycles: float = 3,
                               ramp_cycles: float = 2.0, pml_size: int = 16, pml_alpha: float = 2.0, receivers=None, element_model: str = "point",
-                              upsampling_rate: int = 5):
+                              upsampling_rate: int = 5, layer_model: str = "sponge"):
     """Steady state of one steering at the drive frequency -> (Dataset{p_max = p_min = A [Pa], intensity [W/cm^2], phase [cycles]} on
     ``params.coords``, raw): the full-wave model driven through the end of the run, locked in at ``freq`` over its last ``lockin_cycles``
     cycles (DESIGN.md section 2 "full-wave model", kernel section 5.15).
@@ -483,8 +525,9 @@ def run_fullwave_steady_state(arr, params, delays=None, apod=None, freq: float =
     the lag of p behind sin(2 pi freq t); Nw freq dt is not a whole number, so both carry a leakage of the order 1 / (2 Nw) that nothing
     corrects.  intensity = 1e-4 A^2 / (2 rho c) with the impedance rules of ``run_fullwave_simulation``.  ``receivers`` [P, 3] in the
     coordinates' units adds "receiver_amplitude", "receiver_phase" and "receiver_sums" (C_r + i S_r, trilinear weights) to ``raw``.
-    ``element_model`` / ``upsampling_rate`` are ``run_fullwave_simulation``'s."""
+    ``element_model`` / ``upsampling_rate`` / ``layer_model`` are ``run_fullwave_simulation``'s."""
     element_model, upsampling_rate = checked_element_model(element_model, upsampling_rate if element_model == "aperture" else 1)
+    layer_model = checked_layer_model(layer_model)
     n_el = arr.numelements()
     delays = np.zeros(n_el) if delays is None else np.asarray(delays, dtype=np.float64)
     apod = np.ones(n_el) if apod is None else np.asarray(apod, dtype=np.float64)
@@ -506,7 +549,7 @@ def run_fullwave_steady_state(arr, params, delays=None, apod=None, freq: float =
     A0 = apod * np.asarray(area, dtype=np.float64) * p0 * float(freq) / c_ref
     geom = aperture_geometry(arr, grid_from_coords(coords)[1], upsampling_rate) if element_model == "aperture" else None
     run = steady_state_run(params, pos, A0, delays, freq, dt, t_end, cfl, ref_values_only, lockin_cycles, settle_cycles, ramp_cycles, pml_size,
-                           pml_alpha, receivers_m=rec_m, volume=True, apertures=geom)
+                           pml_alpha, receivers_m=rec_m, volume=True, apertures=geom, **_layer_kw(layer_model))
     w0, nw = run["window"]
     A, psi = lockin_amplitude_phase(run["C"], run["S"], nw)
     c_ref, rho_ref, cs, rho = run["medium"]
@@ -520,7 +563,7 @@ def run_fullwave_steady_state(arr, params, delays=None, apod=None, freq: float =
            "phase": ds.make_dataarray(psi32, coords=coords, dims=dims, name="phase", attrs=PHASE_ATTRS)}
     raw = {"dt": run["dt"], "n_steps": run["n_steps"], "dt_max": run["dt_max"], "window": (w0, nw), "points_per_wavelength": run["points_per_wavelength"],
            "cycles": run["cycles"], "t_end": run["t_end"], "backend": "openlifu_amd/hip-gfx950", "element_model": element_model,
-           "aperture_entries": run["aperture_entries"] if element_model == "aperture" else None}
+           "aperture_entries": run["aperture_entries"] if element_model == "aperture" else None, "layer_model": layer_model}
     if rec_m is not None:
         ra, rp = lockin_amplitude_phase(run["rec_C"], run["rec_S"], nw)
         raw["receiver_amplitude"], raw["receiver_phase"] = ra, rp
@@ -538,5 +581,5 @@ def _advertise_without(fn, *names):
     fn.__signature__ = sig.replace(parameters=[p for name, p in sig.parameters.items() if name not in names])
 
 
-_advertise_without(run_fullwave_simulation, "element_model")
-_advertise_without(run_fullwave_steady_state, "element_model", "upsampling_rate")
+_advertise_without(run_fullwave_simulation, "element_model", "layer_model")
+_advertise_without(run_fullwave_steady_state, "element_model", "upsampling_rate", "layer_model")

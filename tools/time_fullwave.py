@@ -2,7 +2,7 @@
 """Time kernel 5 (full-wave model, k_fullwave.hip): ms per step and achieved bytes/s at 256^3 plus absorbing layers, for the uniform
 instantiation and for a skull-slab medium (five coefficient volumes streamed).
 
-  python tools/time_fullwave.py [--n 256] [--pml 16] [--steps 300] [--lockin | --aperture [--rounds 3]] [--out profiles/fullwave_time.json]
+  python tools/time_fullwave.py [--n 256] [--pml 16] [--steps 300] [--layers pml] [--lockin | --aperture [--rounds 3]] [--out profiles/fullwave_time.json]
 
 A run of --steps steps is bracketed by olx_sync (after one untimed warm-up run of 20 steps); the step is three launches (inject,
 velocity, pressure-and-record).  Bytes per voxel and step are the compulsory traffic of DESIGN.md section 5.14 -- every volume a launch
@@ -127,9 +127,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--aperture", action="store_true", help="time 256 aperture elements against 256 point sources (section 5.18)")
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--layers", choices=("sponge", "pml"), default="sponge", help="the layer model (section 5.19): pml = split layers")
     a = ap.parse_args()
     if a.aperture:
         return aperture_main(a)
+    layer_bytes = 24.0 * (1.0 - (a.n / (a.n + 2.0 * a.pml)) ** 3) if a.layers == "pml" else 0.0      # three components read and written in the layer voxels
     n = a.n + 2 * a.pml
     h = 0.25e-3
     shape = (n, n, n)
@@ -144,7 +146,7 @@ def main():
     rows = []
     for name, (c, rho, alpha) in media.items():
         dt = 0.9 * 6.0 / (7.0 * float(np.max(c)) * np.sqrt(3.0) / h)
-        ctx.fullwave_plan((h,) * 3, shape, c, rho, alpha, 1500.0, a.pml, 2.0, dt)
+        ctx.fullwave_plan((h,) * 3, shape, c, rho, alpha, 1500.0, a.pml, 2.0, dt, layer_model=a.layers)
         ctx.fullwave_sources(src, [1.0], [0.0], 500e3, 1e6, 0.0, a.steps)
         for psq in (False, True):
             ctx.fullwave_run(0, 20, psq=psq)
@@ -153,9 +155,9 @@ def main():
             ctx.fullwave_run(0, a.steps, psq=psq)
             ctx.sync()
             ms = (time.perf_counter() - t0) * 1e3 / a.steps
-            b = BYTES[name] + (8 if psq else 0)
+            b = round(BYTES[name] + (8 if psq else 0) + layer_bytes, 2)
             tbps = b * vox / (ms * 1e-3) / 1e12
-            rows.append({"medium": name, "sum_p2": psq, "grid": list(shape), "steps": a.steps, "ms_per_step": round(ms, 4), "bytes_per_voxel_step": b,
+            rows.append({"medium": name, "layers": a.layers, "sum_p2": psq, "grid": list(shape), "steps": a.steps, "ms_per_step": round(ms, 4), "bytes_per_voxel_step": b,
                          "achieved_TBps": round(tbps, 3), "fraction_of_copy": round(tbps / COPY_TBPS, 3)})
             print(json.dumps(rows[-1]), flush=True)
         if not a.lockin:
@@ -170,9 +172,9 @@ def main():
             ctx.fullwave_run(0, a.steps)
             ctx.sync()
             ms = (time.perf_counter() - t0) * 1e3 / a.steps
-            b = BYTES[name] + 16
+            b = round(BYTES[name] + 16 + layer_bytes, 2)
             tbps = b * vox / (ms * 1e-3) / 1e12
-            rows.append({"medium": name, "sum_p2": False, "lockin": label, "grid": list(shape), "steps": a.steps, "ms_per_step": round(ms, 4),
+            rows.append({"medium": name, "layers": a.layers, "sum_p2": False, "lockin": label, "grid": list(shape), "steps": a.steps, "ms_per_step": round(ms, 4),
                          "bytes_per_voxel_step": b, "achieved_TBps": round(tbps, 3), "fraction_of_copy": round(tbps / COPY_TBPS, 3)})
             print(json.dumps(rows[-1]), flush=True)
     ctx.close()
