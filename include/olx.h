@@ -458,6 +458,28 @@ int olx_fullwave_sources_elements(olx_ctx *ctx, int n_entries, const long long *
  * olx_fullwave_run starts at step 0; a lock-in is cleared as by a source call); the entry table stays on the device.  OLX_ESTATE
  * when the last source call was not olx_fullwave_sources_elements. */
 int olx_fullwave_drive(olx_ctx *ctx, const double *A, const double *tau);
+/* Drives of the element-factored table besides the bare burst (DESIGN.md section 2 "full-wave model: drives", section 5.20).  With
+ * s0_e(n) the drive of olx_fullwave_sources_elements, evaluated for negative n too, and g_c[0 .. M_c) the drive taps of element e's
+ * class c = class_of_element[e] on the plan's dt grid (taps[row[c] .. row[c + 1])), the drive table becomes
+ *   s_e(n) = sum_{m = 0}^{M_c - 1} g_c[m] s0_e(n - m)      (double, m ascending, from 0.0, each product and sum rounded on its own),
+ * so taps [1.0] give s0_e(n) bit for bit.  Two launches fill it: fullwave_drive_k evaluates the bare burst for the steps
+ * -(M_max - 1) .. n_steps - 1, fullwave_drive_fir_k sums it; the step loop is unchanged.  The argument shape is
+ * olx_field_pulse_response's, without its cap on the classes: every element may have its own.  Valid after
+ * olx_fullwave_sources_elements; it re-fills the table and resets the run and the lock-in as olx_fullwave_drive does.  n_classes = 0
+ * returns to the bare drive (the pointers may be NULL); olx_fullwave_drive (new A, tau) keeps the response; every source call,
+ * olx_fullwave_layers and olx_fullwave_plan clear it.  OLX_ESTATE: the last source call was not olx_fullwave_sources_elements, or the
+ * table is a sampled one.  OLX_EINVAL before the device is touched: n_classes < 0 or > n_el, a class outside [0, n_classes), a row
+ * table that does not start at 0 or is not strictly increasing (a class without taps), more than OLX_PULSE_RESPONSE_MAX_TAPS taps in
+ * a class, a tap that is not finite, an extended table ((n_steps + M_max - 1) n_el doubles) above 2^28 bytes. */
+int olx_fullwave_drive_response(olx_ctx *ctx, int n_classes, const int32_t *class_of_element, const int32_t *row, const double *taps);
+/* Sampled waveforms: table[n_steps][n_el] finite doubles replace the drive table as they are (entry q then adds
+ * (float)(amplitude[q] table[n][elements[q]]) at step n).  Same state rule and reset as olx_fullwave_drive_response.  Afterwards
+ * olx_fullwave_drive and olx_fullwave_drive_response answer OLX_ESTATE until the next source call: A and tau mean nothing to a sampled
+ * table.  OLX_EINVAL, before the device is touched, for a value that is not finite. */
+int olx_fullwave_drive_table(olx_ctx *ctx, const double *table);
+/* The current drive table, [n_steps][n_el] doubles, as the step loop reads it.  OLX_ESTATE without an element-factored table.
+ * Synchronous. */
+int olx_fullwave_fetch_drive(olx_ctx *ctx, double *table);
 /* The layer model of the plan (DESIGN.md section 2 "full-wave model: split layers", section 5.19): 0 = the multiplicative sponge of
  * olx_fullwave_plan, 1 = split perfectly matched layers.  With sigma_a(d) = pml_alpha (c_ref / h_a) (d / pml_size)^4 of the plan, d_c the
  * depth of a voxel's centre and d_f that of its + face [voxels], r_a = exp(-sigma_a(d_c) dt / 2) and s_a = exp(-sigma_a(d_f) dt / 2)

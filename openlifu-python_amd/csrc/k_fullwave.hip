@@ -1,5 +1,5 @@
 // kernel 5 (fullwave_pack_k, fullwave_inject_k, fullwave_vel_k, fullwave_pres_k, fullwave_trace_k, fullwave_receive_k; element apertures:
-// fullwave_aperture_k, fullwave_drive_k, fullwave_inject_elem_k): full-wave FDTD field model --
+// fullwave_aperture_k, fullwave_drive_k, fullwave_inject_elem_k; response drive: fullwave_drive_fir_k): full-wave FDTD field model --
 // linear acoustics, first order in (p, v) on a staggered grid, second order in time, fourth order in space.
 // gfx950 (CDNA4, wave64) only.  Definition: DESIGN.md section 2 ("full-wave model") and section 5.14, fp64 oracle tests/fullwave_oracle.py.
 //
@@ -20,6 +20,9 @@
 //   apertures opt-in: fullwave_aperture_k spreads each element's rectangle over the voxels (weights W_e(m), fp64, once per
 //             geometry); the sources then stand in element-factored form -- entries (voxel, element, amp_{e,m}) and a drive table s_e(n) filled
 //             by ONE launch of fullwave_drive_k -- and fullwave_inject_elem_k takes the place of inject: p[vox] += (float)(amp_{e,m} s_e(n))
+//   drives    opt-in (DESIGN.md section 2 "full-wave model: drives", section 5.20): the drive table of the element-factored form is filled with the bare
+//             burst (fullwave_drive_k), with the burst through per-class drive taps (fullwave_drive_k over the steps -(M_max - 1) .. n_steps - 1, then
+//             fullwave_drive_fir_k), or with sampled waveforms as uploaded; the step loop reads the table and is the same for all three
 // D = d_x[i] d_y[j] d_z[k] from three 1-D tables (1 in the interior, the absorbing layers' decay per step outside it).
 // Split layers (opt-in, olx_fullwave_layers; DESIGN.md section 2 "full-wave model: split layers", section 5.19): two 1-D tables per axis take the place
 // of d -- s_a (face depth) for the velocity launch fullwave_vel_k<UNI, SPLIT>, v_a <- s_a (s_a v_a - b_a d+_a p), and r_a (centre depth) for the
@@ -103,14 +106,18 @@ __global__ void fullwave_inject_k(float* __restrict__ p, const long long* __rest
 }
 
 // element-factored sources: the drive s_e(n) of every (step, element), one lane each, formed as fullwave_inject_k forms
-// it and exactly 0.0 outside the burst; the step loop then holds no trigonometry
+// it and exactly 0.0 outside the burst; the step loop then holds no trigonometry.  Lane g holds row g / n_el of the table, which is step
+// n = n0 + row (n0 = 0 for the drive table itself, -(M_max - 1) for the extended bare table of the response drive: a negative n goes through
+// the same expression), and writes drive[row ns + e es]: (ns, es) = (n_el, 1) is the step-major drive table, (1, rows) the element-major
+// extended table that fullwave_drive_fir_k reads along n.
 __global__ __launch_bounds__(FW_BLOCK) void fullwave_drive_k(const double* __restrict__ A, const double* __restrict__ tau, const FullwaveSource S, int n_el,
-                                                             long long total, double* __restrict__ drive) {
+                                                             long long total, long long n0, long long ns, long long es, double* __restrict__ drive) {
     const long long g = (long long)blockIdx.x * FW_BLOCK + threadIdx.x;
     if (g >= total || !OLX_IN(g, total, 21)) return;
-    const long long n = g / n_el;
-    const int e = (int)(g - n * n_el);
-    if (!OLX_IN(e, n_el, 22)) return;
+    const long long row = g / n_el;
+    const int e = (int)(g - row * n_el);
+    const long long n = n0 + row, at = row * ns + e * es;
+    if (!OLX_IN(e, n_el, 22) || !OLX_IN(at, total, 32)) return;
     const double u = ((double)n - 0.5) * S.dt - tau[e];
     double s = 0.0;
     if (u >= 0.0 && u < S.T) {
@@ -123,7 +130,38 @@ __global__ __launch_bounds__(FW_BLOCK) void fullwave_drive_k(const double* __res
         }
         s = A[e] * env * sin(2.0 * M_PI * ph);
     }
-    drive[g] = s;
+    drive[at] = s;
+}
+
+// the response drive (DESIGN.md section 2 "full-wave model: drives"): s_e(n) = sum_{m < M_c} g_c[m] s0_e(n - m), c the class of element e, in
+// fp64 with m ascending from 0.0, every product and sum rounded on its own -- taps [1.0] give s0_e(n) bit for bit.  One block is one element and
+// FW_BLOCK consecutive steps, so the whole block shares a class: its taps (at most FW_FIR_TAPS) are staged in LDS once, and a wave reads 64
+// consecutive doubles of the element-major extended table ext[n_el][rows] (rows = n_steps + lead, row lead + n = step n) per tap.
+constexpr int FW_FIR_TAPS = 256;     // OLX_PULSE_RESPONSE_MAX_TAPS
+__global__ __launch_bounds__(FW_BLOCK) void fullwave_drive_fir_k(const double* __restrict__ ext, const int* __restrict__ cls, const int* __restrict__ row,
+                                                                 const double* __restrict__ taps, int n_el, int n_classes, int n_taps, int n_steps, int lead,
+                                                                 double* __restrict__ drive) {
+#pragma clang fp contract(off)
+    __shared__ double g_s[FW_FIR_TAPS];
+    const int e = (int)(blockIdx.x % (unsigned)n_el);
+    const long long n = (long long)(blockIdx.x / (unsigned)n_el) * FW_BLOCK + threadIdx.x;
+    // (every return before the barrier is taken by the whole block: e, c and M are the block's)
+    if (!OLX_IN(e, n_el, 33)) return;
+    const int c = cls[e];
+    if (!OLX_IN(c, n_classes, 34)) return;
+    const int r0 = row[c], M = row[c + 1] - r0;
+    if (!OLX_IN(M - 1, FW_FIR_TAPS, 35) || !OLX_IN(M - 1, lead + 1, 35) || !OLX_IN(r0 + M - 1, n_taps, 36) || !OLX_IN(r0, n_taps, 36)) return;
+    for (int t = threadIdx.x; t < M; t += FW_BLOCK) g_s[t] = taps[r0 + t];
+    __syncthreads();
+    if (n >= n_steps) return;
+    const long long rows = (long long)n_steps + lead, base = (long long)e * rows + lead + n;
+    double acc = 0.0;
+    for (int m = 0; m < M; ++m) {
+        if (!OLX_IN(base - m, (long long)n_el * rows, 37)) break;
+        acc = acc + g_s[m] * ext[base - m];
+    }
+    const long long at = n * n_el + e;
+    if (OLX_IN(at, (long long)n_steps * n_el, 38)) drive[at] = acc;
 }
 
 // the sources of step n in element-factored form: row r of the CSR table is one voxel, its entries (amp_{e,m}, e) add in table order
@@ -436,6 +474,17 @@ void olx_fullwave_aperture_weights(olx_ctx* c, int n_el, long long max_box, long
 
 void olx_fullwave_drive_fill(olx_ctx* c) {
     const long long total = (long long)c->fw_steps * c->fw_nel;
-    hipLaunchKernelGGL(fullwave_drive_k, dim3((unsigned)((total + FW_BLOCK - 1) / FW_BLOCK)), dim3(FW_BLOCK), 0, c->stream, c->d_fw_dA, c->d_fw_dtau, c->fw_src,
-                       c->fw_nel, total, c->d_fw_drive);
+    if (c->fw_drive_mode != 1) {
+        hipLaunchKernelGGL(fullwave_drive_k, dim3((unsigned)((total + FW_BLOCK - 1) / FW_BLOCK)), dim3(FW_BLOCK), 0, c->stream, c->d_fw_dA, c->d_fw_dtau, c->fw_src,
+                           c->fw_nel, total, 0ll, (long long)c->fw_nel, 1ll, c->d_fw_drive);
+        return;
+    }
+    // the response drive: the bare burst of the steps -(M_max - 1) .. n_steps - 1, element-major, then the classes' taps over it
+    const int lead = c->fw_resp_mmax - 1;
+    const long long rows = (long long)c->fw_steps + lead, ext = rows * c->fw_nel;
+    hipLaunchKernelGGL(fullwave_drive_k, dim3((unsigned)((ext + FW_BLOCK - 1) / FW_BLOCK)), dim3(FW_BLOCK), 0, c->stream, c->d_fw_dA, c->d_fw_dtau, c->fw_src,
+                       c->fw_nel, ext, -(long long)lead, 1ll, rows, c->d_fw_dext);
+    const long long chunks = ((long long)c->fw_steps + FW_BLOCK - 1) / FW_BLOCK;
+    hipLaunchKernelGGL(fullwave_drive_fir_k, dim3((unsigned)(chunks * c->fw_nel)), dim3(FW_BLOCK), 0, c->stream, c->d_fw_dext, c->d_fw_gcls, c->d_fw_grow,
+                       c->d_fw_gtaps, c->fw_nel, c->fw_resp_classes, c->fw_resp_ntaps, c->fw_steps, lead, c->d_fw_drive);
 }

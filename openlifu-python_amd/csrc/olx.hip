@@ -3028,7 +3028,7 @@ int olx_fullwave_plan(olx_ctx* c, const olx_grid* g, const float* sound_speed, c
     P.dt = (float)dt;
     P.c0 = (float)sound_speed0; P.rho0 = (float)density0; P.alpha0 = (float)absorption0;
     c->fw_uniform = !sound_speed && !density && !absorption;
-    c->fw_dt = dt; c->fw_dt_max = dt_max; c->fw_elem = false;
+    c->fw_dt = dt; c->fw_dt_max = dt_max; c->fw_elem = false; c->fw_drive_mode = 0;
     c->fw_layers = 0; c->fw_pml = pml_size; c->fw_pml_alpha = pml_alpha; c->fw_c_ref = c_ref;   // every plan returns to the sponge (olx_fullwave_layers)
     for (int a = 0; a < 3; ++a) { c->fw_h[a] = g->spacing[a]; c->fw_origin[a] = g->origin[a]; }
     for (DevBuf<float>* b : {&c->d_fw_p, &c->d_fw_v[0], &c->d_fw_v[1], &c->d_fw_v[2], &c->d_fw_pmax, &c->d_fw_pmin}) { int rc = b->reserve(c, vox); if (rc) return rc; }
@@ -3079,7 +3079,7 @@ int olx_fullwave_layers(olx_ctx* c, int model) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // as a source call: the sources, the lock-in and the run state go
-    c->fw_sourced = false; c->fw_next = -1; c->fw_elem = false;
+    c->fw_sourced = false; c->fw_next = -1; c->fw_elem = false; c->fw_drive_mode = 0;
     c->fw_lock = false; c->fw_lock_vol = false; c->fw_lock_nrec = 0; c->fw_lock_entries = 0;
     c->fw_steps = 0; c->fw_npts = 0; c->fw_entries = 0;
     c->fw_layers = 0;
@@ -3163,7 +3163,7 @@ int olx_fullwave_sources(olx_ctx* c, int n_entries, const long long* voxels, con
     FullwaveSource& S = c->fw_src;
     S = FullwaveSource{};
     S.freq = freq; S.T = cycles / freq; S.Tr = ramp_cycles / freq; S.dt = c->fw_dt; S.n_vox = (int)svox.size();
-    c->fw_entries = n_entries; c->fw_steps = n_steps; c->fw_npts = n_points; c->fw_elem = false;
+    c->fw_entries = n_entries; c->fw_steps = n_steps; c->fw_npts = n_points; c->fw_elem = false; c->fw_drive_mode = 0;
     c->fw_sourced = true;
     return OLX_OK;
 }
@@ -3225,7 +3225,7 @@ int olx_fullwave_sources_elements(olx_ctx* c, int n_entries, const long long* vo
     FullwaveSource& S = c->fw_src;
     S = FullwaveSource{};
     S.freq = freq; S.T = cycles / freq; S.Tr = ramp_cycles / freq; S.dt = c->fw_dt; S.n_vox = (int)svox.size();
-    c->fw_entries = n_entries; c->fw_steps = n_steps; c->fw_npts = n_points; c->fw_elem = true; c->fw_nel = n_el;
+    c->fw_entries = n_entries; c->fw_steps = n_steps; c->fw_npts = n_points; c->fw_elem = true; c->fw_nel = n_el; c->fw_drive_mode = 0;   // a source call returns to the bare drive
     c->fw_sourced = true;
     return olx_fullwave_drive(c, A, tau_s);
 }
@@ -3233,6 +3233,7 @@ int olx_fullwave_sources_elements(olx_ctx* c, int n_entries, const long long* vo
 int olx_fullwave_drive(olx_ctx* c, const double* A, const double* tau_s) {
     if (!c) return OLX_EINVAL;
     if (!c->fw_planned || !c->fw_sourced || !c->fw_elem) return fail(c, OLX_ESTATE, "olx_fullwave_drive: needs olx_fullwave_sources_elements as the last source call");
+    if (c->fw_drive_mode == 2) return fail(c, OLX_ESTATE, "olx_fullwave_drive: the drive table is a sampled one (olx_fullwave_drive_table); A and tau mean nothing to it until the next source call");
     if (!A || !tau_s) return fail(c, OLX_EINVAL, "olx_fullwave_drive: null A / tau");
     for (int e = 0; e < c->fw_nel; ++e)
         if (!std::isfinite(A[e]) || !std::isfinite(tau_s[e])) return fail(c, OLX_EINVAL, "olx_fullwave_drive: element %d: A and delay must be finite", e);
@@ -3244,6 +3245,94 @@ int olx_fullwave_drive(olx_ctx* c, const double* A, const double* tau_s) {
     HIPCHK(c, hipMemcpy(c->d_fw_dtau, tau_s, sizeof(double) * c->fw_nel, hipMemcpyHostToDevice));
     olx_fullwave_drive_fill(c);
     HIPCHK(c, hipGetLastError());
+    return OLX_OK;
+}
+
+// the run starts again, without a lock-in until olx_fullwave_lockin asks for one (the reset of olx_fullwave_drive)
+static void fw_drive_reset(olx_ctx* c) {
+    c->fw_next = -1;
+    c->fw_lock = false; c->fw_lock_vol = false; c->fw_lock_nrec = 0; c->fw_lock_entries = 0;
+}
+
+int olx_fullwave_drive_response(olx_ctx* c, int n_classes, const int32_t* class_of_element, const int32_t* row, const double* taps) {
+    if (!c) return OLX_EINVAL;
+    if (!c->fw_planned || !c->fw_sourced || !c->fw_elem) return fail(c, OLX_ESTATE, "olx_fullwave_drive_response: needs olx_fullwave_sources_elements as the last source call");
+    if (c->fw_drive_mode == 2) return fail(c, OLX_ESTATE, "olx_fullwave_drive_response: the drive table is a sampled one (olx_fullwave_drive_table) until the next source call");
+    const int n_el = c->fw_nel;
+    int m_max = 0;
+    if (n_classes != 0) {
+        if (n_classes < 0 || n_classes > n_el)
+            return fail(c, OLX_EINVAL, "olx_fullwave_drive_response: %d classes for %d elements (0 returns to the bare drive, at most one class per element)", n_classes, n_el);
+        if (!class_of_element || !row || !taps) return fail(c, OLX_EINVAL, "olx_fullwave_drive_response: null pointer");
+        if (row[0] != 0) return fail(c, OLX_EINVAL, "olx_fullwave_drive_response: the row table must start at 0, got %d", (int)row[0]);
+        for (int r = 0; r < n_classes; ++r) {
+            if (row[r + 1] <= row[r]) return fail(c, OLX_EINVAL, "olx_fullwave_drive_response: the row table must be strictly increasing (class %d has no taps)", r);
+            if (row[r + 1] - row[r] > OLX_PULSE_RESPONSE_MAX_TAPS)
+                return fail(c, OLX_EINVAL, "olx_fullwave_drive_response: class %d has %d taps, at most OLX_PULSE_RESPONSE_MAX_TAPS = %d", r, (int)(row[r + 1] - row[r]),
+                            OLX_PULSE_RESPONSE_MAX_TAPS);
+            m_max = std::max(m_max, (int)(row[r + 1] - row[r]));
+        }
+        for (int e = 0; e < n_el; ++e)
+            if (class_of_element[e] < 0 || class_of_element[e] >= n_classes)
+                return fail(c, OLX_EINVAL, "olx_fullwave_drive_response: element %d: class %d outside 0 .. %d", e, (int)class_of_element[e], n_classes - 1);
+        for (int g = 0; g < row[n_classes]; ++g)
+            if (!std::isfinite(taps[g])) return fail(c, OLX_EINVAL, "olx_fullwave_drive_response: tap %d is not finite", g);
+        const double ext_bytes = ((double)c->fw_steps + (m_max - 1)) * n_el * sizeof(double);
+        if (ext_bytes > 268435456.0)
+            return fail(c, OLX_EINVAL, "olx_fullwave_drive_response: an extended drive table of (%d + %d) steps x %d elements (%g bytes) is too large (2^28 bytes)",
+                        c->fw_steps, m_max - 1, n_el, ext_bytes);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // the run and the lock-in are reset only once the tables stand on the device: a call that fails before leaves the drive table, the run and the
+    // lock-in as they were
+    if (n_classes == 0) {
+        c->fw_drive_mode = 0;
+    } else {
+        static_assert(sizeof(int) == sizeof(int32_t), "the class and row tables go up as they are");
+        const int n_taps = row[n_classes];
+        int rc = c->d_fw_gcls.reserve(c, n_el);
+        if (!rc) rc = c->d_fw_grow.reserve(c, (size_t)n_classes + 1);
+        if (!rc) rc = c->d_fw_gtaps.reserve(c, n_taps);
+        if (!rc) rc = c->d_fw_dext.reserve(c, ((size_t)c->fw_steps + (m_max - 1)) * n_el);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpy(c->d_fw_gcls, class_of_element, sizeof(int) * n_el, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_fw_grow, row, sizeof(int) * ((size_t)n_classes + 1), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_fw_gtaps, taps, sizeof(double) * n_taps, hipMemcpyHostToDevice));
+        c->fw_drive_mode = 1; c->fw_resp_classes = n_classes; c->fw_resp_ntaps = n_taps; c->fw_resp_mmax = m_max;
+    }
+    fw_drive_reset(c);
+    olx_fullwave_drive_fill(c);
+    HIPCHK(c, hipGetLastError());
+    return OLX_OK;
+}
+
+int olx_fullwave_drive_table(olx_ctx* c, const double* table) {
+    if (!c) return OLX_EINVAL;
+    if (!c->fw_planned || !c->fw_sourced || !c->fw_elem) return fail(c, OLX_ESTATE, "olx_fullwave_drive_table: needs olx_fullwave_sources_elements as the last source call");
+    if (!table) return fail(c, OLX_EINVAL, "olx_fullwave_drive_table: null table");
+    const size_t total = (size_t)c->fw_steps * c->fw_nel;
+    for (size_t g = 0; g < total; ++g)
+        if (!std::isfinite(table[g]))
+            return fail(c, OLX_EINVAL, "olx_fullwave_drive_table: step %lld, element %d: the drive must be finite", (long long)(g / c->fw_nel), (int)(g % c->fw_nel));
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    fw_drive_reset(c);      // before the copy, on purpose: a copy that fails leaves a table that is neither the old nor the new one, and no run may continue over it
+    HIPCHK(c, hipMemcpy(c->d_fw_drive, table, sizeof(double) * total, hipMemcpyHostToDevice));
+    c->fw_drive_mode = 2;
+    return OLX_OK;
+}
+
+int olx_fullwave_fetch_drive(olx_ctx* c, double* table) {
+    if (!c) return OLX_EINVAL;
+    if (!c->fw_planned || !c->fw_sourced || !c->fw_elem) return fail(c, OLX_ESTATE, "olx_fullwave_fetch_drive: needs olx_fullwave_sources_elements as the last source call");
+    if (!table) return fail(c, OLX_EINVAL, "olx_fullwave_fetch_drive: null table");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+#ifdef OLX_DEBUG_BOUNDS
+    { int rc_ = report_bounds(c); if (rc_) return rc_; }
+#endif
+    HIPCHK(c, hipMemcpy(table, c->d_fw_drive, sizeof(double) * (size_t)c->fw_steps * c->fw_nel, hipMemcpyDeviceToHost));
     return OLX_OK;
 }
 

@@ -202,6 +202,12 @@ struct olx_ctx {
     // s_e(n) of every (step, element) stands in a table that olx_fullwave_drive re-fills; fw_elem says which inject kernel olx_fullwave_run launches
     bool fw_elem = false; int fw_nel = 0;
     DevBuf<int> d_fw_sel; DevBuf<double> d_fw_drive, d_fw_dA, d_fw_dtau;   // [entries] element; [fw_steps][fw_nel] drive; [fw_nel] A_e, tau_e
+    // what fills the drive table: 0 the bare burst, 1 the burst through the classes' drive taps (olx_fullwave_drive_response: fullwave_drive_k
+    // fills the extended bare table, fullwave_drive_fir_k sums it), 2 a sampled table as uploaded (olx_fullwave_drive_table).  Every source call,
+    // olx_fullwave_layers and olx_fullwave_plan return to 0.
+    int fw_drive_mode = 0, fw_resp_classes = 0, fw_resp_ntaps = 0, fw_resp_mmax = 0;
+    DevBuf<int> d_fw_gcls, d_fw_grow; DevBuf<double> d_fw_gtaps;   // [fw_nel] class of each element; [classes + 1] row offsets; [fw_resp_ntaps] taps
+    DevBuf<double> d_fw_dext;                 // [fw_nel][fw_steps + fw_resp_mmax - 1] bare drive of the steps -(fw_resp_mmax - 1) .. fw_steps - 1, element-major
     // aperture weights (olx_fullwave_apertures): the planned grid in fp64, per-element geometry and index box, the dense weights of every box
     double fw_h[3] = {0, 0, 0}, fw_origin[3] = {0, 0, 0};
     DevBuf<FullwaveAperture> d_fw_ap; DevBuf<double> d_fw_apw;   // [elements]; [sum of the boxes' voxels]

@@ -33,7 +33,7 @@ void olx_thermal_trace_last(olx_ctx* c, int step);                              
 void olx_fullwave_pack(olx_ctx* c, const float* cs, const float* rho, const float* alpha);   // 5  fullwave_pack_k (coefficient volumes of a heterogeneous medium)
 void olx_fullwave_step(olx_ctx* c, int step, bool pii);                                      // 5  fullwave_inject_k | fullwave_inject_elem_k, fullwave_vel_k, fullwave_pres_k, fullwave_trace_k (one step)
 void olx_fullwave_aperture_weights(olx_ctx* c, int n_el, long long max_box, long long total);   // 5  fullwave_aperture_k (dense weights of every element's index box)
-void olx_fullwave_drive_fill(olx_ctx* c);                                                    // 5  fullwave_drive_k (the drive table of the element-factored sources)
+void olx_fullwave_drive_fill(olx_ctx* c);                                                    // 5  fullwave_drive_k (the drive table of the element-factored sources; with a response: the extended bare table, then fullwave_drive_fir_k)
 void olx_eikonal_init(olx_ctx* c, const float* cs);                      // 6  eikonal_init_k (the init set into both c->d_ek_T; cs = the device sound-speed volume, or null: uniform c->ek.c0)
 void olx_eikonal_sweep(olx_ctx* c, const float* cs, int sweep);          // 6  eikonal_sweep_k (Jacobi sweep number `sweep` >= 1 over its box; its flag is c->d_ek_flag[sweep - 1])
 void olx_eikonal_sample_launch(olx_ctx* c, int n_points, int n_entries); // 6  eikonal_sample_k (the CSR table of c->d_ek_row / d_ek_vox / d_ek_w into c->d_ek_out)

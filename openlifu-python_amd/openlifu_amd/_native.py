@@ -47,6 +47,7 @@ SYMBOLS = [
     "olx_thermal_plan", "olx_thermal_schedule", "olx_thermal_source", "olx_thermal_run", "olx_thermal_fetch",
     "olx_fullwave_plan", "olx_fullwave_sources", "olx_fullwave_run", "olx_fullwave_fetch", "olx_fullwave_lockin", "olx_fullwave_fetch_lockin",
     "olx_fullwave_apertures", "olx_fullwave_sources_elements", "olx_fullwave_drive", "olx_fullwave_layers",
+    "olx_fullwave_drive_response", "olx_fullwave_drive_table", "olx_fullwave_fetch_drive",
     "olx_eikonal_solve", "olx_eikonal_sample", "olx_eikonal_fetch",
     "olx_bf_set_medium", "olx_bf_solve_medium",
     "olx_bf_set_attenuation", "olx_bf_solve_compensated",
@@ -179,6 +180,9 @@ def load(require_gpu: bool = True):
         lib.olx_fullwave_sources_elements.argtypes = [vp, c_int, POINTER(ctypes.c_longlong), POINTER(c_int), dp, c_int, dp, dp, c_double, c_double, c_double,
                                                       c_int, c_int, POINTER(ctypes.c_longlong)]
         lib.olx_fullwave_drive.argtypes = [vp, dp, dp]
+        lib.olx_fullwave_drive_response.argtypes = [vp, c_int, POINTER(c_int32), POINTER(c_int32), dp]
+        lib.olx_fullwave_drive_table.argtypes = [vp, dp]
+        lib.olx_fullwave_fetch_drive.argtypes = [vp, dp]
         lib.olx_fullwave_layers.argtypes = [vp, c_int]
         lib.olx_eikonal_solve.argtypes = [vp, POINTER(OlxGrid), fp, c_double, dp, c_double, c_int, POINTER(c_int)]
         lib.olx_eikonal_sample.argtypes = [vp, c_int, POINTER(c_int), POINTER(ctypes.c_longlong), dp, dp]
@@ -786,6 +790,7 @@ class Context:
         self._chk(self._lib.olx_fullwave_plan(self._h, ctypes.byref(g), *[_fptr(a) for a in vols], *scal, float(c_ref), int(pml_size),
                                               float(pml_alpha), float(dt), ctypes.byref(dt_max)))
         self._fw_shape = shape
+        self._fw_nel = None          # a new plan clears the sources
         if layer_model == "pml":
             self.fullwave_layers(1)
         return float(dt_max.value)
@@ -794,6 +799,7 @@ class Context:
         """The layer model of the plan: 0 = sponge, 1 = split layers.  Clears the sources, the lock-in and the run."""
         self._chk(self._lib.olx_fullwave_layers(self._h, int(model)))
         self._fw_steps = self._fw_npts = 0
+        self._fw_nel = None          # no element-factored table (fullwave_sources_elements sets it)
         self._fw_lock_vol, self._fw_lock_nrec = False, 0
 
     def fullwave_sources(self, voxels, amplitude, tau, freq, cycles, ramp_cycles, n_steps, points=None):
@@ -807,7 +813,7 @@ class Context:
         lp = POINTER(ctypes.c_longlong)
         self._chk(self._lib.olx_fullwave_sources(self._h, int(vx.size), vx.ctypes.data_as(lp), _dptr(am), _dptr(ta), float(freq), float(cycles),
                                                  float(ramp_cycles), int(n_steps), int(pts.size), pts.ctypes.data_as(lp)))
-        self._fw_steps, self._fw_npts = int(n_steps), int(pts.size)
+        self._fw_steps, self._fw_npts, self._fw_nel = int(n_steps), int(pts.size), None
         self._fw_lock_vol, self._fw_lock_nrec = False, 0
 
     def fullwave_apertures(self, centre, u_axis, v_axis, size, n_w, n_l, capacity=None):
@@ -865,6 +871,48 @@ class Context:
             raise ValueError(f"A and tau must have shape ({n_el},), got {AA.shape}, {ta.shape}")
         self._chk(self._lib.olx_fullwave_drive(self._h, _dptr(AA), _dptr(ta)))
         self._fw_lock_vol, self._fw_lock_nrec = False, 0
+
+    def _fw_elements(self, who):
+        """n_el of the element-factored table, or NativeError (the library's OLX_ESTATE, before an array of unknown length goes to it)"""
+        n_el = getattr(self, "_fw_nel", None)
+        if n_el is None:
+            raise NativeError(f"[olx {OLX_ESTATE}] {who}: needs fullwave_sources_elements as the last source call")
+        return n_el
+
+    def fullwave_drive_response(self, class_of_element=None, taps=()):
+        """The drive of the element-factored table through per-class drive taps (olx_fullwave_drive_response): ``class_of_element`` [n_el] ints
+        and ``taps``, one 1-D fp64 array on the plan's dt grid per class (at most n_el classes of at most 256 taps).  No classes (the default)
+        returns to the bare drive.  The run starts again and a lock-in is cleared; the class ids and the taps are checked by the library."""
+        taps = [np.ascontiguousarray(t, dtype=np.float64).ravel() for t in taps]
+        if not taps:
+            self._chk(self._lib.olx_fullwave_drive_response(self._h, 0, None, None, None))
+        else:
+            cls = np.ascontiguousarray(class_of_element, dtype=np.int32).ravel()
+            n_el = self._fw_elements("fullwave_drive_response")
+            if cls.size != n_el:
+                raise ValueError(f"class_of_element must have one entry per element ({n_el}), got {cls.size}")
+            row = np.concatenate([[0], np.cumsum([t.size for t in taps])]).astype(np.int32)
+            flat = np.concatenate(taps) if row[-1] else np.zeros(1)
+            self._chk(self._lib.olx_fullwave_drive_response(self._h, len(taps), cls.ctypes.data_as(POINTER(c_int32)), row.ctypes.data_as(POINTER(c_int32)),
+                                                            _dptr(flat)))
+        self._fw_lock_vol, self._fw_lock_nrec = False, 0
+
+    def fullwave_drive_table(self, table):
+        """Sampled waveforms: ``table`` [n_steps, n_el] fp64 replaces the drive table as it is (olx_fullwave_drive_table); ``fullwave_drive`` and
+        ``fullwave_drive_response`` are then refused until the next source call.  The run starts again and a lock-in is cleared."""
+        tb = np.ascontiguousarray(table, dtype=np.float64)
+        shape = (self._fw_steps, self._fw_elements("fullwave_drive_table"))
+        if tb.shape != shape:
+            raise ValueError(f"the drive table must have shape {shape} (steps, elements), got {tb.shape}")
+        self._chk(self._lib.olx_fullwave_drive_table(self._h, _dptr(tb)))
+        self._fw_lock_vol, self._fw_lock_nrec = False, 0
+
+    def fullwave_fetch_drive(self):
+        """The current drive table s[n_steps, n_el] (fp64) of the element-factored sources, as the step loop reads it."""
+        shape = (self._fw_steps, self._fw_elements("fullwave_fetch_drive"))
+        out = np.empty(shape, dtype=np.float64)
+        self._chk(self._lib.olx_fullwave_fetch_drive(self._h, _dptr(out)))
+        return out
 
     def fullwave_run(self, first_step: int = 0, n_steps=None, psq: bool = False):
         n_steps = self._fw_steps - int(first_step) if n_steps is None else int(n_steps)

@@ -527,7 +527,9 @@ class Engine:
         """The source call of a planned full-wave run.  ``sources`` is (voxel, amplitude, tau) per entry -- olx_fullwave_sources -- or a dict,
         the element-factored form of olx_fullwave_sources_elements: {"A" [E], "tau" [E]} plus either "voxels", "elements", "amplitude" per
         entry, or "geometry" = (centre [E, 3] m in the padded grid's frame, u, v, size, n_w, n_l): the rectangles whose weights
-        olx_fullwave_apertures forms on the plan, amplitude = W dt c(voxel)^2 4 pi / (2 pi freq h_x h_y h_z)."""
+        olx_fullwave_apertures forms on the plan, amplitude = W dt c(voxel)^2 4 pi / (2 pi freq h_x h_y h_z).  The dict may carry a drive besides
+        the bare burst, applied after the source call: "response" = (class_of_element [E], [taps_c]) -- the drive taps of sim/field.py
+        ``drive_taps`` on the plan's dt grid -- or "table" = [n_steps, E] sampled waveforms."""
         if not isinstance(sources, dict):
             self.fullwave_aperture_entries = None
             return self.ctx.fullwave_sources(*sources, freq=freq, **kw)
@@ -541,7 +543,11 @@ class Engine:
         else:
             vox, el, amp = sources["voxels"], sources["elements"], sources["amplitude"]
         self.fullwave_aperture_entries = int(np.size(vox))
-        return self.ctx.fullwave_sources_elements(vox, el, amp, sources["A"], sources["tau"], freq=freq, **kw)
+        self.ctx.fullwave_sources_elements(vox, el, amp, sources["A"], sources["tau"], freq=freq, **kw)
+        if sources.get("response") is not None:      # (class_of_element, [taps_c]): the burst through the drive taps (olx_fullwave_drive_response)
+            self.ctx.fullwave_drive_response(*sources["response"])
+        if sources.get("table") is not None:         # [n_steps, n_el]: sampled waveforms as they are (olx_fullwave_drive_table)
+            self.ctx.fullwave_drive_table(sources["table"])
 
     def fullwave_steady(self, spacing_m, n_padded, medium, c_ref, pml_size, pml_alpha, dt, n_steps, sources, freq, cycles, ramp_cycles, window,
                         volume=True, receivers=None, layer_model="sponge"):

@@ -73,12 +73,15 @@ def parse_pulsed_drive_model(value):
     return model
 
 
-def drive_taps(arr, dt):
+def drive_taps(arr, dt, max_classes=PULSE_RESPONSE_MAX_CLASSES, max_taps=PULSE_RESPONSE_MAX_TAPS, what="pulsed field model"):
     """(class_of_element int32 [N], [taps_r fp64]): the drive taps g_e = H_arr * H_el,e of every element on the ``dt`` grid (DESIGN.md
     section 2), the drive of ``Transducer.calc_output`` being sum_m g_e[m] burst((k - m) dt).  H_arr = the array's response resampled to
     ``dt`` ([1] without one); H_el,e = [1] without a response, [h0] for a length-1 response, else the element's resampled to ``dt``.
     Elements whose taps are exactly equal share a class, numbered by first appearance.  A transducer without any response gives no classes
-    (the plain kernel runs).  ValueError for a class longer than PULSE_RESPONSE_MAX_TAPS or more than PULSE_RESPONSE_MAX_CLASSES classes."""
+    (the plain kernel runs).  ValueError, naming the model ``what``, for a class longer than ``max_taps`` or more than ``max_classes`` classes:
+    the defaults are the pulsed model's (PULSE_RESPONSE_MAX_TAPS, PULSE_RESPONSE_MAX_CLASSES); the full-wave model keeps its table per element
+    and passes ``max_classes = n_el``."""
+    max_classes, max_taps = int(max_classes), int(max_taps)
     dt = float(dt)
     n = arr.numelements()
     cls = np.zeros(n, dtype=np.int32)
@@ -100,12 +103,12 @@ def drive_taps(arr, dt):
         g = np.convolve(h_arr, h_el, mode="full")
         key = g.tobytes()
         if key not in index:
-            if len(g) > PULSE_RESPONSE_MAX_TAPS:
-                raise ValueError(f"pulsed field model: element {e}'s impulse response has {len(g)} taps at dt = {dt:g} s, "
-                                 f"at most {PULSE_RESPONSE_MAX_TAPS} are supported")
-            if len(taps) == PULSE_RESPONSE_MAX_CLASSES:
-                raise ValueError(f"pulsed field model: the elements carry more than {PULSE_RESPONSE_MAX_CLASSES} different impulse responses "
-                                 f"(at most {PULSE_RESPONSE_MAX_CLASSES} classes of identical drive taps are supported)")
+            if len(g) > max_taps:
+                raise ValueError(f"{what}: element {e}'s impulse response has {len(g)} taps at dt = {dt:g} s, "
+                                 f"at most {max_taps} are supported")
+            if len(taps) >= max_classes:
+                raise ValueError(f"{what}: the elements carry more than {max_classes} different impulse responses "
+                                 f"(at most {max_classes} classes of identical drive taps are supported)")
             index[key] = len(taps)
             taps.append(g)
         cls[e] = index[key]

@@ -304,6 +304,43 @@ def _layer_kw(layer_model):
     return {} if layer_model == "sponge" else {"layer_model": layer_model}
 
 
+DRIVE_MODELS = ("impulse_response",)      # what drives the elements besides the bare burst, opt-in (DESIGN.md section 2 "full-wave model: drives")
+
+
+def checked_drive_model(drive_model):
+    """The model or ValueError: None (the bare burst; the transducer's impulse responses are ignored) or "impulse_response"."""
+    if drive_model is not None and drive_model not in DRIVE_MODELS:
+        raise ValueError(f'full-wave simulation: drive_model must be None or one of {DRIVE_MODELS}, got {drive_model!r}')
+    return drive_model
+
+
+def response_of(arr, dt):
+    """The drive taps of ``arr`` on the ``dt`` grid as the full-wave model takes them -> (class_of_element int32 [E], [taps_c], M [E] taps of
+    each element's class), or None for a transducer without any response.  sim/field.py ``drive_taps`` with one class per element allowed."""
+    from .field import drive_taps
+    cls, taps = drive_taps(arr, dt, max_classes=max(1, arr.numelements()), what="full-wave simulation")
+    if not taps:
+        return None
+    return cls, taps, np.asarray([len(taps[c]) for c in cls], dtype=np.int64)
+
+
+def checked_source_waveforms(source_waveforms, n_el, dt, delays, drive_model):
+    """``source_waveforms`` as a float64 [n_el, n_t] array, or ValueError: it needs an explicit dt > 0 and no delays, and excludes
+    ``drive_model``."""
+    if drive_model is not None:
+        raise ValueError("full-wave simulation: source_waveforms and drive_model exclude each other (a sampled waveform carries its own response)")
+    if delays is not None:
+        raise ValueError("full-wave simulation: source_waveforms take no delays (delay the waveforms themselves)")
+    if not (np.isfinite(dt) and dt > 0):
+        raise ValueError(f"full-wave simulation: source_waveforms are samples on the step grid and need an explicit dt > 0, got {dt}")
+    W = np.asarray(source_waveforms, dtype=np.float64)
+    if W.ndim != 2 or W.shape[0] != n_el or W.shape[1] < 1:
+        raise ValueError(f"source_waveforms must have shape ({n_el}, n_t) with n_t >= 1, got {W.shape}")
+    if not np.all(np.isfinite(W)):
+        raise ValueError("full-wave simulation: source_waveforms must be finite")
+    return W
+
+
 def _broadcast(value, ref, shape):
     return np.full(shape, ref, dtype=np.float64) if value is None else np.asarray(value, dtype=np.float64)
 
@@ -331,7 +368,7 @@ def run_fullwave_simulation(arr, params, delays=None, apod=None, freq: float = 1
                             dt: float = 0, t_end: float = 0, cfl: float = 0.3, bli_tolerance: float = 0.05, upsampling_rate: int = 5,
                             gpu: bool = True, ref_values_only: bool = False, *, pml_size: int = 16, pml_alpha: float = 2.0,
                             ramp_cycles: float = 0.0, pulse_intensity_integral: bool = False, record_points=None, element_model: str = "point",
-                            layer_model: str = "sponge"):
+                            layer_model: str = "sponge", drive_model=None, source_waveforms=None):
     """Full-wave simulation of one steering -> (Dataset{p_max [Pa], p_min [Pa], intensity [W/cm^2]} on ``params.coords``, raw).
 
     The leading arguments are ``run_simulation``'s; ``gpu`` is accepted and ignored (there is no CPU path).  ``element_model`` "point"
@@ -343,10 +380,22 @@ def run_fullwave_simulation(arr, params, delays=None, apod=None, freq: float = 1
     the coordinates' units adds "p_trace" [P, n_steps] (p after each step), "t" and "trace_voxels" to ``raw``.  ``layer_model`` "sponge"
     (the default) damps every field of a layer voxel each step; "pml" runs split perfectly matched layers (``split_layer_tables``), which
     leave a wave travelling along a layer alone, so a grid cropped narrowly around the beam keeps its on-axis amplitude;
-    ``raw["layer_model"]`` reports it."""
+    ``raw["layer_model"]`` reports it.
+
+    ``drive_model`` None (the default) drives every element with the bare tone burst: the ``impulse_response`` of the transducer and of its
+    elements is ignored.  "impulse_response" opts in to them: element e's drive is sum_m g_e[m] burst((n - m) dt) with the drive taps
+    g_e = H_arr * H_el,e of sim/field.py ``drive_taps`` on the run's dt grid (at most 256 taps; every element may have its own), formed on the
+    device (fullwave_drive_fir_k; DESIGN.md section 2 "full-wave model: drives").  Both element models then go through the element-factored source form;
+    a transducer without any response runs the default path.  With ``t_end = 0`` the run grows by the longest response.
+    ``source_waveforms`` [n_el, n_t] drives element e with the samples A_e W[e, n] at step n, in units of the bare burst -- sin(2 pi freq
+    (n - 1/2) dt) reproduces a CW drive -- padded with zeros to n_steps = max(n_t, ceil(t_end / dt)); it needs an explicit ``dt``, takes no
+    ``delays``, ignores ``cycles`` and ``ramp_cycles`` and excludes ``drive_model``.  ``raw["drive_model"]`` ("impulse_response",
+    "source_waveforms" or None) and ``raw["drive_taps"]`` (the largest number of taps, None without the opt-in) report the drive."""
     element_model, upsampling_rate = checked_element_model(element_model, upsampling_rate if element_model == "aperture" else 1)
     layer_model = checked_layer_model(layer_model)
+    drive_model = checked_drive_model(drive_model)
     n_el = arr.numelements()
+    W = None if source_waveforms is None else checked_source_waveforms(source_waveforms, n_el, float(dt), delays, drive_model)
     delays = np.zeros(n_el) if delays is None else np.asarray(delays, dtype=np.float64)
     apod = np.ones(n_el) if apod is None else np.asarray(apod, dtype=np.float64)
     if delays.shape != (n_el,) or apod.shape != (n_el,):
@@ -362,15 +411,37 @@ def run_fullwave_simulation(arr, params, delays=None, apod=None, freq: float = 1
     origin, spacing, n = grid_from_coords(coords)
     n = tuple(int(v) for v in n)
     c_ref, rho_ref, cs, rho, alpha = _medium_of(params, freq, ref_values_only)
-    dt, n_steps, dt_max, ppw = fullwave_time_axis(spacing, n, cs, freq, cycles, delays, dt, t_end, cfl)
+    response = table = None
+    if W is not None:
+        # the samples are the run: n_steps = max(n_t, ceil(t_end / dt)); the burst's length means nothing here (cycles = 1 passes the checks)
+        cycles, ramp_cycles = 1.0, 0.0
+        dt, n_steps, dt_max, ppw = fullwave_time_axis(spacing, n, cs, freq, cycles, 0.0, dt, t_end if float(t_end) > 0 else W.shape[1] * float(dt), cfl)
+        n_steps = max(W.shape[1], n_steps if float(t_end) > 0 else 0)
+        if n_steps >= 2 ** 31:
+            raise ValueError(f"full-wave simulation: {n_steps} steps is too many")
+    elif drive_model is not None:
+        # dt does not depend on the delays: form it first, resample the responses to it, then let the run end M_e - 1 steps later for element e
+        dt = fullwave_time_axis(spacing, n, cs, freq, cycles, delays, dt, t_end, cfl)[0]
+        response = response_of(arr, dt)
+        lead = 0.0 if response is None else (response[2] - 1) * dt
+        dt, n_steps, dt_max, ppw = fullwave_time_axis(spacing, n, cs, freq, cycles, delays + lead, dt, t_end, cfl)
+    else:
+        dt, n_steps, dt_max, ppw = fullwave_time_axis(spacing, n, cs, freq, cycles, delays, dt, t_end, cfl)
+    factored = response is not None or W is not None      # the element-factored source form: its drive table is where both drives go
     pos, _, area, _ = Engine._table_of(arr)
     p0 = float(amplitude) * (1.0 if arr.sensitivity is None else float(arr.sensitivity))
+    if element_model == "aperture" or factored:
+        A = apod * np.asarray(area, dtype=np.float64) * p0 * float(freq) / float(c_ref)
     if element_model == "aperture":
         geom = aperture_geometry(arr, spacing, upsampling_rate)
         check_apertures_inside(geom, origin, spacing, n)
-        A = apod * np.asarray(area, dtype=np.float64) * p0 * float(freq) / float(c_ref)
+    elif factored:
+        ijk, amp, _, el = monopole_table(pos, np.ones(n_el), delays, origin, spacing, n, cs, freq, dt)
     else:
         ijk, amp, tau, _ = source_table(pos, area, apod, delays, origin, spacing, n, cs, c_ref, freq, p0, dt)
+    if W is not None:
+        table = np.zeros((n_steps, n_el))
+        table[:W.shape[1]] = (A[:, None] * W).T
     trace_voxels = tr_ijk = None
     if record_points is not None:
         from .thermal import _trace_voxels      # (the same nearest-voxel rule as the thermal traces)
@@ -384,7 +455,16 @@ def run_fullwave_simulation(arr, params, delays=None, apod=None, freq: float = 1
     vols = [v if np.ndim(v) == 0 else pad_volume(v, pml_size) for v in (cs, rho, alpha)]
     logging.info("Running full-wave simulation")
     eng = get_engine()
-    sources = (lin(ijk), amp, tau) if element_model == "point" else {"geometry": _padded_geometry(geom, origin, spacing, pml_size), "A": A, "tau": delays}
+    if element_model == "aperture":
+        sources = {"geometry": _padded_geometry(geom, origin, spacing, pml_size), "A": A, "tau": delays}
+    elif factored:
+        sources = {"voxels": lin(ijk), "elements": el, "amplitude": amp, "A": A, "tau": delays}
+    else:
+        sources = (lin(ijk), amp, tau)
+    if response is not None:
+        sources["response"] = response[:2]
+    if table is not None:
+        sources["table"] = table
     pmax, pmin, psq, trace = eng.fullwave(spacing, npad, vols, c_ref, pml_size, pml_alpha, dt, n_steps, sources, freq, cycles,
                                           ramp_cycles, psq=bool(pulse_intensity_integral), points=None if tr_ijk is None else lin(tr_ijk),
                                           **_layer_kw(layer_model))
@@ -399,7 +479,9 @@ def run_fullwave_simulation(arr, params, delays=None, apod=None, freq: float = 1
     dataset = ds.make_dataset(out)
     raw = {"p_max": pmax, "p_min": -pmin, "dt": dt, "n_steps": n_steps, "dt_max": dt_max, "points_per_wavelength": ppw,
            "backend": "openlifu_amd/hip-gfx950", "element_model": element_model, "layer_model": layer_model,
-           "aperture_entries": eng.fullwave_aperture_entries if element_model == "aperture" else None}
+           "aperture_entries": eng.fullwave_aperture_entries if element_model == "aperture" else None,
+           "drive_model": "source_waveforms" if W is not None else drive_model,
+           "drive_taps": None if drive_model is None else 1 if response is None else int(response[2].max())}
     if pulse_intensity_integral:
         pii = (1e-4 * dt * crop_volume(psq, pml_size).astype(np.float64) / Z).astype(np.float32)
         dataset["pulse_intensity_integral"] = ds.make_dataarray(pii, coords=coords, dims=dims, name="pulse_intensity_integral",
@@ -444,14 +526,19 @@ def lockin_amplitude_phase(C, S, nw: int):
 
 def steady_state_run(params, pos_m, A, tau, freq, dt=0.0, t_end=0.0, cfl=0.3, ref_values_only=False, lockin_cycles=4, settle_cycles=3,
                      ramp_cycles=2.0, pml_size=16, pml_alpha=2.0, receivers_m=None, volume=True, what="element", apertures=None,
-                     receiver_apertures=None, *, layer_model="sponge"):
+                     receiver_apertures=None, *, layer_model="sponge", drive_model=None, arr=None):
     """One driven run of monopoles (``pos_m`` [E, 3] m, free-field amplitude ``A`` [Pa m], delay ``tau`` [s]) with the lock-in over its
     last ``lockin_cycles`` cycles -> dict(C, S (cropped volumes or None), rec_C, rec_S (float64 [R] or None), dt, n_steps, window,
     points_per_wavelength, cycles, t_end, medium = (c_ref, rho_ref, cs, rho), aperture_entries).  ``apertures`` (``aperture_geometry``)
     makes the sources the elements' rectangles, ``pos_m`` being ignored; ``receiver_apertures`` makes the receivers the aperture averages
-    sum_m W_e(m) p(m) of those rectangles in place of ``receivers_m``.  ``layer_model`` is ``run_fullwave_simulation``'s.  Every refusal is
-    raised before any device call."""
+    sum_m W_e(m) p(m) of those rectangles in place of ``receivers_m``.  ``layer_model`` is ``run_fullwave_simulation``'s.
+    ``drive_model="impulse_response"`` drives the monopoles through the impulse responses of the transducer ``arr`` (``response_of``; one
+    monopole per element of ``arr``): the default ``t_end`` grows by (M_max - 1) dt and the dict gains "drive_taps" = M_max.  Every refusal
+    is raised before any device call."""
     layer_model = checked_layer_model(layer_model)
+    drive_model = checked_drive_model(drive_model)
+    if drive_model is not None and arr is None:
+        raise ValueError("full-wave steady state: drive_model needs the transducer whose impulse responses drive the elements (arr)")
     pml_size = int(pml_size)
     if pml_size < 0 or not (np.isfinite(pml_alpha) and pml_alpha >= 0):
         raise ValueError(f"full-wave simulation: pml_size must be >= 0 and pml_alpha finite and >= 0, got {pml_size}, {pml_alpha}")
@@ -467,16 +554,29 @@ def steady_state_run(params, pos_m, A, tau, freq, dt=0.0, t_end=0.0, cfl=0.3, re
     tau = np.asarray(tau, dtype=np.float64)
     total = float(ramp_cycles) + float(settle_cycles) + float(lockin_cycles)
     dt, n_steps, dt_max, ppw = fullwave_time_axis(spacing, n, cs, freq, total, tau, dt, t_end, cfl)
+    response, lead = None, 0.0
+    if drive_model is not None:
+        response = response_of(arr, dt)
+        if response is not None:
+            if response[0].shape != tau.shape:
+                raise ValueError(f"full-wave steady state: the transducer has {response[0].size} elements, the run {tau.size} monopoles")
+            lead = float(response[2].max() - 1) * dt
+            if lead > 0:      # the longest response reaches that far behind the burst: the default run waits for it
+                dt, n_steps, dt_max, ppw = fullwave_time_axis(spacing, n, cs, freq, total, tau + lead, dt, t_end, cfl)
     t_end = float(t_end)
-    if t_end == 0:      # (the default fullwave_time_axis has just taken: |n h| / c_min + max tau + total / freq)
+    if t_end == 0:      # (the default fullwave_time_axis has just taken: |n h| / c_min + max tau + total / freq, plus the longest response)
         h = np.broadcast_to(np.asarray(spacing, dtype=np.float64), (3,))
         t_end = (float(np.sqrt(np.sum((np.asarray(n, dtype=np.float64) * h) ** 2))) / float(np.min(cs)) + (float(tau.max()) if tau.size else 0.0)
                  + total / float(freq))
+        if lead > 0:
+            t_end += lead
     cycles = float(np.ceil(float(freq) * t_end) + 1.0)      # the drive lasts through the end of the run
     w0, nw = lockin_window(n_steps, dt, freq, lockin_cycles)
     if apertures is not None:
         check_apertures_inside(apertures, origin, spacing, n, what=what)
         sources = {"geometry": _padded_geometry(apertures, origin, spacing, pml_size), "A": np.asarray(A, dtype=np.float64), "tau": tau}
+    elif response is not None:      # the element-factored form carries the drive table the response goes into
+        ijk, amp, _, el = monopole_table(pos_m, np.ones(tau.shape), tau, origin, spacing, n, cs, freq, dt, what=what)
     else:
         ijk, amp, tt, _ = monopole_table(pos_m, A, tau, origin, spacing, n, cs, freq, dt, what=what)
     row = r_ijk = r_w = None
@@ -495,8 +595,12 @@ def steady_state_run(params, pos_m, A, tau, freq, dt=0.0, t_end=0.0, cfl=0.3, re
     vols = [v if np.ndim(v) == 0 else pad_volume(v, pml_size) for v in (cs, rho, alpha)]
     logging.info("Running full-wave steady-state simulation")
     eng = get_engine()
-    if apertures is None:
+    if apertures is None and response is not None:
+        sources = {"voxels": lin(ijk), "elements": el, "amplitude": amp, "A": np.asarray(A, dtype=np.float64), "tau": tau}
+    elif apertures is None:
         sources = (lin(ijk), amp, tt)
+    if response is not None:
+        sources["response"] = response[:2]
     if receiver_apertures is not None:
         receivers = {"geometry": _padded_geometry(receiver_apertures, origin, spacing, pml_size)}
     else:
@@ -508,13 +612,14 @@ def steady_state_run(params, pos_m, A, tau, freq, dt=0.0, t_end=0.0, cfl=0.3, re
         rc = rs = np.zeros(0)
     return {"C": None if vc is None else crop_volume(vc, pml_size), "S": None if vs is None else crop_volume(vs, pml_size), "rec_C": rc, "rec_S": rs,
             "dt": dt, "n_steps": n_steps, "dt_max": dt_max, "window": (w0, nw), "points_per_wavelength": ppw, "cycles": cycles, "t_end": t_end,
-            "medium": (c_ref, rho_ref, cs, rho), "aperture_entries": eng.fullwave_aperture_entries}
+            "medium": (c_ref, rho_ref, cs, rho), "aperture_entries": eng.fullwave_aperture_entries,
+            "drive_taps": None if drive_model is None else 1 if response is None else int(response[2].max())}
 
 
 def run_fullwave_steady_state(arr, params, delays=None, apod=None, freq: float = 1e6, amplitude: float = 1, dt: float = 0, t_end: float = 0,
                               cfl: float = 0.3, ref_values_only: bool = False, *, lockin_cycles: float = 4, settle_cycles: float = 3,
                               ramp_cycles: float = 2.0, pml_size: int = 16, pml_alpha: float = 2.0, receivers=None, element_model: str = "point",
-                              upsampling_rate: int = 5, layer_model: str = "sponge"):
+                              upsampling_rate: int = 5, layer_model: str = "sponge", drive_model=None):
     """Steady state of one steering at the drive frequency -> (Dataset{p_max = p_min = A [Pa], intensity [W/cm^2], phase [cycles]} on
     ``params.coords``, raw): the full-wave model driven through the end of the run, locked in at ``freq`` over its last ``lockin_cycles``
     cycles (DESIGN.md section 2 "full-wave model", kernel section 5.15).
@@ -525,9 +630,12 @@ def run_fullwave_steady_state(arr, params, delays=None, apod=None, freq: float =
     the lag of p behind sin(2 pi freq t); Nw freq dt is not a whole number, so both carry a leakage of the order 1 / (2 Nw) that nothing
     corrects.  intensity = 1e-4 A^2 / (2 rho c) with the impedance rules of ``run_fullwave_simulation``.  ``receivers`` [P, 3] in the
     coordinates' units adds "receiver_amplitude", "receiver_phase" and "receiver_sums" (C_r + i S_r, trilinear weights) to ``raw``.
-    ``element_model`` / ``upsampling_rate`` / ``layer_model`` are ``run_fullwave_simulation``'s."""
+    ``element_model`` / ``upsampling_rate`` / ``layer_model`` / ``drive_model`` are ``run_fullwave_simulation``'s: with
+    ``drive_model="impulse_response"`` the steady state carries the responses' gain and lag at ``freq``, and the default ``t_end`` grows by
+    (M_max - 1) dt; ``raw["drive_model"]`` and ``raw["drive_taps"]`` report the drive."""
     element_model, upsampling_rate = checked_element_model(element_model, upsampling_rate if element_model == "aperture" else 1)
     layer_model = checked_layer_model(layer_model)
+    drive_model = checked_drive_model(drive_model)
     n_el = arr.numelements()
     delays = np.zeros(n_el) if delays is None else np.asarray(delays, dtype=np.float64)
     apod = np.ones(n_el) if apod is None else np.asarray(apod, dtype=np.float64)
@@ -549,7 +657,8 @@ def run_fullwave_steady_state(arr, params, delays=None, apod=None, freq: float =
     A0 = apod * np.asarray(area, dtype=np.float64) * p0 * float(freq) / c_ref
     geom = aperture_geometry(arr, grid_from_coords(coords)[1], upsampling_rate) if element_model == "aperture" else None
     run = steady_state_run(params, pos, A0, delays, freq, dt, t_end, cfl, ref_values_only, lockin_cycles, settle_cycles, ramp_cycles, pml_size,
-                           pml_alpha, receivers_m=rec_m, volume=True, apertures=geom, **_layer_kw(layer_model))
+                           pml_alpha, receivers_m=rec_m, volume=True, apertures=geom, **_layer_kw(layer_model),
+                           **({} if drive_model is None else {"drive_model": drive_model, "arr": arr}))
     w0, nw = run["window"]
     A, psi = lockin_amplitude_phase(run["C"], run["S"], nw)
     c_ref, rho_ref, cs, rho = run["medium"]
@@ -563,7 +672,8 @@ def run_fullwave_steady_state(arr, params, delays=None, apod=None, freq: float =
            "phase": ds.make_dataarray(psi32, coords=coords, dims=dims, name="phase", attrs=PHASE_ATTRS)}
     raw = {"dt": run["dt"], "n_steps": run["n_steps"], "dt_max": run["dt_max"], "window": (w0, nw), "points_per_wavelength": run["points_per_wavelength"],
            "cycles": run["cycles"], "t_end": run["t_end"], "backend": "openlifu_amd/hip-gfx950", "element_model": element_model,
-           "aperture_entries": run["aperture_entries"] if element_model == "aperture" else None, "layer_model": layer_model}
+           "aperture_entries": run["aperture_entries"] if element_model == "aperture" else None, "layer_model": layer_model,
+           "drive_model": drive_model, "drive_taps": run.get("drive_taps")}
     if rec_m is not None:
         ra, rp = lockin_amplitude_phase(run["rec_C"], run["rec_S"], nw)
         raw["receiver_amplitude"], raw["receiver_phase"] = ra, rp
@@ -581,5 +691,5 @@ def _advertise_without(fn, *names):
     fn.__signature__ = sig.replace(parameters=[p for name, p in sig.parameters.items() if name not in names])
 
 
-_advertise_without(run_fullwave_simulation, "element_model", "layer_model")
-_advertise_without(run_fullwave_steady_state, "element_model", "upsampling_rate", "layer_model")
+_advertise_without(run_fullwave_simulation, "element_model", "layer_model", "drive_model", "source_waveforms")
+_advertise_without(run_fullwave_steady_state, "element_model", "upsampling_rate", "layer_model", "drive_model")

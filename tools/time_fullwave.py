@@ -2,7 +2,7 @@
 """Time kernel 5 (full-wave model, k_fullwave.hip): ms per step and achieved bytes/s at 256^3 plus absorbing layers, for the uniform
 instantiation and for a skull-slab medium (five coefficient volumes streamed).
 
-  python tools/time_fullwave.py [--n 256] [--pml 16] [--steps 300] [--layers pml] [--lockin | --aperture [--rounds 3]] [--out profiles/fullwave_time.json]
+  python tools/time_fullwave.py [--n 256] [--pml 16] [--steps 300] [--layers pml] [--lockin | --aperture [--rounds 3] | --response M [--rounds 3]] [--out profiles/fullwave_time.json]
 
 A run of --steps steps is bracketed by olx_sync (after one untimed warm-up run of 20 steps); the step is three launches (inject,
 velocity, pressure-and-record).  Bytes per voxel and step are the compulsory traffic of DESIGN.md section 5.14 -- every volume a launch
@@ -16,7 +16,15 @@ step: C and S read and written), and the volume sums with 64 receivers of 8 entr
 upsampling rate 5 on the uniform medium, against the same array as 256 point sources -- the two alternate in ONE process on ONE box
 (--rounds times each, the median is reported) -- with the number of (element, voxel) entries, and the build of the weight table on the
 device (olx_fullwave_apertures, wall time of the call) against a NumPy scatter build of the same table (np.add.at over the 8 corners
-of every point)."""
+of every point).
+
+--response M times the fill of the drive table through drive taps next to the run itself: 256 point elements in
+element-factored form, one class of M Hann-windowed taps at the drive frequency on all of them, --steps steps.  olx_fullwave_drive re-fills the
+table -- two small uploads (A, tau) and the launches, fullwave_drive_k alone for the bare drive, fullwave_drive_k over the extended range plus
+fullwave_drive_fir_k with the response -- between two olx_sync; the median of --rounds calls of each is reported, with the run's ms per step.
+The figure is the wall time of the whole call (host checks, a stream synchronise, the two uploads, the launches, the final sync): an upper
+bound on the launches, of which the bare fill shows the share that is not the response's ("response_minus_bare_ms").  The figures of DESIGN.md
+section 5.20 are `--response 64 --steps 4000 --rounds 5` and `--response 256 --steps 4000 --rounds 5`."""
 import argparse
 import json
 import os
@@ -118,6 +126,53 @@ def aperture_main(a):
             f.write("\n")
 
 
+def response_main(a):
+    n = a.n + 2 * a.pml
+    h = 0.25e-3
+    shape = (n, n, n)
+    dt = 0.9 * 6.0 / (7.0 * 1500.0 * np.sqrt(3.0) / h)
+    g = (np.arange(16) - 7.5) * 3.0e-3 + (n // 2 + 0.3) * h
+    centre = np.array([[x, y, (a.pml + 2.3) * h] for x in g for y in g])
+    E, M = len(centre), a.response
+    A, tau = np.ones(E), (np.arange(E) % 7) * 0.37 * dt
+    scale = dt * 1500.0 ** 2 * 4 * np.pi / (2 * np.pi * 500e3 * h ** 3)
+    pr, pv, pw = numpy_scatter_table(centre, np.zeros((E, 2)), np.ones(E, dtype=np.int32), np.ones(E, dtype=np.int32), h, n)
+    pe = np.repeat(np.arange(E, dtype=np.int32), np.diff(pr))
+    m = np.arange(M, dtype=np.float64)
+    taps = 0.5 * (1.0 - np.cos(2.0 * np.pi * (m + 1.0) / (M + 1.0))) * np.cos(2.0 * np.pi * 500e3 * dt * m)
+    ctx = nat.Context(0)
+    ctx.fullwave_plan((h,) * 3, shape, 1500.0, 1000.0, 0.0, 1500.0, a.pml, 2.0, dt)
+    ctx.fullwave_sources_elements(pv, pe, pw * scale, A, tau, 500e3, 1e6, 0.0, a.steps)
+    fills = {"bare": [], "response": []}
+    for name in ("bare", "response"):
+        if name == "response":
+            ctx.fullwave_drive_response(np.zeros(E, dtype=np.int32), [taps])          # (untimed: the first call creates the buffers)
+        ctx.fullwave_drive(A, tau)
+        ctx.sync()
+        for _ in range(a.rounds):
+            t0 = time.perf_counter()
+            ctx.fullwave_drive(A, tau)
+            ctx.sync()
+            fills[name].append((time.perf_counter() - t0) * 1e3)
+    ctx.fullwave_run(0, 20)
+    ctx.sync()
+    t0 = time.perf_counter()
+    ctx.fullwave_run(0, a.steps)
+    ctx.sync()
+    run_ms = (time.perf_counter() - t0) * 1e3
+    ctx.close()
+    fill = float(np.median(fills["response"]))
+    out = {"tool": "tools/time_fullwave.py --response", "grid": list(shape), "steps": a.steps, "rounds": a.rounds, "elements": E, "taps": M,
+           "fill_ms": {k: round(float(np.median(t)), 4) for k, t in fills.items()}, "fill_ms_all": {k: [round(x, 4) for x in t] for k, t in fills.items()},
+           "response_minus_bare_ms": round(fill - float(np.median(fills["bare"])), 4),
+           "run_ms": round(run_ms, 2), "ms_per_step": round(run_ms / a.steps, 4), "fill_over_run": round(fill / run_ms, 6)}
+    print(json.dumps(out), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=256)
@@ -128,9 +183,14 @@ def main():
     ap.add_argument("--aperture", action="store_true", help="time 256 aperture elements against 256 point sources (section 5.18)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--layers", choices=("sponge", "pml"), default="sponge", help="the layer model (section 5.19): pml = split layers")
+    ap.add_argument("--response", type=int, default=0, metavar="M", help="time the drive-table fill through M taps next to the run (section 5.20)")
     a = ap.parse_args()
     if a.aperture:
         return aperture_main(a)
+    if a.response:
+        if not 1 <= a.response <= 256:
+            ap.error("--response takes 1 .. 256 taps")
+        return response_main(a)
     layer_bytes = 24.0 * (1.0 - (a.n / (a.n + 2.0 * a.pml)) ** 3) if a.layers == "pml" else 0.0      # three components read and written in the layer voxels
     n = a.n + 2 * a.pml
     h = 0.25e-3
